@@ -2,7 +2,17 @@
 """Benchmark of the hot path: training users/sec of the mini-batch
 negative-sampling loop (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step,
+higher_is_better, dtype, the workload's description).  Everything else it can measure or check -- the
+roofline, Recall@20 against the oracle, the CPU baseline, the multi-GPU alternatives -- runs with --full.
+
+--dump-outputs DIR: what the timed path computed, as DIR/<name>.npy (float32), taken at the end of the
+timed region: every model parameter after the last timed step (the state a caller of Recoder.train
+receives) and losses.npy, the training losses of the K timed steps.  At most 64 MB in all: larger
+parameters are cut to a fixed, seeded sample of their rows.  Inputs are seeded, so two builds run with
+the same arguments can be compared file by file.
 
 The timed region is K steps of ``Recoder.train`` itself -- the drop-in API (reference
 model.py:256-437) -- bracketed by two step marks: the first one fires before ANYTHING of timed
@@ -15,7 +25,7 @@ rank per GPU; the USERS are sharded over the ranks (north_star's partitioning; w
 B users per rank per step) with two in-order RCCL groups of gradient all-reduces per step (decoder
 side, then encoder side), captured with the step's kernels in the replayed graphs.
 
-Also reported:
+Also reported with --full:
   roofline     -- every launch group of the production step (rk_ae_train_step) bracketed with HIP
                   events on the step's stream, in the first (eager) group of the warm-up and in ONE
                   whole group of the timed region (the second one; enqueued eagerly: on the HIP
@@ -317,6 +327,26 @@ def recall_check(rec, model, cfg, csr, n_held=1000, k=20):
                        "oracle/recoder_oracle.py evaluate on the same parameters" % (k, csr_in.shape[0]))
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: the most it writes
+
+
+def output_snapshot(model, reserve_bytes):
+  """{name: float32 array} of the model's parameters, on the host.  If they exceed DUMP_BYTES less
+  `reserve_bytes`, every parameter keeps the same fraction of its rows, drawn with a fixed seed."""
+  named = sorted(model.named_parameters())
+  total = sum(p.numel() * 4 for _, p in named)
+  keep = min(1.0, (DUMP_BYTES - reserve_bytes) / float(max(total, 1)))
+  snap = {}
+  for i, (name, p) in enumerate(named):
+    t = p.detach()
+    if keep < 1.0:
+      n = t.shape[0]
+      rows = np.sort(np.random.RandomState(i).choice(n, max(1, int(n * keep)), replace=False))
+      t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+    snap[name] = t.float().cpu().numpy()
+  return snap
+
+
 def alt_large_batch(cfg, csr, B_alt, W, K, world, rank, device, sync_all, env=None, label=None):
   """The same workload, users-DP, with B_alt users per rank and step: C2's union item set
   saturates at ~20 k items, so past B ~ 2 000 per rank the contractions, the exchange and the Adam sweep stop
@@ -427,6 +457,10 @@ def main():
   ap.add_argument("--steps", type=int, default=200)
   ap.add_argument("--warmup", type=int, default=24)
   ap.add_argument("--config", default="c2")
+  ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed path's outputs as DIR/<name>.npy")
+  ap.add_argument("--full", action="store_true",
+                  help="also the roofline, Recall@20 vs the oracle, the CPU baseline and the multi-GPU alternatives "
+                       "(--sample, --cpu-*, --alt*, --no-cpu-baseline and --no-recall act on these only)")
   ap.add_argument("--cpu-steps", type=int, default=1000)   # bounded by --cpu-seconds
   ap.add_argument("--cpu-seconds", type=float, default=20.0, help="wall-clock bound of the cpu_baseline leg")
   ap.add_argument("--cpu-threads", type=int, default=16)
@@ -525,16 +559,17 @@ def main():
   G = max(1, int(rec.graph_group))          # steps per replayed graph (recoder_amd/graph.py)
 
   def plan_warm(i):
-    # warm-up: the first group of steps runs eagerly with every launch group bracketed, the rest
+    # warm-up: the first group of steps runs eagerly (--full: with every launch group bracketed), the rest
     # replays the captured graphs (so that the timed region starts with warm graphs)
     # (i counts from 0 on the graph path and from 1 on the eagerly sequenced ones: <= covers both)
-    return "all" if i <= min(G, max(1, W // 2)) else ("eager" if args.eager_groups else None)
+    return "all" if args.full and i <= min(G, max(1, W // 2)) else ("eager" if args.eager_groups else None)
 
   # Where the launch groups behind `roofline.kernels` are bracketed with HIP events: by default in the
   # G steps right BEHIND the clock (same process, same state, `sampled` says so) -- event records are
   # barrier packets between the launches and cost a bracketed step ~12 us, which the graded interval
   # must not contain.  --sample timed: inside the timed region as in rounds 1-3.
-  SAMPLE_POST = args.sample == "post"
+  # Without --full nothing is bracketed and the run ends with the timed region.
+  SAMPLE_POST = args.sample == "post" or not args.full
   SAMPLED = ("post-clock group (the %d steps right behind the timed region, same process)" % G) if SAMPLE_POST \
       else "timed region"
 
@@ -608,7 +643,12 @@ def main():
     if getattr(lib_t, "enabled", False):
       lib_t.enabled = False
       T["entries"] = lib_t.summary()
-    return not SAMPLE_POST                           # end the training here
+    if args.dump_outputs:
+      # (the state the timed steps left: --full goes on with the post-clock group behind this mark)
+      rec._sync_user_rows()
+      if rank == 0:
+        T["outputs"] = output_snapshot(model, 4 * K + (1 << 16))    # (the losses, the .npy headers)
+    return not (args.full and SAMPLE_POST)           # end the training here
 
   def install():
     rec._engine().time_plan = plan_warm
@@ -625,9 +665,9 @@ def main():
       eng.lib.enabled = True
     return False
   rec.step_marks = {0: install, W: start, W + K: stop}
-  if cfg["kind"] != "ae" or len(cfg["hidden_layers"]) > 1:
+  if args.full and (cfg["kind"] != "ae" or len(cfg["hidden_layers"]) > 1):
     rec.step_marks[W + K - n_sample] = sample_on
-  if SAMPLE_POST:
+  if args.full and SAMPLE_POST:
     rec.step_marks[W + K + G] = lambda: True
   prewarm = args.prewarm
   if prewarm > 0:
@@ -652,7 +692,7 @@ def main():
   # on real links validates or refutes DESIGN section 6's pricing in one shot
   exch = None
   dp_obj = getattr(rec, "_dp", None)
-  if multi and dp_obj is not None and getattr(dp_obj, "direct", False):
+  if args.full and multi and dp_obj is not None and getattr(dp_obj, "direct", False):
     try:
       bucket = 4 * int(getattr(eng, "n_cap_last", 0) or eng.n_cap) * h0
       exch = dp_obj.microbench(max(bucket, 1 << 20), device, iters=20)
@@ -666,10 +706,10 @@ def main():
   global_rows = B * world if multi else B
   value = K * global_rows / dt              # users consumed by all ranks per second
 
-  want_alt = multi and (world > 1 or args.alt == "1") and \
+  want_alt = args.full and multi and (world > 1 or args.alt == "1") and \
       args.alt != "0" and os.environ.get("RK_PARALLEL", "users") in ("users", "auto")
   B_large = (4000 if world > 1 else 0) if args.alt_large < 0 else args.alt_large
-  if cfg["kind"] != "ae" or B_large * world > n_users:
+  if not args.full or cfg["kind"] != "ae" or B_large * world > n_users:
     B_large = 0
   out = None
 
@@ -681,6 +721,48 @@ def main():
     print(json.dumps(out), flush=True)
 
   if rank == 0:
+    out = {
+      "metric": "train_users_per_sec", "value": value, "unit": "users/s",
+      "n_gpus": world, "steps": K, "warmup": W,
+      "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak",
+      # fp32 storage, accumulation and element-wise math everywhere; decode / dZ / dW multiply fp16
+      # hi+lo pairs (3 products) of the fp32 operands on the 16-bit MFMA, fp32 accumulate.  BASELINE configs[1] says "bf16": plain bf16 operands miss the 1e-5
+      # parity bar north_star sets (measured, DESIGN.md section 4), so they are not used.
+      "vs_baseline": None,
+      "dtype": "f32" if GEMM_F32 else
+               ("bf16 operands in the decoder GEMMs (f32 accumulate), f32 elsewhere" if GEMM_BF16 else
+                "f32 (decoder GEMMs: split 16-bit operands, f32 accumulate)"),
+      "data": "synthetic",
+      "config": {"workload": cfg["workload"], "api": "Recoder.train", "batch_size_per_gpu": B,
+                 "global_batch": global_rows,
+                 "parallelism": "dp%d (users sharded; gradient buckets: %s; %s)" % (
+                     world, getattr(dp_obj, "exchange_mode", "allreduce"),
+                     "owned-row SparseAdam" if getattr(eng, "owned_rows", False) else "replicated Adam")
+                                if multi else "dp1",
+                 "first_loss": float(losses[0]), "last_loss": float(losses[-1]),
+                 "host_enqueue_ms_per_step": T["enqueue"] / K * 1e3,
+                 "graph_replay": bool(getattr(rec, "_graph_stepper", None) is not None),
+                 "steps_per_graph": G,
+                 "pretouch": ("parameters + Adam moments read %d x in front of the clock (cache + clock warm)"
+                              % max(1, args.pretouch_reps)) if not args.no_pretouch else "none",
+                 "first_group_collation": ("in front of the clock; the look-ahead collation behind the last "
+                                           "timed group runs inside it (one per group, as in steady state)")
+                                          if T.get("precollated") else "inside the timed region, in front of step 0"},
+    }
+    if GEMM_BF16:
+      out["variant"] = ("RK_GEMM_PREC=bf16: plain bf16 operands, ONE product per contraction on the current kernel family (round 6) -- the dtype BASELINE configs[1] names; a SEPARATE "
+                        "data point that misses the 1e-5 parity bar (see `recall`: product vs the fp32 oracle); "
+                        "the graded line is the default run")
+    if same_dev:
+      out["INVALID"] = "--one-gpu-gloo: all ranks share one GPU, gloo collectives (a code-path test)"
+    if args.dump_outputs:
+      assert len(losses) >= W + K, (len(losses), W, K)
+      os.makedirs(args.dump_outputs, exist_ok=True)
+      dump = dict(T["outputs"], losses=losses[W:W + K].astype(np.float32))
+      for name, a in dump.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+  if rank == 0 and args.full:
     # per-step n_b / nnz of (up to 50 of) the timed steps: host recomputation, outside the timing
     shard = csr
     if multi:
@@ -905,55 +987,22 @@ def main():
                     event_pair_overhead_ms=ev_over, kernels=kernels, small_launches=small,
                     step=dict(ideal_us=ideal_us, kernel_chain_us=chain_us,
                               measured_us=dt / K * 1e6, frac=ideal_us / (dt / K * 1e6)))
-    out = {
-      "metric": "train_users_per_sec", "value": value, "unit": "users/s",
-      "n_gpus": world, "steps": K, "warmup": W,
-      "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak",
-      # fp32 storage, accumulation and element-wise math everywhere; decode / dZ / dW multiply fp16
-      # hi+lo pairs (3 products) of the fp32 operands on the 16-bit MFMA, fp32 accumulate.  BASELINE configs[1] says "bf16": plain bf16 operands miss the 1e-5
-      # parity bar north_star sets (measured, DESIGN.md section 4), so they are not used.
-      "vs_baseline": None,
-      "dtype": "f32" if GEMM_F32 else
-               ("bf16 operands in the decoder GEMMs (f32 accumulate), f32 elsewhere" if GEMM_BF16 else
-                "f32 (decoder GEMMs: split 16-bit operands, f32 accumulate)"),
-      "data": "synthetic",
-      "config": {"workload": cfg["workload"], "api": "Recoder.train", "batch_size_per_gpu": B,
-                 "global_batch": global_rows,
-                 "parallelism": "dp%d (users sharded; gradient buckets: %s; %s)" % (
-                     world, getattr(dp_obj, "exchange_mode", "allreduce"),
-                     "owned-row SparseAdam" if getattr(eng, "owned_rows", False) else "replicated Adam")
-                                if multi else "dp1",
-                 "avg_sampled_items": n_b, "avg_nnz_per_batch": nnz,
-                 "first_loss": float(losses[0]), "last_loss": float(losses[-1]),
-                 "host_enqueue_ms_per_step": T["enqueue"] / K * 1e3,
-                 "graph_replay": bool(getattr(rec, "_graph_stepper", None) is not None),
-                 "steps_per_graph": G, "bracketed_group_is_graph": bool(T.get("timed_graph")),
-                 "kernel_brackets": SAMPLED,
-                 "pretouch": ("parameters + Adam moments read %d x in front of the clock (cache + clock warm)"
-                              % max(1, args.pretouch_reps)) if not args.no_pretouch else "none",
-                 "step_kernels": {0: "csrc/decode16.hip + dw3.hip", 1: "csrc/pgemm.hip",
-                                  3: "csrc/fdecode.hip + pgemm.hip dW"}.get(step_mode) if one_call else "per-entry sequencing",
-                 "first_group_collation": ("in front of the clock; the look-ahead collation behind the last "
-                                           "timed group runs inside it (one per group, as in steady state)")
-                                          if T.get("precollated") else "inside the timed region, in front of step 0",
-                 "lazy_adam": ({"period": lazy_L, "avg_rows_swept_per_table": LAZY_ROWS, "of_rows": n_items,
-                                "need_lists": bool(getattr(getattr(rec, "_graph_stepper", None), "need_lists", False)),
-                                "block_item_cover": getattr(getattr(rec, "_graph_stepper", None), "need_cover", None),
-                                "note": "dense Adam's rows without a gradient that the next step does not read are caught "
-                                        "up later by replaying their missed steps, bit for bit (csrc/optim.hip "
-                                        "table_sweep_lazy; RK_ADAM_LAZY=0: every row every step); the last step of "
-                                        "the timed region leaves every row up to date"}
-                               if LAZY_ROWS is not None else None),
-                 "exchange_microbench": exch,
-                 "alt_item_parallel": None, "alt_large_batch": None, "alt_local_item_sets": None},
-      "roofline": roofline,
-    }
-    if GEMM_BF16:
-      out["variant"] = ("RK_GEMM_PREC=bf16: plain bf16 operands, ONE product per contraction on the current kernel family (round 6) -- the dtype BASELINE configs[1] names; a SEPARATE "
-                        "data point that misses the 1e-5 parity bar (see `recall`: product vs the fp32 oracle); "
-                        "the graded line is the default run")
-    if same_dev:
-      out["INVALID"] = "--one-gpu-gloo: all ranks share one GPU, gloo collectives (a code-path test)"
+    out["config"].update({
+      "avg_sampled_items": n_b, "avg_nnz_per_batch": nnz,
+      "bracketed_group_is_graph": bool(T.get("timed_graph")), "kernel_brackets": SAMPLED,
+      "step_kernels": {0: "csrc/decode16.hip + dw3.hip", 1: "csrc/pgemm.hip",
+                       3: "csrc/fdecode.hip + pgemm.hip dW"}.get(step_mode) if one_call else "per-entry sequencing",
+      "lazy_adam": ({"period": lazy_L, "avg_rows_swept_per_table": LAZY_ROWS, "of_rows": n_items,
+                     "need_lists": bool(getattr(getattr(rec, "_graph_stepper", None), "need_lists", False)),
+                     "block_item_cover": getattr(getattr(rec, "_graph_stepper", None), "need_cover", None),
+                     "note": "dense Adam's rows without a gradient that the next step does not read are caught "
+                             "up later by replaying their missed steps, bit for bit (csrc/optim.hip "
+                             "table_sweep_lazy; RK_ADAM_LAZY=0: every row every step); the last step of "
+                             "the timed region leaves every row up to date"}
+                    if LAZY_ROWS is not None else None),
+      "exchange_microbench": exch,
+      "alt_item_parallel": None, "alt_large_batch": None, "alt_local_item_sets": None})
+    out["roofline"] = roofline
     if world == 1 and not multi and not args.no_recall:
       # Recall@20 of the trained state, product vs oracle (outside the timed region)
       try:

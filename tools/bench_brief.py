@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """One line per bench.py JSON line on stdin: ms/step and the bracketed launch groups (us).
-    python bench.py ... | python tools/bench_brief.py [label]"""
+    python bench.py --full ... | python tools/bench_brief.py [label]"""
 import json
 import sys
 
