@@ -1,10 +1,14 @@
-"""Build librecoder_hip.so (hand-written HIP kernels + C ABI) for gfx950.
+"""Build the two HIP libraries (hand-written kernels + C ABI) for gfx950.
 
     python -m recoder_amd.build [--force]
 
-hipcc cross-compiles without a GPU; the built library stays in-tree
-(recoder_amd/csrc/librecoder_hip.so, git-ignored) so that it travels with the
-repository snapshot to the GPU box.
+librecoder_hip.so  the training and recommend path (include/recoder_hip.h)
+librecoder_index.so  exact item similarity (include/recoder_index.h), a library of its
+                   own so that the training library's exported symbol set stays as it is
+
+hipcc cross-compiles without a GPU; the built libraries stay in-tree
+(recoder_amd/csrc/*.so, git-ignored) so that they travel with the repository
+snapshot to the GPU box.
 """
 import os
 import subprocess
@@ -12,7 +16,9 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "librecoder_hip.so")
+INDEX_LIB = os.path.join(CSRC, "librecoder_index.so")
 SOURCES = ["capi.hip", "collate.hip", "encoder.hip", "gemm.hip", "decode16.hip", "linear.hip", "dw3.hip", "pgemm.hip", "fdecode.hip", "optim.hip", "topk.hip", "step.hip", "comm.hip"]
+INDEX_SOURCES = ["index.hip"]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified register
 # file); without it hipcc copied all accumulators AGPR<->VGPR around every k-tile
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -28,14 +34,11 @@ def _stale(target, deps):
   return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_library(force=False, verbose=True):
+def _build_one(lib, sources, headers, force, verbose):
   hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-  headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
-      [os.path.join(os.path.dirname(CSRC), "..", "include", "recoder_hip.h"),
-       os.path.join(os.path.dirname(CSRC), "..", "include", "recoder_hip_probe.h")]
   objs = []
   procs = []
-  for src in SOURCES:
+  for src in sources:
     s = os.path.join(CSRC, src)
     o = os.path.join(CSRC, src.replace(".hip", ".o"))
     objs.append(o)
@@ -54,15 +57,25 @@ def build_library(force=False, verbose=True):
       print("FAILED:", src)
   if failed:
     raise RuntimeError("hipcc failed")
-  if force or procs or _stale(LIB, objs):
+  if force or procs or _stale(lib, objs):
     # (-z defs: an internal helper that is declared but defined nowhere must fail HERE, not at dlopen on the GPU box)
-    cmd = [hipcc, "--offload-arch=gfx950", "--offload-compress", "-shared", "-fPIC", "-Wl,-z,defs", "-o", LIB] + objs + ["-ldl"]
+    cmd = [hipcc, "--offload-arch=gfx950", "--offload-compress", "-shared", "-fPIC", "-Wl,-z,defs", "-o", lib] + objs + ["-ldl"]
     if verbose:
       print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
+  return lib
+
+
+def build_library(force=False, verbose=True):
+  """Build both libraries (each only if one of its sources or headers is newer); returns the training library's path."""
+  include = os.path.join(os.path.dirname(CSRC), "..", "include")
+  headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
+      [os.path.join(include, "recoder_hip.h"), os.path.join(include, "recoder_hip_probe.h")]
+  _build_one(LIB, SOURCES, headers, force, verbose)
+  _build_one(INDEX_LIB, INDEX_SOURCES, [os.path.join(include, "recoder_index.h")], force, verbose)
   return LIB
 
 
 if __name__ == "__main__":
   build_library(force="--force" in sys.argv)
-  print("built", LIB)
+  print("built", LIB, INDEX_LIB)
