@@ -1,0 +1,100 @@
+/*
+ * recoder_als.h -- C ABI of librecoder_als.so (MI355X / gfx950 only).
+ *
+ * Implicit-feedback alternating least squares (Hu, Koren & Volinsky 2008) for a
+ * MatrixFactorization with activation "none": score s_ui = x_u . y_i + b_i, loss
+ *   L = sum_{u, i} w_ui (r_ui - s_ui)^2 + reg (sum_u |x_u|^2 + sum_i |y_i|^2),  w_ui = 1 + alpha [r_ui > 0]
+ * over the WHOLE user x item matrix (zeros off the support of R).  The bias b is held fixed.
+ * A library of its own, beside librecoder_hip.so and librecoder_index.so, so that neither of their
+ * symbol sets changes; the Python binding is recoder_amd/_als_lib.py, the driver recoder_amd/als.py.
+ *
+ * One half-step solves every row x_u of one table with the other table F fixed:
+ *   (G + sum_{j in u} a_j f_j f_j^T) x_u = sum_{j in u} ((1 + a_j) r_j - a_j c_j) f_j - s_u v,
+ *   G = F^T F + reg I,  a_j = alpha [r_j > 0],
+ *   user side: c_j = b[col_j] (col_bias), s_u = 1, v = F^T b;
+ *   item side: c_j = b[row] (row_bias), s_u = b[row], v = F^T 1 (column sums of the fixed table).
+ *
+ * Conventions (those of recoder_hip.h)
+ *   - every function returns 0 on success, <0 on error; rk_als_last_error() gives a
+ *     thread-local message.
+ *   - every pointer is a DEVICE pointer owned by the caller; nothing is retained past the call.
+ *   - every launch goes on the caller's hipStream_t (passed as void*); no call synchronises
+ *     the host; no call allocates (scratch comes from a workspace the caller sizes with the
+ *     *_workspace_bytes query).
+ *   - tables are row-major fp32 with an explicit leading dimension (in elements); G is [h, h]
+ *     with leading dimension h.  CSR: int64 indptr [rows + 1], int32 column indices, fp32 values
+ *     (NULL: every value is 1.0).
+ *
+ * Numerics (all f32; every call is bitwise repeatable)
+ *   - rk_als_gram splits the rows into chunks fixed by (rows) alone; each chunk is one k-ascending
+ *     f32 chain on v_mfma_f32_32x32x2_f32, the chunks are added in ascending order.  No atomics.
+ *     G[i][j] and G[j][i] are one stored value (bitwise symmetric).
+ *   - rk_als_solve: a row's result depends only on its CSR row, G, v, the fixed table, the biases
+ *     and its own current value: any [row_lo, row_hi) gives bitwise the rows of the full solve,
+ *     whatever path (stashed or streamed factor rows, G from LDS or from memory) a row takes.
+ */
+#ifndef RECODER_ALS_H
+#define RECODER_ALS_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* (the library is built with -fvisibility=hidden: what this header declares is what it exports) */
+#pragma GCC visibility push(default)
+
+int rk_als_version(void);
+const char *rk_als_last_error(void);
+
+/* largest embedding size the kernels take */
+int rk_als_max_h(void);
+
+/* bytes of workspace rk_als_gram needs for a [rows, h] table (>= 0; < 0 on bad arguments) */
+int64_t rk_als_gram_workspace_bytes(int32_t rows, int32_t h);
+
+/*
+ * G = F^T F + reg I ([h, h]) and v = F^T w ([h]; w NULL: all ones, the column sums) for the table
+ * F [rows, ldf], rows >= 0 (rows == 0 gives G = reg I, v = 0), 1 <= h <= rk_als_max_h().
+ */
+int rk_als_gram(const float *F, int32_t rows, int32_t h, int32_t ldf, const float *w, float reg, float *G,
+                float *v, void *ws, int64_t ws_bytes, void *stream);
+
+/* rk_als_solve flags (tests and measurements; 0 picks the paths by h and row length) */
+#define RK_ALS_FORCE_STREAM 1 /* re-read every factor row from memory on every CG step */
+#define RK_ALS_G_GLOBAL 2     /* read G from memory even when it fits in LDS */
+
+/*
+ * cg_steps conjugate-gradient steps, warm-started from X[r], on the normal equations above for
+ * every row r in [row_lo, row_hi) of the CSR (indptr / indices / data); X [>= row_hi, ldx] is
+ * updated in place.  F [>, ldf]: the fixed table (its rows indexed by the CSR's columns); G, v from
+ * rk_als_gram of F; exactly one of col_bias / row_bias may be non-NULL (both NULL: b = 0).
+ * A row's factor rows are gathered once into LDS and every CG step runs from there when they fit;
+ * longer rows stream them from memory on every step.
+ */
+int rk_als_solve(const int64_t *indptr, const int32_t *indices, const float *data, int32_t row_lo,
+                 int32_t row_hi, const float *F, int32_t ldf, int32_t h, const float *G, const float *v,
+                 const float *col_bias, const float *row_bias, float alpha, int32_t cg_steps, float *X,
+                 int32_t ldx, int32_t flags, void *stream);
+
+/* bytes of workspace rk_als_objective needs for a CSR of `rows` rows */
+int64_t rk_als_objective_workspace_bytes(int32_t rows);
+
+/*
+ * out[0] = L (float64) for X [rows, ldx] (users), Y [cols, ldy] (items), bias [cols] (NULL: 0) and
+ * the user x item CSR.  Gx, sx: rk_als_gram of X with w = NULL; Gy, cy: rk_als_gram of Y with
+ * w = bias; both with this reg.  The sparse part (per stored entry: w (r - s)^2 - s^2) is one row
+ * per wave, the rest comes from the Grams: tr(X^T X Y^T Y) + 2 sx . cy + rows |b|^2 + reg (tr X^T X
+ * + tr Y^T Y); every sum in float64 in a fixed order.
+ */
+int rk_als_objective(const int64_t *indptr, const int32_t *indices, const float *data, int32_t rows,
+                     int32_t cols, const float *X, int32_t ldx, const float *Y, int32_t ldy, int32_t h,
+                     const float *bias, float alpha, float reg, const float *Gx, const float *Gy,
+                     const float *sx, const float *cy, void *ws, int64_t ws_bytes, double *out, void *stream);
+
+#pragma GCC visibility pop
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RECODER_ALS_H */

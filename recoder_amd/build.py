@@ -1,10 +1,12 @@
-"""Build the two HIP libraries (hand-written kernels + C ABI) for gfx950.
+"""Build the three HIP libraries (hand-written kernels + C ABI) for gfx950.
 
     python -m recoder_amd.build [--force]
 
 librecoder_hip.so  the training and recommend path (include/recoder_hip.h)
 librecoder_index.so  exact item similarity (include/recoder_index.h), a library of its
                    own so that the training library's exported symbol set stays as it is
+librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recoder_als.h),
+                   likewise a library of its own
 
 hipcc cross-compiles without a GPU; the built libraries stay in-tree
 (recoder_amd/csrc/*.so, git-ignored) so that they travel with the repository
@@ -17,8 +19,10 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "librecoder_hip.so")
 INDEX_LIB = os.path.join(CSRC, "librecoder_index.so")
+ALS_LIB = os.path.join(CSRC, "librecoder_als.so")
 SOURCES = ["capi.hip", "collate.hip", "encoder.hip", "gemm.hip", "decode16.hip", "linear.hip", "dw3.hip", "pgemm.hip", "fdecode.hip", "optim.hip", "topk.hip", "step.hip", "comm.hip"]
 INDEX_SOURCES = ["index.hip"]
+ALS_SOURCES = ["als.hip"]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified register
 # file); without it hipcc copied all accumulators AGPR<->VGPR around every k-tile
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -67,15 +71,16 @@ def _build_one(lib, sources, headers, force, verbose):
 
 
 def build_library(force=False, verbose=True):
-  """Build both libraries (each only if one of its sources or headers is newer); returns the training library's path."""
+  """Build the libraries (each only if one of its sources or headers is newer); returns the training library's path."""
   include = os.path.join(os.path.dirname(CSRC), "..", "include")
   headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
       [os.path.join(include, "recoder_hip.h"), os.path.join(include, "recoder_hip_probe.h")]
   _build_one(LIB, SOURCES, headers, force, verbose)
   _build_one(INDEX_LIB, INDEX_SOURCES, [os.path.join(include, "recoder_index.h")], force, verbose)
+  _build_one(ALS_LIB, ALS_SOURCES, [os.path.join(include, "recoder_als.h")], force, verbose)
   return LIB
 
 
 if __name__ == "__main__":
   build_library(force="--force" in sys.argv)
-  print("built", LIB, INDEX_LIB)
+  print("built", LIB, INDEX_LIB, ALS_LIB)

@@ -79,6 +79,7 @@ class Recoder(object):
     self.step_marks = {}
     self.last_epoch_losses = None
     self.loss_history = []      # per-epoch arrays of the per-step training losses
+    self.als_history = []       # train_als: the ALS objective after each iteration
     self.__model_initialized = False
     self.__optimizer_state_dict = None
     self.__sparse_optimizer_state_dict = None
@@ -374,6 +375,28 @@ class Recoder(object):
                 iters_per_epoch=iters_per_epoch, eval_num_users=eval_num_users,
                 eval_batch_size=eval_batch_size)
     self._sync_user_rows()
+
+  def train_als(self, train_dataset, num_iterations=10, reg=100.0, cg_steps=3):
+    """Implicit-feedback alternating least squares for a MatrixFactorization with activation 'none'
+    (recoder_amd/als.py): minimises the configured MSELoss(confidence=alpha, reduction='sum') over the
+    whole user x item matrix plus reg (|X|^2 + |Y|^2), the bias held fixed, each row solved with
+    ``cg_steps`` warm-started conjugate-gradient steps.  Builds a fresh optimizer of
+    ``optimizer_type``, so that ``save_state`` and ``train`` work on the tables it leaves.  Returns
+    (and keeps in ``als_history``) the objective after each iteration."""
+    from . import als
+    alpha = als.check_config(self.model, self.loss, self.loss_params, num_iterations, reg, cg_steps)
+    als.check_not_distributed()
+    log.info("ALS: %d iterations, reg %g, confidence %g, %d CG steps", num_iterations, reg, alpha, cg_steps)
+    # (a fresh optimizer: Adam moments of an earlier train() do not describe the ALS tables)
+    self.optimizer = self.sparse_optimizer = None
+    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
+    ucsr, icsr = als.csr_pair(als.host_matrix(train_dataset), self.num_users, self.num_items, self.device)
+    m = self.model
+    self.als_history = als.fit(m.user_embedding_layer.weight.data, m.item_embedding_layer.weight.data,
+                               m.bias.data, ucsr, icsr, alpha, float(reg), int(cg_steps), int(num_iterations))
+    self._weights_written()
+    return list(self.als_history)
 
   def _pick_engine_for(self, train_dataset):
     """Combinations the fused step does not cover train through the generic engine (torch autograd

@@ -1,0 +1,171 @@
+"""CPU: librecoder_als.so is built beside the other two libraries and exports exactly what
+include/recoder_als.h declares (each bound in _als_lib.SIGNATURES); the other libraries' exports are
+unchanged; Recoder.train_als rejects what it does not implement before any GPU work; the float64
+restatement the GPU tests compare against is itself an exact solver when run to h CG steps."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from tests import als_util
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ALS_HEADER = os.path.join(ROOT, "include", "recoder_als.h")
+INDEX_HEADER = os.path.join(ROOT, "include", "recoder_index.h")
+TRAIN_HEADERS = [os.path.join(ROOT, "include", "recoder_hip.h"), os.path.join(ROOT, "include", "recoder_hip_probe.h")]
+
+
+def _declared(paths):
+  src = "".join(open(p).read() for p in paths)
+  src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+  return sorted(set(re.findall(r"\b(rk_[a-z0-9_]+)\s*\(", src)))
+
+
+def _exports(path):
+  out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
+  return sorted(l.split()[-1] for l in out.splitlines() if " T " in l)
+
+
+@pytest.fixture(scope="module")
+def built():
+  from recoder_amd.build import ALS_LIB, INDEX_LIB, LIB, build_library
+  build_library(verbose=False)
+  return LIB, INDEX_LIB, ALS_LIB
+
+
+def test_build_produces_the_als_library(built):
+  assert os.path.exists(built[2])
+
+
+def test_als_library_exports_exactly_its_header(built):
+  from recoder_amd import _als_lib
+  declared = _declared([ALS_HEADER])
+  assert declared and all(s.startswith("rk_als_") for s in declared)
+  assert _exports(built[2]) == declared
+  assert sorted(_als_lib.SIGNATURES) == declared
+  lib = _als_lib.load()
+  assert lib.rk_als_version() >= 100
+  assert lib.rk_als_max_h() == 512
+  assert isinstance(lib.rk_als_last_error(), bytes)
+  # the workspace queries are host arithmetic: no device needed
+  assert lib.rk_als_gram_workspace_bytes(0, 8) == 8 * 9 * 4
+  assert lib.rk_als_gram_workspace_bytes(20108, 64) > 0
+  assert lib.rk_als_gram_workspace_bytes(10, 513) < 0
+  assert lib.rk_als_objective_workspace_bytes(1000) == 8000
+
+
+def test_other_libraries_exports_are_unchanged(built):
+  exported = _exports(built[0])
+  assert exported == _declared(TRAIN_HEADERS)
+  assert len(exported) == 80
+  assert not any(s.startswith(("rk_ix_", "rk_als_")) for s in exported)
+  assert _exports(built[1]) == _declared([INDEX_HEADER])
+  assert not any(s.startswith("rk_als_") for s in _exports(built[1]))
+
+
+def _rec(model=None, loss="mse", loss_params=None, **kw):
+  from recoder_amd.model import Recoder
+  from recoder_amd.nn import MatrixFactorization
+  model = MatrixFactorization(16) if model is None else model
+  return Recoder(model=model, loss=loss, loss_params={"confidence": 10.0} if loss_params is None else loss_params,
+                 optimizer_type="adam", **kw)
+
+
+def _dataset():
+  import scipy.sparse as sp
+  from recoder_amd.data import RecommendationDataset
+  return RecommendationDataset(sp.csr_matrix(np.eye(5, dtype=np.float32)))
+
+
+@pytest.mark.parametrize("case", [
+    "autoencoder", "activation", "dropout", "loss_logloss", "loss_logistic", "mse_extra_params",
+    "mse_module_mean", "bce_module", "cg_steps", "num_iterations", "reg", "h_zero", "h_too_big"])
+def test_train_als_rejects_before_gpu_work(case, monkeypatch):
+  # (every module imported before patching: one imported inside the patch would keep the stand-in)
+  import recoder_amd.als  # noqa: F401
+  import recoder_amd.data  # noqa: F401
+  import recoder_amd.model as model_mod
+  from recoder_amd import device
+  from recoder_amd.losses import MSELoss
+  from recoder_amd.nn import DynamicAutoencoder, MatrixFactorization
+
+  def no_gpu(*a, **k):
+    raise AssertionError("GPU work started")
+  monkeypatch.setattr(device, "require_gpu", no_gpu)
+  monkeypatch.setattr(model_mod, "require_gpu", no_gpu)
+  rec = {
+    "autoencoder": lambda: _rec(DynamicAutoencoder(hidden_layers=[16])),
+    "activation": lambda: _rec(MatrixFactorization(16, activation_type="tanh")),
+    "dropout": lambda: _rec(MatrixFactorization(16, dropout_prob=0.1)),
+    "loss_logloss": lambda: _rec(loss="logloss", loss_params={}),
+    "loss_logistic": lambda: _rec(loss="logistic", loss_params={}),
+    "mse_extra_params": lambda: _rec(loss_params={"confidence": 1.0, "reduction": "sum"}),
+    "mse_module_mean": lambda: _rec(loss=MSELoss(confidence=3.0)),
+    "bce_module": lambda: _rec(loss=torch.nn.BCEWithLogitsLoss(reduction="sum")),
+    "cg_steps": lambda: _rec(),
+    "num_iterations": lambda: _rec(),
+    "reg": lambda: _rec(),
+    "h_zero": lambda: _rec(MatrixFactorization(0)),
+    "h_too_big": lambda: _rec(MatrixFactorization(513)),
+  }[case]()
+  kw = {"cg_steps": {"cg_steps": 0}, "num_iterations": {"num_iterations": -1}, "reg": {"reg": -1.0}}.get(case, {})
+  with pytest.raises(ValueError):
+    rec.train_als(_dataset(), **kw)
+  assert rec.model is not None and getattr(rec.model, "user_embedding_layer", None) is None
+
+
+def test_train_als_accepts_an_mse_sum_module_without_gpu_work():
+  """The configuration check passes for MSELoss(reduction='sum') and for 'mse' without params."""
+  from recoder_amd import als
+  from recoder_amd.losses import MSELoss
+  from recoder_amd.nn import MatrixFactorization
+  assert als.check_config(MatrixFactorization(8), MSELoss(confidence=4.0, reduction="sum"), {}, 1, 1.0, 1) == 4.0
+  assert als.check_config(MatrixFactorization(512), "mse", {}, 0, 0.0, 3) == 0.0
+  assert als.check_config(MatrixFactorization(1), "mse", {"confidence": 10}, 2, 100.0, 1) == 10.0
+
+
+def test_train_als_is_single_gpu(monkeypatch):
+  import torch.distributed as dist
+  monkeypatch.setattr(dist, "is_available", lambda: True)
+  monkeypatch.setattr(dist, "is_initialized", lambda: True)
+  monkeypatch.setattr(dist, "get_world_size", lambda *a: 2)
+  rec = _rec()
+  with pytest.raises(NotImplementedError):
+    rec.train_als(_dataset())
+
+
+@pytest.mark.parametrize("side", ["user", "item"])
+@pytest.mark.parametrize("alpha", [0.0, 10.0])
+def test_restatement_cg_with_h_steps_is_an_exact_solve(side, alpha):
+  """h = 8: CG run to >= h steps (3 h) solves each row's normal equations (the oracle pins itself)."""
+  h = 8
+  csr = als_util.random_csr(30, 40, 0.2, seed=1, values="counts", empty_rows=(3,))
+  if side == "item":
+    csr = csr.T.tocsr()
+  rng = np.random.RandomState(2)
+  F = rng.randn(csr.shape[1], h)
+  X = rng.randn(csr.shape[0], h)
+  bias = rng.randn(csr.shape[1] if side == "user" else csr.shape[0])
+  got = als_util.half_step(csr, F, X, bias, alpha, 2.0, 3 * h, side)
+  want = als_util.half_step(csr, F, X, bias, alpha, 2.0, h, side, exact=True)
+  np.testing.assert_allclose(got, want, rtol=0, atol=1e-9 * np.abs(want).max())
+
+
+def test_restatement_normal_equations_minimise_the_objective():
+  """The exact user half-step is the minimiser of L in X (with the bias): every perturbation raises L."""
+  h = 4
+  csr = als_util.random_csr(12, 15, 0.3, seed=4, values="counts")
+  rng = np.random.RandomState(5)
+  X, Y, b = rng.randn(12, h), rng.randn(15, h), rng.randn(15)
+  Xs = als_util.half_step(csr, Y, X, b, 3.0, 0.5, 0, "user", exact=True)
+  L0 = als_util.objective(csr, Xs, Y, b, 3.0, 0.5)
+  for _ in range(5):
+    assert als_util.objective(csr, Xs + 1e-3 * rng.randn(*Xs.shape), Y, b, 3.0, 0.5) > L0
+  Ys = als_util.half_step(csr.T.tocsr(), Xs, Y, b, 3.0, 0.5, 0, "item", exact=True)
+  L1 = als_util.objective(csr, Xs, Ys, b, 3.0, 0.5)
+  assert L1 <= L0
+  for _ in range(5):
+    assert als_util.objective(csr, Xs, Ys + 1e-3 * rng.randn(*Ys.shape), b, 3.0, 0.5) > L1
