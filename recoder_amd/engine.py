@@ -8,7 +8,9 @@ host synchronisation.  All arithmetic is in the HIP library; torch is used for
 device memory and streams only.
 """
 import ctypes
+import enum
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -24,6 +26,46 @@ LOSS_IDS = {"mse": LOSS_MSE, "logistic": LOSS_BCE, "logloss": LOSS_MNLL}
 
 def _f32(x):
   return float(np.float32(x))
+
+
+class Decode(enum.Enum):
+  """Decode family of a step sequenced entry by entry (FusedEngine._decode_path)."""
+  FDEC = "rk_fdec_loss_dz"                 # register-resident fused decode; the dZ partials in ws
+  DZ_PLANES = "rk_decode_loss_dz_planes"   # plane decode; the dZ partials of its column tiles in ws
+  PG = "rk_pg_decode_loss"                 # pipelined pair planes (the multinomial loss: rk_pg_decode_mnll)
+  PLANES = "rk_decode_loss_planes"         # plane decode; the dZ product on the W^T image behind it
+  PLAIN = "rk_decode_loss"                 # the in-loop operand split
+
+  @property
+  def image(self):
+    """dLoss/dLogits is left as a plane image (dW and dZ read it; the operand split needs no W^T image)."""
+    return self in (Decode.FDEC, Decode.PG)
+
+
+class Rows(enum.Enum):
+  """Where a step left the decoder-side row gradient."""
+  DENSE = 0        # G_de
+  DW3 = 1          # K slabs in ws_dw at rk_dw3_slabs (csrc/dw3.hip)
+  PG = 2           # K slabs at the head of ws_dw (rk_pg_dw)
+
+
+class Bias(enum.Enum):
+  """Where a step left the decoder bias gradient."""
+  DENSE = 0        # gb_de
+  TILES = 1        # the decode's row-tile column sums of dO in gb_part
+  SLABS = 2        # one partial per K slab of dW in gb_part
+
+
+class GradLayout(NamedTuple):
+  """Where the last training step left its gradients (FusedEngine.grads): the Adam sweep, grad_views,
+  the gradient accessors and graph.GraphStepper read it."""
+  blk: object                  # the block whose item set indexes the decoder-side rows
+  B: int
+  loss: object                 # the step's loss scalar (device)
+  rows: Rows = Rows.DENSE
+  bias: Bias = Bias.DENSE
+  en_segs: int = 0             # > 0: gb_en as that many row-segment partials in gb_en_parts (> 1: G_en too)
+  decode: Decode = None        # the decode family of an entry-by-entry step
 
 
 class ParamState:
@@ -108,13 +150,10 @@ class FusedEngine:
     self.time_plan = None
     self._time_samples = []                # (entry name, event0, event1)
     self._time_keep = []
-    self._gb_lazy = None
-    self._pending_loss = None
+    self.grads = None                      # GradLayout of the last training step
     self.item_parallel = None              # parallel.ItemParallel when the items are sharded
     self._cstep = None
     self._c_calls = 0
-    # dW on a stream of its own next to the dZ -> encoder-backward chain; RK_DW_BRANCH=0: in line
-    self.dw_branch = True
     self._dw_objs = None
     # operand ranges of the split-fp16 decoder contractions (include/recoder_hip.h rk_amax):
     # [0..63] max |Z| (filled per call when the activation is unbounded), [64..127] an upper bound
@@ -192,11 +231,10 @@ class FusedEngine:
                               self.lib.rk_pg_dz_workspace_bytes(B_cap, h0),
                               self.lib.rk_pg_dw_workspace_bytes(B_cap, h0, n_cap)) // 4 + 64, **f)
     self.split16 = bool(self.lib.rk_gemm_split16())
-    self._dw_slabs = None
     # dW as a branch of the one-call step (rk_ae_step_t.dw_stream): a workspace of its own
     self.ws_dw = (torch.zeros(max(self.lib.rk_dw3_workspace_bytes(B_cap, h0, n_cap),
                                   self.lib.rk_pg_dw_workspace_bytes(B_cap, h0, n_cap)) // 4 + 64, **f)
-                  if self.split16 and self.dw_branch else None)
+                  if self.split16 else None)
     # Z^T as bf16 planes for the dW kernel, written by the encoder forward of the one-call step
     # (zeroed once: the padding columns are never written)
     self.zt_planes = torch.zeros(self.lib.rk_dw3_planes_bytes(B_cap, h0) // 4 + 16, **f)
@@ -336,11 +374,11 @@ class FusedEngine:
   # The updates of one step are collected as rk_adam_job_t records and issued through
   # rk_adam_multi, ten per launch (a hidden-stack model has ~11 parameter tensors, i.e. ~11 launches and FFI calls
   # otherwise).  Index arrays that are int64 (MF user rows) go through rk_adam_rows directly.
-  def _job(self, s, n_rows, h, g, pos=None, rows=None, n_dev=None, n_cap=0, parts=None):
+  # rp: the replay context of graph.GraphStepper (None: an eagerly enqueued step).
+  def _job(self, s, n_rows, h, g, rp, pos=None, rows=None, n_dev=None, n_cap=0, parts=None):
     """parts = (pointer, g_parts, g_stride, gstride_dev, gparts_dev): the gradient is the sum, in
     order, of that many partial arrays (rk_adam_job_t) instead of the single array `g`."""
     from ._lib import RkAdamJob
-    rp = getattr(self, "_replay", None)
     if rp is None:
       s.step += 1
     lr, b1, b2, eps = self._adam_args(s)
@@ -364,32 +402,24 @@ class FusedEngine:
         j.lazy_need_list, j.lazy_need_count = lz["need"]
     self._jobs.append(j)
 
-  def _flush_jobs(self, stream):
+  def _flush_jobs(self, stream, loss=None):
+    """Issue the collected jobs.  loss = (partials, count, denom, out): the deferred reduction of the step's
+    loss rides on the last launch (as in rk_ae_train_step).  Returns `loss` when no launch took it."""
     from ._lib import RkAdamJob
     jobs, self._jobs = self._jobs, []
     for i in range(0, len(jobs), ADAM_MULTI_MAX):
       chunk = jobs[i:i + ADAM_MULTI_MAX]
       arr = (RkAdamJob * len(chunk))(*chunk)
-      pend = self._pending_loss if i + ADAM_MULTI_MAX >= len(jobs) else None
-      if pend is not None:
-        # the deferred reduction of the step's loss partials rides on the sweep (as in rk_ae_train_step)
-        n_part, denom, out = pend[:3]
-        src = pend[3] if len(pend) > 3 else self.loss_part
-        self._pending_loss = None
-        check(self.lib.rk_adam_multi(arr, len(chunk), ptr(src), n_part, denom, ptr(out), stream),
-              "rk_adam_multi")
-      else:
-        check(self.lib.rk_adam_multi(arr, len(chunk), None, 0, 1.0, None, stream), "rk_adam_multi")
+      src, n_part, denom, out = (loss if loss is not None and i + ADAM_MULTI_MAX >= len(jobs)
+                                 else (None, 0, 1.0, None))
+      check(self.lib.rk_adam_multi(arr, len(chunk), ptr(src), n_part, denom, ptr(out), stream), "rk_adam_multi")
+    return None if jobs else loss
 
-  def _adam_table(self, s, pos, G, h, n_rows, stream, parts=None):
-    self._job(s, n_rows, h, G, pos=pos, parts=parts)
-
-  def _adam_rows(self, s, idx32, idx64, n_dev, n_cap, G, h, stream, parts=None):
+  def _adam_rows(self, s, idx32, idx64, n_dev, n_cap, G, h, stream, rp, parts=None):
     if idx32 is not None and n_dev is not None:
-      self._job(s, 0, h, G, rows=idx32, n_dev=n_dev, n_cap=n_cap, parts=parts)
+      self._job(s, 0, h, G, rp, rows=idx32, n_dev=n_dev, n_cap=n_cap, parts=parts)
       return
     assert parts is None
-    rp = getattr(self, "_replay", None)
     if rp is None:
       s.step += 1
     lr, b1, b2, eps = self._adam_args(s)
@@ -397,11 +427,9 @@ class FusedEngine:
                                 n_cap, ptr(G), lr, b1, b2, eps,
                                 s.step if rp is None else rp["slots"][s.name] + 1, stream), "rk_adam_rows")
 
-  def _adam_dense(self, s, g, stream):
-    self._job(s, 1, s.p.numel(), g)
-
   # --------------------------------------------------------------- forward
-  def _ae_forward(self, blk, row_off, B, keep_noise, keep_drop, train, stream):
+  def _ae_forward(self, blk, row_off, B, keep_noise, keep_drop, train, stream, split_w=None):
+    """split_w: the RkPlanes whose W image the launch writes for the decode of this block."""
     m, lib = self.model, self.lib
     p_noise = float(m.noise_prob) if train else 0.0
     ip = self.item_parallel if train else None
@@ -414,19 +442,16 @@ class FusedEngine:
                                          stream), "rk_ae_encode_fwd_partial")
       ip.allreduce_sum(self.enc[0][:B * h0])
       check(lib.rk_bias_act(ptr(self.enc[0]), ptr(m.en_bias), B, h0, self.act, stream), "rk_bias_act")
-    elif train and getattr(self, "_split_w_with_fwd", False):
+    elif train and split_w is not None:
       # the W_de[items] half of the decode's operand split rides on this launch (as in the one-call
-      # step); _loss then only cuts Z
+      # step); _decode then only cuts Z
       self._check_weight_range()
       W_de, _ = self._decoder_params()
       check(lib.rk_ae_encode_fwd_split_w(blk.ref, row_off, B, ptr(m.en_embedding_layer.weight),
                                          ptr(m.en_bias), self.h[0], ptr(keep_noise), p_noise, self.seed,
                                          self.rng_step, ptr(blk.users), self.act, ptr(self.enc[0]),
-                                         ptr(W_de), ptr(self.ranges),
-                                         ctypes.byref(self.planes_nowt if getattr(self, "_split_nowt", False)
-                                                      else self.planes), stream),
+                                         ptr(W_de), ptr(self.ranges), ctypes.byref(split_w), stream),
             "rk_ae_encode_fwd")
-      self._w_split_of = blk
     else:
       check(lib.rk_ae_encode_fwd(blk.ref, row_off, B, ptr(m.en_embedding_layer.weight),
                                  ptr(m.en_bias), self.h[0], ptr(keep_noise), p_noise, self.seed,
@@ -554,89 +579,67 @@ class FusedEngine:
             not lib.rk_gemm_plain_bf16() and self.item_parallel is None and
             not lib.rk_decode_dz_fused_ok(B, self.h[0], n_cap, self.loss_id))
 
-  def _loss(self, z, B, tgt, row_off, denom_rows, stream, out=None, ip=None, defer=False, fuse_dz=False,
-            zt_ws=None, pg_ok=False, fdec_ok=False, own_block=True):
-    """decode + loss; leaves dLoss/dLogits in self.dO. Returns device scalar.  ip: the
-    block holds an item shard (parallel.ItemParallel) -- only the multinomial loss needs to
-    know: its softmax statistics are combined over the ranks."""
+  def _decode_path(self, B, tgt, row_off, own_block, tied, lazy):
+    """The decode family of a step sequenced entry by entry, from the configuration and the shape."""
+    if self.planes is None or self.item_parallel is not None:
+      return Decode.PLAIN
+    # (users-DP too: dW then leaves ONE dense array for the exchange -- rk_pg_dw_dz_reduce dense)
+    if not tied and self._fdec_entry_ok(B, tgt.n_cap, row_off, own_block):
+      return Decode.FDEC
+    # the operands are split once and the decode launch leaves the dZ partials of its column tiles in self.ws
+    if self.lib.rk_decode_dz_fused_ok(B, self.h[0], tgt.n_cap, self.loss_id):
+      return Decode.DZ_PLANES
+    # outside the fused launch's domain (multinomial loss, h > 256, >= 1024 rows): the pipelined pair-plane
+    # kernels, else the plane decode with the dZ product on the W^T image
+    if lazy and not tied and self._pg_entry_ok(B, tgt.n_cap):
+      return Decode.PG
+    return Decode.PLANES
+
+  def _decode(self, z, B, tgt, row_off, denom_rows, stream, ip=None, path=Decode.PLAIN, zt_ws=None,
+              w_done=False):
+    """decode + loss on the family `path`: leaves dLoss/dLogits in self.dO and the loss partials in
+    self.loss_part, returns their count.  ip: the block holds an item shard (parallel.ItemParallel) -- only
+    the multinomial loss needs to know: its softmax statistics are combined over the ranks.  zt_ws: the
+    workspace of the step's dW launch, at whose head the split launch writes Z^T as that kernel's fp16 pair
+    planes (one launch less inside rk_decode_bwd_dw2).  w_done: the encoder forward of this step already cut
+    W_de[items of this block] (rk_ae_encode_fwd_split_w)."""
     lib = self.lib
     W, b = self._decoder_params()
+    h0 = self.h[0]
     inv_B = _f32(np.float32(1.0) / np.float32(denom_rows))
-    out = self.loss_out if out is None else out
-    self._dz_in_ws = False
-    self._dz_on_planes = False
-    self._dz_pg = False
-    self._dz_fdec = False
-    # zt_ws: the workspace the step's dW launch will use -- the split launch then writes Z^T as that
-    # kernel's fp16 pair planes at its head (one launch less inside rk_decode_bwd_dw2)
-    self._zt_ready = None
-    if zt_ws is not None and not self.lib.rk_split_zt_ok():
-      zt_ws = None
-    # (the encoder forward of this step already cut W_de[items of this block]: rk_ae_encode_fwd_split_w)
-    w_done = getattr(self, "_w_split_of", None) is tgt and tgt is not None
-    self._w_split_of = None
-    if fuse_dz and fdec_ok and ip is None and self._fdec_entry_ok(B, tgt.n_cap, row_off, own_block):
-      h0 = self.h[0]
-      rg = self._ranges(z, B * h0, stream)
+    rg = self._ranges(z, B * h0, stream)
+    if path is not Decode.PLAIN:
+      # ONE split launch: the W image (unless the encoder forward cut it) and the Z image; the W^T image
+      # and the Z^T planes unless dLoss/dLogits is left as a plane image
       check(lib.rk_split_wz(None if w_done else ptr(W), ptr(z), B, h0, tgt.ref, rg,
-                               ctypes.byref(self.planes_nowt), None, stream), "rk_split_wz")
+                            ctypes.byref(self.planes_nowt if path.image else self.planes),
+                            None if path.image else ptr(zt_ws), stream), "rk_split_wz")
+    if path is Decode.FDEC:
       check(lib.rk_fdec_loss_dz(ctypes.byref(self.planes), B, tgt.ref, row_off, ptr(b), self.loss_id,
                                 self.confidence, inv_B, ptr(self.dO), self.do_rows, ptr(self.do_scales),
                                 ptr(self.loss_part), ptr(self.ws), stream), "rk_fdec_loss_dz")
-      self._dz_pg = True          # (dO is a plane image: dW reads it -- granule 32 x 64, self._dz_fdec)
-      self._dz_fdec = True
-    elif fuse_dz and ip is None and self.planes is not None and self.split16 and self.ws_dw is not None and \
-        self.item_parallel is None and lib.rk_decode_dz_fused_ok(B, self.h[0], tgt.n_cap, self.loss_id):
-      # training steps sequenced entry by entry (hidden stacks, bottleneck dropout, MatrixFactorization):
-      # the operands are split once (two launches) and the decode launch leaves the dZ partials of its
-      # column tiles in self.ws (rk_decode_loss_dz_planes) -- the dZ launch, its pass over dO and the
-      # in-loop operand splits go; rk_decode_dz_reduce follows where rk_decode_bwd_dz stood, dW works
-      # in its own workspace in between
-      h0 = self.h[0]
-      rg = self._ranges(z, B * h0, stream)
-      check(lib.rk_split_wz(None if w_done else ptr(W), ptr(z), B, h0, tgt.ref, rg, ctypes.byref(self.planes),
-                               ptr(zt_ws), stream), "rk_split_wz")
-      self._zt_ready = None if zt_ws is None else zt_ws.data_ptr()
+    elif path is Decode.DZ_PLANES:
+      # (rk_decode_dz_reduce follows where rk_decode_bwd_dz stood; dW works in its own workspace in between)
       check(lib.rk_decode_loss_dz_planes(ctypes.byref(self.planes), B, tgt.ref, row_off, ptr(b), self.loss_id,
                                          self.confidence, inv_B, ptr(self.dO), ptr(self.loss_part),
                                          ptr(self.gb_part), ptr(self.ws), stream), "rk_decode_loss_dz_planes")
-      self._dz_in_ws = True
-    elif fuse_dz and pg_ok and ip is None and self._pg_entry_ok(B, tgt.n_cap):
-      # outside the fused launch's domain: decode + loss, dZ and dW on the pipelined pair-plane kernels --
-      # ONE split launch (W image unless the encoder forward cut it, Z image; no W^T image, no Z^T planes),
-      # dLoss/dLogits as a plane image; the multinomial loss as a statistics pass + the decode / loss pass
-      # (no logits matrix, no rk_mnll_finish)
-      h0 = self.h[0]
-      rg = self._ranges(z, B * h0, stream)
-      check(lib.rk_split_wz(None if w_done else ptr(W), ptr(z), B, h0, tgt.ref, rg,
-                               ctypes.byref(self.planes_nowt), None, stream), "rk_split_wz")
-      if self.loss_id == LOSS_MNLL:
-        check(lib.rk_pg_decode_mnll(ctypes.byref(self.planes), B, tgt.ref, row_off, ptr(b), inv_B,
-                                    ptr(self.mnll_ws), ptr(self.dO), self.do_rows, ptr(self.do_scales), None,
-                                    ptr(self.loss_part), ptr(self.gb_part), stream), "rk_pg_decode_mnll")
-      else:
-        check(lib.rk_pg_decode_loss(ctypes.byref(self.planes), B, tgt.ref, row_off, ptr(b), self.loss_id,
-                                    self.confidence, inv_B, ptr(self.dO), self.do_rows, ptr(self.do_scales),
-                                    None, ptr(self.loss_part), ptr(self.gb_part), stream), "rk_pg_decode_loss")
-      self._dz_pg = True
-    elif fuse_dz and ip is None and self.planes is not None and self.split16 and self.item_parallel is None:
-      # outside the fused launch's domain (multinomial loss, h > 256, >= 1024 rows): still the plane
-      # kernels -- ONE split launch, then the copy -> LDS -> MFMA decode; the dZ product follows on the
-      # W^T image (rk_decode_bwd_dz_planes) where rk_decode_bwd_dz would split W_de in its k-loop again
-      h0 = self.h[0]
-      rg = self._ranges(z, B * h0, stream)
-      check(lib.rk_split_wz(None if w_done else ptr(W), ptr(z), B, h0, tgt.ref, rg, ctypes.byref(self.planes),
-                               ptr(zt_ws), stream), "rk_split_wz")
-      self._zt_ready = None if zt_ws is None else zt_ws.data_ptr()
+    elif path is Decode.PG and self.loss_id == LOSS_MNLL:
+      # a statistics pass + the decode / loss pass (no logits matrix, no rk_mnll_finish)
+      check(lib.rk_pg_decode_mnll(ctypes.byref(self.planes), B, tgt.ref, row_off, ptr(b), inv_B,
+                                  ptr(self.mnll_ws), ptr(self.dO), self.do_rows, ptr(self.do_scales), None,
+                                  ptr(self.loss_part), ptr(self.gb_part), stream), "rk_pg_decode_mnll")
+    elif path is Decode.PG:
+      check(lib.rk_pg_decode_loss(ctypes.byref(self.planes), B, tgt.ref, row_off, ptr(b), self.loss_id,
+                                  self.confidence, inv_B, ptr(self.dO), self.do_rows, ptr(self.do_scales),
+                                  None, ptr(self.loss_part), ptr(self.gb_part), stream), "rk_pg_decode_loss")
+    elif path is Decode.PLANES:
       check(lib.rk_decode_loss_planes(ctypes.byref(self.planes), B, tgt.ref, row_off, ptr(b), self.loss_id,
                                       self.confidence, inv_B, ptr(self.dO), 0, ptr(self.loss_part),
                                       ptr(self.gb_part), stream), "rk_decode_loss_planes")
-      self._dz_on_planes = True
     else:
-      check(lib.rk_decode_loss(ptr(z), B, self.h[0], tgt.ref, row_off, ptr(W), ptr(b), self.loss_id,
+      check(lib.rk_decode_loss(ptr(z), B, h0, tgt.ref, row_off, ptr(W), ptr(b), self.loss_id,
                                self.confidence, inv_B, ptr(self.dO), 0, ptr(self.loss_part),
-                               ptr(self.gb_part), self._ranges(z, B * self.h[0], stream), stream),
-            "rk_decode_loss")
+                               ptr(self.gb_part), rg, stream), "rk_decode_loss")
     if self.loss_id == LOSS_MNLL and ip is not None:
       # per-row {max, sum exp} of the local logits -> all ranks' pairs -> global log-sum-exp
       stats = torch.empty(B, 2, dtype=torch.float32, device=self.device)
@@ -648,21 +651,12 @@ class FusedEngine:
       gmax, glog = gmax.contiguous(), glog.contiguous()
       check(lib.rk_mnll_finish(ptr(self.dO), B, tgt.ref, row_off, inv_B, ptr(gmax), ptr(glog),
                                ptr(tsum), ptr(self.loss_part), stream), "rk_mnll_finish")
-      n_part = B
-    elif self.loss_id == LOSS_MNLL and self._dz_pg:
-      n_part = self.lib.rk_loss_partials(B, tgt.n_cap)     # (one partial per tile, as mse / logistic)
-    elif self.loss_id == LOSS_MNLL:
+      return B
+    if self.loss_id == LOSS_MNLL and not path.image:
       check(lib.rk_mnll_finish(ptr(self.dO), B, tgt.ref, row_off, inv_B, None, None, None, ptr(self.loss_part),
                                stream), "rk_mnll_finish")
-      n_part = B
-    else:
-      n_part = self.lib.rk_loss_partials(B, tgt.n_cap)     # all slots (unused ones hold 0)
-    if defer:        # (train_step: summed by the step's Adam launch, see _flush_jobs)
-      self._pending_loss = (n_part, float(denom_rows), out)
-      return out
-    check(lib.rk_loss_reduce(ptr(self.loss_part), n_part, float(denom_rows), ptr(out), stream),
-          "rk_loss_reduce")
-    return out
+      return B
+    return self.lib.rk_loss_partials(B, tgt.n_cap)     # all slots (unused ones hold 0; the images: one per tile)
 
   # ------------------------------------------------------------------ steps
   def compute_loss(self, blk, row_off, B, tgt=None, out=None):
@@ -673,7 +667,10 @@ class FusedEngine:
       z = self._ae_forward(blk, row_off, B, None, None, False, stream)
     else:
       z = self._mf_forward(blk.users[row_off:row_off + B], B, None, False, stream)
-    return self._loss(z, B, tgt if tgt is not None else blk, row_off, B, stream, out)
+    out = self.loss_out if out is None else out
+    n_part = self._decode(z, B, tgt if tgt is not None else blk, row_off, B, stream)
+    check(self.lib.rk_loss_reduce(ptr(self.loss_part), n_part, float(B), ptr(out), stream), "rk_loss_reduce")
+    return out
 
   def train_step(self, blk, row_off, B, keep_noise=None, keep_drop=None, out=None,
                  global_rows=None, tgt=None, replay=None):
@@ -701,116 +698,86 @@ class FusedEngine:
         raise RuntimeError("FusedEngine: a separate target matrix has no sharded formulation")
     if self.c_step_eligible() and tgt is None and not (ip is not None and self.loss_id == LOSS_MNLL):
       return self._c_train_step(blk, row_off, B, keep_noise, out, global_rows, main_s, replay=replay)
-    if replay is not None:
-      # graph replay of the per-entry sequencing (graph.GraphStepper): what changes per step comes
-      # from the device-resident cursor (include/recoder_hip.h rk_replay_t); the host counters are
-      # advanced by the stepper, `out` is the base of the epoch's loss buffer
-      from ._lib import RkReplay
-      ctx = RkReplay()
-      ctx.cursor, ctx.off, ctx.B = replay["cursor"], replay["off"], B
-      ctx.users_base, ctx.adam_table, ctx.tab_stride = replay["users"], replay["table"], replay["tab_stride"]
-      ctx.cursor_next, ctx.advance = replay["next"] if replay.get("next") is not None else (None, 0)
-      raw_lib = _lib.load()
-      raw_lib.rk_replay_set(ctypes.byref(ctx))
-      self._replay = replay
-      try:
-        return self._entry_train_step(blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s)
-      finally:
-        self._replay = None
-        raw_lib.rk_replay_set(None)
-    return self._entry_train_step(blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s)
+    if replay is None:
+      return self._entry_train_step(blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s, None)
+    # graph replay of the per-entry sequencing (graph.GraphStepper): what changes per step comes
+    # from the device-resident cursor (include/recoder_hip.h rk_replay_t); the host counters are
+    # advanced by the stepper, `out` is the base of the epoch's loss buffer
+    from ._lib import RkReplay
+    ctx = RkReplay()
+    ctx.cursor, ctx.off, ctx.B = replay["cursor"], replay["off"], B
+    ctx.users_base, ctx.adam_table, ctx.tab_stride = replay["users"], replay["table"], replay["tab_stride"]
+    ctx.cursor_next, ctx.advance = replay["next"] if replay.get("next") is not None else (None, 0)
+    raw_lib = _lib.load()
+    raw_lib.rk_replay_set(ctypes.byref(ctx))
+    try:
+      return self._entry_train_step(blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s, replay)
+    finally:
+      raw_lib.rk_replay_set(None)
 
-  def _entry_train_step(self, blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s):
+  def _entry_train_step(self, blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s, replay):
     """The step sequenced entry by entry from here (hidden stacks, bottleneck dropout,
-    MatrixFactorization, separate target blocks, the multi-GPU variants)."""
+    MatrixFactorization, separate target blocks, the multi-GPU variants).  replay: the replay
+    context of graph.GraphStepper (None: enqueued eagerly)."""
     lib, m = self.lib, self.model
     ip = self.item_parallel
     tb = blk if tgt is None else tgt
-    self._gb_lazy = None
-    self._gb_en_segs = 0
-    self._pg_step = False
     stream = ctypes.c_void_p(main_s.cuda_stream)
-    if getattr(self, "_replay", None) is None:
+    if replay is None:
       self.rng_step += 1
     h0 = self.h[0]
     rows = B if global_rows is None else global_rows
-    if self.kind == "ae":
-      # (the plane kernels will decode this block: its W_de[items] split can ride on the encoder forward)
-      self._w_split_of = None
-      self._split_w_with_fwd = (tgt is None and ip is None and self.planes is not None and self.split16 and
-                                self.item_parallel is None and not bool(m.is_constrained))
-      self._split_nowt = bool(self._split_w_with_fwd and self.allreduce is None and
-                              (self._pg_entry_ok(B, blk.n_cap) or
-                               self._fdec_entry_ok(B, blk.n_cap, row_off, tgt is None)))
-      z = self._ae_forward(blk, row_off, B, keep_noise, keep_drop, True, stream)
-      self._split_w_with_fwd = False
-    else:
-      rp = getattr(self, "_replay", None)
-      # (replay: the C entry points take the step's users from the cursor; the pointer is a placeholder)
-      users = blk.users[row_off:row_off + B] if rp is None else rp["users_t"]
-      z = self._mf_forward(users, B, keep_drop, True, stream)
+    tied = self.kind == "ae" and bool(m.is_constrained)
     # single process: nothing has to exist as an array of its own for an exchange, so the small
     # reductions of the step ride on its Adam launch as they do in rk_ae_train_step -- the loss
     # partials, the decode epilogue's row-tile column sums (decoder bias gradient) and the K slabs
     # of the bf16-pipe dW (three launches less)
-    tied = self.kind == "ae" and bool(m.is_constrained)
     lazy = ip is None and self.allreduce is None
-    # (dW will work in ws_dw with its K slabs kept for the Adam sweep: see keep_slabs below)
-    zt_ws = self.ws_dw if (lazy and not tied and self.split16 and self.ws_dw is not None and
-                           True) else None
+    path = self._decode_path(B, tb, row_off, tb is blk, tied, lazy)
+    # dW works in ws_dw and keeps its K slabs there for the Adam sweep; the decode's operand split
+    # writes Z^T as its planes at that workspace's head where the path has a Z^T plane image
+    keep_slabs = lazy and not tied and self.split16
+    zt = keep_slabs and path in (Decode.DZ_PLANES, Decode.PLANES) and bool(lib.rk_split_zt_ok())
+    # (the plane kernels decode this block: its W_de[items] split can ride on the encoder forward)
+    split_w = self.kind == "ae" and tgt is None and not tied and path is not Decode.PLAIN
+    if self.kind == "ae":
+      z = self._ae_forward(blk, row_off, B, keep_noise, keep_drop, True, stream,
+                           split_w=(self.planes_nowt if path.image else self.planes) if split_w else None)
+    else:
+      # (replay: the C entry points take the step's users from the cursor; the pointer is a placeholder)
+      users = blk.users[row_off:row_off + B] if replay is None else replay["users_t"]
+      z = self._mf_forward(users, B, keep_drop, True, stream)
     # data parallel + graph replay: the rank's share of the loss goes to a scalar of its own, travels with
     # the gradients, and the step's Adam launch files the sum under the step's slot of `out` (the epoch's
     # loss buffer) and publishes the next cursor -- as the one-call step does (_c_train_step)
-    dp_replay = self.allreduce is not None and getattr(self, "_replay", None) is not None and ip is None
-    loss = self._loss(z, B, tb, row_off, rows, stream, self.loss_dp if dp_replay else out, ip=ip, defer=lazy,
-                      fuse_dz=True, zt_ws=zt_ws,
-                      pg_ok=lazy and not tied and self.ws_dw is not None,
-                      # (users-DP too: dW then leaves ONE dense array for the exchange -- rk_pg_dw_dz_reduce dense)
-                      fdec_ok=ip is None and not tied and self.ws_dw is not None, own_block=tb is blk)
-    self._loss_target = loss
+    dp_replay = self.allreduce is not None and replay is not None and ip is None
+    loss = self.loss_dp if dp_replay else (self.loss_out if out is None else out)
+    n_part = self._decode(z, B, tb, row_off, rows, stream, ip=ip, path=path,
+                          zt_ws=self.ws_dw if zt else None, w_done=split_w)
+    pending = None
+    if lazy:         # (summed by the step's Adam launch, see _flush_jobs)
+      pending = (self.loss_part, n_part, float(rows), loss)
+    else:
+      check(lib.rk_loss_reduce(ptr(self.loss_part), n_part, float(rows), ptr(loss), stream), "rk_loss_reduce")
 
     # ---- dW = dO^T . z  (+ decoder bias gradient) ----
-    keep_slabs = lazy and not tied and self.split16 and self.ws_dw is not None
-    # replayed steps: dW (it needs dO and z only) as a branch on the stepper's side stream next to
-    # dZ -> hidden stacks -> encoder backward, joined in front of the Adam sweeps -- as the one-call
-    # step does (rk_ae_step_t.dw_stream); its K slabs live in a workspace of their own
-    rp = getattr(self, "_replay", None)
-    # (off by default: with a dozen more launches on the chain the two cross-queue edges cost more
-    # than the overlap buys -- C3 0.307 vs 0.300 ms, C4 0.150 vs 0.147 ms per step; RK_DW_BRANCH_ENTRY=1)
-    dw_side = rp.get("dw_stream") if (rp is not None and keep_slabs and self.dw_branch and
-                                      False) else None
-    dw_stream = stream
-    if dw_side is not None:
-      if getattr(self, "_dw_ev", None) is None:
-        self._dw_ev = (torch.cuda.Event(), torch.cuda.Event())
-      self._dw_ev[0].record(main_s)
-      dw_side.wait_event(self._dw_ev[0])
-      dw_stream = ctypes.c_void_p(dw_side.cuda_stream)
+    dw_rows, gb = Rows.DENSE, Bias.DENSE
+    # dO from rk_mnll_finish: its column sums (the decoder bias gradient) need a pass over dO
+    mnll_colsum = self.loss_id == LOSS_MNLL and not path.image
     # dW (it needs dO and z only) can wait for the encoder backward and share its launch
-    # (rk_decode_bwd_dw2_encode_bwd: one launch less on the chain) when both work on ONE block, the K
-    # slabs stay in the dW workspace for the Adam sweep and no side stream is in play
-    defer_dw = (keep_slabs and dw_side is None and self.kind == "ae" and tb is blk and
-                True and
+    # (rk_decode_bwd_dw2_encode_bwd: one launch less on the chain) when both work on ONE block and the K
+    # slabs stay in the dW workspace for the Adam sweep
+    defer_dw = (keep_slabs and self.kind == "ae" and tb is blk and
                 bool(lib.rk_dw_encode_bwd_fused_ok(row_off, B)))
-    self._dw_deferred = None
-    self._dw_colsum = False
+    dz_done = False                    # the dZ slab reduce rode on the dW launch
     if defer_dw:
-      if self.loss_id == LOSS_MNLL and not self._dz_pg:
-        # (dO comes from rk_mnll_finish: its column sums -- the decoder bias gradient -- are taken by
-        # extra workgroups of the dW || encoder-backward launch)
-        self._dw_colsum = True
-      elif getattr(self, "_dz_fdec", False):
-        pass                     # (the fused decode has no column sums to give: the deferred launch takes them from the image)
-      elif lazy:
-        self._gb_lazy = (cdiv(B, self.row_tile), tb)
-      else:
-        check(lib.rk_colsum(ptr(self.gb_part), cdiv(B, self.row_tile), tb.n_cap, 0, ptr(tb.counts),
-                            ptr(self.gb_de), stream), "rk_colsum")
-      self._dw_deferred = z
-    elif self.loss_id == LOSS_MNLL and not self._dz_pg:
-      # dO was produced by rk_mnll_finish: column sums need a pass over dO
-      self._dw(z, B, tb, self.gb_de, dw_stream, keep_slabs)
-    elif getattr(self, "_dz_fdec", False):
+      # (mnll_colsum: extra workgroups of the deferred launch take the column sums; the fused decode has
+      # none to give: that launch takes them from the image)
+      if not mnll_colsum and path is not Decode.FDEC:
+        gb = Bias.TILES
+    elif mnll_colsum:
+      dw_rows = self._dw(z, B, tb, self.gb_de, stream, keep_slabs, path, zt)
+    elif path is Decode.FDEC:
       # the fused decode leaves no column sums: the dW launch takes the bias gradient from the image's columns
       # -- and, MatrixFactorization (nothing before the Adam sweep reads dZ), the slab reduce as a third range
       zact = None if self.drop_active else self.enc[0]
@@ -819,29 +786,20 @@ class FusedEngine:
                                    ptr(zact), self.act, ptr(self.dbott), 0 if keep_slabs else 1, stream),
             "rk_pg_dw_dz_reduce")
       # (single process: the K slabs stay in ws_dw for the Adam sweep to add up; users-DP: one dense G_de)
-      self._dw_slabs = (tb, B) if keep_slabs else None
-      self._ws_dw_live = bool(keep_slabs)
-      self._pg_step = bool(keep_slabs)
-      self._dz_done = True
+      dw_rows = Rows.PG if keep_slabs else Rows.DENSE
+      dz_done = True
     else:
       # the loss epilogue already reduced dO per row tile: sum those few rows
       if lazy:
-        self._gb_lazy = (cdiv(B, self.row_tile), tb)
+        gb = Bias.TILES
       else:
         check(lib.rk_colsum(ptr(self.gb_part), cdiv(B, self.row_tile), tb.n_cap, 0, ptr(tb.counts),
                             ptr(self.gb_de), stream), "rk_colsum")
       # MatrixFactorization: nothing between the decode and the Adam sweep reads dZ (the user rows'
       # gradient), so the reduce of the decode launch's dZ partials rides on the dW launch
-      red = None
-      if (self.kind != "ae" and getattr(self, "_dz_in_ws", False) and keep_slabs and dw_side is None and
-          ip is None and self.lib.rk_dw_pairs()):
-        red = (self.ws, None if self.drop_active else self.enc[0], self.dbott)
-      self._dw(z, B, tb, None, dw_stream, keep_slabs, red=red)
-      if red is not None:
-        self._dz_in_ws = False
-        self._dz_done = True
-    if dw_side is not None:
-      self._dw_ev[1].record(dw_side)
+      dz_done = (self.kind != "ae" and path is Decode.DZ_PLANES and keep_slabs and bool(self.lib.rk_dw_pairs()))
+      red = (self.ws, None if self.drop_active else self.enc[0], self.dbott) if dz_done else None
+      dw_rows = self._dw(z, B, tb, None, stream, keep_slabs, path, zt, red=red)
     # (replayed: a captured collective has a fixed size -- the exchange covers the block's capacity, rows past
     # n_b are never read by the update -- and nothing of the step is read on the host)
     n_b_host = None if self.allreduce is None else (blk.n_cap if dp_replay else self.allreduce.n_b(blk))
@@ -861,26 +819,23 @@ class FusedEngine:
     # PRODUCER of the gradient it applies to -- the dZ reduce for the decoder's last hidden output, each
     # layer's dX epilogue for its input activation -- so a layer's backward is ONE launch (dX, dW and
     # the bias gradient's column sums: rk_linear_bwd_pre) instead of an act' pass + the products
-    stack_pre = (self.kind == "ae" and self.nl > 0 and not self.drop_active and ip is None and
-                 True)
+    stack_pre = self.kind == "ae" and self.nl > 0 and not self.drop_active and ip is None
     zact = self.enc[0] if fuse_act else (self.dec[self.nl - 1] if stack_pre else None)
-    if getattr(self, "_dz_done", False):
-      self._dz_done = False            # (summed by the dW launch: rk_decode_bwd_dw2_dz_reduce)
-    elif getattr(self, "_dz_in_ws", False):
+    if dz_done:
+      pass
+    elif path is Decode.DZ_PLANES:
       check(lib.rk_decode_dz_reduce(ptr(self.ws), B, h0, tb.ref, ptr(zact),
                                     self.act, ptr(dz), stream), "rk_decode_dz_reduce")
-      self._dz_in_ws = False
-    elif getattr(self, "_dz_fdec", False):
+    elif path is Decode.FDEC:
       check(lib.rk_fdec_dz_reduce(ptr(self.ws), B, h0, tb.ref, ptr(zact), self.act, ptr(dz), stream),
             "rk_fdec_dz_reduce")
-    elif getattr(self, "_dz_pg", False):
+    elif path is Decode.PG:
       check(lib.rk_pg_dz(ptr(self.dO), ptr(self.do_scales), 64, 32, B, ctypes.byref(self.planes), tb.ref,
                          ptr(zact), self.act, ptr(dz), ptr(self.ws), stream), "rk_pg_dz")
-    elif getattr(self, "_dz_on_planes", False):
+    elif path is Decode.PLANES:
       check(lib.rk_decode_bwd_dz_planes(ptr(self.dO), B, ctypes.byref(self.planes), tb.ref,
                                         ptr(zact), self.act, ptr(dz),
                                         ptr(self.ws), stream), "rk_decode_bwd_dz_planes")
-      self._dz_on_planes = False
     else:
       check(lib.rk_decode_bwd_dz(ptr(self.dO), B, h0, tb.ref, ptr(W_de),
                                  ptr(zact), self.act, ptr(dz),
@@ -944,31 +899,27 @@ class FusedEngine:
         check(lib.rk_act_grad(ptr(self.denc[0]), ptr(self.enc[0]), B * h0, self.act, stream),
               "rk_act_grad")
       G_en = self.G_de if tied else self.G_en      # tied: accumulates on top of dW's rows
-      if getattr(self, "_dw_deferred", None) is not None:
-        zz, self._dw_deferred = self._dw_deferred, None
-        zt = ptr(self.ws_dw) if getattr(self, "_zt_ready", None) == self.ws_dw.data_ptr() else None
-        if getattr(self, "_dz_fdec", False):
+      if defer_dw:
+        zt_ws = ptr(self.ws_dw) if zt else None
+        if path is Decode.FDEC:
           # (the fused decode's image: granule 32 x 64; its columns' sums = the decoder bias gradient ride along)
           check(lib.rk_pg_dw_encode_bwd(ptr(self.dO), ptr(self.do_scales), 32, 64, B, ctypes.byref(self.planes),
                                         blk.ref, ptr(self.ws_dw), row_off, ptr(self.denc[0]), ptr(G_en),
                                         ptr(self.gb_en), ptr(self.gb_de), stream), "rk_pg_dw_encode_bwd")
-          self._pg_step = True
-        elif getattr(self, "_dz_pg", False):
+        elif path is Decode.PG:
           check(lib.rk_pg_dw_encode_bwd(ptr(self.dO), ptr(self.do_scales), 64, 32, B, ctypes.byref(self.planes),
                                         blk.ref, ptr(self.ws_dw), row_off, ptr(self.denc[0]), ptr(G_en),
                                         ptr(self.gb_en), None, stream), "rk_pg_dw_encode_bwd")
-          self._pg_step = True
-        elif self._dw_colsum:
-          check(lib.rk_decode_bwd_dw2_encode_bwd_colsum(ptr(self.dO), ptr(zz), B, h0, blk.ref, ptr(self.ws_dw),
-                                                        zt, ptr(self.ranges), row_off, ptr(self.denc[0]),
+        elif mnll_colsum:
+          check(lib.rk_decode_bwd_dw2_encode_bwd_colsum(ptr(self.dO), ptr(z), B, h0, blk.ref, ptr(self.ws_dw),
+                                                        zt_ws, ptr(self.ranges), row_off, ptr(self.denc[0]),
                                                         ptr(G_en), ptr(self.gb_en), ptr(self.gb_de), stream),
                 "rk_decode_bwd_dw2_encode_bwd_colsum")
         else:
-          check(lib.rk_decode_bwd_dw2_encode_bwd(ptr(self.dO), ptr(zz), B, h0, blk.ref, ptr(self.ws_dw), zt,
+          check(lib.rk_decode_bwd_dw2_encode_bwd(ptr(self.dO), ptr(z), B, h0, blk.ref, ptr(self.ws_dw), zt_ws,
                                                  ptr(self.ranges), row_off, ptr(self.denc[0]), ptr(G_en),
                                                  ptr(self.gb_en), stream), "rk_decode_bwd_dw2_encode_bwd")
-        self._dw_slabs = (blk, B)
-        self._ws_dw_live = True
+        dw_rows = Rows.PG if path.image else Rows.DW3
       else:
         check(lib.rk_ae_encode_bwd(blk.ref, row_off, B, ptr(self.denc[0]), h0, ptr(G_en),
                                    1 if tied else 0, ptr(self.gb_en), stream), "rk_ae_encode_bwd")
@@ -980,6 +931,7 @@ class FusedEngine:
                              self.seed ^ 0xd0d0, self.rng_step, stream), "rk_dropout")
       if not fuse_act:
         check(lib.rk_act_grad(ptr(self.dbott), ptr(self.enc[0]), n, self.act, stream), "rk_act_grad")
+    self.grads = GradLayout(tb, B, loss, dw_rows, gb, decode=path)
 
     if self.allreduce is not None:
       # data parallel over users: every gradient of the step (live rows of both tables, gathered
@@ -990,13 +942,11 @@ class FusedEngine:
       if getattr(self, "owned_rows", False):
         self._owned_exchange(blk, n_b_host)
       else:
-        self.allreduce.reduce(self.grad_views(n_b_host, "all"))
+        self.allreduce.reduce(self.grad_views(n_b_host))
       if dp_replay:
-        self._pending_loss = (1, 1.0, out, self.loss_dp)
+        pending = (self.loss_dp, 1, 1.0, out)
         loss = out
-    if dw_side is not None:
-      main_s.wait_event(self._dw_ev[1])
-    self._apply_updates(blk, row_off, B, stream, "all", tgt=tb)
+    self._apply_updates(blk, row_off, B, stream, replay, pending, tgt=tb)
     if getattr(self, "_own", None) is not None:
       self._owned_publish(blk)
     return loss
@@ -1028,7 +978,7 @@ class FusedEngine:
     lo = offs[dp.rank]
     self._own = dict(offs=offs, tabs=tabs, lo=lo, cnt=offs[dp.rank + 1] - lo, n_b=n_b,
                      cnt_dev=torch.tensor([offs[dp.rank + 1] - lo], dtype=torch.int32, device=self.device))
-    rest = [v for v in self.grad_views(n_b, "all") if not (v.data_ptr() in own_g and v.numel() == n_b * h0)]
+    rest = [v for v in self.grad_views(n_b) if not (v.data_ptr() in own_g and v.numel() == n_b * h0)]
     dp.reduce(rest)
 
   def _owned_publish(self, blk):
@@ -1046,46 +996,42 @@ class FusedEngine:
     # rows it wrote -- MAX over the ranks of the 64 slots (non-negative fp32 bit patterns order as ints)
     dp.union_marks(self.ranges[64:])
 
-  def _dw(self, z, B, blk, gb_de, stream, keep_slabs=False, red=None):
+  def _dw(self, z, B, blk, gb_de, stream, keep_slabs, path, zt, red=None):
     """G_de = dO^T . z (+ gb_de = colsum(dO) if asked): the bf16-pipe kernel (csrc/dw3.hip) unless
     RK_GEMM_PREC=f32 keeps the contractions on the fp32 MFMA.  keep_slabs: leave the K slabs
     unsummed in the dW workspace of its own (the dZ product that follows reuses `ws`) for the Adam
-    sweep to add up."""
+    sweep to add up.  zt: the step's decode wrote the Z^T pair planes at the head of that workspace.
+    Returns where the rows went (Rows)."""
     h0 = self.h[0]
-    self._dw_slabs = None
-    self._ws_dw_live = False
-    if self.split16:
-      # fp16 pairs (rk_decode_bwd_dw2: three products, the scale of z from self.ranges -- the bound
-      # rk_amax left there for this z when the activation is unbounded) unless RK_DW_PREC=bf16x3
-      G, ws = (None, self.ws_dw) if keep_slabs else (self.G_de, self.ws)
-      if getattr(self, "_dz_in_ws", False):
-        ws = self.ws_dw                  # (self.ws holds the decode launch's dZ partials until the reduce)
-      if getattr(self, "_dz_pg", False):
-        assert keep_slabs and gb_de is None and red is None
-        check(self.lib.rk_pg_dw(ptr(self.dO), ptr(self.do_scales), 64, 32, B, ctypes.byref(self.planes), blk.ref,
-                                ptr(ws), None, stream), "rk_pg_dw")
-        self._pg_step = True
-      elif self.lib.rk_dw_pairs():
-        # (Z^T pair planes already at the head of this workspace: rk_split_wz of this step's decode)
-        zt = ptr(ws) if getattr(self, "_zt_ready", None) == ws.data_ptr() else None
-        if red is not None:
-          # red = (the decode launch's dZ partials, Zact or None, dZ): summed by extra workgroups here
-          assert G is None and gb_de is None
-          check(self.lib.rk_decode_bwd_dw2_dz_reduce(ptr(self.dO), ptr(z), B, h0, blk.ref, ptr(ws), zt,
-                                                     ptr(self.ranges), ptr(red[0]), ptr(red[1]), self.act,
-                                                     ptr(red[2]), stream), "rk_decode_bwd_dw2_dz_reduce")
-        else:
-          check(self.lib.rk_decode_bwd_dw2(ptr(self.dO), ptr(z), B, h0, blk.ref, ptr(G), ptr(gb_de), ptr(ws),
-                                           zt, ptr(self.ranges), stream), "rk_decode_bwd_dw2")
-      else:
-        check(self.lib.rk_decode_bwd_dw3(ptr(self.dO), ptr(z), B, h0, blk.ref, ptr(G), ptr(gb_de), ptr(ws),
-                                         None, stream), "rk_decode_bwd_dw3")
-      if keep_slabs:
-        self._dw_slabs = (blk, B)
-        self._ws_dw_live = True
-    else:
+    if not self.split16:
       check(self.lib.rk_decode_bwd_dw(ptr(self.dO), ptr(z), B, h0, blk.ref, ptr(self.G_de), ptr(gb_de),
                                       stream), "rk_decode_bwd_dw")
+      return Rows.DENSE
+    # fp16 pairs (rk_decode_bwd_dw2: three products, the scale of z from self.ranges -- the bound
+    # rk_amax left there for this z when the activation is unbounded) unless RK_DW_PREC=bf16x3
+    G, ws = (None, self.ws_dw) if keep_slabs else (self.G_de, self.ws)
+    if path is Decode.DZ_PLANES:
+      ws = self.ws_dw                  # (self.ws holds the decode launch's dZ partials until the reduce)
+    if path is Decode.PG:
+      assert keep_slabs and gb_de is None and red is None
+      check(self.lib.rk_pg_dw(ptr(self.dO), ptr(self.do_scales), 64, 32, B, ctypes.byref(self.planes), blk.ref,
+                              ptr(ws), None, stream), "rk_pg_dw")
+      return Rows.PG
+    if self.lib.rk_dw_pairs():
+      zt = ptr(ws) if zt else None     # (zt implies keep_slabs: ws is ws_dw)
+      if red is not None:
+        # red = (the decode launch's dZ partials, Zact or None, dZ): summed by extra workgroups here
+        assert G is None and gb_de is None
+        check(self.lib.rk_decode_bwd_dw2_dz_reduce(ptr(self.dO), ptr(z), B, h0, blk.ref, ptr(ws), zt,
+                                                   ptr(self.ranges), ptr(red[0]), ptr(red[1]), self.act,
+                                                   ptr(red[2]), stream), "rk_decode_bwd_dw2_dz_reduce")
+      else:
+        check(self.lib.rk_decode_bwd_dw2(ptr(self.dO), ptr(z), B, h0, blk.ref, ptr(G), ptr(gb_de), ptr(ws),
+                                         zt, ptr(self.ranges), stream), "rk_decode_bwd_dw2")
+    else:
+      check(self.lib.rk_decode_bwd_dw3(ptr(self.dO), ptr(z), B, h0, blk.ref, ptr(G), ptr(gb_de), ptr(ws),
+                                       None, stream), "rk_decode_bwd_dw3")
+    return Rows.DW3 if keep_slabs else Rows.DENSE
 
   def c_step_eligible(self):
     """The one-call step (rk_ae_train_step) covers DynamicAutoencoder([h]) without bottleneck
@@ -1113,7 +1059,6 @@ class FusedEngine:
       self._cstep = st
     if replay is None:
       self.rng_step += 1
-    self._gb_lazy = None
     rows = B if global_rows is None else global_rows
     st.blk = ctypes.pointer(blk.c)
     st.row_off, st.B, st.h, st.act = row_off, B, self.h[0], self.act
@@ -1156,9 +1101,8 @@ class FusedEngine:
     # (whole single-GPU steps) leaves its K slabs in the workspace and runs the plain encoder backward
     dw3 = plain and self.split16 and self.item_parallel is None
     segmented = plain and not dw3
-    self._dw_slabs = (blk, B) if dw3 else None
     st.gb_en = ptr(self.gb_en_parts if segmented else self.gb_en)
-    self._gb_en_segs = self.lib.rk_encode_bwd_segments(B) if segmented else 0
+    en_segs = self.lib.rk_encode_bwd_segments(B) if segmented else 0
     self.n_cap_last = blk.n_cap
     st.loss_part, st.loss_out = ptr(self.loss_part), ptr(loss_dst)
     st.stream = main_s.cuda_stream
@@ -1178,8 +1122,7 @@ class FusedEngine:
       st.lazy_need_list, st.lazy_need_count = lz.get("need") or (None, None)
     if dp is not None and self.ws_dw is not None and not m.is_constrained:
       st.ws_dw = ptr(self.ws_dw)        # (phased steps: dW's own workspace lets the decode launch keep its dZ slabs)
-    self._ws_dw_live = False
-    if dw3 and self.ws_dw is not None:
+    if dw3:
       if self._dw_objs is None:
         raw0 = _lib.load()
         self._dw_objs = (torch.cuda.Stream(device=self.device), raw0.rk_event_create(0), raw0.rk_event_create(0))
@@ -1187,14 +1130,12 @@ class FusedEngine:
       dws = replay.get("dw_stream") if replay is not None else None
       st.ws_dw, st.dw_stream = ptr(self.ws_dw), (dws or self._dw_objs[0]).cuda_stream
       st.dw_fork, st.dw_join = self._dw_objs[1], self._dw_objs[2]
-      self._ws_dw_live = True
     if replay is not None:
       st.cursor, st.cursor_off, st.adam_table = replay["cursor"], replay["off"], replay["table"]
       if replay.get("next") is not None:         # last step of a group: publish the next cursor
         st.cursor_next, st.cursor_advance = replay["next"]
       st.users = replay["users"]             # base of the epoch's user order (offset on the device)
     self._c_calls += 1
-    self._pg_step = False
     name = None
     if self.time_plan is not None and (replay is None or replay.get("timed")):
       name = self.time_plan(replay["index"] if replay is not None else self._c_calls)
@@ -1218,6 +1159,7 @@ class FusedEngine:
     else:
       st.time_entry = 0
     ip = self.item_parallel
+    dw_rows, gb = (Rows.DW3 if dw3 else Rows.DENSE), Bias.DENSE
     if ip is not None:
       # item parallel (parallel.ItemParallel): the block holds every user of the global
       # batch restricted to this rank's items; two [B, h] all-reduces per step.  `out` gets
@@ -1235,19 +1177,20 @@ class FusedEngine:
       st.phase = STEP_IP_TAIL
       check(raw.rk_ae_train_step(ctypes.byref(st)), "rk_ae_train_step")
       if self.loss_id != LOSS_MNLL:
-        self._gb_lazy = (cdiv(B, self.row_tile), blk)
+        gb = Bias.TILES
     elif dp is None:
       st.phase = STEP_ALL
       flags = int(raw.rk_ae_step_uses_pg(ctypes.byref(st)))
       mode = flags & 15
       self._step_flags = flags     # (bit 4: the bias gradient as output column h of the dW tiles -- recoder_hip.h)
-      self._pg_step = bool(mode)
+      if dw3 and mode:
+        dw_rows = Rows.PG
       self._step_mode = mode       # (0: decode16 / dw3 kernels, 1: csrc/pgemm.h, 3: csrc/fdecode.hip + pgemm's dW; bench.py names the kernels by it)
       check(raw.rk_ae_train_step(ctypes.byref(st)), "rk_ae_train_step")
       if self.loss_id != LOSS_MNLL and mode != 3:
-        self._gb_lazy = (cdiv(B, self.row_tile), blk)    # (mode 3: gb_de itself, from the dO image)
+        gb = Bias.TILES                  # (mode 3: gb_de itself, from the dO image)
       elif flags & 16:
-        self._gb_lazy = ("slabs", blk)                   # (... or one slab per K slab of dW in gb_part)
+        gb = Bias.SLABS                  # (... or one slab per K slab of dW in gb_part)
     else:
       # data parallel over users: forward + whole backward locally, then the live gradient rows
       # of both tables, the gathered-bias gradient, the encoder bias gradient and the loss go out
@@ -1339,7 +1282,7 @@ class FusedEngine:
       if zero is not None:
         names_ = ["en_embedding_layer.weight"] + ([] if tied else ["de_embedding_layer.weight"])
         dp.zero_publish([S[n_].p.data for n_ in names_], h0, extra_max=self.ranges[64:])
-    self._loss_target = out
+    self.grads = GradLayout(blk, B, out, dw_rows, gb, en_segs)
     return out
 
   def _zero_grad_tails(self, blk, arrays, stream):
@@ -1400,36 +1343,32 @@ class FusedEngine:
   def decoder_bias_grad(self, n_b):
     """gb_de[:n_b] of the last training step (tests).  The one-call step consumes the
     decode epilogue's row-tile partials directly and never materialises gb_de."""
-    if self._gb_lazy is None:
+    g = self.grads
+    if g.bias is Bias.DENSE:
       return self.gb_de[:n_b].clone()
-    tiles, blk = self._gb_lazy
-    if tiles == "slabs":
-      ns = int(blk.counts[4].item())
-      return sum(self.gb_part[k * blk.n_cap:k * blk.n_cap + n_b] for k in range(ns))
-    ld = blk.counts_host()[2]
+    if g.bias is Bias.SLABS:
+      ns = int(g.blk.counts[4].item())
+      return sum(self.gb_part[k * g.blk.n_cap:k * g.blk.n_cap + n_b] for k in range(ns))
+    tiles, ld = cdiv(g.B, self.row_tile), g.blk.counts_host()[2]
     return self.gb_part[:tiles * ld].view(tiles, ld)[:, :n_b].sum(0)
 
   def decoder_row_grad(self, n_b):
     """G_de[:n_b] of the last training step (tests): the one-call step leaves it as K slabs in the
     workspace (summed by rk_adam_multi while it reads the gradient)."""
-    h0 = self.h[0]
-    if self._dw_slabs is None:
+    g, h0 = self.grads, self.h[0]
+    if g.rows is Rows.DENSE:
       return self.G_de[:n_b * h0].view(n_b, h0).clone()
-    blk, B = self._dw_slabs
-    ws = self.ws_dw if getattr(self, "_ws_dw_live", False) else self.ws
-    if getattr(self, "_pg_step", False):           # rk_pg_dw: the slabs start at the workspace's head
-      ns, off = int(blk.counts[4].item()), 0
-      stride = blk.n_cap * h0
-      return sum(ws[off + k * stride:off + k * stride + n_b * h0].view(n_b, h0) for k in range(ns))
-    ns = int(blk.counts[4].item())
-    off = (self.lib.rk_dw3_slabs(ptr(ws), B, h0) - ws.data_ptr()) // 4
-    stride = blk.n_cap * h0
+    ws = self.ws_dw
+    ns = int(g.blk.counts[4].item())
+    # (rk_pg_dw: the slabs start at the workspace's head)
+    off = 0 if g.rows is Rows.PG else (self.lib.rk_dw3_slabs(ptr(ws), g.B, h0) - ws.data_ptr()) // 4
+    stride = g.blk.n_cap * h0
     return sum(ws[off + k * stride:off + k * stride + n_b * h0].view(n_b, h0) for k in range(ns))
 
   def encoder_bias_grad(self):
     """gb_en of the last training step (tests): the one-call step leaves it as row-segment
     partial vectors for rk_adam_multi."""
-    n, h0 = getattr(self, "_gb_en_segs", 0), self.h[0]
+    n, h0 = self.grads.en_segs, self.h[0]
     if not n:
       return self.gb_en.clone()
     return self.gb_en_parts[:n * h0].view(n, h0).sum(0)
@@ -1437,7 +1376,7 @@ class FusedEngine:
   def encoder_row_grad(self, n_b):
     """G_en[:n_b] of the last training step (tests): the one-call step leaves it as
     row-segment partial arrays for rk_adam_multi when the batch has more than 512 rows."""
-    n, h0 = getattr(self, "_gb_en_segs", 0), self.h[0]
+    n, h0 = self.grads.en_segs, self.h[0]
     if n <= 1:
       return self.G_en[:n_b * h0].view(n_b, h0).clone()
     stride = self.n_cap_last * h0
@@ -1476,38 +1415,39 @@ class FusedEngine:
     return out
 
   # ------------------------------------------------------- data parallelism
-  def grad_views(self, n_b, part="all"):
+  def grad_views(self, n_b):
     """Views of everything a data-parallel step must SUM over the ranks: the
     live n_b gradient rows, the gathered-bias gradient, the dense gradients and
-    the (already 1/(N*B)-scaled) loss.  'decoder' = what the dW chain produces,
-    'encoder' = the rest.  MF user-row gradients are rank-private (each user
-    lives on one rank) and are not reduced."""
+    the (already 1/(N*B)-scaled) loss.  MF user-row gradients are rank-private
+    (each user lives on one rank) and are not reduced."""
     h0 = self.h[0]
     tied = self.kind == "ae" and bool(self.model.is_constrained)
-    dec = [self.gb_de[:n_b], self._loss_target]
+    out = [self.gb_de[:n_b], self.grads.loss]
     if not tied:
-      dec.append(self.G_de[:n_b * h0])
-    enc = []
+      out.append(self.G_de[:n_b * h0])
     if self.kind == "ae":
-      m = self.model
-      enc.append(self.G_de[:n_b * h0] if tied else self.G_en[:n_b * h0])
-      enc.append(self.gb_en)
-      enc += self.g_enc_w + self.g_enc_b + [g for g in self.g_dec_w if g is not None] + self.g_dec_b
-    return dec if part == "decoder" else enc if part == "encoder" else dec + enc
+      out.append(self.G_de[:n_b * h0] if tied else self.G_en[:n_b * h0])
+      out.append(self.gb_en)
+      out += self.g_enc_w + self.g_enc_b + [g for g in self.g_dec_w if g is not None] + self.g_dec_b
+    return out
 
   # ---------------------------------------------------------------- updates
-  def _apply_updates(self, blk, row_off, B, stream, part="all", tgt=None):
-    """part: 'decoder' = the decoder / item table and its gathered bias (their
-    gradients come from the dW chain), 'encoder' = everything else, 'all'.  tgt: the block whose
-    item set the decoder-side gradient rows are indexed by (default: blk)."""
+  def _apply_updates(self, blk, row_off, B, stream, rp, loss, tgt=None):
+    """The Adam updates of an entry-by-entry step, from the gradients where self.grads says they are.
+    rp: the replay context (None: eager); loss: the deferred reduction of the step's loss
+    (_flush_jobs); tgt: the block whose item set the decoder-side gradient rows are indexed by
+    (default: blk)."""
     m, S = self.model, self.states
     h0 = self.h[0]
     n_items = blk.n_items
     tb = blk if tgt is None else tgt
-    dec = part in ("all", "decoder")
-    enc = part in ("all", "encoder")
-
     own = getattr(self, "_own", None)
+
+    def job(name, G, pos, n_rows, h, parts=None):
+      self._job(S[name], n_rows, h, G, rp, pos=pos, parts=parts)
+
+    def dense(name, g):
+      job(name, g, None, 1, S[name].p.numel())
 
     def table(name, G, b=None, parts=None):
       b = blk if b is None else b
@@ -1517,73 +1457,59 @@ class FusedEngine:
         # of the world partial arrays the exchange left in R
         R = own["tabs"][name]
         cnt = own["cnt"]
-        self._adam_rows(s, b.items[own["lo"]:], None, own["cnt_dev"], max(cnt, 1), R, h0, stream,
+        self._adam_rows(s, b.items[own["lo"]:], None, own["cnt_dev"], max(cnt, 1), R, h0, stream, rp,
                         parts=(ptr(R), self.allreduce.world, max(cnt, 1) * h0, None, None))
       elif s.sparse:
-        self._adam_rows(s, b.items, None, b.counts, b.n_cap, G, h0, stream, parts=parts)
+        self._adam_rows(s, b.items, None, b.counts, b.n_cap, G, h0, stream, rp, parts=parts)
       else:
-        self._adam_table(s, b.pos, G, h0, n_items, stream, parts=parts)
+        job(name, G, b.pos, n_items, h0, parts)
 
-    # gradients the step left as partial arrays (train_step, single process)
+    # gradients the step left as partial arrays (single process)
+    g = self.grads
     dw_parts = gb_parts = None
-    if dec and self._dw_slabs is not None and self._dw_slabs[0] is tb:
-      ws = self.ws_dw if self._ws_dw_live else self.ws
-      if getattr(self, "_pg_step", False):
-        dw_parts = (ptr(ws), self.lib.rk_pg_dw_splits(self._dw_slabs[1], h0, tb.n_cap), tb.n_cap * h0, None,
-                    tb.counts.data_ptr() + 4 * 4)
-      else:
-        dw_parts = (self.lib.rk_dw3_slabs(ptr(ws), self._dw_slabs[1], h0), self.lib.rk_dw3_max_splits(),
-                    tb.n_cap * h0, None, tb.counts.data_ptr() + 4 * 4)
-    if dec and self._gb_lazy is not None and self._gb_lazy[1] is tb:
-      gb_parts = (ptr(self.gb_part), self._gb_lazy[0], 0, tb.counts.data_ptr() + 2 * 4, None)
+    if g.rows is Rows.PG:
+      dw_parts = (ptr(self.ws_dw), self.lib.rk_pg_dw_splits(g.B, h0, tb.n_cap), tb.n_cap * h0, None,
+                  tb.counts.data_ptr() + 4 * 4)
+    elif g.rows is Rows.DW3:
+      dw_parts = (self.lib.rk_dw3_slabs(ptr(self.ws_dw), g.B, h0), self.lib.rk_dw3_max_splits(),
+                  tb.n_cap * h0, None, tb.counts.data_ptr() + 4 * 4)
+    if g.bias is Bias.TILES:
+      gb_parts = (ptr(self.gb_part), cdiv(g.B, self.row_tile), 0, tb.counts.data_ptr() + 2 * 4, None)
 
     if self.kind == "ae":
-      en_w = "en_embedding_layer.weight"
       if m.is_constrained:
-        if enc:
-          table(en_w, self.G_de)          # tied table: G_de holds dW + encoder rows
+        table("en_embedding_layer.weight", self.G_de)          # tied table: G_de holds dW + encoder rows
       else:
-        if enc:
-          table(en_w, self.G_en)
-        if dec:
-          table("de_embedding_layer.weight", self.G_de, tb, dw_parts)
-      if enc:
-        self._adam_dense(S["_DynamicAutoencoder__en_linear_embedding_layer.bias"], self.gb_en, stream)
-        for i in range(self.nl):
-          self._adam_dense(S["encoding_layers.%d.weight" % i], self.g_enc_w[i], stream)
-          self._adam_dense(S["encoding_layers.%d.bias" % i], self.g_enc_b[i], stream)
-          if not m.is_constrained:
-            self._adam_dense(S["decoding_layers.%d.weight" % i], self.g_dec_w[i], stream)
-          self._adam_dense(S["decoding_layers.%d.bias" % i], self.g_dec_b[i], stream)
-      if dec:
-        # decoder bias: a dense [n_items] gradient (index_select backward), wd = 0
-        self._adam_table(S["_DynamicAutoencoder__de_linear_embedding_layer.bias"], tb.pos,
-                         self.gb_de, 1, n_items, stream, parts=gb_parts)
+        table("en_embedding_layer.weight", self.G_en)
+        table("de_embedding_layer.weight", self.G_de, tb, dw_parts)
+      dense("_DynamicAutoencoder__en_linear_embedding_layer.bias", self.gb_en)
+      for i in range(self.nl):
+        dense("encoding_layers.%d.weight" % i, self.g_enc_w[i])
+        dense("encoding_layers.%d.bias" % i, self.g_enc_b[i])
+        if not m.is_constrained:
+          dense("decoding_layers.%d.weight" % i, self.g_dec_w[i])
+        dense("decoding_layers.%d.bias" % i, self.g_dec_b[i])
+      # decoder bias: a dense [n_items] gradient (index_select backward), wd = 0
+      job("_DynamicAutoencoder__de_linear_embedding_layer.bias", self.gb_de, tb.pos, n_items, 1, gb_parts)
+      self._flush_jobs(stream, loss)
+      return
+    lib = self.lib
+    users = blk.users[row_off:row_off + B] if rp is None else rp["users_t"]
+    su = S["user_embedding_layer.weight"]
+    if su.sparse and getattr(self, "_users32", None) is not None:
+      # (the forward's gather left the users as int32 rows + count: a job of the one Adam launch)
+      u32 = self._users32
+      self._adam_rows(su, u32[1:], None, u32[:1], B, self.dbott, h0, stream, rp)
+    elif su.sparse:
+      self._adam_rows(su, None, users, None, B, self.dbott, h0, stream, rp)
     else:
-      lib = self.lib
-      if enc:
-        rp = getattr(self, "_replay", None)
-        users = blk.users[row_off:row_off + B] if rp is None else rp["users_t"]
-        su = S["user_embedding_layer.weight"]
-        if su.sparse and getattr(self, "_users32", None) is not None:
-          # (the forward's gather left the users as int32 rows + count: a job of the one Adam launch)
-          u32 = self._users32
-          self._adam_rows(su, u32[1:], None, u32[:1], B, self.dbott, h0, stream)
-        elif su.sparse:
-          self._adam_rows(su, None, users, None, B, self.dbott, h0, stream)
-        else:
-          check(lib.rk_scatter_pos(ptr(self.pos_u), ptr(users), B, 0, stream), "rk_scatter_pos")
-          self._adam_table(su, self.pos_u, self.dbott, h0, m.num_users, stream)
-          if dec:
-            table("item_embedding_layer.weight", self.G_de, tb, dw_parts)
-            self._adam_table(S["bias"], tb.pos, self.gb_de, 1, n_items, stream, parts=gb_parts)
-            dec = False
-          self._flush_jobs(stream)       # before the user-row map is cleared again
-          check(lib.rk_scatter_pos(ptr(self.pos_u), ptr(users), B, 1, stream), "rk_scatter_pos")
-      if dec:
-        table("item_embedding_layer.weight", self.G_de, tb, dw_parts)
-        self._adam_table(S["bias"], tb.pos, self.gb_de, 1, n_items, stream, parts=gb_parts)
-    self._flush_jobs(stream)
+      check(lib.rk_scatter_pos(ptr(self.pos_u), ptr(users), B, 0, stream), "rk_scatter_pos")
+      job("user_embedding_layer.weight", self.dbott, self.pos_u, m.num_users, h0)
+    table("item_embedding_layer.weight", self.G_de, tb, dw_parts)
+    job("bias", self.gb_de, tb.pos, n_items, 1, gb_parts)
+    self._flush_jobs(stream, loss)
+    if not su.sparse:
+      check(lib.rk_scatter_pos(ptr(self.pos_u), ptr(users), B, 1, stream), "rk_scatter_pos")   # (the map cleared again)
 
   # ------------------------------------------------------------- inference
   def encode_eval(self, blk, row_off, B):

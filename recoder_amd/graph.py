@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import PAR_B_DE, PAR_B_EN, PAR_W_DE, PAR_W_EN, RkAeStep, check, ptr
+from .engine import Rows
 
 _PAR_NAMES = {PAR_W_EN: "en_embedding_layer.weight",
               PAR_B_EN: "_DynamicAutoencoder__en_linear_embedding_layer.bias",
@@ -243,8 +244,8 @@ class GraphStepper:
     check(lib.rk_event_record(self.ev_fork, self._h(self.main)), "rk_event_record")
     check(lib.rk_stream_wait_event(self._h(self.side), self.ev_fork), "rk_stream_wait_event")
     # ONE side stream carries both kinds of side work, interleaved: the dW kernel of step g (the
-    # engine enqueues it there behind the step's decode, engine.dw_branch) and then the collation of
-    # block g of the next group -- dW(g) is needed by the Adam sweep of step g, the collation only
+    # one-call step enqueues it there behind the step's decode, rk_ae_step_t.dw_stream) and then the
+    # collation of block g of the next group -- dW(g) is needed by the Adam sweep of step g, the collation only
     # at the end of the group, and a third concurrent branch ends up behind one of the others on
     # the same hardware queue.  The order of the branches inside a capture decides which one the
     # graph keeps on the launching stream's queue: with step 0 captured first the training chain
@@ -271,7 +272,7 @@ class GraphStepper:
           # (released by the event the step records behind its decode: the collation's workgroups
           # beside the fused decode + dZ launch doubled it, 26 -> 47 us)
           ev = getattr(self.eng, "_dw_objs", None)
-          if self.c_step and ev is not None and self.eng._ws_dw_live:
+          if self.c_step and ev is not None and self.eng.grads.rows is not Rows.DENSE:
             check(lib.rk_stream_wait_event(self._h(self.side), ev[1]), "rk_stream_wait_event")
           self._collate_many(self.blocks[1 - slot], n_steps, self.side, slot)
           if self.need_lists and n_steps >= 2:

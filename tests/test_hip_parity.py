@@ -470,10 +470,37 @@ def _fuzz_cases(n=20, seed=2024):
 STEP_CASES += _fuzz_cases(40)
 
 
+# the decode families (engine.Decode) the entry-by-entry steps of these cases run on, one case per family: a case
+# that silently moves to another family still meets the tolerances -- this shows that the suite drives every
+# branch of the step's dispatch (RK_GEMM_PREC=f32, test_gemm_precision: all of them on the plain decode)
+DECODE_FAMILIES = {
+  "mf128_mse_sparse": {"FDEC"},
+  "ae128_72_40_constrained": {"DZ_PLANES"},
+  "big_then_ragged_mf16": {"PG", "DZ_PLANES"},
+  "ae64_32_logloss": {"PLANES"},
+}
+
+
+def _expected_decode_families(name):
+  knobs = [os.environ.get(k) for k in ("RK_FDEC", "RK_PG", "RK_GEMM_PREC")]
+  if name not in DECODE_FAMILIES or knobs not in ([None, None, None], [None, None, "f32"]):
+    return None
+  return {"PLAIN"} if knobs[2] == "f32" else DECODE_FAMILIES[name]
+
+
 @pytest.mark.parametrize("name,c,shape,B,S", STEP_CASES, ids=[x[0] for x in STEP_CASES])
-def test_steps_match_oracle(name, c, shape, B, S):
+def test_steps_match_oracle(name, c, shape, B, S, monkeypatch):
   from recoder_amd.data import RecommendationDataset
+  from recoder_amd.engine import FusedEngine
   from recoder_amd.model import Recoder
+  families = []
+  decode_path = FusedEngine._decode_path
+
+  def recorded_decode_path(self, *args):
+    path = decode_path(self, *args)
+    families.append(path.name)
+    return path
+  monkeypatch.setattr(FusedEngine, "_decode_path", recorded_decode_path)
   n_users, n_items, deg = shape
   csr = synth_csr(n_users, n_items, deg, seed=len(name), ratings=(c["loss"] == "mse"))
   if name.startswith("edge"):
@@ -553,6 +580,9 @@ def test_steps_match_oracle(name, c, shape, B, S):
   rel = np.abs(losses - ref_losses) / np.abs(ref_losses)
   print(name, "losses", losses[:3], "ref", ref_losses[:3], "max rel", rel.max())
   assert rel.max() < LOSS_RTOL
+  want = _expected_decode_families(name)
+  if want is not None:
+    assert set(families) == want, (name, families)
   # gradients of the last step (buffers are still intact after the update)
   eng = rec._engine()
   grads = o.grads()
