@@ -1,4 +1,4 @@
-"""Build the three HIP libraries (hand-written kernels + C ABI) for gfx950.
+"""Build the four HIP libraries (hand-written kernels + C ABI) for gfx950.
 
     python -m recoder_amd.build [--force]
 
@@ -6,6 +6,8 @@ librecoder_hip.so  the training and recommend path (include/recoder_hip.h)
 librecoder_index.so  exact item similarity (include/recoder_index.h), a library of its
                    own so that the training library's exported symbol set stays as it is
 librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recoder_als.h),
+                   likewise a library of its own
+librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own
 
 hipcc cross-compiles without a GPU; the built libraries stay in-tree
@@ -20,9 +22,11 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "librecoder_hip.so")
 INDEX_LIB = os.path.join(CSRC, "librecoder_index.so")
 ALS_LIB = os.path.join(CSRC, "librecoder_als.so")
+VAE_LIB = os.path.join(CSRC, "librecoder_vae.so")
 SOURCES = ["capi.hip", "collate.hip", "encoder.hip", "gemm.hip", "decode16.hip", "linear.hip", "dw3.hip", "pgemm.hip", "fdecode.hip", "optim.hip", "topk.hip", "step.hip", "comm.hip"]
 INDEX_SOURCES = ["index.hip"]
 ALS_SOURCES = ["als.hip"]
+VAE_SOURCES = ["vae.hip"]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified register
 # file); without it hipcc copied all accumulators AGPR<->VGPR around every k-tile
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -78,9 +82,11 @@ def build_library(force=False, verbose=True):
   _build_one(LIB, SOURCES, headers, force, verbose)
   _build_one(INDEX_LIB, INDEX_SOURCES, [os.path.join(include, "recoder_index.h")], force, verbose)
   _build_one(ALS_LIB, ALS_SOURCES, [os.path.join(include, "recoder_als.h")], force, verbose)
+  # (vae.hip includes csrc/common.h for the counter RNG and the step cursor: the training headers too)
+  _build_one(VAE_LIB, VAE_SOURCES, headers + [os.path.join(include, "recoder_vae.h")], force, verbose)
   return LIB
 
 
 if __name__ == "__main__":
   build_library(force="--force" in sys.argv)
-  print("built", LIB, INDEX_LIB, ALS_LIB)
+  print("built", LIB, INDEX_LIB, ALS_LIB, VAE_LIB)

@@ -169,6 +169,14 @@ class FusedEngine:
     self.act_bounded = model.activation_type in ("tanh", "sigmoid")
     self._w_range_stale = True
     self._w_range_key = None
+    # VariationalAutoencoder: the encoder's last Linear is the head [mu | logvar] (2d wide, no activation),
+    # the stochastic bottleneck between it and the decoder lives in librecoder_vae.so (_vae_sample)
+    from .nn import VariationalAutoencoder
+    self.vae = isinstance(model, VariationalAutoencoder)
+    self.vae_lib = None
+    if self.vae:
+      from . import _vae_lib
+      self.vae_lib = _vae_lib.load()
     if kind == "ae":
       self.h = list(model.hidden_layers)
       self.nl = len(self.h) - 1
@@ -179,6 +187,8 @@ class FusedEngine:
       self.nl = 0
       if self.h[0] % 4 != 0:
         raise ValueError("embedding_size must be a multiple of 4 (16-byte embedding rows)")
+    # output widths of the encoder side: enc[i] is [B, eh[i]] (the VAE head: 2d)
+    self.eh = self.h[:-1] + [2 * self.h[-1]] if self.vae else self.h
 
   # ------------------------------------------------------------------ setup
   def ensure_capacity(self, B_cap, n_cap):
@@ -258,11 +268,16 @@ class FusedEngine:
       ctypes.memmove(ctypes.byref(self.planes_nowt), ctypes.byref(self.planes), ctypes.sizeof(RkPlanes))
       self.planes_nowt.wt = None
     self.n_part = self.lib.rk_loss_partials(B_cap, n_cap)
-    self.loss_part = torch.zeros(self.n_part, **f)
+    # (VAE: the rows' beta * KL partials follow the decode's at loss_part[n_part : n_part + B], _vae_sample)
+    self.loss_part = torch.zeros(self.n_part + (B_cap if self.vae else 0), **f)
     self.loss_out = torch.zeros(1, **f)
     # activations: enc[i] = output of encoder layer i (post activation), i = 0..nl
-    self.enc = [torch.empty(B_cap * self.h[i], **f) for i in range(self.nl + 1)]
-    self.denc = [torch.empty(B_cap * self.h[i], **f) for i in range(self.nl + 1)]
+    self.enc = [torch.empty(B_cap * self.eh[i], **f) for i in range(self.nl + 1)]
+    self.denc = [torch.empty(B_cap * self.eh[i], **f) for i in range(self.nl + 1)]
+    if self.vae:
+      # z (the decoder's input), the gradient at z, the eps of the step's sample
+      d = self.h[-1]
+      self.vae_z, self.vae_dz, self.vae_eps = (torch.empty(B_cap * d, **f) for _ in range(3))
     hb = self.h[-1]
     self.bott = torch.empty(B_cap * hb, **f)         # post-dropout bottleneck
     # dec[i] = output of decoder layer i (i = 0..nl-1); sizes reversed(h)[i+1]
@@ -428,8 +443,9 @@ class FusedEngine:
                                 s.step if rp is None else rp["slots"][s.name] + 1, stream), "rk_adam_rows")
 
   # --------------------------------------------------------------- forward
-  def _ae_forward(self, blk, row_off, B, keep_noise, keep_drop, train, stream, split_w=None):
-    """split_w: the RkPlanes whose W image the launch writes for the decode of this block."""
+  def _ae_forward(self, blk, row_off, B, keep_noise, keep_drop, train, stream, split_w=None, vae=None):
+    """split_w: the RkPlanes whose W image the launch writes for the decode of this block.  vae: keyword
+    arguments of _vae_sample (VariationalAutoencoder)."""
     m, lib = self.model, self.lib
     p_noise = float(m.noise_prob) if train else 0.0
     ip = self.item_parallel if train else None
@@ -458,11 +474,14 @@ class FusedEngine:
                                  self.rng_step, ptr(blk.users), self.act, ptr(self.enc[0]), stream),
             "rk_ae_encode_fwd")
     for i, layer in enumerate(m.encoding_layers):
-      check(lib.rk_linear_fwd(ptr(self.enc[i]), ptr(layer.weight), ptr(layer.bias), B, self.h[i + 1],
-                              self.h[i], 0, self.act, ptr(self.enc[i + 1]), stream), "rk_linear_fwd")
+      act = ACT["none"] if self.vae and i == self.nl - 1 else self.act      # (the VAE head: no activation)
+      check(lib.rk_linear_fwd(ptr(self.enc[i]), ptr(layer.weight), ptr(layer.bias), B, self.eh[i + 1],
+                              self.eh[i], 0, act, ptr(self.enc[i + 1]), stream), "rk_linear_fwd")
     z = self.enc[self.nl]
     self.drop_active = bool(train and m.dropout_prob > 0.0)
-    if self.drop_active:
+    if self.vae:
+      z = self._vae_sample(blk, row_off, B, train, stream, **(vae or {}))
+    elif self.drop_active:
       n = B * self.h[-1]
       self.bott[:n].copy_(z[:n])
       check(lib.rk_dropout(ptr(self.bott), ptr(keep_drop), n, self.h[-1], float(m.dropout_prob),
@@ -516,6 +535,24 @@ class FusedEngine:
                            self.seed ^ 0xd0d0, self.rng_step, stream), "rk_dropout")
       z = self.bott
     return z
+
+  def _vae_sample(self, blk, row_off, B, train, stream, beta=None, eps=None, rp=None):
+    """z of the VariationalAutoencoder from its head's output enc[nl] = [mu | logvar] (rk_vae_sample): a sample
+    (train) or mu.  beta: also write every row's beta * KL behind the decode's loss partials, at
+    loss_part[n_part : n_part + B] (the step's loss reduction adds them).  eps: an injected [B, d] eps
+    (Recoder.eps_hook) instead of the counter RNG.  rp: the replay context -- the RNG step, the rows' user ids
+    and beta then come from the step cursor (beta from rp["beta"], the epoch's table)."""
+    d = self.h[-1]
+    cursor, off, users, table = None, 0, ptr(blk.users), None
+    if rp is not None:
+      cursor, off, users, table, row_off = rp["cursor"], rp["off"], rp["users"], rp["beta"], 0
+    kl = None if beta is None else self.loss_part.data_ptr() + 4 * self.n_part
+    from ._vae_lib import check as vcheck
+    vcheck(self.vae_lib.rk_vae_sample(ptr(self.enc[self.nl]), B, d, 1 if train else 0, ptr(eps), self.seed,
+                                      self.rng_step, users, row_off, cursor, off, table,
+                                      _f32(0.0 if beta is None else beta), ptr(self.vae_z),
+                                      ptr(self.vae_eps) if train else None, kl, stream), "rk_vae_sample")
+    return self.vae_z
 
   def _decoder_params(self):
     m = self.model
@@ -664,16 +701,20 @@ class FusedEngine:
     self.ensure_capacity(B, max(blk.n_cap, tgt.n_cap if tgt is not None else 0))
     stream = current_stream()
     if self.kind == "ae":
-      z = self._ae_forward(blk, row_off, B, None, None, False, stream)
+      # (VAE: z = mu, and beta * KL with the beta of the next training step)
+      vae = dict(beta=self.model.beta()) if self.vae else None
+      z = self._ae_forward(blk, row_off, B, None, None, False, stream, vae=vae)
     else:
       z = self._mf_forward(blk.users[row_off:row_off + B], B, None, False, stream)
     out = self.loss_out if out is None else out
     n_part = self._decode(z, B, tgt if tgt is not None else blk, row_off, B, stream)
+    if self.vae:
+      n_part = self.n_part + B
     check(self.lib.rk_loss_reduce(ptr(self.loss_part), n_part, float(B), ptr(out), stream), "rk_loss_reduce")
     return out
 
   def train_step(self, blk, row_off, B, keep_noise=None, keep_drop=None, out=None,
-                 global_rows=None, tgt=None, replay=None):
+                 global_rows=None, tgt=None, replay=None, eps=None):
     """One optimisation step on rows [row_off, row_off+B) of the collated
     block (model.py:383-404).  ``global_rows`` = rows summed over all ranks
     (data parallel); the loss/gradients are normalised by it.
@@ -699,7 +740,8 @@ class FusedEngine:
     if self.c_step_eligible() and tgt is None and not (ip is not None and self.loss_id == LOSS_MNLL):
       return self._c_train_step(blk, row_off, B, keep_noise, out, global_rows, main_s, replay=replay)
     if replay is None:
-      return self._entry_train_step(blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s, None)
+      return self._entry_train_step(blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s, None,
+                                    eps=eps)
     # graph replay of the per-entry sequencing (graph.GraphStepper): what changes per step comes
     # from the device-resident cursor (include/recoder_hip.h rk_replay_t); the host counters are
     # advanced by the stepper, `out` is the base of the epoch's loss buffer
@@ -715,10 +757,11 @@ class FusedEngine:
     finally:
       raw_lib.rk_replay_set(None)
 
-  def _entry_train_step(self, blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s, replay):
+  def _entry_train_step(self, blk, row_off, B, keep_noise, keep_drop, out, global_rows, tgt, main_s, replay,
+                        eps=None):
     """The step sequenced entry by entry from here (hidden stacks, bottleneck dropout,
-    MatrixFactorization, separate target blocks, the multi-GPU variants).  replay: the replay
-    context of graph.GraphStepper (None: enqueued eagerly)."""
+    MatrixFactorization, VariationalAutoencoder, separate target blocks, the multi-GPU variants).  replay: the
+    replay context of graph.GraphStepper (None: enqueued eagerly).  eps: the injected [B, d] eps of a VAE step."""
     lib, m = self.lib, self.model
     ip = self.item_parallel
     tb = blk if tgt is None else tgt
@@ -728,6 +771,13 @@ class FusedEngine:
     h0 = self.h[0]
     rows = B if global_rows is None else global_rows
     tied = self.kind == "ae" and bool(m.is_constrained)
+    vae = None
+    if self.vae:
+      # the KL weight of this step (replayed: the epoch's table, graph.GraphStepper); the host counts the steps
+      beta = m.beta()
+      if replay is None:
+        m.anneal_step += 1
+      vae = dict(beta=beta, eps=eps, rp=replay)
     # single process: nothing has to exist as an array of its own for an exchange, so the small
     # reductions of the step ride on its Adam launch as they do in rk_ae_train_step -- the loss
     # partials, the decode epilogue's row-tile column sums (decoder bias gradient) and the K slabs
@@ -742,7 +792,8 @@ class FusedEngine:
     split_w = self.kind == "ae" and tgt is None and not tied and path is not Decode.PLAIN
     if self.kind == "ae":
       z = self._ae_forward(blk, row_off, B, keep_noise, keep_drop, True, stream,
-                           split_w=(self.planes_nowt if path.image else self.planes) if split_w else None)
+                           split_w=(self.planes_nowt if path.image else self.planes) if split_w else None,
+                           vae=vae)
     else:
       # (replay: the C entry points take the step's users from the cursor; the pointer is a placeholder)
       users = blk.users[row_off:row_off + B] if replay is None else replay["users_t"]
@@ -754,6 +805,8 @@ class FusedEngine:
     loss = self.loss_dp if dp_replay else (self.loss_out if out is None else out)
     n_part = self._decode(z, B, tb, row_off, rows, stream, ip=ip, path=path,
                           zt_ws=self.ws_dw if zt else None, w_done=split_w)
+    if self.vae:
+      n_part = self.n_part + B          # (the rows' beta * KL partials behind the decode's)
     pending = None
     if lazy:         # (summed by the step's Adam launch, see _flush_jobs)
       pending = (self.loss_part, n_part, float(rows), loss)
@@ -810,6 +863,8 @@ class FusedEngine:
     # gradient w.r.t. the decoder's input: straight into the encoder side's buffer unless the
     # bottleneck dropout has to be undone on the way (MF: dbott is the gathered user rows' gradient)
     bott_grad = self.denc[self.nl] if (self.kind == "ae" and not self.drop_active) else self.dbott
+    if self.vae:
+      bott_grad = self.vae_dz          # (the gradient at z: rk_vae_sample_bwd turns it into the head's dE)
     dz = bott_grad
     if self.kind == "ae" and self.nl > 0:
       dz = self.ddec[self.nl - 1]
@@ -858,9 +913,11 @@ class FusedEngine:
         else:
           w, wt, gw, acc = layer.weight, 0, self.g_dec_w[i], 0
         if stack_pre:
-          # (ddec[i] arrives with act'(dec[i]) in it; dX leaves with act'(x): x is the layer's input)
+          # (ddec[i] arrives with act'(dec[i]) in it; dX leaves with act'(x): x is the layer's input -- except
+          # the VAE's z, which is no activation output)
+          x_act = None if self.vae and i == 0 else ptr(x)
           check(lib.rk_linear_bwd_pre(ptr(self.ddec[i]), ptr(x), ptr(w), B, rh[i + 1], rh[i], wt, self.act,
-                                      ptr(dx), ptr(gw), acc, ptr(self.g_dec_b[i]), ptr(x), stream),
+                                      ptr(dx), ptr(gw), acc, ptr(self.g_dec_b[i]), x_act, stream),
                 "rk_linear_bwd_pre")
           continue
         check(lib.rk_linear_bwd(ptr(self.ddec[i]), ptr(self.dec[i]), ptr(x), ptr(w), B, rh[i + 1],
@@ -873,6 +930,14 @@ class FusedEngine:
                              float(m.dropout_prob), self.seed ^ 0xd0d0, self.rng_step, stream),
               "rk_dropout")
         self.denc[self.nl][:n].copy_(self.dbott[:n])
+      if self.vae:
+        # dE = [dmu | dlogvar] of the head: its dYpre (the head has no activation)
+        cursor, off, table = (None, 0, None) if replay is None else (replay["cursor"], replay["off"], replay["beta"])
+        from ._vae_lib import check as vcheck
+        vcheck(self.vae_lib.rk_vae_sample_bwd(ptr(self.enc[self.nl]), ptr(self.vae_eps), ptr(self.vae_dz), B,
+                                              self.h[-1], _f32(np.float32(1.0) / np.float32(rows)), cursor, off,
+                                              table, _f32(vae["beta"]), ptr(self.denc[self.nl]), stream),
+               "rk_vae_sample_bwd")
       # encoder Linear stack, last to first
       for i in range(self.nl - 1, -1, -1):
         layer = m.encoding_layers[i]
@@ -880,7 +945,7 @@ class FusedEngine:
         # folded into that product's epilogue instead of an rk_act_grad launch behind it)
         if stack_pre:
           check(lib.rk_linear_bwd_pre(ptr(self.denc[i + 1]), ptr(self.enc[i]), ptr(layer.weight), B,
-                                      self.h[i + 1], self.h[i], 0, self.act, ptr(self.denc[i]),
+                                      self.eh[i + 1], self.eh[i], 0, self.act, ptr(self.denc[i]),
                                       ptr(self.g_enc_w[i]), 1 if m.is_constrained else 0,
                                       ptr(self.g_enc_b[i]), ptr(self.enc[i]), stream), "rk_linear_bwd_pre")
           if i == 0:
@@ -888,7 +953,7 @@ class FusedEngine:
           continue
         last = i == 0 and not fuse_act
         check(lib.rk_linear_bwd_dact(ptr(self.denc[i + 1]), ptr(self.enc[i + 1]), ptr(self.enc[i]),
-                                     ptr(layer.weight), B, self.h[i + 1], self.h[i], 0, self.act,
+                                     ptr(layer.weight), B, self.eh[i + 1], self.eh[i], 0, self.act,
                                      ptr(self.denc[i]), ptr(self.g_enc_w[i]),
                                      1 if m.is_constrained else 0, ptr(self.g_enc_b[i]),
                                      ptr(self.enc[0]) if last else None, stream),
@@ -1039,6 +1104,8 @@ class FusedEngine:
     m = self.model
     if getattr(self, "owned_rows", False):
       return False          # (owned-row Adam under users-DP: sequenced from Python, _owned_exchange)
+    if self.vae:
+      return False          # (the stochastic bottleneck + KL term: the entry-by-entry step)
     return self.use_c_step and self.kind == "ae" and self.nl == 0 and not (m.dropout_prob > 0.0)
 
   def _c_train_step(self, blk, row_off, B, keep_noise, out, global_rows, main_s, replay=None):

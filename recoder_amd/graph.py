@@ -66,6 +66,10 @@ class GraphStepper:
     self.tab_stride = 4 if self.c_step else max(1, len(engine.states))
     self.table = torch.zeros((self.steps_cap + self.G) * self.tab_stride * 8, dtype=torch.float32, device=device)
     self.table_host = torch.zeros((self.steps_cap + self.G) * self.tab_stride * 8, dtype=torch.float32).pin_memory()
+    # VariationalAutoencoder: the KL weight of every step of the epoch (rk_vae_sample reads entry
+    # cursor[0] - cursor[1] + off), filled by begin_epoch from the model's anneal_step
+    self.vae = bool(getattr(engine, "vae", False))
+    self.beta = torch.zeros(self.steps_cap + self.G, dtype=torch.float32, device=device) if self.vae else None
     # stream capture needs a stream of its own (not the default stream torch work runs on)
     self.main = torch.cuda.Stream(device=device)
     self.side = torch.cuda.Stream(device=device)
@@ -225,6 +229,8 @@ class GraphStepper:
     if self.lazy:
       replay["lazy"] = dict(names=self.lazy, pos_next=None if next_blk is None else ptr(next_blk.pos),
                             need=self._need_of(self.blocks[slot][g], next_blk))
+    if self.vae:
+      replay["beta"] = ptr(self.beta)
     if self.c_step:
       self.eng._c_train_step(self.blocks[slot][g], 0, self.B, None, self.loss_buf,
                              None if self.dp is None else self.B * self.dp.world, self.main, replay=replay)
@@ -342,6 +348,11 @@ class GraphStepper:
       check(self.lib.rk_adam_consts(lr, b1, b2, eps, wd, s.step + 1, n_full + self.G, self.tab_stride * 8,
                                     th.data_ptr() + k * 8 * 4), "rk_adam_consts")
     self.table.copy_(th, non_blocking=False)
+    if self.vae:
+      # (the same host arithmetic as an eagerly enqueued step's beta: bitwise the same values)
+      m = self.eng.model
+      self.beta.copy_(torch.tensor([m.beta(m.anneal_step + i) for i in range(self.beta.numel())],
+                                   dtype=torch.float32), non_blocking=False)
     self.global_step = int(global_step)
     self.epoch_base = int(global_step)
     self._cursor_at = None
@@ -540,6 +551,8 @@ class GraphStepper:
     for _, name in self._slot_items():
       S[name].step += k
     self.eng.rng_step += k
+    if self.vae:
+      self.eng.model.anneal_step += k
 
   def losses(self, n):
     return self.loss_buf[:n]

@@ -14,6 +14,9 @@ Two hooks exist because a GPU cannot reproduce the reference's CPU RNG streams
       torch RNG, so noise-free runs reproduce the reference's order);
   ``mask_hook(step, users, nnz) -> (keep_noise | None, keep_drop | None)``
       explicit dropout keep-masks for a sampling group (default: counter RNG).
+  ``eps_hook(step, users) -> float32 [rows, d] | None``  VariationalAutoencoder: the eps of the
+      bottleneck sample of training step ``step`` whose rows are ``users`` (default: counter RNG).
+Either hook turns the HIP-graph replay of the training steps off.
 """
 import logging
 import os
@@ -30,7 +33,7 @@ from .device import Block, DeviceCSR, require_gpu
 from .engine import FusedEngine
 from .losses import MSELoss, MultinomialNLLLoss
 from .metrics import RecommenderEvaluator
-from .nn import DynamicAutoencoder, FactorizationModel, MatrixFactorization
+from .nn import DynamicAutoencoder, FactorizationModel, MatrixFactorization, VariationalAutoencoder
 from .recommender import InferenceRecommender
 
 log = logging.getLogger("recoder_amd")
@@ -69,6 +72,7 @@ class Recoder(object):
     self.users = None
     self.user_order_hook = None
     self.mask_hook = None
+    self.eps_hook = None
     # steps collated per side-stream hand-over (CollatePrefetcher)
     self.prefetch_group = 4
     # steps per replayed HIP graph (graph.py)
@@ -96,11 +100,41 @@ class Recoder(object):
     self.__model_initialized = True
 
   def _fused_kind(self):
-    if isinstance(self.model, DynamicAutoencoder):
+    # (a VariationalAutoencoder runs the autoencoder's entry-by-entry step with its bottleneck: FusedEngine.vae)
+    if isinstance(self.model, (DynamicAutoencoder, VariationalAutoencoder)):
       return "ae"
     if isinstance(self.model, MatrixFactorization):
       return "mf"
     return None
+
+  def _check_vae(self):
+    """A VariationalAutoencoder trains on the fused HIP step only (no generic torch path, no sharded step):
+    what that step does not cover raises ValueError here, before any GPU work."""
+    if not isinstance(self.model, VariationalAutoencoder):
+      return
+    self.model._validate()
+    if self.optimizer_type != "adam":
+      raise ValueError("VariationalAutoencoder trains with optimizer_type='adam' only (the fused HIP step)")
+    if isinstance(self.loss, str):
+      if self.loss not in ("mse", "logistic", "logloss"):
+        raise ValueError("Unknown loss function {}".format(self.loss))
+      extra = set(self.loss_params) - ({"confidence"} if self.loss == "mse" else set())
+      if extra:
+        raise ValueError("VariationalAutoencoder: loss_params %s are outside the fused loss epilogues" % sorted(extra))
+    elif isinstance(self.loss, (MSELoss, MultinomialNLLLoss)):
+      if self.loss.reduction != "sum":
+        raise ValueError("VariationalAutoencoder: the fused loss epilogues compute reduction='sum' only")
+    elif isinstance(self.loss, torch.nn.BCEWithLogitsLoss):
+      if self.loss.reduction != "sum" or self.loss.weight is not None or self.loss.pos_weight is not None:
+        raise ValueError("VariationalAutoencoder: BCEWithLogitsLoss with weights or a reduction other than "
+                         "'sum' is outside the fused loss epilogues")
+    else:
+      raise ValueError("VariationalAutoencoder: the loss must be 'mse', 'logistic', 'logloss' or their modules")
+    import torch.distributed as dist
+    multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    if (multi or os.environ.get("RK_FORCE_DP") == "1" or os.environ.get("RK_PARALLEL") == "items" or
+        getattr(self, "_dp_override", None) is not None or getattr(self, "_ip_override", None) is not None):
+      raise ValueError("VariationalAutoencoder has no users-DP or item-parallel step")
 
   def _use_generic(self):
     """True when the combination has no fused HIP step and trains through torch
@@ -228,6 +262,7 @@ class Recoder(object):
 
   def _engine(self):
     if self.__engine is None:
+      self._check_vae()
       self.__init_loss_module()
       if self._use_generic():
         from .generic import GenericEngine
@@ -329,6 +364,7 @@ class Recoder(object):
     log.info("lr {} wd {} batch {} optimizer {} milestones {} loss {}".format(
         lr, weight_decay, batch_size, self.optimizer_type, lr_milestones, self.loss))
 
+    self._check_vae()
     if num_sampling_users == 0:
       num_sampling_users = batch_size
     if eval_batch_size is None:
@@ -775,7 +811,13 @@ class Recoder(object):
           kd = None
           if keep_drop is not None:
             kd = keep_drop[r:r + rows].contiguous()
-          yield blk, r, rows, keep_noise, kd, tgt_blk
+          eps = None
+          if self.eps_hook is not None:
+            # (the consumer has counted the steps before this one: _global_step is this step's index)
+            eps = self.eps_hook(self._global_step, order[off + r:off + r + rows])
+            if eps is not None:
+              eps = torch.as_tensor(eps, dtype=torch.float32).to(self.device).contiguous()
+          yield blk, r, rows, keep_noise, kd, tgt_blk, eps
       pf.release(slot)
 
   def _train(self, train_dataloader, val_dataloader, num_epochs, current_epoch, lr_scheduler,
@@ -828,11 +870,12 @@ class Recoder(object):
         iters_to_process = num_batches
 
       n_done = 0
-      for batch_itr, (blk, row_off, rows, keep_noise, keep_drop, tgt_blk) in iterator:
+      for batch_itr, (blk, row_off, rows, keep_noise, keep_drop, tgt_blk, eps) in iterator:
         dp = getattr(self, "_dp", None)
         engine.train_step(blk, row_off, rows, keep_noise, keep_drop,
                           out=loss_buf[n_done:n_done + 1],
-                          global_rows=(rows * dp.world if dp is not None else None), tgt=tgt_blk)
+                          global_rows=(rows * dp.world if dp is not None else None), tgt=tgt_blk,
+                          **({} if eps is None else dict(eps=eps)))
         n_done += 1
         self._global_step += 1
         if batch_itr % iters_per_epoch == 0:
@@ -909,7 +952,8 @@ class Recoder(object):
               self.graph_group <= 8):
         return False
     ds = dataloader.dataset
-    return (self.mask_hook is None and dataloader.num_sampling_users == dataloader.batch_size and
+    return (self.mask_hook is None and self.eps_hook is None and
+            dataloader.num_sampling_users == dataloader.batch_size and
             ds.device_target_csr() is None and iters_per_epoch == num_batches and
             len(ds) >= dataloader.batch_size)
 

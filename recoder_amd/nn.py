@@ -75,7 +75,8 @@ def _check_act(act):
 def fused_supported(model):
   """True when the HIP kernels cover this model instance: a fused activation and 16-byte
   embedding rows (hidden_layers[0] / embedding_size a multiple of 4)."""
-  h0 = model.hidden_layers[0] if isinstance(model, DynamicAutoencoder) else model.embedding_size
+  h0 = (model.hidden_layers[0] if isinstance(model, (DynamicAutoencoder, VariationalAutoencoder))
+        else model.embedding_size)
   return model.activation_type in _ACTS and h0 % 4 == 0
 
 
@@ -255,3 +256,128 @@ class MatrixFactorization(FactorizationModel):
       return F.linear(u, self.item_embedding_layer.weight, self.bias)
     return F.linear(u, self.item_embedding_layer(target_items),
                     self.bias.index_select(0, target_items))
+
+
+class VariationalAutoencoder(FactorizationModel):
+  """Mult-VAE (Liang et al. 2018, "Variational Autoencoders for Collaborative Filtering") over
+  variable item subsets, trained on the fused HIP step.
+
+  For ``hidden_layers = [h_0, ..., h_{L-1}]`` (L >= 2, d = h_{L-1}): the encoder of
+  DynamicAutoencoder (L2-normalised input, input dropout ``noise_prob``, ``act(x . W_en[I] + b_en)``,
+  Linear layers with ``act``) up to h_{L-2}, then a head ``Linear(h_{L-2}, 2d)`` without activation
+  that gives ``[mu | logvar]``.  Training samples ``z = mu + eps * exp(0.5 logvar)``, evaluation takes
+  ``z = mu``; the decoder is DynamicAutoencoder's for the reversed sizes (no tied weights, no bottleneck
+  dropout).  The step's loss adds ``beta * KL`` with ``beta = kl_cap * min(1, anneal_step /
+  anneal_steps)`` (``kl_cap`` when ``anneal_steps == 0``); ``anneal_step`` counts the training steps
+  taken and travels in ``model_params()``.
+
+  Not a DynamicAutoencoder subclass: every path that treats a DynamicAutoencoder as such would drop the
+  KL term.  The state-dict keys are DynamicAutoencoder's (the LinearEmbedding biases included), the
+  last ``encoding_layers`` entry being the head.
+  """
+
+  # (what the fused engine reads of an autoencoder: this model has neither)
+  is_constrained = False
+  dropout_prob = 0.0
+
+  def __init__(self, hidden_layers=None, activation_type="tanh", noise_prob=0.0, sparse=False,
+               kl_cap=0.2, anneal_steps=200000):
+    super().__init__()
+    self.hidden_layers = hidden_layers
+    self.activation_type = activation_type
+    self.noise_prob = noise_prob
+    self.sparse = sparse
+    self.kl_cap = kl_cap
+    self.anneal_steps = anneal_steps
+    self.anneal_step = 0
+    self.num_items = None
+    self.num_embeddings = None
+    self.noise_layer = None
+    if hidden_layers is not None:         # (None: the sizes come from load_model_params)
+      self._validate()
+
+  def _validate(self):
+    h = self.hidden_layers
+    if h is None or len(h) < 2:
+      raise ValueError("VariationalAutoencoder needs hidden_layers with at least two sizes "
+                       "([..., h_{L-2}, d]: the last is the latent size)")
+    if any(int(x) < 1 for x in h):
+      raise ValueError("hidden_layers must be positive sizes")
+    if not float(self.kl_cap) >= 0.0:
+      raise ValueError("kl_cap must be >= 0")
+    if int(self.anneal_steps) < 0:
+      raise ValueError("anneal_steps must be >= 0")
+    if self.activation_type not in _ACTS:
+      raise ValueError("VariationalAutoencoder trains on the fused HIP kernels only: activation_type must be "
+                       "one of %s" % (_ACTS,))
+    if int(h[0]) % 4 != 0:
+      raise ValueError("hidden_layers[0] must be a multiple of 4 (16-byte embedding rows)")
+    if not 0.0 <= float(self.noise_prob) < 1.0:
+      raise ValueError("noise_prob must be in [0, 1)")
+
+  def beta(self, step=None):
+    """The KL weight of the training step after `step` steps (default: the next one)."""
+    g = self.anneal_step if step is None else step
+    if int(self.anneal_steps) == 0:
+      return float(self.kl_cap)
+    return float(self.kl_cap) * min(1.0, float(g) / float(self.anneal_steps))
+
+  # -- the four-method contract ------------------------------------------
+  def init_model(self, num_items=None, num_users=None):
+    self._validate()
+    self.num_items = num_items
+    self.num_embeddings = num_items
+    h = list(self.hidden_layers)
+    d = h[-1]
+    # DynamicAutoencoder's scheme and order: the encoder side, then the decoder side
+    self.en_embedding_layer = nn.Embedding(num_items, h[0], sparse=self.sparse)
+    self._DynamicAutoencoder__en_linear_embedding_layer = LinearEmbedding(self.en_embedding_layer,
+                                                                          input_based=True)
+    self.encoding_layers = nn.Sequential(*DynamicAutoencoder._coding_layers(h[:-1] + [2 * d]))
+    nn.init.xavier_uniform_(self.en_embedding_layer.weight)
+    nn.init.constant_(self.en_bias, 0)
+    dec = DynamicAutoencoder._coding_layers(list(reversed(h)))
+    self.de_embedding_layer = nn.Embedding(num_items, h[0], sparse=self.sparse)
+    self.decoding_layers = nn.Sequential(*dec)
+    self._DynamicAutoencoder__de_linear_embedding_layer = LinearEmbedding(self.de_embedding_layer,
+                                                                          input_based=False)
+    nn.init.xavier_uniform_(self.de_embedding_layer.weight)
+    nn.init.constant_(self.de_bias, 0)
+    self.noise_layer = nn.Dropout(p=self.noise_prob) if self.noise_prob > 0.0 else None
+
+  def model_params(self):
+    return {
+      "hidden_layers": self.hidden_layers,
+      "activation_type": self.activation_type,
+      "noise_prob": self.noise_prob,
+      "sparse": self.sparse,
+      "kl_cap": self.kl_cap,
+      "anneal_steps": self.anneal_steps,
+      "anneal_step": int(self.anneal_step),
+    }
+
+  def load_model_params(self, model_params):
+    self.hidden_layers = model_params["hidden_layers"]
+    self.activation_type = model_params["activation_type"]
+    self.noise_prob = model_params["noise_prob"]
+    self.sparse = model_params.get("sparse", self.sparse)
+    self.kl_cap = model_params["kl_cap"]
+    self.anneal_steps = model_params["anneal_steps"]
+    self.anneal_step = int(model_params.get("anneal_step", 0))
+    self._validate()
+
+  # -- accessors used by the engine ---------------------------------------
+  @property
+  def en_bias(self):
+    return self._DynamicAutoencoder__en_linear_embedding_layer.bias
+
+  @property
+  def de_bias(self):
+    return self._DynamicAutoencoder__de_linear_embedding_layer.bias
+
+  def forward(self, input, input_users=None, input_items=None, target_users=None,
+              target_items=None):
+    """Dense-input forward on the HIP kernels (z = mu in eval mode, a counter-RNG sample in
+    training mode); no autograd."""
+    from .engine import ae_dense_forward
+    return ae_dense_forward(self, input, input_items, target_items)
