@@ -1,0 +1,103 @@
+/*
+ * recoder_ease.h -- C ABI of librecoder_ease.so (MI355X / gfx950 only).
+ *
+ * EASE (Steck, "Embarrassingly Shallow Autoencoders for Sparse Data", WWW 2019): a linear
+ * item-item autoencoder with a zero diagonal and a closed-form solution.  For the user x item
+ * matrix X (values as stored), reg > 0 and n items:
+ *   G = X^T X                      [n, n]
+ *   P = (G + reg I)^-1
+ *   B[i][j] = -P[i][j] / P[j][j]   (i != j),   B[j][j] = 0
+ *   scores(u, :) = X[u, :] . B
+ * A library of its own, beside the training, index, ALS and VAE libraries, so that none of their
+ * symbol sets changes; the Python binding is recoder_amd/_ease_lib.py, the driver recoder_amd/ease.py.
+ *
+ * Conventions (those of recoder_als.h)
+ *   - every function returns 0 on success, <0 on error; rk_ease_last_error() gives a
+ *     thread-local message.
+ *   - every pointer is a DEVICE pointer owned by the caller; nothing is retained past the call.
+ *   - every launch goes on the caller's hipStream_t (passed as void*); no call synchronises
+ *     the host; no call allocates (scratch comes from a workspace the caller sizes with the
+ *     *_workspace_bytes query).
+ *   - matrices are row-major fp32 with an explicit leading dimension (in elements).  CSR: int64
+ *     indptr [rows + 1], int32 column indices ascending inside a row, fp32 values (NULL: every
+ *     value is 1.0).
+ *
+ * Numerics (all f32 in memory; every call is bitwise repeatable, whatever the values)
+ *   - rk_ease_gram: A[i][j] is ONE f32 fmaf chain  fma(x_ui, x_uj, .)  over the users u of item i in
+ *     ascending order, from 0, then + reg on the diagonal.  No atomics: a column belongs to one
+ *     wave, a wave takes the users one after the other.  x_ui x_uj == x_uj x_ui and the users of i
+ *     that also hold j are the users of j that also hold i, so A[i][j] and A[j][i] are the same chain:
+ *     bitwise symmetric.  Integer-valued interactions with every sum below 2^24 give the exact Gram.
+ *   - rk_ease_spd_inverse: blocked Gauss-Jordan (the sweep operator) without pivoting, block width
+ *     64, on the whole matrix (2 n^3 flop; the symmetry is not used).  The 64 x 64 pivot block is
+ *     inverted in float64 and kept in float64 for the two panels (float64 fma chains, rounded to f32
+ *     once); the rank-64 update is one k-ascending f32 chain on v_mfma_f32_32x32x2_f32 subtracted
+ *     from the stored value with a compensated (Kahan) subtraction whose carries live in a second
+ *     n x n image in the workspace and are folded in at the end: the many updates that are below half
+ *     an ulp of a large diagonal are not lost.  The result is symmetric up to rounding, not bitwise.
+ *   - rk_ease_finalize: one correctly rounded f32 divide per element.
+ *   - rk_ease_scores: one ascending f32 fmaf chain per output, from 0, over the user's stored
+ *     entries: a score depends neither on the strip nor on the user's position in the batch.
+ */
+#ifndef RECODER_EASE_H
+#define RECODER_EASE_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* (the library is built with -fvisibility=hidden: what this header declares is what it exports) */
+#pragma GCC visibility push(default)
+
+int rk_ease_version(void);
+const char *rk_ease_last_error(void);
+
+/*
+ * A = X^T X + reg I, dense [n_items, lda], written once, every element of the n_items x n_items
+ * square.  (t_*): the item-major CSR (X^T, n_items rows, columns = users); (u_*): the user-major
+ * CSR (X, n_users rows, columns = items) of the SAME matrix; t_data and u_data are both NULL or
+ * both given.  n_users >= 0, n_items >= 1.
+ */
+int rk_ease_gram(const int64_t *t_indptr, const int32_t *t_indices, const float *t_data,
+                 const int64_t *u_indptr, const int32_t *u_indices, const float *u_data, int32_t n_users,
+                 int32_t n_items, float reg, float *A, int64_t lda, void *stream);
+
+/* bytes of workspace rk_ease_spd_inverse needs for an [n, n] matrix: n * n * 4 for the carries plus the
+ * panels (> 0; < 0 on bad arguments) */
+int64_t rk_ease_spd_inverse_workspace_bytes(int32_t n);
+
+/*
+ * A <- A^-1 in place for a symmetric positive-definite A [n, lda], n >= 1.  status: one int32 the
+ * call first sets to 0, then to 1 + (index of the first pivot that was not > 0, or not finite) if
+ * there is one; such a pivot is replaced by 1 and the call runs to its end without a fault (A is
+ * then garbage).  The caller reads status after synchronising the stream.
+ */
+int rk_ease_spd_inverse(float *A, int32_t n, int64_t lda, void *ws, int64_t ws_bytes, int32_t *status,
+                        void *stream);
+
+/*
+ * B[i][j] = P[i][j] / (-P[j][j]) for i != j, B[j][j] = +0; diag [n] receives diag(P) (always
+ * written: the leave-one-out diagnostics use it).  B may be P (in place) or a second buffer that
+ * does not overlap it.
+ */
+int rk_ease_finalize(const float *P, int32_t n, int64_t ldp, float *B, int64_t ldb, float *diag,
+                     void *stream);
+
+/*
+ * out[u][c] = sum over the entries (j, x_uj) of CSR row u, ascending, of x_uj * W[j][lo + c], for
+ * u in [0, n_rows) and c in [0, hi - lo); 0 <= lo < hi, every j is a row of W [>, ldw] and W has at
+ * least hi columns.  out [n_rows, ldo], ldo >= hi - lo; columns past hi - lo are left as they are.
+ * Workgroups that share a column tile run next to one another, so that the rows of W a batch
+ * shares are read from L2 / MALL.
+ */
+int rk_ease_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
+                   const float *W, int64_t ldw, int32_t lo, int32_t hi, float *out, int64_t ldo,
+                   void *stream);
+
+#pragma GCC visibility pop
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RECODER_EASE_H */

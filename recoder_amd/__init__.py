@@ -7,3 +7,13 @@ Drop-in for the reference's training path: ``Recoder`` / ``FactorizationModel``
 # value of the reference's recoder.__version__ (recoder/__init__.py:1); stored
 # in checkpoints as 'recoder_version' (model.py:207)
 __version__ = "0.4.0"
+
+__all__ = ["ShallowAutoencoder"]
+
+
+def __getattr__(name):
+  # (lazy: importing the package alone does not import torch)
+  if name == "ShallowAutoencoder":
+    from .nn import ShallowAutoencoder
+    return ShallowAutoencoder
+  raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -33,7 +33,8 @@ from .device import Block, DeviceCSR, require_gpu
 from .engine import FusedEngine
 from .losses import MSELoss, MultinomialNLLLoss
 from .metrics import RecommenderEvaluator
-from .nn import DynamicAutoencoder, FactorizationModel, MatrixFactorization, VariationalAutoencoder
+from .nn import (DynamicAutoencoder, FactorizationModel, MatrixFactorization, ShallowAutoencoder,
+                 VariationalAutoencoder)
 from .recommender import InferenceRecommender
 
 log = logging.getLogger("recoder_amd")
@@ -365,6 +366,9 @@ class Recoder(object):
         lr, weight_decay, batch_size, self.optimizer_type, lr_milestones, self.loss))
 
     self._check_vae()
+    if isinstance(self.model, ShallowAutoencoder):
+      raise ValueError("a ShallowAutoencoder is fitted in closed form: call train_ease(train_dataset) "
+                       "(gradient steps would not keep its zero diagonal)")
     if num_sampling_users == 0:
       num_sampling_users = batch_size
     if eval_batch_size is None:
@@ -433,6 +437,40 @@ class Recoder(object):
                                m.bias.data, ucsr, icsr, alpha, float(reg), int(cg_steps), int(num_iterations))
     self._weights_written()
     return list(self.als_history)
+
+  def train_ease(self, train_dataset, reg=None):
+    """The closed-form EASE fit of a ShallowAutoencoder (recoder_amd/ease.py): ``item_weights`` becomes
+    ``-P / diag(P)`` by columns with a zero diagonal, ``P = (X^T X + reg I)^-1`` for the dataset's
+    interaction matrix X (values as stored).  ``reg`` None takes the model's; an explicit value is stored
+    back into the model, so that a checkpoint's ``model_params`` describe the weights it holds.  The
+    configured ``loss`` plays no part: EASE minimises the squared error with an L2 penalty by
+    construction.  Builds a fresh optimizer of ``optimizer_type`` so that ``save_state`` works.  Returns
+    ``info``: n, nnz, reg and the milliseconds of the Gram, the inverse and finalize (HIP events)."""
+    from . import als, ease
+    if not isinstance(self.model, ShallowAutoencoder):
+      raise ValueError("train_ease fits a ShallowAutoencoder, not %s" % type(self.model).__name__)
+    reg = ease.check_reg(self.model.reg if reg is None else reg)
+    ease.check_not_distributed()
+    n_hint = self.num_items
+    if n_hint is None and len(train_dataset.items):
+      n_hint = int(np.max(train_dataset.items)) + 1
+    if n_hint:
+      # (before init_model allocates the n x n parameter: a 1 M-item catalogue gets a ValueError, not an OOM)
+      ease.check_memory(n_hint, free_bytes=float("inf"))
+    log.info("EASE: reg %g", reg)
+    self.model.reg = reg
+    self.optimizer = self.sparse_optimizer = None
+    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    first = not self.__model_initialized
+    if first:
+      require_gpu()
+      ease.check_memory(n_hint or 1)                 # (the parameter itself is the n x n matrix)
+    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
+    pair = als.csr_pair(als.host_matrix(train_dataset), self.num_users, self.num_items, self.device)
+    _, info = ease.fit(pair, reg, out=self.model.item_weights.data)
+    self.ease_info = info
+    self._weights_written()
+    return {k: v for k, v in info.items() if k != "diag"}
 
   def _pick_engine_for(self, train_dataset):
     """Combinations the fused step does not cover train through the generic engine (torch autograd
@@ -1108,6 +1146,7 @@ class Recoder(object):
     ws = getattr(self, "_eval_ws", None)
     if ws is None or ws["n_items"] != n_items:
       ws = self._eval_ws = dict(n_items=n_items, blk=None, strips={}, scores=None, cand=None)
+    ws["dcsr"] = dcsr
     blk = ws["blk"]
     if blk is None or blk.S_cap < B or blk.nnz_cap < max(1, dcsr.nnz):
       blk = ws["blk"] = Block(max(B, blk.S_cap if blk else 0),
@@ -1125,6 +1164,10 @@ class Recoder(object):
     blk, B, n_items = self._input_block(users_interactions)
     ld = blk.ld_cap
     out = torch.empty(B, ld, dtype=torch.float32, device=self.device)
+    if isinstance(self.model, ShallowAutoencoder):
+      from . import ease
+      ease.scores(self._eval_ws["dcsr"], self.model.item_weights.data, 0, n_items, out=out, ld=ld, n_rows=B)
+      return out[:, :n_items], blk, B
     engine.predict_scores(blk, 0, B, out, ld, blk)
     return out[:, :n_items], blk, B
 
@@ -1161,18 +1204,20 @@ class Recoder(object):
     from .device import current_stream
     lib = _lib.load()
     engine = self._engine()
-    if getattr(engine, "generic", False) or k > lib.rk_topk_max_k():
+    ease_model = isinstance(self.model, ShallowAutoencoder)
+    if (getattr(engine, "generic", False) and not ease_model) or k > lib.rk_topk_max_k():
       return self._recommend_dense(users_interactions, k)
     blk, B, n_items = self._input_block(users_interactions)
     ws = self._eval_ws
-    z = engine.encode_eval(blk, 0, B)
+    z = None if ease_model else engine.encode_eval(blk, 0, B)
     strip = max(k, min(n_items, int(self.eval_strip_items)))
     bounds = [(lo, min(n_items, lo + strip)) for lo in range(0, n_items, strip)]
     if len(bounds) > 1 and bounds[-1][1] - bounds[-1][0] < k:      # a last strip shorter than k:
       lo0 = bounds[-2][0]                                         # merge it into the one before
       bounds = bounds[:-2] + [(lo0, n_items)]
     ns = len(bounds)
-    if ns > 1 and os.environ.get("RK_EVAL_FUSED", "1") != "0" and hasattr(engine, "recommend_fused"):
+    if ns > 1 and not ease_model and os.environ.get("RK_EVAL_FUSED", "1") != "0" and \
+        hasattr(engine, "recommend_fused"):
       # catalogues of more than one strip: the top-k filter rides in the decode's epilogue (no score
       # matrix, no passes over it): a strided sample of the catalogue bounds every row's k-th best
       # score from below, the decode over all items keeps only what reaches the bound
@@ -1195,6 +1240,14 @@ class Recoder(object):
     cand_idx, cand_val = ws["cand"][0][:B], ws["cand"][1][:B]
     scores = ws["scores"]
     for s, (lo, hi) in enumerate(bounds):
+      if ease_model:
+        # a ShallowAutoencoder's strip of scores: the users' CSR rows times item_weights[:, lo:hi]
+        from . import ease
+        ease.scores(ws["dcsr"], self.model.item_weights.data, lo, hi, out=scores, ld=ld, n_rows=B)
+        _lib.check(lib.rk_topk_masked(scores.data_ptr(), B, hi - lo, ld, blk.ref, 0, k, lo, 1,
+                                      cand_idx[:, s * k:].data_ptr(), cand_val[:, s * k:].data_ptr(),
+                                      ns * k, current_stream()), "rk_topk_masked")
+        continue
       key = (lo, hi, B)
       sblk = ws["strips"].get(key)
       if sblk is None:

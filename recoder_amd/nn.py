@@ -381,3 +381,74 @@ class VariationalAutoencoder(FactorizationModel):
     training mode); no autograd."""
     from .engine import ae_dense_forward
     return ae_dense_forward(self, input, input_items, target_items)
+
+
+class ShallowAutoencoder(FactorizationModel):
+  """EASE (Steck 2019, "Embarrassingly Shallow Autoencoders for Sparse Data"): the linear item-item
+  autoencoder ``scores = input @ item_weights`` with a zero diagonal, fitted in closed form by
+  ``Recoder.train_ease`` (recoder_amd/ease.py) -- ``B = -P / diag(P)`` by columns,
+  ``P = (X^T X + reg I)^-1``.
+
+  One parameter, ``item_weights`` [num_items, num_items], zero until fitted; ``reg`` travels in
+  ``model_params()``.  Gradient training would not keep the zero diagonal, so ``Recoder.train`` refuses
+  this model and points at ``train_ease``.
+  """
+
+  def __init__(self, reg=500.0):
+    super().__init__()
+    self.reg = reg
+    self.num_items = None
+    self.item_weights = None
+    self._validate()
+
+  def _validate(self):
+    if not float(self.reg) > 0.0 or float(self.reg) == float("inf"):
+      raise ValueError("ShallowAutoencoder needs a finite reg > 0 (got %r)" % (self.reg,))
+
+  def init_model(self, num_items=None, num_users=None):
+    self._validate()
+    self.num_items = num_items
+    self.item_weights = nn.Parameter(torch.zeros(num_items, num_items), requires_grad=False)
+
+  def model_params(self):
+    return {"reg": float(self.reg)}
+
+  def load_model_params(self, model_params):
+    self.reg = float(model_params["reg"])
+    self._validate()
+
+  def forward(self, input, input_users=None, input_items=None, target_users=None,
+              target_items=None):
+    """``input @ item_weights[input_items][:, target_items]`` on the HIP kernel (rk_ease_scores): the
+    dense input's non-zeros as a CSR over the catalogue, ascending; no autograd.  On the host
+    (no device tensors) it is ``torch_forward``."""
+    if not input.is_cuda:
+      with torch.no_grad():
+        return self.torch_forward(input, input_users, input_items, target_users, target_items)
+    from . import ease
+    from types import SimpleNamespace
+    n = self.item_weights.shape[0]
+    nz = input.nonzero()
+    rows, cols = nz[:, 0], nz[:, 1]
+    vals = input[rows, cols].to(torch.float32)
+    if input_items is not None:
+      cols = input_items.to(torch.int64)[cols]
+      order = torch.argsort(rows * n + cols)          # (ascending item ids inside a row)
+      rows, cols, vals = rows[order], cols[order], vals[order]
+    B = input.shape[0]
+    indptr = torch.zeros(B + 1, dtype=torch.int64, device=input.device)
+    indptr[1:] = torch.cumsum(torch.bincount(rows, minlength=B), 0)
+    indices = cols.to(torch.int32) if cols.numel() else torch.zeros(1, dtype=torch.int32, device=input.device)
+    csr = SimpleNamespace(indptr=indptr, indices=indices.contiguous(), data=vals.contiguous(), shape=(B, n))
+    out = ease.scores(csr, self.item_weights.data)
+    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
+
+  def torch_forward(self, input, input_users=None, input_items=None, target_users=None,
+                    target_items=None):
+    """The same forward in torch ops (the generic engine's validation loss; host tensors)."""
+    w = self.item_weights
+    if input_items is not None:
+      w = w.index_select(0, input_items.to(torch.int64))
+    if target_items is not None:
+      w = w.index_select(1, target_items.to(torch.int64))
+    return input.to(w.dtype) @ w
