@@ -85,6 +85,7 @@ class Recoder(object):
     self.last_epoch_losses = None
     self.loss_history = []      # per-epoch arrays of the per-step training losses
     self.als_history = []       # train_als: the ALS objective after each iteration
+    self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.__model_initialized = False
     self.__optimizer_state_dict = None
     self.__sparse_optimizer_state_dict = None
@@ -437,6 +438,45 @@ class Recoder(object):
                                m.bias.data, ucsr, icsr, alpha, float(reg), int(cg_steps), int(num_iterations))
     self._weights_written()
     return list(self.als_history)
+
+  def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
+    """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
+    (recoder_amd/svd.py): the item table becomes V, the top ``embedding_size`` right singular vectors of
+    the dataset's interaction matrix A (values as stored), the user table U = A V, the bias 0, so that a
+    user's scores are the row of ``A V V^T``.  V comes from a randomized SVD with a sketch of
+    ``embedding_size + oversample`` columns and ``num_power_iterations`` power iterations, seeded by
+    ``seed``; a fixed seed gives the same bits.  The configured ``loss`` plays no part.  Builds a fresh
+    optimizer of ``optimizer_type``, so that ``save_state``, ``train`` and ``train_als`` work on the
+    tables it leaves.  Returns (and keeps in ``svd_info``) h, l, nnz, the singular values, the
+    milliseconds of the sparse products and of the orthonormalisations (HIP events), those of the host's
+    eigendecomposition, and ``ritz_residual`` = max_k |A^T u_k - sigma_k^2 v_k| / sigma_1^2: flat spectra
+    converge slowly, and this is the signal to raise ``num_power_iterations``."""
+    from . import als, svd
+    h, l = svd.check_config(self.model, oversample, num_power_iterations, seed)
+    svd.check_not_distributed()
+    n_users, n_items = self.num_users, self.num_items
+    if n_users is None and len(train_dataset.users):
+      n_users = int(np.max(train_dataset.users)) + 1
+    if n_items is None and len(train_dataset.items):
+      n_items = int(np.max(train_dataset.items)) + 1
+    svd.check_rank(l, n_users or 0, n_items or 0)
+    svd.check_memory(n_users, n_items, l, 0, free_bytes=float("inf"))
+    log.info("PureSVD: h %d, l %d, %d power iterations, seed %d", h, l, num_power_iterations, seed)
+    # (a fresh optimizer: Adam moments of an earlier train() do not describe these tables)
+    self.optimizer = self.sparse_optimizer = None
+    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
+    svd.check_rank(l, self.num_users, self.num_items)
+    host = als.host_matrix(train_dataset)
+    svd.check_memory(self.num_users, self.num_items, l, host.nnz)
+    ucsr, icsr = als.csr_pair(host, self.num_users, self.num_items, self.device)
+    m = self.model
+    info = svd.fit(m.user_embedding_layer.weight.data, m.item_embedding_layer.weight.data, ucsr, icsr,
+                   int(oversample), int(num_power_iterations), int(seed))
+    m.bias.data.zero_()
+    self._weights_written()
+    self.svd_info = info
+    return dict(info)
 
   def train_ease(self, train_dataset, reg=None):
     """The closed-form EASE fit of a ShallowAutoencoder (recoder_amd/ease.py): ``item_weights`` becomes
