@@ -1,0 +1,101 @@
+/*
+ * recoder_rp3.h -- C ABI of librecoder_rp3.so (MI355X / gfx950 only).
+ *
+ * RP3beta (Paudel, Christoffel, Newell & Bernstein 2016, "Updatable, accurate, diverse, and scalable
+ * recommendations for interactive applications"; P3alpha: Cooper et al. 2014): a sparse item-item
+ * model from three-step random walks on the user-item graph.  The stored non-zero entries of the
+ * user x item matrix are the edges; their values play no part in the fit.  With r_v the number of
+ * items of user v, d_i the number of users of item i and U(i) the users of item i:
+ *   S_ij = sum over v in U(i) and U(j) of r_v^-alpha              (walk i -> v -> j)
+ *   W_ij = d_i^-alpha * S_ij * d_j^-beta   (j != i),   W_ii = 0
+ *   row i keeps its K largest W_ij > 0 by (W descending, j ascending); everything else is 0
+ *   scores(u, :) = x_u . W                                         (x_u: the user's stored values)
+ * The model is [n, K]: an n x n (or block x n) image of W never exists in device memory.
+ * A library of its own, beside the training, index, ALS, VAE, EASE and SVD libraries, so that none
+ * of their symbol sets changes; the Python binding is recoder_amd/_rp3_lib.py, the driver
+ * recoder_amd/rp3.py.
+ *
+ * Conventions (those of recoder_als.h / recoder_ease.h)
+ *   - every function returns 0 on success, <0 on error; rk_rp3_last_error() gives a
+ *     thread-local message.
+ *   - every pointer is a DEVICE pointer owned by the caller; nothing is retained past the call.
+ *   - every launch goes on the caller's hipStream_t (passed as void*); no call synchronises
+ *     the host; no call allocates (scratch comes from a workspace the caller sizes with the
+ *     *_workspace_bytes query).
+ *   - CSR: int64 indptr [rows + 1], int32 column indices ascending inside a row, without repeats.
+ *
+ * The three weight vectors of rk_rp3_fit are INPUTS, made on the host: no pow runs on the device.
+ * RP3beta passes user_w[v] = r_v^-alpha, row_scale[i] = d_i^-alpha, col_scale[j] = d_j^-beta.  The
+ * same kernel therefore also gives P3alpha (col_scale = 1, i.e. beta = 0) and weighted cosine kNN
+ * (user_w = 1, row_scale = col_scale = d^-1/2): the driver builds neither.
+ *
+ * Numerics (f32; every call is bitwise repeatable and a row's result depends on the data alone)
+ *   - S_ij is ONE f32 add chain from +0 of user_w[v] over the users v of item i, ascending, that also
+ *     hold j.  No atomics on data: a column belongs to one wave of the row's workgroup, and a wave
+ *     takes the users one after the other.
+ *   - W_ij = (row_scale[i] * S_ij) * col_scale[j]: two f32 roundings, in that order.
+ *   - selection: the K-th largest value is found exactly by radix selection on the float bits, ties
+ *     at that value go to the lower ids (a second radix selection on the ids), and the kept entries
+ *     are sorted by id.
+ *   - rk_rp3_scores: one ascending f32 fmaf chain per output, from +0, over the user's stored
+ *     entries: a score depends neither on the strip nor on the user's position in the batch.
+ */
+#ifndef RECODER_RP3_H
+#define RECODER_RP3_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* (the library is built with -fvisibility=hidden: what this header declares is what it exports) */
+#pragma GCC visibility push(default)
+
+int rk_rp3_version(void);
+const char *rk_rp3_last_error(void);
+
+/* the largest K of rk_rp3_fit / rk_rp3_scores (1024) */
+int rk_rp3_max_neighbours(void);
+
+/* the largest n_items whose row accumulators live in LDS; a larger catalogue keeps one n-float row
+ * (and one n-entry candidate list) per resident workgroup in the workspace */
+int rk_rp3_lds_items(void);
+
+/* bytes of workspace rk_rp3_fit needs for n_items (host arithmetic; > 0; < 0 on bad arguments) */
+int64_t rk_rp3_fit_workspace_bytes(int32_t n_items);
+
+/*
+ * Rows [row_lo, row_hi) of the model: one fused pass per source item i (accumulate, scale, select,
+ * compact).  (t_*): the item-major CSR (n_items rows, columns = users); (u_*): the user-major CSR
+ * (n_users rows, columns = items) of the SAME matrix.  user_w [n_users], row_scale [n_items] and
+ * col_scale [n_items] are >= 0.  1 <= K <= rk_rp3_max_neighbours(), 0 <= row_lo <= row_hi <= n_items.
+ *   nbr_ids   int32 [n_items, K]  the kept j of row i, ascending; -1 past nbr_count[i]
+ *   nbr_w     f32   [n_items, K]  their W_ij; +0 past nbr_count[i]
+ *   nbr_count int32 [n_items]     how many were kept (<= K)
+ * Rows outside [row_lo, row_hi) are not touched.  Rows are handed to the resident workgroups
+ * through one counter in the workspace, in ascending order: a row costs sum over v in U(i) of r_v,
+ * which differs by orders of magnitude, and a workgroup that finishes a light row takes the next.
+ * ws must be 256-byte aligned.
+ */
+int rk_rp3_fit(const int64_t *t_indptr, const int32_t *t_indices, const int64_t *u_indptr,
+               const int32_t *u_indices, int32_t n_users, int32_t n_items, const float *user_w,
+               const float *row_scale, const float *col_scale, int32_t K, int32_t row_lo, int32_t row_hi,
+               int32_t *nbr_ids, float *nbr_w, int32_t *nbr_count, void *ws, int64_t ws_bytes, void *stream);
+
+/*
+ * out[u][c] = sum over the entries (i, x_ui) of CSR row u, ascending, of x_ui * W[i][lo + c] for those
+ * i whose kept row contains lo + c, for u in [0, n_rows) and c in [0, hi - lo); columns nobody reaches
+ * are +0.  data NULL: every value is 1.0.  0 <= lo < hi <= n_items; an entry outside [0, n_items)
+ * adds nothing.  out [n_rows, ldo], ldo >= hi - lo; columns past hi - lo are left as they are.
+ * The layout is what rk_topk_masked reads.
+ */
+int rk_rp3_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
+                  int32_t n_items, const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count,
+                  int32_t K, int32_t lo, int32_t hi, float *out, int64_t ldo, void *stream);
+
+#pragma GCC visibility pop
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RECODER_RP3_H */

@@ -8,7 +8,7 @@ Drop-in for the reference's training path: ``Recoder`` / ``FactorizationModel``
 # in checkpoints as 'recoder_version' (model.py:207)
 __version__ = "0.4.0"
 
-__all__ = ["ShallowAutoencoder"]
+__all__ = ["ShallowAutoencoder", "RandomWalkItemModel"]
 
 
 def __getattr__(name):
@@ -16,4 +16,7 @@ def __getattr__(name):
   if name == "ShallowAutoencoder":
     from .nn import ShallowAutoencoder
     return ShallowAutoencoder
+  if name == "RandomWalkItemModel":
+    from .nn import RandomWalkItemModel
+    return RandomWalkItemModel
   raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,4 +1,5 @@
-"""Build the six HIP libraries (hand-written kernels + C ABI) for gfx950.
+"""Build the six HIP libraries of the training, index, ALS, VAE, EASE and SVD paths and a seventh for
+RP3beta (hand-written kernels + C ABI) for gfx950.
 
     python -m recoder_amd.build [--force]
 
@@ -13,6 +14,8 @@ librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencod
                    (include/recoder_ease.h), likewise a library of its own
 librecoder_svd.so  the randomized truncated SVD behind PureSVD for MatrixFactorization
                    (include/recoder_svd.h), likewise a library of its own
+librecoder_rp3.so  the RP3beta item-graph fit and its scores for RandomWalkItemModel
+                   (include/recoder_rp3.h), likewise a library of its own
 
 hipcc cross-compiles without a GPU; the built libraries stay in-tree
 (recoder_amd/csrc/*.so, git-ignored) so that they travel with the repository
@@ -29,12 +32,14 @@ ALS_LIB = os.path.join(CSRC, "librecoder_als.so")
 VAE_LIB = os.path.join(CSRC, "librecoder_vae.so")
 EASE_LIB = os.path.join(CSRC, "librecoder_ease.so")
 SVD_LIB = os.path.join(CSRC, "librecoder_svd.so")
+RP3_LIB = os.path.join(CSRC, "librecoder_rp3.so")
 SOURCES = ["capi.hip", "collate.hip", "encoder.hip", "gemm.hip", "decode16.hip", "linear.hip", "dw3.hip", "pgemm.hip", "fdecode.hip", "optim.hip", "topk.hip", "step.hip", "comm.hip"]
 INDEX_SOURCES = ["index.hip"]
 ALS_SOURCES = ["als.hip"]
 VAE_SOURCES = ["vae.hip"]
 EASE_SOURCES = ["ease.hip"]
 SVD_SOURCES = ["svd.hip"]
+RP3_SOURCES = ["rp3.hip"]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified register
 # file); without it hipcc copied all accumulators AGPR<->VGPR around every k-tile
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -95,9 +100,10 @@ def build_library(force=False, verbose=True):
   _build_one(EASE_LIB, EASE_SOURCES, [os.path.join(include, "recoder_ease.h")], force, verbose)
   # (svd.hip includes csrc/common.h for the counter RNG, as vae.hip does)
   _build_one(SVD_LIB, SVD_SOURCES, headers + [os.path.join(include, "recoder_svd.h")], force, verbose)
+  _build_one(RP3_LIB, RP3_SOURCES, [os.path.join(include, "recoder_rp3.h")], force, verbose)
   return LIB
 
 
 if __name__ == "__main__":
   build_library(force="--force" in sys.argv)
-  print("built", LIB, INDEX_LIB, ALS_LIB, VAE_LIB, EASE_LIB, SVD_LIB)
+  print("built", LIB, INDEX_LIB, ALS_LIB, VAE_LIB, EASE_LIB, SVD_LIB, RP3_LIB)

@@ -1,0 +1,422 @@
+// RP3beta: the sparse item-graph model (include/recoder_rp3.h, librecoder_rp3.so).
+//
+//   rk_rp3_fit     one workgroup (16 waves) per source item i at a time, rows handed out through a counter.
+//                  accumulate: every wave walks the users of item i in order and adds user_w[v] to the
+//                    columns of user v it owns (64-column granules, round robin over the waves): one add
+//                    chain per column, ascending users, no atomics on data.  The accumulators are a row in
+//                    LDS (n <= FT_LDS_ITEMS) or a row of the workspace; the workspace path also lists the
+//                    columns it touches (a column's first touch is seen from its -0 fill), so that
+//                    everything after costs the row's candidates, not n
+//                  scale: W = (row_scale[i] * S) * col_scale[j], the diagonal 0
+//                  select: radix selection (4 x 8 bits) of the K-th largest float, then of the id up to which
+//                    values equal to it are kept
+//                  compact: the kept entries gathered in LDS, sorted by id (bitonic), written with padding
+//   rk_rp3_scores  one workgroup per (user, tile of 8192 columns held in LDS); each of its 8 waves owns
+//                  1024 columns and walks the user's entries in order, adding x * w of the neighbours
+//                  that fall in its columns
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/recoder_rp3.h"
+
+static thread_local char g_rp3_err[512] = "";
+
+static void rp3_set_error(const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_rp3_err, sizeof(g_rp3_err), fmt, ap);
+  va_end(ap);
+}
+
+#define RP3_REQUIRE(cond, msg)                                             \
+  do {                                                                     \
+    if (!(cond)) {                                                         \
+      rp3_set_error("%s: %s", __func__, msg);                              \
+      return -2;                                                           \
+    }                                                                      \
+  } while (0)
+
+#define RP3_CHECK_LAUNCH(name)                                             \
+  do {                                                                     \
+    hipError_t e__ = hipGetLastError();                                    \
+    if (e__ != hipSuccess) {                                               \
+      rp3_set_error("%s: %s", name, hipGetErrorString(e__));               \
+      return -1;                                                           \
+    }                                                                      \
+  } while (0)
+
+namespace {
+
+// ------------------------------------------------------------------------ fit
+constexpr int FT_WAVES = 16;
+constexpr int FT_THREADS = FT_WAVES * 64;
+constexpr int FT_LDS_ITEMS = 12288;           // 48 KB of accumulators + 9 KB of selection state: two workgroups per CU
+constexpr int FT_MAX_K = 1024;
+constexpr int FT_GROUPS = 512;                // resident workgroups: two on each of the 256 CUs
+constexpr uint32_t FT_UNTOUCHED = 0x80000000u;    // -0: (first touch) 0 + w, bitwise the chain from +0
+
+inline int64_t ft_acc_stride(int n) { return ((int64_t)n + 63) / 64 * 64; }
+// entries of one wave's candidate list: the columns it owns (64 of every 1024, rounded up)
+inline int64_t ft_list_stride(int n) { return ((int64_t)n + 1023) / 1024 * 64; }
+
+__device__ inline uint32_t f2u(float v) { return __float_as_uint(v); }
+
+// Wave 0, all 64 lanes: the bin in which the need-th element falls, counting from bin 255 down (desc)
+// or from bin 0 up.  o[0] = bin (-1: fewer than need elements), o[1] = its rank inside the bin (1-based),
+// o[2] = the bin's count, o[3] = the total.
+__device__ void ft_pick(const int *hist, int need, int lane, bool desc, int *o) {
+  int h[4], s = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = 4 * lane + q;
+    h[q] = hist[desc ? 255 - r : r];
+    s += h[q];
+  }
+  int incl = s;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += t;
+  }
+  const int total = __shfl(incl, 63, 64);
+  if (lane == 0) o[3] = total;
+  if (total < need) {
+    if (lane == 0) o[0] = -1;
+    return;
+  }
+  int run = incl - s;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (run < need && need <= run + h[q]) {
+      const int r = 4 * lane + q;
+      o[0] = desc ? 255 - r : r;
+      o[1] = need - run;
+      o[2] = h[q];
+    }
+    run += h[q];
+  }
+}
+
+template <bool WS>
+__global__ __launch_bounds__(FT_THREADS) void rp3_fit_kernel(
+    const int64_t *__restrict__ t_indptr, const int32_t *__restrict__ t_indices,
+    const int64_t *__restrict__ u_indptr, const int32_t *__restrict__ u_indices, int n_users, int n,
+    const float *__restrict__ user_w, const float *__restrict__ row_scale, const float *__restrict__ col_scale,
+    int K, int row_lo, int row_hi, int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_w,
+    int32_t *__restrict__ nbr_count, int *counter, float *ws_acc, int *ws_cand, int64_t acc_stride, int ch) {
+  __shared__ float lds_acc[WS ? 1 : FT_LDS_ITEMS];
+  __shared__ int kid[FT_MAX_K];
+  __shared__ float kw[FT_MAX_K];
+  __shared__ int hist[256];
+  __shared__ int wcnt[FT_WAVES];
+  __shared__ int sh[8];          // 0: the row's offset; 1..4: ft_pick's answer; 5: entries gathered
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float *acc = WS ? ws_acc + (int64_t)blockIdx.x * acc_stride : lds_acc;
+  int *cand = WS ? ws_cand + (int64_t)blockIdx.x * FT_WAVES * ch : nullptr;
+  int *mylist = WS ? cand + (int64_t)wv * ch : nullptr;
+
+  auto for_cands = [&](auto f) {
+    if (!WS) {
+      for (int j = tid; j < n; j += FT_THREADS) f(j);
+    } else {
+#pragma unroll 1
+      for (int w = 0; w < FT_WAVES; ++w) {
+        const int c = wcnt[w];
+        const int *L = cand + (int64_t)w * ch;
+        for (int s = tid; s < c; s += FT_THREADS) f(L[s]);
+      }
+    }
+  };
+
+  if (WS)
+    for (int c = tid; c < n; c += FT_THREADS) acc[c] = -0.f;
+
+  for (;;) {
+    __syncthreads();
+    if (tid == 0) sh[0] = atomicAdd(counter, 1);
+    __syncthreads();
+    const int64_t i64 = (int64_t)row_lo + sh[0];
+    if (i64 >= row_hi) break;
+    const int i = (int)i64;
+    if (!WS) {
+      for (int c = tid; c < n; c += FT_THREADS) acc[c] = 0.f;
+      __syncthreads();
+    }
+
+    // ---- accumulate: (user, row start, row end, weight) fetched 64 at a time, as rk_ease_gram does
+    int mycnt = 0;
+    const int64_t e0 = t_indptr[i], e1 = t_indptr[i + 1];
+    for (int64_t eb = e0; eb < e1; eb += 64) {
+      const int cnt = e1 - eb < 64 ? (int)(e1 - eb) : 64;
+      int64_t r0 = 0, r1 = 0;
+      float uw = 0.f;
+      if (lane < cnt) {
+        const int u = t_indices[eb + lane];
+        if (u >= 0 && u < n_users) {           // (a bad index reads nothing)
+          r0 = u_indptr[u];
+          r1 = u_indptr[u + 1];
+          uw = user_w[u];
+        }
+      }
+      for (int l = 0; l < cnt; ++l) {
+        const int64_t p0 = __shfl(r0, l, 64), p1 = __shfl(r1, l, 64);
+        const float w = __shfl(uw, l, 64);
+        for (int64_t p = p0; p < p1; p += 64) {       // (wave-uniform bounds)
+          const int64_t q = p + lane;
+          int c = 0;
+          bool mine = false;
+          if (q < p1) {
+            c = u_indices[q];
+            mine = c >= 0 && c < n && ((c >> 6) & (FT_WAVES - 1)) == wv;
+          }
+          if (WS) {
+            // columns of one user are distinct: no two lanes meet.  The next user's adds may come from
+            // other lanes of this wave: the fence keeps them behind these stores
+            bool first = false;
+            if (mine) {
+              const float old = acc[c];
+              first = f2u(old) == FT_UNTOUCHED;
+              acc[c] = (first ? 0.f : old) + w;
+            }
+            const unsigned long long m = __ballot(first);
+            if (first) {
+              const int pos = mycnt + __popcll(m & ((1ull << lane) - 1ull));
+              if (pos < ch) mylist[pos] = c;
+            }
+            mycnt += __popcll(m);
+            __threadfence_block();
+          } else {
+            if (mine) acc[c] += w;
+          }
+        }
+      }
+    }
+    if (WS && lane == 0) wcnt[wv] = mycnt < ch ? mycnt : ch;
+    if (tid < 256) hist[tid] = 0;
+    if (tid == 0) sh[5] = 0;
+    __syncthreads();
+
+    // ---- scale, and the histogram of the top byte
+    const float rs = row_scale[i];
+    for_cands([&](int j) {
+      float w = __fmul_rn(__fmul_rn(rs, acc[j]), col_scale[j]);
+      if (j == i) w = 0.f;
+      acc[j] = w;
+      if (w > 0.f) atomicAdd(&hist[f2u(w) >> 24], 1);
+    });
+    __syncthreads();
+
+    // ---- select: T = the K-th largest value's bits, need = how many equal to T are kept, J = up to which id
+    uint32_t T = 0, tmask = 0;
+    int need = K, J = INT_MAX;
+    bool all = false;
+#pragma unroll 1
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      if (shift != 24) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for_cands([&](int j) {
+          const float w = acc[j];
+          const uint32_t k = f2u(w);
+          if (w > 0.f && (k & tmask) == T) atomicAdd(&hist[(k >> shift) & 255], 1);
+        });
+        __syncthreads();
+      }
+      if (wv == 0) ft_pick(hist, need, lane, true, sh + 1);
+      __syncthreads();
+      if (shift == 24 && sh[4] <= K) {
+        all = true;
+        break;
+      }
+      T |= (uint32_t)sh[1] << shift;
+      tmask |= 255u << shift;
+      need = sh[2];
+    }
+    if (!all && sh[3] > need) {
+      uint32_t jp = 0, jm = 0;
+#pragma unroll 1
+      for (int shift = 24; shift >= 0; shift -= 8) {
+        if (((uint32_t)(n - 1) >> shift) != 0) {      // (otherwise: every id has zeros here)
+          if (tid < 256) hist[tid] = 0;
+          __syncthreads();
+          for_cands([&](int j) {
+            if (f2u(acc[j]) == T && ((uint32_t)j & jm) == jp) atomicAdd(&hist[((uint32_t)j >> shift) & 255], 1);
+          });
+          __syncthreads();
+          if (wv == 0) ft_pick(hist, need, lane, false, sh + 1);
+          __syncthreads();
+          jp |= (uint32_t)sh[1] << shift;
+          need = sh[2];
+        }
+        jm |= 255u << shift;
+      }
+      J = (int)jp;
+    }
+
+    // ---- compact: gather (any order), sort by id, store
+    for_cands([&](int j) {
+      const float w = acc[j];
+      const uint32_t k = f2u(w);
+      if (w > 0.f && (all || k > T || (k == T && j <= J))) {
+        const int pos = atomicAdd(&sh[5], 1);
+        if (pos < FT_MAX_K) {
+          kid[pos] = j;
+          kw[pos] = w;
+        }
+      }
+    });
+    __syncthreads();
+    const int kept = sh[5] < K ? sh[5] : K;
+    int P = 1;
+    while (P < kept) P <<= 1;
+    if (tid >= kept && tid < P) kid[tid] = INT_MAX;
+    __syncthreads();
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+      for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
+        const int o = tid ^ j2;
+        if (tid < P && o > tid) {
+          const int a = kid[tid], b = kid[o];
+          if ((a > b) == ((tid & k2) == 0)) {
+            kid[tid] = b;
+            kid[o] = a;
+            const float wa = kw[tid];
+            kw[tid] = kw[o];
+            kw[o] = wa;
+          }
+        }
+        __syncthreads();
+      }
+    for (int c = tid; c < K; c += FT_THREADS) {
+      nbr_ids[(int64_t)i * K + c] = c < kept ? kid[c] : -1;
+      nbr_w[(int64_t)i * K + c] = c < kept ? kw[c] : 0.f;
+    }
+    if (tid == 0) nbr_count[i] = kept;
+    if (WS) for_cands([&](int j) { acc[j] = -0.f; });
+  }
+}
+
+// --------------------------------------------------------------------- scores
+constexpr int SC_WAVES = 8;
+constexpr int SC_SUB = 1024;                  // columns a wave owns
+constexpr int SC_TILE = SC_WAVES * SC_SUB;    // 32 KB of LDS
+
+__global__ __launch_bounds__(SC_WAVES * 64) void rp3_scores_kernel(
+    const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const float *__restrict__ data,
+    int n_items, const int32_t *__restrict__ nbr_ids, const float *__restrict__ nbr_w,
+    const int32_t *__restrict__ nbr_count, int K, int lo, int width, float *__restrict__ out, int64_t ldo) {
+  __shared__ float tile[SC_TILE];
+  const int u = blockIdx.x;                             // (users fastest: neighbours share a column tile)
+  const int t0 = blockIdx.y * SC_TILE;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t wlo = (int64_t)lo + t0 + wv * SC_SUB;
+  const int64_t whi = wlo + SC_SUB < (int64_t)lo + width ? wlo + SC_SUB : (int64_t)lo + width;
+  float *mine = tile + wv * SC_SUB;
+  for (int c = lane; c < SC_SUB; c += 64) mine[c] = 0.f;
+  if (wlo < whi) {
+    const int64_t e0 = indptr[u], e1 = indptr[u + 1];
+    for (int64_t eb = e0; eb < e1; eb += 64) {
+      const int cnt = e1 - eb < 64 ? (int)(e1 - eb) : 64;
+      int it = 0, nc = 0;
+      float xv = 0.f;
+      if (lane < cnt) {
+        it = indices[eb + lane];
+        if (it >= 0 && it < n_items) {         // (a bad index adds nothing)
+          nc = nbr_count[it];
+          nc = nc < 0 ? 0 : (nc > K ? K : nc);
+          xv = data ? data[eb + lane] : 1.f;
+        }
+      }
+      for (int l = 0; l < cnt; ++l) {
+        const int c = __shfl(nc, l, 64);
+        const float x = __shfl(xv, l, 64);
+        const int64_t base = (int64_t)__shfl(it, l, 64) * K;
+        for (int s = lane; s < c; s += 64) {            // ids of one row are distinct: no two lanes meet
+          const int j = nbr_ids[base + s];
+          if (j >= wlo && j < whi) mine[j - wlo] = fmaf(x, nbr_w[base + s], mine[j - wlo]);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int w = width - t0 < SC_TILE ? width - t0 : SC_TILE;
+  float *row = out + (int64_t)u * ldo + t0;
+  for (int c = threadIdx.x; c < w; c += SC_WAVES * 64) row[c] = tile[c];
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------ ABI
+extern "C" {
+
+int rk_rp3_version(void) { return 100; }
+
+const char *rk_rp3_last_error(void) { return g_rp3_err; }
+
+int rk_rp3_max_neighbours(void) { return FT_MAX_K; }
+
+int rk_rp3_lds_items(void) { return FT_LDS_ITEMS; }
+
+int64_t rk_rp3_fit_workspace_bytes(int32_t n_items) {
+  if (n_items < 1) {
+    rp3_set_error("%s: n_items must be >= 1", __func__);
+    return -2;
+  }
+  if (n_items <= FT_LDS_ITEMS) return 256;
+  return 256 + (int64_t)FT_GROUPS * (ft_acc_stride(n_items) + FT_WAVES * ft_list_stride(n_items)) * 4;
+}
+
+int rk_rp3_fit(const int64_t *t_indptr, const int32_t *t_indices, const int64_t *u_indptr,
+               const int32_t *u_indices, int32_t n_users, int32_t n_items, const float *user_w,
+               const float *row_scale, const float *col_scale, int32_t K, int32_t row_lo, int32_t row_hi,
+               int32_t *nbr_ids, float *nbr_w, int32_t *nbr_count, void *ws, int64_t ws_bytes, void *stream) {
+  RP3_REQUIRE(t_indptr && t_indices && u_indptr && u_indices && user_w && row_scale && col_scale && nbr_ids &&
+                  nbr_w && nbr_count && ws, "null pointer");
+  RP3_REQUIRE(n_users >= 0 && n_items >= 1 && n_items < INT_MAX - 2048, "bad sizes");
+  RP3_REQUIRE(K >= 1 && K <= FT_MAX_K, "K outside [1, rk_rp3_max_neighbours()]");
+  RP3_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= n_items, "bad row range");
+  RP3_REQUIRE(ws_bytes >= rk_rp3_fit_workspace_bytes(n_items), "workspace too small");
+  RP3_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
+  if (row_lo == row_hi) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  int *counter = (int *)ws;
+  if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
+    rp3_set_error("%s: hipMemsetAsync failed", __func__);
+    return -1;
+  }
+  const int rows = row_hi - row_lo;
+  const int groups = rows < FT_GROUPS ? rows : FT_GROUPS;
+  if (n_items <= FT_LDS_ITEMS) {
+    hipLaunchKernelGGL(rp3_fit_kernel<false>, dim3(groups), dim3(FT_THREADS), 0, s, t_indptr, t_indices, u_indptr,
+                       u_indices, n_users, n_items, user_w, row_scale, col_scale, K, row_lo, row_hi, nbr_ids, nbr_w,
+                       nbr_count, counter, (float *)nullptr, (int *)nullptr, (int64_t)0, 0);
+  } else {
+    const int64_t stride = ft_acc_stride(n_items), ch = ft_list_stride(n_items);
+    float *acc = (float *)((char *)ws + 256);
+    int *cand = (int *)(acc + (int64_t)FT_GROUPS * stride);
+    hipLaunchKernelGGL(rp3_fit_kernel<true>, dim3(groups), dim3(FT_THREADS), 0, s, t_indptr, t_indices, u_indptr,
+                       u_indices, n_users, n_items, user_w, row_scale, col_scale, K, row_lo, row_hi, nbr_ids, nbr_w,
+                       nbr_count, counter, acc, cand, stride, (int)ch);
+  }
+  RP3_CHECK_LAUNCH("rp3_fit_kernel");
+  return 0;
+}
+
+int rk_rp3_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
+                  int32_t n_items, const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count,
+                  int32_t K, int32_t lo, int32_t hi, float *out, int64_t ldo, void *stream) {
+  RP3_REQUIRE(indptr && indices && nbr_ids && nbr_w && nbr_count && out, "null pointer");
+  RP3_REQUIRE(n_rows >= 0 && n_items >= 1 && K >= 1 && K <= FT_MAX_K, "bad sizes");
+  RP3_REQUIRE(0 <= lo && lo < hi && hi <= n_items && ldo >= hi - lo, "bad strip");
+  if (n_rows == 0) return 0;
+  const int width = hi - lo;
+  const dim3 grid(n_rows, (width + SC_TILE - 1) / SC_TILE);
+  hipLaunchKernelGGL(rp3_scores_kernel, grid, dim3(SC_WAVES * 64), 0, (hipStream_t)stream, indptr, indices, data,
+                     n_items, nbr_ids, nbr_w, nbr_count, K, lo, width, out, ldo);
+  RP3_CHECK_LAUNCH("rp3_scores_kernel");
+  return 0;
+}
+
+}  // extern "C"

@@ -33,8 +33,8 @@ from .device import Block, DeviceCSR, require_gpu
 from .engine import FusedEngine
 from .losses import MSELoss, MultinomialNLLLoss
 from .metrics import RecommenderEvaluator
-from .nn import (DynamicAutoencoder, FactorizationModel, MatrixFactorization, ShallowAutoencoder,
-                 VariationalAutoencoder)
+from .nn import (DynamicAutoencoder, FactorizationModel, MatrixFactorization, RandomWalkItemModel,
+                 ShallowAutoencoder, VariationalAutoencoder)
 from .recommender import InferenceRecommender
 
 log = logging.getLogger("recoder_amd")
@@ -86,6 +86,7 @@ class Recoder(object):
     self.loss_history = []      # per-epoch arrays of the per-step training losses
     self.als_history = []       # train_als: the ALS objective after each iteration
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
+    self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.__model_initialized = False
     self.__optimizer_state_dict = None
     self.__sparse_optimizer_state_dict = None
@@ -370,6 +371,9 @@ class Recoder(object):
     if isinstance(self.model, ShallowAutoencoder):
       raise ValueError("a ShallowAutoencoder is fitted in closed form: call train_ease(train_dataset) "
                        "(gradient steps would not keep its zero diagonal)")
+    if isinstance(self.model, RandomWalkItemModel):
+      raise ValueError("a RandomWalkItemModel is fitted in closed form from the interaction graph: call "
+                       "train_rp3beta(train_dataset)")
     if num_sampling_users == 0:
       num_sampling_users = batch_size
     if eval_batch_size is None:
@@ -511,6 +515,49 @@ class Recoder(object):
     self.ease_info = info
     self._weights_written()
     return {k: v for k, v in info.items() if k != "diag"}
+
+  def train_rp3beta(self, train_dataset, alpha=None, beta=None, neighbours=None):
+    """The closed-form RP3beta fit of a RandomWalkItemModel (recoder_amd/rp3.py): every item keeps its
+    ``neighbours`` largest ``W[i, j] = d_i^-alpha * (sum over the users v of i and j of r_v^-alpha) * d_j^-beta``
+    over the dataset's interaction graph (the stored entries are the edges; their values play no part
+    in the fit, they weigh the user's history when scoring).  ``None`` takes the model's value; explicit
+    values are stored back into the model, so that a checkpoint's ``model_params`` describe the weights it
+    holds, and another ``neighbours`` re-allocates the model's tensors.  The configured ``loss`` plays no
+    part.  Builds a fresh optimizer of ``optimizer_type`` so that ``save_state`` works.  Returns
+    ``info``: n, nnz, alpha, beta, neighbours, kept (entries kept over all rows) and fit_ms (HIP events)."""
+    from . import als, rp3
+    m = self.model
+    if not isinstance(m, RandomWalkItemModel):
+      raise ValueError("train_rp3beta fits a RandomWalkItemModel, not %s" % type(m).__name__)
+    alpha, beta, K = rp3.check_config(m, m.alpha if alpha is None else alpha, m.beta if beta is None else beta,
+                                      m.neighbours if neighbours is None else neighbours)
+    rp3.check_not_distributed()
+    n_hint, u_hint = self.num_items, self.num_users
+    if n_hint is None and len(train_dataset.items):
+      n_hint = int(np.max(train_dataset.items)) + 1
+    if u_hint is None and len(train_dataset.users):
+      u_hint = int(np.max(train_dataset.users)) + 1
+    if n_hint:
+      # (before init_model allocates: a catalogue that cannot fit gets a ValueError, not an OOM)
+      rp3.check_memory(u_hint or 0, n_hint, K, 0, free_bytes=float("inf"))
+    log.info("RP3beta: alpha %g, beta %g, %d neighbours", alpha, beta, K)
+    m.alpha, m.beta = alpha, beta
+    self.optimizer = self.sparse_optimizer = None
+    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    if not self.__model_initialized:
+      require_gpu()
+      m.neighbours = K
+    elif K != m.item_weights.shape[1]:
+      m.allocate(K, self.device)
+    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
+    m = self.model
+    host = als.host_matrix(train_dataset)
+    rp3.check_memory(self.num_users, self.num_items, K, host.nnz, allocate_model=False)
+    pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
+    _, _, _, info = rp3.fit(pair, alpha, beta, K, out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))
+    self.rp3_info = info
+    self._weights_written()
+    return dict(info)
 
   def _pick_engine_for(self, train_dataset):
     """Combinations the fused step does not cover train through the generic engine (torch autograd
@@ -1208,6 +1255,12 @@ class Recoder(object):
       from . import ease
       ease.scores(self._eval_ws["dcsr"], self.model.item_weights.data, 0, n_items, out=out, ld=ld, n_rows=B)
       return out[:, :n_items], blk, B
+    if isinstance(self.model, RandomWalkItemModel):
+      from . import rp3
+      m = self.model
+      rp3.scores(self._eval_ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, 0, n_items,
+                 out=out, ld=ld, n_rows=B)
+      return out[:, :n_items], blk, B
     engine.predict_scores(blk, 0, B, out, ld, blk)
     return out[:, :n_items], blk, B
 
@@ -1244,7 +1297,8 @@ class Recoder(object):
     from .device import current_stream
     lib = _lib.load()
     engine = self._engine()
-    ease_model = isinstance(self.model, ShallowAutoencoder)
+    rp3_model = isinstance(self.model, RandomWalkItemModel)
+    ease_model = isinstance(self.model, ShallowAutoencoder) or rp3_model     # (scores from the CSR rows, no encoder)
     if (getattr(engine, "generic", False) and not ease_model) or k > lib.rk_topk_max_k():
       return self._recommend_dense(users_interactions, k)
     blk, B, n_items = self._input_block(users_interactions)
@@ -1281,9 +1335,15 @@ class Recoder(object):
     scores = ws["scores"]
     for s, (lo, hi) in enumerate(bounds):
       if ease_model:
-        # a ShallowAutoencoder's strip of scores: the users' CSR rows times item_weights[:, lo:hi]
-        from . import ease
-        ease.scores(ws["dcsr"], self.model.item_weights.data, lo, hi, out=scores, ld=ld, n_rows=B)
+        # a ShallowAutoencoder's or RandomWalkItemModel's strip of scores: the users' CSR rows times W[:, lo:hi]
+        if rp3_model:
+          from . import rp3
+          m = self.model
+          rp3.scores(ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, lo, hi, out=scores,
+                     ld=ld, n_rows=B)
+        else:
+          from . import ease
+          ease.scores(ws["dcsr"], self.model.item_weights.data, lo, hi, out=scores, ld=ld, n_rows=B)
         _lib.check(lib.rk_topk_masked(scores.data_ptr(), B, hi - lo, ld, blk.ref, 0, k, lo, 1,
                                       cand_idx[:, s * k:].data_ptr(), cand_val[:, s * k:].data_ptr(),
                                       ns * k, current_stream()), "rk_topk_masked")

@@ -452,3 +452,102 @@ class ShallowAutoencoder(FactorizationModel):
     if target_items is not None:
       w = w.index_select(1, target_items.to(torch.int64))
     return input.to(w.dtype) @ w
+
+
+class RandomWalkItemModel(FactorizationModel):
+  """RP3beta (Paudel, Christoffel, Newell & Bernstein 2016): a sparse item-item model from three-step
+  random walks on the user-item graph, ``scores = input @ W`` with
+  ``W[i, j] = d_i^-alpha * (sum over the users v of i and j of r_v^-alpha) * d_j^-beta`` off the diagonal,
+  every row cut to its ``neighbours`` largest entries, fitted by ``Recoder.train_rp3beta``
+  (recoder_amd/rp3.py).  ``beta`` is the popularity penalty and matters: too large a value ranks by
+  rarity alone.
+
+  Three tensors, all in ``state_dict()``: ``item_neighbours`` int32 [num_items, neighbours] (the kept j
+  of every row, ascending, -1 where a row has fewer), ``item_weights`` f32 of the same shape and
+  ``neighbour_counts`` int32 [num_items]; empty until fitted.  ``alpha``, ``beta`` and ``neighbours``
+  travel in ``model_params()``.  The fit is closed-form: ``Recoder.train`` refuses this model and points
+  at ``train_rp3beta``.
+  """
+
+  def __init__(self, alpha=0.6, beta=0.3, neighbours=100):
+    super().__init__()
+    self.alpha = alpha
+    self.beta = beta
+    self.neighbours = neighbours
+    self.num_items = None
+    self.item_weights = None
+    self._validate()
+
+  def _validate(self):
+    from .rp3 import check_params
+    self.alpha, self.beta, self.neighbours = check_params(self.alpha, self.beta, self.neighbours)
+
+  def init_model(self, num_items=None, num_users=None):
+    self._validate()
+    self.num_items = num_items
+    self.allocate(self.neighbours, None)
+
+  def allocate(self, neighbours, device):
+    """(Re-)create the three tensors for ``neighbours`` columns: no neighbours, zero weights."""
+    n, K = self.num_items, int(neighbours)
+    self.neighbours = K
+    self._buffers.pop("item_neighbours", None)
+    self._buffers.pop("neighbour_counts", None)
+    self.register_buffer("item_neighbours", torch.full((n, K), -1, dtype=torch.int32, device=device))
+    self.item_weights = nn.Parameter(torch.zeros(n, K, device=device), requires_grad=False)
+    self.register_buffer("neighbour_counts", torch.zeros(n, dtype=torch.int32, device=device))
+
+  def model_params(self):
+    return {"alpha": float(self.alpha), "beta": float(self.beta), "neighbours": int(self.neighbours)}
+
+  def load_model_params(self, model_params):
+    self.alpha = float(model_params["alpha"])
+    self.beta = float(model_params["beta"])
+    self.neighbours = int(model_params["neighbours"])
+    self._validate()
+
+  def dense_weights(self, dtype=torch.float32):
+    """W [num_items, num_items]: the kept entries scattered into a dense matrix (small catalogues only)."""
+    n, K = self.item_weights.shape
+    W = torch.zeros(n, n, dtype=dtype, device=self.item_weights.device)
+    ids = self.item_neighbours.to(torch.int64)
+    live = torch.arange(K, device=ids.device)[None, :] < self.neighbour_counts.to(torch.int64)[:, None]
+    rows = torch.arange(n, device=ids.device)[:, None].expand(n, K)
+    W[rows[live], ids[live]] = self.item_weights.data.to(dtype)[live]
+    return W
+
+  def forward(self, input, input_users=None, input_items=None, target_users=None,
+              target_items=None):
+    """``input @ W[input_items][:, target_items]`` on the HIP kernel (rk_rp3_scores): the dense input's
+    non-zeros as a CSR over the catalogue, ascending; no autograd.  On the host (no device tensors)
+    it is ``torch_forward``."""
+    if not input.is_cuda:
+      with torch.no_grad():
+        return self.torch_forward(input, input_users, input_items, target_users, target_items)
+    from . import rp3
+    from types import SimpleNamespace
+    n = self.item_weights.shape[0]
+    nz = input.nonzero()
+    rows, cols = nz[:, 0], nz[:, 1]
+    vals = input[rows, cols].to(torch.float32)
+    if input_items is not None:
+      cols = input_items.to(torch.int64)[cols]
+      order = torch.argsort(rows * n + cols)          # (ascending item ids inside a row)
+      rows, cols, vals = rows[order], cols[order], vals[order]
+    B = input.shape[0]
+    indptr = torch.zeros(B + 1, dtype=torch.int64, device=input.device)
+    indptr[1:] = torch.cumsum(torch.bincount(rows, minlength=B), 0)
+    indices = cols.to(torch.int32) if cols.numel() else torch.zeros(1, dtype=torch.int32, device=input.device)
+    csr = SimpleNamespace(indptr=indptr, indices=indices.contiguous(), data=vals.contiguous(), shape=(B, n))
+    out = rp3.scores(csr, self.item_neighbours, self.item_weights.data, self.neighbour_counts)
+    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
+
+  def torch_forward(self, input, input_users=None, input_items=None, target_users=None,
+                    target_items=None):
+    """The same forward in torch ops: the kept entries scattered into a dense W (host tensors)."""
+    w = self.dense_weights()
+    if input_items is not None:
+      w = w.index_select(0, input_items.to(torch.int64))
+    if target_items is not None:
+      w = w.index_select(1, target_items.to(torch.int64))
+    return input.to(w.dtype) @ w
