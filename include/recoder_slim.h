@@ -1,0 +1,114 @@
+/*
+ * recoder_slim.h -- C ABI of librecoder_slim.so (MI355X / gfx950 only).
+ *
+ * SLIM (Ning & Karypis 2011, "SLIM: Sparse Linear Methods for Top-N Recommender Systems"): the learned
+ * sparse item-item model.  With G = X^T X over the stored values of the user x item matrix (values >= 0),
+ * column j of W solves
+ *   min over w >= 0, w_j = 0 of   1/2 |x_j - X w|^2 + (l2/2) |w|^2 + l1 |w|_1
+ * by cyclic coordinate descent in the covariance-update form of Friedman, Hastie & Tibshirani 2010
+ * ("Regularization paths for generalized linear models via coordinate descent"), a column keeps at most
+ * K entries, and scores(u, :) = x_u . W.  The model is stored by COLUMN: [n, K] ids / weights and [n]
+ * counts.  A library of its own, beside the training, index, ALS, VAE, EASE, SVD and RP3beta libraries,
+ * so that none of their symbol sets changes; the Python binding is recoder_amd/_slim_lib.py, the driver
+ * recoder_amd/slim.py.
+ *
+ * Conventions (those of recoder_rp3.h)
+ *   - every function returns 0 on success, <0 on error; rk_slim_last_error() gives a
+ *     thread-local message.
+ *   - every pointer is a DEVICE pointer owned by the caller; nothing is retained past the call.
+ *   - every launch goes on the caller's hipStream_t (passed as void*); no call synchronises
+ *     the host; no call allocates (scratch comes from a workspace the caller sizes with the
+ *     *_workspace_bytes query).
+ *   - CSR: int64 indptr [rows + 1], int32 column indices ascending inside a row, without repeats.
+ *
+ * Screening (exact, not a heuristic).  The update of coordinate k of column j thresholds
+ *   t_k = G_jk - sum over m != k of G_km w_m.
+ * With G >= 0 (the values are >= 0) and w >= 0 (the constraint) the sum is >= 0, so t_k <= G_jk at every
+ * point of every sweep.  A k with G_jk <= l1 therefore has t_k <= l1 for ever: its weight is 0 at the
+ * start and no update ever moves it, and a coordinate at 0 changes nothing for the others.  The
+ * candidates of column j are {k != j : G[j][k] > l1}, in ascending k; everything else is never visited,
+ * and the result is the one of the sweep over all k != j.
+ *
+ * The algorithm (f32; no reductions anywhere; every call is bitwise repeatable and a column's result
+ * depends on G, inv_denom, l1, K, max_sweeps and tol alone)
+ *   state    w[c] = +0 and q[c] = G[j][cand[c]] for every candidate c      (q_c = G_jk - sum_m G_km w_m,
+ *            the own term included)
+ *   a sweep  for c ascending, k = cand[c]:
+ *              t   = fmaf(G[k][k], w[c], q[c])
+ *              new = (t > l1) ? (t - l1) * inv_denom[k] : +0        (one f32 subtraction, one f32 multiply)
+ *              d   = new - w[c]
+ *              d != 0:  q[c'] = fmaf(-d, G[k][cand[c']], q[c']) for every candidate c' (c included; row k
+ *                       of G is read: the Gram is symmetric), then w[c] = new
+ *   stop     after the first sweep whose max |d| (f32) is <= tol, or after max_sweeps sweeps; a column
+ *            without candidates runs no sweep.  Every loop is bounded by max_sweeps x candidates.
+ *   cut      the support is {c : w[c] > 0}; a support larger than K keeps its K largest by (w descending,
+ *            id ascending), without a refit; the kept entries are stored with ascending ids.
+ * inv_denom [n] is an INPUT, made on the host as 1 / (float64(G_kk) + l2) rounded once to f32: no division
+ * runs on the device and l2 enters nowhere else.
+ *
+ * rk_slim_scores: one ascending f32 fmaf chain per output, from +0, over the kept entries of the output's
+ * column: a score depends neither on the strip nor on the user's position in the batch.
+ */
+#ifndef RECODER_SLIM_H
+#define RECODER_SLIM_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* (the library is built with -fvisibility=hidden: what this header declares is what it exports) */
+#pragma GCC visibility push(default)
+
+int rk_slim_version(void);
+const char *rk_slim_last_error(void);
+
+/* the largest K of rk_slim_fit / rk_slim_scores (1024) */
+int rk_slim_max_neighbours(void);
+
+/* the largest candidate count of a column whose state (cand, q, w, G_kk, inv_denom) lives in LDS; a column
+ * with more candidates keeps it in its workgroup's slice of the workspace.  The result does not depend
+ * on where the state lives. */
+int rk_slim_lds_candidates(void);
+
+/* bytes of workspace rk_slim_fit needs for n_items (host arithmetic; > 0; < 0 on bad arguments) */
+int64_t rk_slim_fit_workspace_bytes(int32_t n_items);
+
+/*
+ * Columns [col_lo, col_hi) of the model.  G [n_items, ldg] f32 is the symmetric Gram (ldg >= n_items),
+ * inv_denom [n_items] f32 as above; l1 >= 0, tol >= 0, max_sweeps >= 1, 1 <= K <= rk_slim_max_neighbours(),
+ * 0 <= col_lo <= col_hi <= n_items.
+ *   nbr_ids     int32 [n_items, K]  the kept k of column j, ascending; -1 past nbr_count[j]
+ *   nbr_w       f32   [n_items, K]  their W[k][j]; +0 past nbr_count[j]
+ *   nbr_count   int32 [n_items]     how many were kept (<= K)
+ *   col_sweeps  int32 [n_items]     the sweeps run (0 without candidates).  A column that ran fewer than
+ *                                   max_sweeps met the tolerance; one that ran max_sweeps may not have
+ *   col_support int32 [n_items]     the entries > 0 before the cut (> K: the column was cut)
+ * Columns outside [col_lo, col_hi) are not touched.  One wave solves a column; columns are handed to the
+ * resident workgroups through one counter in the workspace, in ascending order: a column costs
+ * sweeps x candidates^2, which differs by orders of magnitude, and a workgroup that finishes a light
+ * column takes the next.  A G entry that is not > l1 (negative and NaN included) is no candidate.
+ * ws must be 256-byte aligned.
+ */
+int rk_slim_fit(const float *G, int64_t ldg, int32_t n_items, const float *inv_denom, float l1, int32_t K,
+                int32_t max_sweeps, float tol, int32_t col_lo, int32_t col_hi, int32_t *nbr_ids, float *nbr_w,
+                int32_t *nbr_count, int32_t *col_sweeps, int32_t *col_support, void *ws, int64_t ws_bytes,
+                void *stream);
+
+/*
+ * out[u][c] = sum over the kept entries (k, w) of column lo + c, ascending, of x_uk * w for those k that CSR
+ * row u stores (looked up by binary search in the row's ascending indices), for u in [0, n_rows) and c in
+ * [0, hi - lo); a column nobody reaches is +0.  data NULL: every value is 1.0.  0 <= lo < hi <= n_items.
+ * out [n_rows, ldo], ldo >= hi - lo; columns past hi - lo are left as they are.  The layout is what
+ * rk_topk_masked reads.
+ */
+int rk_slim_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
+                   int32_t n_items, const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count,
+                   int32_t K, int32_t lo, int32_t hi, float *out, int64_t ldo, void *stream);
+
+#pragma GCC visibility pop
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RECODER_SLIM_H */

@@ -8,7 +8,7 @@ Drop-in for the reference's training path: ``Recoder`` / ``FactorizationModel``
 # in checkpoints as 'recoder_version' (model.py:207)
 __version__ = "0.4.0"
 
-__all__ = ["ShallowAutoencoder", "RandomWalkItemModel"]
+__all__ = ["ShallowAutoencoder", "RandomWalkItemModel", "SparseLinearModel"]
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
   if name == "RandomWalkItemModel":
     from .nn import RandomWalkItemModel
     return RandomWalkItemModel
+  if name == "SparseLinearModel":
+    from .nn import SparseLinearModel
+    return SparseLinearModel
   raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,0 +1,54 @@
+"""ctypes binding of librecoder_slim.so (the C ABI in include/recoder_slim.h): the SLIM kernels
+for recoder_amd.slim.  Like _lib.py: plain pointers and sizes, no torch types across the boundary,
+no CPU fallback."""
+import ctypes
+import os
+
+# PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
+import torch  # noqa: F401
+
+from ctypes import c_char_p, c_float, c_int32, c_int64, c_void_p
+
+from ._lib import RecoderHipError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "csrc", "librecoder_slim.so")
+
+_P = c_void_p
+
+# name -> (restype, argtypes); every symbol include/recoder_slim.h declares
+SIGNATURES = {
+  "rk_slim_version": (c_int32, []),
+  "rk_slim_last_error": (c_char_p, []),
+  "rk_slim_max_neighbours": (c_int32, []),
+  "rk_slim_lds_candidates": (c_int32, []),
+  "rk_slim_fit_workspace_bytes": (c_int64, [c_int32]),
+  "rk_slim_fit": (c_int32, [_P, c_int64, c_int32, _P, c_float, c_int32, c_int32, c_float, c_int32, c_int32, _P, _P, _P,
+                            _P, _P, _P, c_int64, _P]),
+  "rk_slim_scores": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P]),
+}
+
+_lib = None
+
+
+def load():
+  """Load the SLIM library (once) and bind every declared symbol."""
+  global _lib
+  if _lib is not None:
+    return _lib
+  if not os.path.exists(LIB_PATH):
+    raise RecoderHipError(
+        "librecoder_slim.so not found at %s -- build it with `python -m recoder_amd.build`" % LIB_PATH)
+  lib = ctypes.CDLL(LIB_PATH)
+  for name, (res, args) in SIGNATURES.items():
+    fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
+    fn.restype = res
+    fn.argtypes = args
+  _lib = lib
+  return lib
+
+
+def check(rc, what=""):
+  if rc != 0:
+    msg = load().rk_slim_last_error()
+    raise RecoderHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))

@@ -1,5 +1,5 @@
 """Build the six HIP libraries of the training, index, ALS, VAE, EASE and SVD paths and a seventh for
-RP3beta (hand-written kernels + C ABI) for gfx950.
+RP3beta and an eighth for SLIM (hand-written kernels + C ABI) for gfx950.
 
     python -m recoder_amd.build [--force]
 
@@ -16,6 +16,8 @@ librecoder_svd.so  the randomized truncated SVD behind PureSVD for MatrixFactori
                    (include/recoder_svd.h), likewise a library of its own
 librecoder_rp3.so  the RP3beta item-graph fit and its scores for RandomWalkItemModel
                    (include/recoder_rp3.h), likewise a library of its own
+librecoder_slim.so  the SLIM coordinate-descent fit and its scores for SparseLinearModel
+                   (include/recoder_slim.h), likewise a library of its own
 
 hipcc cross-compiles without a GPU; the built libraries stay in-tree
 (recoder_amd/csrc/*.so, git-ignored) so that they travel with the repository
@@ -33,6 +35,7 @@ VAE_LIB = os.path.join(CSRC, "librecoder_vae.so")
 EASE_LIB = os.path.join(CSRC, "librecoder_ease.so")
 SVD_LIB = os.path.join(CSRC, "librecoder_svd.so")
 RP3_LIB = os.path.join(CSRC, "librecoder_rp3.so")
+SLIM_LIB = os.path.join(CSRC, "librecoder_slim.so")
 SOURCES = ["capi.hip", "collate.hip", "encoder.hip", "gemm.hip", "decode16.hip", "linear.hip", "dw3.hip", "pgemm.hip", "fdecode.hip", "optim.hip", "topk.hip", "step.hip", "comm.hip"]
 INDEX_SOURCES = ["index.hip"]
 ALS_SOURCES = ["als.hip"]
@@ -40,6 +43,7 @@ VAE_SOURCES = ["vae.hip"]
 EASE_SOURCES = ["ease.hip"]
 SVD_SOURCES = ["svd.hip"]
 RP3_SOURCES = ["rp3.hip"]
+SLIM_SOURCES = ["slim.hip"]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified register
 # file); without it hipcc copied all accumulators AGPR<->VGPR around every k-tile
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -101,9 +105,10 @@ def build_library(force=False, verbose=True):
   # (svd.hip includes csrc/common.h for the counter RNG, as vae.hip does)
   _build_one(SVD_LIB, SVD_SOURCES, headers + [os.path.join(include, "recoder_svd.h")], force, verbose)
   _build_one(RP3_LIB, RP3_SOURCES, [os.path.join(include, "recoder_rp3.h")], force, verbose)
+  _build_one(SLIM_LIB, SLIM_SOURCES, [os.path.join(include, "recoder_slim.h")], force, verbose)
   return LIB
 
 
 if __name__ == "__main__":
   build_library(force="--force" in sys.argv)
-  print("built", LIB, INDEX_LIB, ALS_LIB, VAE_LIB, EASE_LIB, SVD_LIB, RP3_LIB)
+  print("built", LIB, INDEX_LIB, ALS_LIB, VAE_LIB, EASE_LIB, SVD_LIB, RP3_LIB, SLIM_LIB)

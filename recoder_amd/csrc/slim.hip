@@ -1,0 +1,337 @@
+// SLIM: the sparse linear item model (include/recoder_slim.h, librecoder_slim.so).
+//
+//   rk_slim_fit     one wave (a workgroup of 64 threads) per column j at a time, columns handed out through a
+//                   counter.
+//                   candidates: two passes over row j of G (count, then fill): {k != j : G[j][k] > l1} ascending,
+//                     with q = G[j][k], w = +0, G[k][k] and inv_denom[k] beside them, in LDS (up to SL_LDS_CANDS)
+//                     or in the workgroup's slice of the workspace
+//                   sweep: the wave evaluates the update of 64 coordinates at once from the current state,
+//                     ballots for the first whose weight changes, applies it (every lane updates its q entries
+//                     from row k of G: element-wise, no reduction) and evaluates again from the coordinate
+//                     behind it.  A coordinate whose new weight equals the old one leaves the state as it is,
+//                     so this is the sequential sweep bit for bit
+//                   cut: a bisection on the float bits finds the K-th largest weight, ties at it go to the
+//                     lower ids; the candidates are ascending, so an ordered compaction stores ascending ids
+//   rk_slim_scores  one thread per (user, column): the column's kept entries in order, each looked up in the
+//                   user's ascending indices by a binary search that starts behind the last one
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/recoder_slim.h"
+
+static thread_local char g_slim_err[512] = "";
+
+static void slim_set_error(const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_slim_err, sizeof(g_slim_err), fmt, ap);
+  va_end(ap);
+}
+
+#define SLIM_REQUIRE(cond, msg)                                            \
+  do {                                                                     \
+    if (!(cond)) {                                                         \
+      slim_set_error("%s: %s", __func__, msg);                             \
+      return -2;                                                           \
+    }                                                                      \
+  } while (0)
+
+#define SLIM_CHECK_LAUNCH(name)                                            \
+  do {                                                                     \
+    hipError_t e__ = hipGetLastError();                                    \
+    if (e__ != hipSuccess) {                                               \
+      slim_set_error("%s: %s", name, hipGetErrorString(e__));              \
+      return -1;                                                           \
+    }                                                                      \
+  } while (0)
+
+namespace {
+
+// ------------------------------------------------------------------------ fit
+constexpr int SL_LDS_CANDS = 960;             // 5 arrays x 960 x 4 B = 18.75 KB: eight workgroups on a CU's 160 KB
+constexpr int SL_MAX_K = 1024;
+constexpr int SL_GROUPS = 2048;               // resident workgroups: eight waves on each of the 256 CUs
+constexpr int SL_ARRAYS = 5;                  // cand, q, w, G_kk, inv_denom
+
+inline int64_t sl_stride(int n) { return ((int64_t)n + 63) / 64 * 64; }
+
+__device__ inline uint32_t f2u(float v) { return __float_as_uint(v); }
+
+__device__ inline int lanes_below(unsigned long long m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
+
+// Column j with C candidates (0 < C <= cap), the state in the five arrays (LDS or workspace).
+__device__ __forceinline__ void sl_column(const float *__restrict__ G, int64_t ldg, int n,
+                                          const float *__restrict__ inv_denom, float l1, int K, int max_sweeps,
+                                          float tol, int j, int C, int *cand, float *q, float *w, float *dg,
+                                          float *iv, int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_w,
+                                          int32_t *__restrict__ nbr_count, int32_t *__restrict__ col_sweeps,
+                                          int32_t *__restrict__ col_support, int lane) {
+  const float *row = G + (int64_t)j * ldg;
+  // ---- fill (the same predicate as the count, so cnt ends at C)
+  int cnt = 0;
+  for (int k0 = 0; k0 < n; k0 += 64) {
+    const int k = k0 + lane;
+    float g = 0.f;
+    bool is = false;
+    if (k < n) {
+      g = row[k];
+      is = k != j && g > l1;
+    }
+    const unsigned long long m = __ballot(is);
+    const int pos = cnt + lanes_below(m, lane);
+    if (is && pos < C) {
+      cand[pos] = k;
+      q[pos] = g;
+      w[pos] = 0.f;
+      dg[pos] = G[(int64_t)k * ldg + k];
+      iv[pos] = inv_denom[k];
+    }
+    cnt += __popcll(m);
+  }
+  __syncthreads();
+
+  // ---- sweeps
+  int sweeps = 0;
+#pragma unroll 1
+  for (int s = 0; s < max_sweeps; ++s) {
+    ++sweeps;
+    float maxd = 0.f;
+#pragma unroll 1
+    for (int b = 0; b < C; b += 64) {
+      const int c = b + lane;
+      const bool in = c < C;
+      const float dk = in ? dg[c] : 0.f, ik = in ? iv[c] : 0.f;
+      int done = b;                            // coordinates below are finished in this sweep
+#pragma unroll 1
+      for (;;) {                               // (at most 64 rounds: done grows every time)
+        float nw = 0.f, dl = 0.f;
+        if (in && c >= done) {
+          const float wc = w[c];
+          const float t = fmaf(dk, wc, q[c]);
+          nw = t > l1 ? __fmul_rn(__fsub_rn(t, l1), ik) : 0.f;
+          dl = __fsub_rn(nw, wc);
+        }
+        const unsigned long long m = __ballot(dl != 0.f);
+        if (m == 0) break;
+        const int f = __ffsll((long long)m) - 1;
+        const float delta = __shfl(dl, f, 64), nv = __shfl(nw, f, 64);
+        const float *rk = G + (int64_t)cand[b + f] * ldg;
+        maxd = fmaxf(maxd, fabsf(delta));
+        for (int c2 = lane; c2 < C; c2 += 64) q[c2] = fmaf(-delta, rk[cand[c2]], q[c2]);
+        if (lane == f) w[c] = nv;
+        __syncthreads();
+        done = b + f + 1;
+      }
+    }
+    if (maxd <= tol) break;
+  }
+
+  // ---- the support, and the K-th largest weight when it is larger than K
+  int S = 0;
+  for (int b = 0; b < C; b += 64) S += __popcll(__ballot(b + lane < C && w[b + lane] > 0.f));
+  const bool all = S <= K;
+  uint32_t T = 0;
+  int need = 0;
+  if (!all) {
+    // the largest T with at least K weights whose bits are >= T (weights > 0: the bits order as the values)
+    uint32_t lo = 1u, hi = 0x7f800000u;
+#pragma unroll 1
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo + 1u) / 2u;
+      int ge = 0;
+      for (int b = 0; b < C; b += 64) {
+        const float v = b + lane < C ? w[b + lane] : 0.f;
+        ge += __popcll(__ballot(v > 0.f && f2u(v) >= mid));
+      }
+      if (ge >= K) lo = mid; else hi = mid - 1u;
+    }
+    T = lo;
+    int gt = 0;
+    for (int b = 0; b < C; b += 64) {
+      const float v = b + lane < C ? w[b + lane] : 0.f;
+      gt += __popcll(__ballot(v > 0.f && f2u(v) > T));
+    }
+    need = K - gt;                             // how many of those equal to T are kept: the lowest ids
+  }
+
+  // ---- ordered compaction
+  int kept = 0, eq = 0;
+  for (int b = 0; b < C; b += 64) {
+    const int c = b + lane;
+    const float v = c < C ? w[c] : 0.f;
+    const bool pos = v > 0.f;
+    const bool iseq = pos && !all && f2u(v) == T;
+    const unsigned long long me = __ballot(iseq);
+    const bool keep = pos && (all || f2u(v) > T || (iseq && eq + lanes_below(me, lane) < need));
+    const unsigned long long mk = __ballot(keep);
+    const int p = kept + lanes_below(mk, lane);
+    if (keep && p < K) {
+      nbr_ids[(int64_t)j * K + p] = cand[c];
+      nbr_w[(int64_t)j * K + p] = v;
+    }
+    kept += __popcll(mk);
+    eq += __popcll(me);
+  }
+  kept = kept < K ? kept : K;
+  for (int c = kept + lane; c < K; c += 64) {
+    nbr_ids[(int64_t)j * K + c] = -1;
+    nbr_w[(int64_t)j * K + c] = 0.f;
+  }
+  if (lane == 0) {
+    nbr_count[j] = kept;
+    col_sweeps[j] = sweeps;
+    col_support[j] = S;
+  }
+}
+
+__global__ __launch_bounds__(64) void slim_fit_kernel(
+    const float *__restrict__ G, int64_t ldg, int n, const float *__restrict__ inv_denom, float l1, int K,
+    int max_sweeps, float tol, int col_lo, int col_hi, int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_w,
+    int32_t *__restrict__ nbr_count, int32_t *__restrict__ col_sweeps, int32_t *__restrict__ col_support,
+    int *counter, float *ws_state, int64_t stride) {
+  __shared__ int l_cand[SL_LDS_CANDS];
+  __shared__ float l_q[SL_LDS_CANDS], l_w[SL_LDS_CANDS], l_dg[SL_LDS_CANDS], l_iv[SL_LDS_CANDS];
+  const int lane = threadIdx.x;
+  float *g_base = ws_state + (int64_t)blockIdx.x * SL_ARRAYS * stride;
+
+  for (;;) {
+    __syncthreads();                           // (the state of the column before is no longer read)
+    int t = 0;
+    if (lane == 0) t = atomicAdd(counter, 1);
+    t = __shfl(t, 0, 64);
+    const int64_t j64 = (int64_t)col_lo + t;
+    if (j64 >= col_hi) break;
+    const int j = (int)j64;
+
+    const float *row = G + (int64_t)j * ldg;
+    int C = 0;
+    for (int k0 = 0; k0 < n; k0 += 64) {
+      const int k = k0 + lane;
+      C += __popcll(__ballot(k < n && k != j && row[k] > l1));
+    }
+    if (C == 0) {
+      for (int c = lane; c < K; c += 64) {
+        nbr_ids[(int64_t)j * K + c] = -1;
+        nbr_w[(int64_t)j * K + c] = 0.f;
+      }
+      if (lane == 0) {
+        nbr_count[j] = 0;
+        col_sweeps[j] = 0;
+        col_support[j] = 0;
+      }
+    } else if (C <= SL_LDS_CANDS) {
+      sl_column(G, ldg, n, inv_denom, l1, K, max_sweeps, tol, j, C, l_cand, l_q, l_w, l_dg, l_iv, nbr_ids, nbr_w,
+                nbr_count, col_sweeps, col_support, lane);
+    } else {                                   // (C <= n - 1 < stride)
+      sl_column(G, ldg, n, inv_denom, l1, K, max_sweeps, tol, j, C, (int *)g_base, g_base + stride,
+                g_base + 2 * stride, g_base + 3 * stride, g_base + 4 * stride, nbr_ids, nbr_w, nbr_count,
+                col_sweeps, col_support, lane);
+    }
+  }
+}
+
+// --------------------------------------------------------------------- scores
+constexpr int SC_THREADS = 256;
+
+__global__ __launch_bounds__(SC_THREADS) void slim_scores_kernel(
+    const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const float *__restrict__ data,
+    const int32_t *__restrict__ nbr_ids, const float *__restrict__ nbr_w, const int32_t *__restrict__ nbr_count,
+    int K, int lo, int width, float *__restrict__ out, int64_t ldo) {
+  const int u = blockIdx.x;                             // (users fastest: neighbours share the columns' entries)
+  const int c = blockIdx.y * SC_THREADS + threadIdx.x;
+  if (c >= width) return;
+  const int64_t e0 = indptr[u];
+  const int64_t len = indptr[u + 1] - e0;
+  float acc = 0.f;
+  if (len > 0) {
+    const int64_t j = (int64_t)lo + c;
+    int cnt = nbr_count[j];
+    cnt = cnt < 0 ? 0 : (cnt > K ? K : cnt);
+    const int32_t *ids = nbr_ids + j * K;
+    const float *wj = nbr_w + j * K;
+    const int32_t *ui = indices + e0;
+    int64_t from = 0;                                   // both lists ascend: the next search starts here
+    for (int s = 0; s < cnt && from < len; ++s) {
+      const int k = ids[s];
+      int64_t a = from, b = len;
+      while (a < b) {
+        const int64_t mid = (a + b) >> 1;
+        if (ui[mid] < k) a = mid + 1; else b = mid;
+      }
+      from = a;
+      if (a < len && ui[a] == k) acc = fmaf(data ? data[e0 + a] : 1.f, wj[s], acc);
+    }
+  }
+  out[(int64_t)u * ldo + c] = acc;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------ ABI
+extern "C" {
+
+int rk_slim_version(void) { return 100; }
+
+const char *rk_slim_last_error(void) { return g_slim_err; }
+
+int rk_slim_max_neighbours(void) { return SL_MAX_K; }
+
+int rk_slim_lds_candidates(void) { return SL_LDS_CANDS; }
+
+int64_t rk_slim_fit_workspace_bytes(int32_t n_items) {
+  if (n_items < 1) {
+    slim_set_error("%s: n_items must be >= 1", __func__);
+    return -2;
+  }
+  if (n_items <= SL_LDS_CANDS) return 256;              // (at most n - 1 candidates: the LDS always holds them)
+  return 256 + (int64_t)SL_GROUPS * SL_ARRAYS * sl_stride(n_items) * 4;
+}
+
+int rk_slim_fit(const float *G, int64_t ldg, int32_t n_items, const float *inv_denom, float l1, int32_t K,
+                int32_t max_sweeps, float tol, int32_t col_lo, int32_t col_hi, int32_t *nbr_ids, float *nbr_w,
+                int32_t *nbr_count, int32_t *col_sweeps, int32_t *col_support, void *ws, int64_t ws_bytes,
+                void *stream) {
+  SLIM_REQUIRE(G && inv_denom && nbr_ids && nbr_w && nbr_count && col_sweeps && col_support && ws, "null pointer");
+  SLIM_REQUIRE(n_items >= 1 && n_items < INT_MAX - 2048 && ldg >= n_items, "bad sizes");
+  SLIM_REQUIRE(K >= 1 && K <= SL_MAX_K, "K outside [1, rk_slim_max_neighbours()]");
+  SLIM_REQUIRE(l1 >= 0.f && l1 < INFINITY, "l1 must be finite and >= 0");
+  SLIM_REQUIRE(tol >= 0.f, "tol must be >= 0");
+  SLIM_REQUIRE(max_sweeps >= 1, "max_sweeps must be >= 1");
+  SLIM_REQUIRE(0 <= col_lo && col_lo <= col_hi && col_hi <= n_items, "bad column range");
+  SLIM_REQUIRE(ws_bytes >= rk_slim_fit_workspace_bytes(n_items), "workspace too small");
+  SLIM_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
+  if (col_lo == col_hi) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  int *counter = (int *)ws;
+  if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
+    slim_set_error("%s: hipMemsetAsync failed", __func__);
+    return -1;
+  }
+  const int cols = col_hi - col_lo;
+  const int groups = cols < SL_GROUPS ? cols : SL_GROUPS;
+  hipLaunchKernelGGL(slim_fit_kernel, dim3(groups), dim3(64), 0, s, G, ldg, n_items, inv_denom, l1, K, max_sweeps,
+                     tol, col_lo, col_hi, nbr_ids, nbr_w, nbr_count, col_sweeps, col_support, counter,
+                     (float *)((char *)ws + 256), sl_stride(n_items));
+  SLIM_CHECK_LAUNCH("slim_fit_kernel");
+  return 0;
+}
+
+int rk_slim_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
+                   int32_t n_items, const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count,
+                   int32_t K, int32_t lo, int32_t hi, float *out, int64_t ldo, void *stream) {
+  SLIM_REQUIRE(indptr && indices && nbr_ids && nbr_w && nbr_count && out, "null pointer");
+  SLIM_REQUIRE(n_rows >= 0 && n_items >= 1 && K >= 1 && K <= SL_MAX_K, "bad sizes");
+  SLIM_REQUIRE(0 <= lo && lo < hi && hi <= n_items && ldo >= hi - lo, "bad strip");
+  if (n_rows == 0) return 0;
+  const int width = hi - lo;
+  const dim3 grid(n_rows, (width + SC_THREADS - 1) / SC_THREADS);
+  hipLaunchKernelGGL(slim_scores_kernel, grid, dim3(SC_THREADS), 0, (hipStream_t)stream, indptr, indices, data,
+                     nbr_ids, nbr_w, nbr_count, K, lo, width, out, ldo);
+  SLIM_CHECK_LAUNCH("slim_scores_kernel");
+  return 0;
+}
+
+}  // extern "C"

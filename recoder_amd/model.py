@@ -34,7 +34,7 @@ from .engine import FusedEngine
 from .losses import MSELoss, MultinomialNLLLoss
 from .metrics import RecommenderEvaluator
 from .nn import (DynamicAutoencoder, FactorizationModel, MatrixFactorization, RandomWalkItemModel,
-                 ShallowAutoencoder, VariationalAutoencoder)
+                 ShallowAutoencoder, SparseLinearModel, VariationalAutoencoder)
 from .recommender import InferenceRecommender
 
 log = logging.getLogger("recoder_amd")
@@ -87,6 +87,7 @@ class Recoder(object):
     self.als_history = []       # train_als: the ALS objective after each iteration
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
+    self.slim_info = None       # train_slim: what the last SLIM fit reported
     self.__model_initialized = False
     self.__optimizer_state_dict = None
     self.__sparse_optimizer_state_dict = None
@@ -374,6 +375,9 @@ class Recoder(object):
     if isinstance(self.model, RandomWalkItemModel):
       raise ValueError("a RandomWalkItemModel is fitted in closed form from the interaction graph: call "
                        "train_rp3beta(train_dataset)")
+    if isinstance(self.model, SparseLinearModel):
+      raise ValueError("a SparseLinearModel is fitted by coordinate descent on the Gram matrix: call "
+                       "train_slim(train_dataset)")
     if num_sampling_users == 0:
       num_sampling_users = batch_size
     if eval_batch_size is None:
@@ -556,6 +560,57 @@ class Recoder(object):
     pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
     _, _, _, info = rp3.fit(pair, alpha, beta, K, out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))
     self.rp3_info = info
+    self._weights_written()
+    return dict(info)
+
+  def train_slim(self, train_dataset, l1_reg=None, l2_reg=None, neighbours=None, max_sweeps=50, tol=1e-5):
+    """The SLIM fit of a SparseLinearModel (recoder_amd/slim.py): column j of W becomes the non-negative
+    elastic-net regression of item j on the other items over the dataset's interaction matrix X (values as
+    stored, all >= 0: ValueError otherwise), ``min over w >= 0, w_j = 0 of 1/2 |x_j - X w|^2 + l2_reg/2 |w|^2 +
+    l1_reg |w|_1``, by cyclic coordinate descent on the Gram, stopped after the first sweep that moves no
+    weight by more than ``tol`` or after ``max_sweeps`` sweeps, and cut to its ``neighbours`` largest
+    weights.  ``None`` takes the model's value; explicit values are stored back into the model, so that a
+    checkpoint's ``model_params`` describe the weights it holds, and another ``neighbours`` re-allocates the
+    model's tensors.  The configured ``loss`` plays no part.  The n x n Gram has to fit the device
+    (EASE's limit; ValueError otherwise).  Builds a fresh optimizer of ``optimizer_type`` so that
+    ``save_state`` works.  Returns (and keeps in ``slim_info``) n, nnz, l1_reg, l2_reg, neighbours, kept
+    (entries kept over all columns), cut_columns (columns whose support was larger than ``neighbours``),
+    unconverged_columns (columns that ran all ``max_sweeps`` sweeps), max_sweeps_run, gram_ms and fit_ms
+    (HIP events)."""
+    from . import als, slim
+    m = self.model
+    if not isinstance(m, SparseLinearModel):
+      raise ValueError("train_slim fits a SparseLinearModel, not %s" % type(m).__name__)
+    l1, l2, K, max_sweeps, tol = slim.check_config(
+        m, m.l1_reg if l1_reg is None else l1_reg, m.l2_reg if l2_reg is None else l2_reg,
+        m.neighbours if neighbours is None else neighbours, max_sweeps, tol)
+    slim.check_not_distributed()
+    n_hint, u_hint = self.num_items, self.num_users
+    if n_hint is None and len(train_dataset.items):
+      n_hint = int(np.max(train_dataset.items)) + 1
+    if u_hint is None and len(train_dataset.users):
+      u_hint = int(np.max(train_dataset.users)) + 1
+    if n_hint:
+      # (before init_model allocates: a catalogue whose Gram cannot fit gets a ValueError, not an OOM)
+      slim.check_memory(u_hint or 0, n_hint, K, 0, free_bytes=float("inf"))
+    host = als.host_matrix(train_dataset)
+    slim.check_values(host)
+    log.info("SLIM: l1_reg %g, l2_reg %g, %d neighbours, at most %d sweeps, tol %g", l1, l2, K, max_sweeps, tol)
+    m.l1_reg, m.l2_reg = l1, l2
+    self.optimizer = self.sparse_optimizer = None
+    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    if not self.__model_initialized:
+      require_gpu()
+      m.neighbours = K
+    elif K != m.item_weights.shape[1]:
+      m.allocate(K, self.device)
+    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
+    m = self.model
+    slim.check_memory(self.num_users, self.num_items, K, host.nnz, allocate_model=False)
+    pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
+    _, _, _, info = slim.fit(pair, l1, l2, K, max_sweeps, tol,
+                             out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))
+    self.slim_info = info
     self._weights_written()
     return dict(info)
 
@@ -1261,6 +1316,12 @@ class Recoder(object):
       rp3.scores(self._eval_ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, 0, n_items,
                  out=out, ld=ld, n_rows=B)
       return out[:, :n_items], blk, B
+    if isinstance(self.model, SparseLinearModel):
+      from . import slim
+      m = self.model
+      slim.scores(self._eval_ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, 0, n_items,
+                  out=out, ld=ld, n_rows=B)
+      return out[:, :n_items], blk, B
     engine.predict_scores(blk, 0, B, out, ld, blk)
     return out[:, :n_items], blk, B
 
@@ -1298,7 +1359,8 @@ class Recoder(object):
     lib = _lib.load()
     engine = self._engine()
     rp3_model = isinstance(self.model, RandomWalkItemModel)
-    ease_model = isinstance(self.model, ShallowAutoencoder) or rp3_model     # (scores from the CSR rows, no encoder)
+    slim_model = isinstance(self.model, SparseLinearModel)
+    ease_model = isinstance(self.model, ShallowAutoencoder) or rp3_model or slim_model     # (scores from the CSR rows, no encoder)
     if (getattr(engine, "generic", False) and not ease_model) or k > lib.rk_topk_max_k():
       return self._recommend_dense(users_interactions, k)
     blk, B, n_items = self._input_block(users_interactions)
@@ -1335,12 +1397,17 @@ class Recoder(object):
     scores = ws["scores"]
     for s, (lo, hi) in enumerate(bounds):
       if ease_model:
-        # a ShallowAutoencoder's or RandomWalkItemModel's strip of scores: the users' CSR rows times W[:, lo:hi]
+        # a ShallowAutoencoder's, RandomWalkItemModel's or SparseLinearModel's strip of scores: the users' CSR rows times W[:, lo:hi]
         if rp3_model:
           from . import rp3
           m = self.model
           rp3.scores(ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, lo, hi, out=scores,
                      ld=ld, n_rows=B)
+        elif slim_model:
+          from . import slim
+          m = self.model
+          slim.scores(ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, lo, hi, out=scores,
+                      ld=ld, n_rows=B)
         else:
           from . import ease
           ease.scores(ws["dcsr"], self.model.item_weights.data, lo, hi, out=scores, ld=ld, n_rows=B)

@@ -551,3 +551,104 @@ class RandomWalkItemModel(FactorizationModel):
     if target_items is not None:
       w = w.index_select(1, target_items.to(torch.int64))
     return input.to(w.dtype) @ w
+
+
+class SparseLinearModel(FactorizationModel):
+  """SLIM (Ning & Karypis 2011): the learned sparse item-item model ``scores = input @ W``, column j of W
+  the non-negative elastic-net regression of item j on the other items,
+  ``min over w >= 0, w_j = 0 of 1/2 |x_j - X w|^2 + l2_reg/2 |w|^2 + l1_reg |w|_1``, cut to its ``neighbours``
+  largest entries, fitted by coordinate descent on the Gram by ``Recoder.train_slim`` (recoder_amd/slim.py).
+  ``l1_reg`` decides the sparsity (a pair of items fewer than ``l1_reg`` users share, weighted by their
+  values, never gets a weight), ``l2_reg`` the shrinkage.  scikit-learn's ``ElasticNet(alpha, l1_ratio,
+  positive=True)`` over U users is ``l1_reg = U * alpha * l1_ratio``, ``l2_reg = U * alpha * (1 - l1_ratio)``.
+
+  Three tensors, all in ``state_dict()``, laid out as ``RandomWalkItemModel``'s but per COLUMN of W:
+  ``item_neighbours`` int32 [num_items, neighbours] (the kept k of column j, ascending, -1 where a column
+  has fewer), ``item_weights`` f32 of the same shape (``W[k, j]``) and ``neighbour_counts`` int32
+  [num_items]; empty until fitted.  ``l1_reg``, ``l2_reg`` and ``neighbours`` travel in ``model_params()``.
+  ``Recoder.train`` refuses this model and points at ``train_slim``.
+  """
+
+  def __init__(self, l1_reg=1.0, l2_reg=1000.0, neighbours=200):
+    super().__init__()
+    self.l1_reg = l1_reg
+    self.l2_reg = l2_reg
+    self.neighbours = neighbours
+    self.num_items = None
+    self.item_weights = None
+    self._validate()
+
+  def _validate(self):
+    from .slim import check_params
+    self.l1_reg, self.l2_reg, self.neighbours = check_params(self.l1_reg, self.l2_reg, self.neighbours)[:3]
+
+  def init_model(self, num_items=None, num_users=None):
+    self._validate()
+    self.num_items = num_items
+    self.allocate(self.neighbours, None)
+
+  def allocate(self, neighbours, device):
+    """(Re-)create the three tensors for ``neighbours`` entries per column: no neighbours, zero weights."""
+    n, K = self.num_items, int(neighbours)
+    self.neighbours = K
+    self._buffers.pop("item_neighbours", None)
+    self._buffers.pop("neighbour_counts", None)
+    self.register_buffer("item_neighbours", torch.full((n, K), -1, dtype=torch.int32, device=device))
+    self.item_weights = nn.Parameter(torch.zeros(n, K, device=device), requires_grad=False)
+    self.register_buffer("neighbour_counts", torch.zeros(n, dtype=torch.int32, device=device))
+
+  def model_params(self):
+    return {"l1_reg": float(self.l1_reg), "l2_reg": float(self.l2_reg), "neighbours": int(self.neighbours)}
+
+  def load_model_params(self, model_params):
+    self.l1_reg = float(model_params["l1_reg"])
+    self.l2_reg = float(model_params["l2_reg"])
+    self.neighbours = int(model_params["neighbours"])
+    self._validate()
+
+  def dense_weights(self, dtype=torch.float32):
+    """W [num_items, num_items]: the kept entries scattered into a dense matrix, ``W[item_neighbours[j, s], j]
+    = item_weights[j, s]`` (small catalogues only)."""
+    n, K = self.item_weights.shape
+    W = torch.zeros(n, n, dtype=dtype, device=self.item_weights.device)
+    ids = self.item_neighbours.to(torch.int64)
+    live = torch.arange(K, device=ids.device)[None, :] < self.neighbour_counts.to(torch.int64)[:, None]
+    cols = torch.arange(n, device=ids.device)[:, None].expand(n, K)
+    W[ids[live], cols[live]] = self.item_weights.data.to(dtype)[live]
+    return W
+
+  def forward(self, input, input_users=None, input_items=None, target_users=None,
+              target_items=None):
+    """``input @ W[input_items][:, target_items]`` on the HIP kernel (rk_slim_scores): the dense input's
+    non-zeros as a CSR over the catalogue, ascending; no autograd.  On the host (no device tensors)
+    it is ``torch_forward``."""
+    if not input.is_cuda:
+      with torch.no_grad():
+        return self.torch_forward(input, input_users, input_items, target_users, target_items)
+    from . import slim
+    from types import SimpleNamespace
+    n = self.item_weights.shape[0]
+    nz = input.nonzero()
+    rows, cols = nz[:, 0], nz[:, 1]
+    vals = input[rows, cols].to(torch.float32)
+    if input_items is not None:
+      cols = input_items.to(torch.int64)[cols]
+      order = torch.argsort(rows * n + cols)          # (ascending item ids inside a row)
+      rows, cols, vals = rows[order], cols[order], vals[order]
+    B = input.shape[0]
+    indptr = torch.zeros(B + 1, dtype=torch.int64, device=input.device)
+    indptr[1:] = torch.cumsum(torch.bincount(rows, minlength=B), 0)
+    indices = cols.to(torch.int32) if cols.numel() else torch.zeros(1, dtype=torch.int32, device=input.device)
+    csr = SimpleNamespace(indptr=indptr, indices=indices.contiguous(), data=vals.contiguous(), shape=(B, n))
+    out = slim.scores(csr, self.item_neighbours, self.item_weights.data, self.neighbour_counts)
+    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
+
+  def torch_forward(self, input, input_users=None, input_items=None, target_users=None,
+                    target_items=None):
+    """The same forward in torch ops: the kept entries scattered into a dense W (host tensors)."""
+    w = self.dense_weights()
+    if input_items is not None:
+      w = w.index_select(0, input_items.to(torch.int64))
+    if target_items is not None:
+      w = w.index_select(1, target_items.to(torch.int64))
+    return input.to(w.dtype) @ w
