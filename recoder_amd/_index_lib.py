@@ -1,7 +1,6 @@
 """ctypes binding of librecoder_index.so (the C ABI in include/recoder_index.h): exact item
 similarity for recoder_amd.embedding.  Like _lib.py: plain pointers and sizes, no torch types
 across the boundary, no CPU fallback."""
-import ctypes
 import os
 
 # PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
@@ -9,7 +8,7 @@ import torch  # noqa: F401
 
 from ctypes import c_char_p, c_float, c_int32, c_void_p
 
-from ._lib import RecoderHipError
+from ._lib import checker, loader
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "librecoder_index.so")
@@ -25,27 +24,5 @@ SIGNATURES = {
   "rk_ix_pool_scores": (c_int32, [_P, c_int32, c_int32, _P, _P, c_int32, _P, _P, c_int32, c_float, _P, _P]),
 }
 
-_lib = None
-
-
-def load():
-  """Load the index library (once) and bind every declared symbol."""
-  global _lib
-  if _lib is not None:
-    return _lib
-  if not os.path.exists(LIB_PATH):
-    raise RecoderHipError(
-        "librecoder_index.so not found at %s -- build it with `python -m recoder_amd.build`" % LIB_PATH)
-  lib = ctypes.CDLL(LIB_PATH)
-  for name, (res, args) in SIGNATURES.items():
-    fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
-    fn.restype = res
-    fn.argtypes = args
-  _lib = lib
-  return lib
-
-
-def check(rc, what=""):
-  if rc != 0:
-    msg = load().rk_ix_last_error()
-    raise RecoderHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+load = loader(LIB_PATH, SIGNATURES)
+check = checker(load, "rk_ix_last_error")

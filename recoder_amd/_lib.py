@@ -247,20 +247,46 @@ class RecoderHipError(RuntimeError):
   pass
 
 
+def bind(path, signatures, hint=""):
+  """dlopen one of the project's libraries and bind every symbol of `signatures` (name -> (restype, argtypes))."""
+  if not os.path.exists(path):
+    raise RecoderHipError("%s not found at %s -- build it with `python -m recoder_amd.build`%s"
+                          % (os.path.basename(path), path, hint))
+  lib = ctypes.CDLL(path)
+  for name, (res, args) in signatures.items():
+    fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
+    fn.restype = res
+    fn.argtypes = args
+  return lib
+
+
+def loader(path, signatures):
+  """load() of a side library (_index_lib.py ... _slim_lib.py): binds it on the first call, returns it on every one."""
+  cache = []
+
+  def load():
+    if not cache:
+      cache.append(bind(path, signatures))
+    return cache[0]
+  load.__doc__ = "Load %s (once) and bind every declared symbol." % os.path.basename(path)
+  return load
+
+
+def checker(load, last_error):
+  """check(rc, what) of a library: a non-zero return code raises with the text of its `last_error` symbol."""
+  def check(rc, what=""):
+    if rc != 0:
+      msg = getattr(load(), last_error)()
+      raise RecoderHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+  return check
+
+
 def load():
   """Load the shared library (once) and bind every declared symbol."""
   global _lib
   if _lib is not None:
     return _lib
-  if not os.path.exists(LIB_PATH):
-    raise RecoderHipError(
-        "librecoder_hip.so not found at %s -- build it with `python -m recoder_amd.build` "
-        "(there is no CPU fallback for the training path)" % LIB_PATH)
-  lib = ctypes.CDLL(LIB_PATH)
-  for name, (res, args) in SIGNATURES.items():
-    fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
-    fn.restype = res
-    fn.argtypes = args
+  lib = bind(LIB_PATH, SIGNATURES, " (there is no CPU fallback for the training path)")
   _install_plan_accessors(lib)
   # the probe header's two entry points under the names tools/ and tests/ were written against
   lib.rk_gemm_probe = lambda buf: lib.rk_probe_buffer(0, buf)
@@ -322,10 +348,7 @@ def _install_plan_accessors(lib):
   lib.rk_pg_decode_granule = granule
 
 
-def check(rc, what=""):
-  if rc != 0:
-    msg = load().rk_last_error()
-    raise RecoderHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+check = checker(load, "rk_last_error")
 
 
 def ptr(t):

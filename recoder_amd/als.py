@@ -22,15 +22,12 @@ import scipy.sparse as sp
 import torch
 
 from . import _als_lib
+from ._lib import ptr
 from .device import canonical_csr, current_stream
 from .losses import MSELoss
 from .nn import MatrixFactorization
 
 MAX_H = 512          # rk_als_max_h()
-
-
-def _ptr(t):
-  return None if t is None else t.data_ptr()
 
 
 # ------------------------------------------------------------------ config
@@ -70,10 +67,10 @@ def check_config(model, loss, loss_params, num_iterations, reg, cg_steps):
   return alpha
 
 
-def check_not_distributed():
+def check_not_distributed(message="train_als runs on one GPU: multi-GPU ALS is not implemented"):
   import torch.distributed as dist
   if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-    raise NotImplementedError("train_als runs on one GPU: multi-GPU ALS is not implemented")
+    raise NotImplementedError(message)
 
 
 # --------------------------------------------------------------------- CSR
@@ -129,7 +126,7 @@ def gram(F, reg, w=None, ws=None):
   G = torch.empty(h, h, dtype=torch.float32, device=F.device)
   v = torch.empty(h, dtype=torch.float32, device=F.device)
   ldf = F.stride(0) if rows else h              # (an empty table's stride is arbitrary)
-  _als_lib.check(lib.rk_als_gram(_ptr(F), rows, h, ldf, _ptr(w), float(reg), _ptr(G), _ptr(v), _ptr(ws),
+  _als_lib.check(lib.rk_als_gram(ptr(F), rows, h, ldf, ptr(w), float(reg), ptr(G), ptr(v), ptr(ws),
                                  ws.numel(), current_stream()), "rk_als_gram")
   return G, v
 
@@ -140,9 +137,9 @@ def solve(csr, F, G, v, X, alpha, cg_steps, col_bias=None, row_bias=None, row_lo
   assert 0 <= row_lo <= row_hi <= min(csr.shape[0], X.shape[0]) and F.shape[0] >= csr.shape[1]
   assert X.shape[1] == F.shape[1] == G.shape[0] and X.stride(1) == 1 and F.stride(1) == 1
   lib = _als_lib.load()
-  _als_lib.check(lib.rk_als_solve(_ptr(csr.indptr), _ptr(csr.indices), _ptr(csr.data), row_lo, row_hi, _ptr(F),
-                                  F.stride(0), F.shape[1], _ptr(G), _ptr(v), _ptr(col_bias), _ptr(row_bias),
-                                  float(alpha), int(cg_steps), _ptr(X), X.stride(0), int(flags),
+  _als_lib.check(lib.rk_als_solve(ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), row_lo, row_hi, ptr(F),
+                                  F.stride(0), F.shape[1], ptr(G), ptr(v), ptr(col_bias), ptr(row_bias),
+                                  float(alpha), int(cg_steps), ptr(X), X.stride(0), int(flags),
                                   current_stream()), "rk_als_solve")
 
 
@@ -154,10 +151,10 @@ def objective(csr, X, Y, bias, alpha, reg, Gx, sx, Gy, cy, out, ws=None):
   need = lib.rk_als_objective_workspace_bytes(rows)
   if ws is None or ws.numel() < need:
     ws = torch.empty(need, dtype=torch.uint8, device=X.device)
-  _als_lib.check(lib.rk_als_objective(_ptr(csr.indptr), _ptr(csr.indices), _ptr(csr.data), rows, Y.shape[0],
-                                      _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), h, _ptr(bias), float(alpha),
-                                      float(reg), _ptr(Gx), _ptr(Gy), _ptr(sx), _ptr(cy), _ptr(ws), ws.numel(),
-                                      _ptr(out), current_stream()), "rk_als_objective")
+  _als_lib.check(lib.rk_als_objective(ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), rows, Y.shape[0],
+                                      ptr(X), X.stride(0), ptr(Y), Y.stride(0), h, ptr(bias), float(alpha),
+                                      float(reg), ptr(Gx), ptr(Gy), ptr(sx), ptr(cy), ptr(ws), ws.numel(),
+                                      ptr(out), current_stream()), "rk_als_objective")
 
 
 # ---------------------------------------------------------------------- fit

@@ -1,5 +1,6 @@
-"""Build the six HIP libraries of the training, index, ALS, VAE, EASE and SVD paths and a seventh for
-RP3beta and an eighth for SLIM (hand-written kernels + C ABI) for gfx950.
+"""Build the HIP libraries (hand-written kernels + C ABI) for gfx950, one row of LIBRARIES each: the
+six HIP libraries of the training, index, ALS, VAE, EASE and SVD paths, a seventh for RP3beta and an
+eighth for SLIM.
 
     python -m recoder_amd.build [--force]
 
@@ -19,6 +20,9 @@ librecoder_rp3.so  the RP3beta item-graph fit and its scores for RandomWalkItemM
 librecoder_slim.so  the SLIM coordinate-descent fit and its scores for SparseLinearModel
                    (include/recoder_slim.h), likewise a library of its own
 
+The seven side libraries share csrc/side_error.h (the last-error buffer and the argument / launch
+checks); each stays one translation unit, so each has its own buffer.
+
 hipcc cross-compiles without a GPU; the built libraries stay in-tree
 (recoder_amd/csrc/*.so, git-ignored) so that they travel with the repository
 snapshot to the GPU box.
@@ -28,22 +32,33 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-LIB = os.path.join(CSRC, "librecoder_hip.so")
-INDEX_LIB = os.path.join(CSRC, "librecoder_index.so")
-ALS_LIB = os.path.join(CSRC, "librecoder_als.so")
-VAE_LIB = os.path.join(CSRC, "librecoder_vae.so")
-EASE_LIB = os.path.join(CSRC, "librecoder_ease.so")
-SVD_LIB = os.path.join(CSRC, "librecoder_svd.so")
-RP3_LIB = os.path.join(CSRC, "librecoder_rp3.so")
-SLIM_LIB = os.path.join(CSRC, "librecoder_slim.so")
-SOURCES = ["capi.hip", "collate.hip", "encoder.hip", "gemm.hip", "decode16.hip", "linear.hip", "dw3.hip", "pgemm.hip", "fdecode.hip", "optim.hip", "topk.hip", "step.hip", "comm.hip"]
-INDEX_SOURCES = ["index.hip"]
-ALS_SOURCES = ["als.hip"]
-VAE_SOURCES = ["vae.hip"]
-EASE_SOURCES = ["ease.hip"]
-SVD_SOURCES = ["svd.hip"]
-RP3_SOURCES = ["rp3.hip"]
-SLIM_SOURCES = ["slim.hip"]
+INCLUDE = os.path.join(os.path.dirname(CSRC), "..", "include")
+# one row per library, in build order: (stem, sources, public headers, whether it depends on the training
+# path's headers (every csrc/*.h and include/recoder_hip*.h), the prefix of its exported names).  A side
+# library depends on its own header and csrc/side_error.h; vae.hip and svd.hip also include csrc/common.h
+# (the counter RNG, the step cursor), so they follow the training headers too.
+LIBRARIES = (
+    ("hip", ["capi.hip", "collate.hip", "encoder.hip", "gemm.hip", "decode16.hip", "linear.hip", "dw3.hip",
+             "pgemm.hip", "fdecode.hip", "optim.hip", "topk.hip", "step.hip", "comm.hip"],
+     ["recoder_hip.h", "recoder_hip_probe.h"], True, "rk_"),
+    ("index", ["index.hip"], ["recoder_index.h"], False, "rk_ix_"),
+    ("als", ["als.hip"], ["recoder_als.h"], False, "rk_als_"),
+    ("vae", ["vae.hip"], ["recoder_vae.h"], True, "rk_vae_"),
+    ("ease", ["ease.hip"], ["recoder_ease.h"], False, "rk_ease_"),
+    ("svd", ["svd.hip"], ["recoder_svd.h"], True, "rk_svd_"),
+    ("rp3", ["rp3.hip"], ["recoder_rp3.h"], False, "rk_rp3_"),
+    ("slim", ["slim.hip"], ["recoder_slim.h"], False, "rk_slim_"),
+)
+
+
+def lib_path(stem):
+  return os.path.join(CSRC, "librecoder_%s.so" % stem)
+
+
+# (the names the bindings, the tests and the tools import)
+LIB, INDEX_LIB, ALS_LIB, VAE_LIB, EASE_LIB, SVD_LIB, RP3_LIB, SLIM_LIB = (lib_path(row[0]) for row in LIBRARIES)
+SOURCES, INDEX_SOURCES, ALS_SOURCES, VAE_SOURCES, EASE_SOURCES, SVD_SOURCES, RP3_SOURCES, SLIM_SOURCES = \
+    (row[1] for row in LIBRARIES)
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified register
 # file); without it hipcc copied all accumulators AGPR<->VGPR around every k-tile
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -93,22 +108,16 @@ def _build_one(lib, sources, headers, force, verbose):
 
 def build_library(force=False, verbose=True):
   """Build the libraries (each only if one of its sources or headers is newer); returns the training library's path."""
-  include = os.path.join(os.path.dirname(CSRC), "..", "include")
-  headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
-      [os.path.join(include, "recoder_hip.h"), os.path.join(include, "recoder_hip_probe.h")]
-  _build_one(LIB, SOURCES, headers, force, verbose)
-  _build_one(INDEX_LIB, INDEX_SOURCES, [os.path.join(include, "recoder_index.h")], force, verbose)
-  _build_one(ALS_LIB, ALS_SOURCES, [os.path.join(include, "recoder_als.h")], force, verbose)
-  # (vae.hip includes csrc/common.h for the counter RNG and the step cursor: the training headers too)
-  _build_one(VAE_LIB, VAE_SOURCES, headers + [os.path.join(include, "recoder_vae.h")], force, verbose)
-  _build_one(EASE_LIB, EASE_SOURCES, [os.path.join(include, "recoder_ease.h")], force, verbose)
-  # (svd.hip includes csrc/common.h for the counter RNG, as vae.hip does)
-  _build_one(SVD_LIB, SVD_SOURCES, headers + [os.path.join(include, "recoder_svd.h")], force, verbose)
-  _build_one(RP3_LIB, RP3_SOURCES, [os.path.join(include, "recoder_rp3.h")], force, verbose)
-  _build_one(SLIM_LIB, SLIM_SOURCES, [os.path.join(include, "recoder_slim.h")], force, verbose)
+  training = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
+      [os.path.join(INCLUDE, h) for h in LIBRARIES[0][2]]
+  for stem, sources, public, needs_training, _ in LIBRARIES:
+    own = [os.path.join(INCLUDE, h) for h in public]
+    headers = training + [h for h in own if h not in training] if needs_training else \
+        own + [os.path.join(CSRC, "side_error.h")]
+    _build_one(lib_path(stem), sources, headers, force, verbose)
   return LIB
 
 
 if __name__ == "__main__":
   build_library(force="--force" in sys.argv)
-  print("built", LIB, INDEX_LIB, ALS_LIB, VAE_LIB, EASE_LIB, SVD_LIB, RP3_LIB, SLIM_LIB)
+  print("built", *(lib_path(row[0]) for row in LIBRARIES))

@@ -11,37 +11,10 @@
 //                     workgroup adds them and the Gram terms in a fixed order
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/recoder_als.h"
-
-static thread_local char g_als_err[512] = "";
-
-static void als_set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_als_err, sizeof(g_als_err), fmt, ap);
-  va_end(ap);
-}
-
-#define ALS_REQUIRE(cond, msg)                                             \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      als_set_error("%s: %s", __func__, msg);                              \
-      return -2;                                                           \
-    }                                                                      \
-  } while (0)
-
-#define ALS_CHECK_LAUNCH(name)                                             \
-  do {                                                                     \
-    hipError_t e__ = hipGetLastError();                                    \
-    if (e__ != hipSuccess) {                                               \
-      als_set_error("%s: %s", name, hipGetErrorString(e__));               \
-      return -1;                                                           \
-    }                                                                      \
-  } while (0)
+#include "side_error.h"
 
 namespace {
 
@@ -560,7 +533,7 @@ int nt_of(int h) { return h <= 64 ? 1 : h <= 128 ? 2 : h <= 256 ? 4 : 8; }
 }  // namespace
 
 extern "C" int rk_als_version(void) { return 100; }
-extern "C" const char *rk_als_last_error(void) { return g_als_err; }
+extern "C" const char *rk_als_last_error(void) { return g_rk_side_err; }
 extern "C" int rk_als_max_h(void) { return MAX_H; }
 
 extern "C" int64_t rk_als_gram_workspace_bytes(int32_t rows, int32_t h) {
@@ -571,20 +544,20 @@ extern "C" int64_t rk_als_gram_workspace_bytes(int32_t rows, int32_t h) {
 
 extern "C" int rk_als_gram(const float *F, int32_t rows, int32_t h, int32_t ldf, const float *w, float reg,
                            float *G, float *v, void *ws, int64_t ws_bytes, void *stream) {
-  ALS_REQUIRE(rows >= 0 && h >= 1 && h <= MAX_H && ldf >= h, "rows >= 0, 1 <= h <= 512, ldf >= h");
-  ALS_REQUIRE(G && v && (rows == 0 || F), "G, v (and F when rows > 0) must be set");
-  ALS_REQUIRE(ws_bytes >= rk_als_gram_workspace_bytes(rows, h) && ws, "workspace too small");
+  RK_SIDE_REQUIRE(rows >= 0 && h >= 1 && h <= MAX_H && ldf >= h, "rows >= 0, 1 <= h <= 512, ldf >= h");
+  RK_SIDE_REQUIRE(G && v && (rows == 0 || F), "G, v (and F when rows > 0) must be set");
+  RK_SIDE_REQUIRE(ws_bytes >= rk_als_gram_workspace_bytes(rows, h) && ws, "workspace too small");
   const GramPlan p = gram_plan(rows, h);
   float *P = (float *)ws;
   float *Pv = P + (int64_t)p.nch * h * h;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(als_gram_partial_kernel, dim3(p.npairs, p.nch), dim3(64), 0, st, F, rows, h, ldf, w, p.chunk,
                      p.ntile, P, Pv);
-  ALS_CHECK_LAUNCH("als_gram_partial");
+  RK_SIDE_CHECK_LAUNCH("als_gram_partial");
   const int64_t n = (int64_t)h * h + h;
   hipLaunchKernelGGL(als_gram_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, Pv, p.nch, h,
                      reg, G, v);
-  ALS_CHECK_LAUNCH("als_gram_reduce");
+  RK_SIDE_CHECK_LAUNCH("als_gram_reduce");
   return 0;
 }
 
@@ -606,13 +579,13 @@ extern "C" int rk_als_solve(const int64_t *indptr, const int32_t *indices, const
                             int32_t row_hi, const float *F, int32_t ldf, int32_t h, const float *G, const float *v,
                             const float *col_bias, const float *row_bias, float alpha, int32_t cg_steps, float *X,
                             int32_t ldx, int32_t flags, void *stream) {
-  ALS_REQUIRE(h >= 1 && h <= MAX_H && ldf >= h && ldx >= h, "1 <= h <= 512, ldf >= h, ldx >= h");
-  ALS_REQUIRE(row_lo >= 0 && row_hi >= row_lo, "0 <= row_lo <= row_hi");
-  ALS_REQUIRE(cg_steps >= 1, "cg_steps >= 1");
-  ALS_REQUIRE(!(col_bias && row_bias), "at most one of col_bias / row_bias");
-  ALS_REQUIRE((flags & ~(RK_ALS_FORCE_STREAM | RK_ALS_G_GLOBAL)) == 0, "unknown flags");
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldf >= h && ldx >= h, "1 <= h <= 512, ldf >= h, ldx >= h");
+  RK_SIDE_REQUIRE(row_lo >= 0 && row_hi >= row_lo, "0 <= row_lo <= row_hi");
+  RK_SIDE_REQUIRE(cg_steps >= 1, "cg_steps >= 1");
+  RK_SIDE_REQUIRE(!(col_bias && row_bias), "at most one of col_bias / row_bias");
+  RK_SIDE_REQUIRE((flags & ~(RK_ALS_FORCE_STREAM | RK_ALS_G_GLOBAL)) == 0, "unknown flags");
   if (row_hi == row_lo) return 0;
-  ALS_REQUIRE(indptr && indices && F && G && v && X, "null pointer");
+  RK_SIDE_REQUIRE(indptr && indices && F && G && v && X, "null pointer");
   const bool g_lds = !(flags & RK_ALS_G_GLOBAL) && (int64_t)h * h * 4 <= G_LDS_MAX;
   const int64_t g_floats = g_lds ? (int64_t)h * h : 0;
   int stash_rows = (int)((SOLVE_LDS / 4 - g_floats) / 4 / h);
@@ -626,7 +599,7 @@ extern "C" int rk_als_solve(const int64_t *indptr, const int32_t *indices, const
     case 4: ALS_SOLVE_LAUNCH(4); break;
     default: ALS_SOLVE_LAUNCH(8); break;
   }
-  ALS_CHECK_LAUNCH("als_solve");
+  RK_SIDE_CHECK_LAUNCH("als_solve");
   return 0;
 }
 
@@ -640,14 +613,14 @@ extern "C" int rk_als_objective(const int64_t *indptr, const int32_t *indices, c
                                 const float *bias, float alpha, float reg, const float *Gx, const float *Gy,
                                 const float *sx, const float *cy, void *ws, int64_t ws_bytes, double *out,
                                 void *stream) {
-  ALS_REQUIRE(rows >= 0 && cols >= 0 && h >= 1 && h <= MAX_H && ldx >= h && ldy >= h,
+  RK_SIDE_REQUIRE(rows >= 0 && cols >= 0 && h >= 1 && h <= MAX_H && ldx >= h && ldy >= h,
               "rows, cols >= 0, 1 <= h <= 512, ldx, ldy >= h");
-  ALS_REQUIRE(Gx && Gy && out && (!bias || (sx && cy)), "null pointer");
-  ALS_REQUIRE(ws && ws_bytes >= rk_als_objective_workspace_bytes(rows), "workspace too small");
+  RK_SIDE_REQUIRE(Gx && Gy && out && (!bias || (sx && cy)), "null pointer");
+  RK_SIDE_REQUIRE(ws && ws_bytes >= rk_als_objective_workspace_bytes(rows), "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   double *part = (double *)ws;
   if (rows > 0) {
-    ALS_REQUIRE(indptr && indices && X && Y, "null pointer");
+    RK_SIDE_REQUIRE(indptr && indices && X && Y, "null pointer");
     const dim3 grid((unsigned)((rows + 3) / 4));
     switch (nt_of(h)) {
       case 1: hipLaunchKernelGGL(als_objective_rows_kernel<1>, grid, dim3(256), 0, st, indptr, indices, data, rows, X, ldx, Y, ldy, h, bias, alpha, part); break;
@@ -655,10 +628,10 @@ extern "C" int rk_als_objective(const int64_t *indptr, const int32_t *indices, c
       case 4: hipLaunchKernelGGL(als_objective_rows_kernel<4>, grid, dim3(256), 0, st, indptr, indices, data, rows, X, ldx, Y, ldy, h, bias, alpha, part); break;
       default: hipLaunchKernelGGL(als_objective_rows_kernel<8>, grid, dim3(256), 0, st, indptr, indices, data, rows, X, ldx, Y, ldy, h, bias, alpha, part); break;
     }
-    ALS_CHECK_LAUNCH("als_objective_rows");
+    RK_SIDE_CHECK_LAUNCH("als_objective_rows");
   }
   hipLaunchKernelGGL(als_objective_final_kernel, dim3(1), dim3(256), 0, st, part, rows, cols, h, bias, reg, Gx, Gy,
                      sx, cy, out);
-  ALS_CHECK_LAUNCH("als_objective_final");
+  RK_SIDE_CHECK_LAUNCH("als_objective_final");
   return 0;
 }

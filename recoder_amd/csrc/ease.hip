@@ -14,37 +14,10 @@
 //   rk_ease_scores       sparse row x dense matrix, one thread per output column, users fastest in the grid
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/recoder_ease.h"
-
-static thread_local char g_ease_err[512] = "";
-
-static void ease_set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ease_err, sizeof(g_ease_err), fmt, ap);
-  va_end(ap);
-}
-
-#define EASE_REQUIRE(cond, msg)                                            \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      ease_set_error("%s: %s", __func__, msg);                             \
-      return -2;                                                           \
-    }                                                                      \
-  } while (0)
-
-#define EASE_CHECK_LAUNCH(name)                                            \
-  do {                                                                     \
-    hipError_t e__ = hipGetLastError();                                    \
-    if (e__ != hipSuccess) {                                               \
-      ease_set_error("%s: %s", name, hipGetErrorString(e__));              \
-      return -1;                                                           \
-    }                                                                      \
-  } while (0)
+#include "side_error.h"
 
 namespace {
 
@@ -350,24 +323,24 @@ extern "C" {
 
 int rk_ease_version(void) { return 100; }
 
-const char *rk_ease_last_error(void) { return g_ease_err; }
+const char *rk_ease_last_error(void) { return g_rk_side_err; }
 
 int rk_ease_gram(const int64_t *t_indptr, const int32_t *t_indices, const float *t_data, const int64_t *u_indptr,
                  const int32_t *u_indices, const float *u_data, int32_t n_users, int32_t n_items, float reg,
                  float *A, int64_t lda, void *stream) {
-  EASE_REQUIRE(t_indptr && t_indices && u_indptr && u_indices && A, "null pointer");
-  EASE_REQUIRE(n_users >= 0 && n_items >= 1 && lda >= n_items, "bad sizes");
-  EASE_REQUIRE((t_data == nullptr) == (u_data == nullptr), "t_data and u_data must both be given or both be NULL");
+  RK_SIDE_REQUIRE(t_indptr && t_indices && u_indptr && u_indices && A, "null pointer");
+  RK_SIDE_REQUIRE(n_users >= 0 && n_items >= 1 && lda >= n_items, "bad sizes");
+  RK_SIDE_REQUIRE((t_data == nullptr) == (u_data == nullptr), "t_data and u_data must both be given or both be NULL");
   const dim3 grid(n_items, (n_items + GR_STRIP - 1) / GR_STRIP);
   hipLaunchKernelGGL(ease_gram_kernel, grid, dim3(GR_WAVES * 64), 0, (hipStream_t)stream, t_indptr, t_indices,
                      t_data, u_indptr, u_indices, u_data, n_users, n_items, reg, A, lda);
-  EASE_CHECK_LAUNCH("ease_gram_kernel");
+  RK_SIDE_CHECK_LAUNCH("ease_gram_kernel");
   return 0;
 }
 
 int64_t rk_ease_spd_inverse_workspace_bytes(int32_t n) {
   if (n < 1) {
-    ease_set_error("%s: n must be >= 1", __func__);
+    rk_side_set_error("%s: n must be >= 1", __func__);
     return -2;
   }
   return 2 * NB * inv_ldw(n) * (int64_t)sizeof(float) + NB * NB * (int64_t)sizeof(double) +
@@ -376,19 +349,19 @@ int64_t rk_ease_spd_inverse_workspace_bytes(int32_t n) {
 
 int rk_ease_spd_inverse(float *A, int32_t n, int64_t lda, void *ws, int64_t ws_bytes, int32_t *status,
                         void *stream) {
-  EASE_REQUIRE(A && ws && status, "null pointer");
-  EASE_REQUIRE(n >= 1 && lda >= n, "bad sizes");
-  EASE_REQUIRE(ws_bytes >= rk_ease_spd_inverse_workspace_bytes(n), "workspace too small");
-  EASE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "workspace must be 16-byte aligned");
+  RK_SIDE_REQUIRE(A && ws && status, "null pointer");
+  RK_SIDE_REQUIRE(n >= 1 && lda >= n, "bad sizes");
+  RK_SIDE_REQUIRE(ws_bytes >= rk_ease_spd_inverse_workspace_bytes(n), "workspace too small");
+  RK_SIDE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "workspace must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int64_t ldw = inv_ldw(n);
   float *Rw = (float *)ws, *Ct = Rw + NB * ldw;
   double *Dv = (double *)(Ct + NB * ldw);
   float *Cc = (float *)(Dv + NB * NB);        // [n, n]: the carries of the compensated update
-  EASE_REQUIRE((int64_t)((n + 255) / 256) * n < ((int64_t)1 << 31), "n too large for one launch");
+  RK_SIDE_REQUIRE((int64_t)((n + 255) / 256) * n < ((int64_t)1 << 31), "n too large for one launch");
   if (hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess ||
       hipMemsetAsync(Cc, 0, (size_t)n * n * sizeof(float), s) != hipSuccess) {
-    ease_set_error("%s: hipMemsetAsync failed", __func__);
+    rk_side_set_error("%s: hipMemsetAsync failed", __func__);
     return -1;
   }
   const int tiles = (int)(ldw / TILE);
@@ -403,32 +376,32 @@ int rk_ease_spd_inverse(float *A, int32_t n, int64_t lda, void *ws, int64_t ws_b
                        Ct, ldw);
   }
   hipLaunchKernelGGL(ease_fold_kernel, dim3((unsigned)((int64_t)((n + 255) / 256) * n)), dim3(256), 0, s, A, Cc, n, lda);
-  EASE_CHECK_LAUNCH("rk_ease_spd_inverse");
+  RK_SIDE_CHECK_LAUNCH("rk_ease_spd_inverse");
   return 0;
 }
 
 int rk_ease_finalize(const float *P, int32_t n, int64_t ldp, float *B, int64_t ldb, float *diag, void *stream) {
-  EASE_REQUIRE(P && B && diag, "null pointer");
-  EASE_REQUIRE(n >= 1 && ldp >= n && ldb >= n, "bad sizes");
-  EASE_REQUIRE((int64_t)((n + 255) / 256) * n < ((int64_t)1 << 31), "n too large for one launch");
+  RK_SIDE_REQUIRE(P && B && diag, "null pointer");
+  RK_SIDE_REQUIRE(n >= 1 && ldp >= n && ldb >= n, "bad sizes");
+  RK_SIDE_REQUIRE((int64_t)((n + 255) / 256) * n < ((int64_t)1 << 31), "n too large for one launch");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ease_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, s, P, n, ldp, diag);
   hipLaunchKernelGGL(ease_finalize_kernel, dim3((unsigned)((int64_t)((n + 255) / 256) * n)), dim3(256), 0, s, P, n, ldp, B, ldb,
                      diag);
-  EASE_CHECK_LAUNCH("rk_ease_finalize");
+  RK_SIDE_CHECK_LAUNCH("rk_ease_finalize");
   return 0;
 }
 
 int rk_ease_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows, const float *W,
                    int64_t ldw, int32_t lo, int32_t hi, float *out, int64_t ldo, void *stream) {
-  EASE_REQUIRE(indptr && indices && W && out, "null pointer");
-  EASE_REQUIRE(n_rows >= 0 && 0 <= lo && lo < hi && ldw >= hi && ldo >= hi - lo, "bad sizes");
+  RK_SIDE_REQUIRE(indptr && indices && W && out, "null pointer");
+  RK_SIDE_REQUIRE(n_rows >= 0 && 0 <= lo && lo < hi && ldw >= hi && ldo >= hi - lo, "bad sizes");
   if (n_rows == 0) return 0;
   const int width = hi - lo;
   const dim3 grid(n_rows, (width + 256 * SC_COLS - 1) / (256 * SC_COLS));
   hipLaunchKernelGGL(ease_scores_kernel, grid, dim3(256), 0, (hipStream_t)stream, indptr, indices, data, W, ldw, lo,
                      width, out, ldo);
-  EASE_CHECK_LAUNCH("ease_scores_kernel");
+  RK_SIDE_CHECK_LAUNCH("ease_scores_kernel");
   return 0;
 }
 

@@ -8,37 +8,10 @@
 //                      chain per dot product, one thread per (user, pool item)
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/recoder_index.h"
-
-static thread_local char g_ix_err[512] = "";
-
-static void ix_set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ix_err, sizeof(g_ix_err), fmt, ap);
-  va_end(ap);
-}
-
-#define IX_REQUIRE(cond, msg)                                              \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      ix_set_error("%s: %s", __func__, msg);                               \
-      return -2;                                                           \
-    }                                                                      \
-  } while (0)
-
-#define IX_CHECK_LAUNCH(name)                                              \
-  do {                                                                     \
-    hipError_t e__ = hipGetLastError();                                    \
-    if (e__ != hipSuccess) {                                               \
-      ix_set_error("%s: %s", name, hipGetErrorString(e__));                \
-      return -1;                                                           \
-    }                                                                      \
-  } while (0)
+#include "side_error.h"
 
 namespace {
 
@@ -218,23 +191,23 @@ constexpr int POOL_LDS_MAX = 64 * 1024;
 }  // namespace
 
 extern "C" int rk_ix_version(void) { return 100; }
-extern "C" const char *rk_ix_last_error(void) { return g_ix_err; }
+extern "C" const char *rk_ix_last_error(void) { return g_rk_side_err; }
 
 extern "C" int rk_ix_normalize(const float *X, int32_t rows, int32_t h, int32_t ldx, float *Y, int32_t ldy,
                                void *stream) {
-  IX_REQUIRE(rows >= 0 && h >= 1 && ldx >= h && ldy >= h, "rows >= 0, h >= 1, ldx >= h, ldy >= h");
-  IX_REQUIRE(X != Y || ldx == ldy, "in place needs ldx == ldy");
+  RK_SIDE_REQUIRE(rows >= 0 && h >= 1 && ldx >= h && ldy >= h, "rows >= 0, h >= 1, ldx >= h, ldy >= h");
+  RK_SIDE_REQUIRE(X != Y || ldx == ldy, "in place needs ldx == ldy");
   if (rows == 0) return 0;
   hipLaunchKernelGGL(ix_normalize_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, X, rows, h,
                      ldx, Y, ldy);
-  IX_CHECK_LAUNCH("ix_normalize");
+  RK_SIDE_CHECK_LAUNCH("ix_normalize");
   return 0;
 }
 
 extern "C" int rk_ix_scores(const float *Qn, int32_t Q, int32_t ldq, const float *En, int32_t lde, int32_t h,
                             int32_t lo, int32_t hi, float *out, int32_t ldo, void *stream) {
-  IX_REQUIRE(Q >= 0 && h >= 1 && ldq >= h && lde >= h, "Q >= 0, h >= 1, ldq >= h, lde >= h");
-  IX_REQUIRE(lo >= 0 && hi >= lo && ldo >= hi - lo, "0 <= lo <= hi, ldo >= hi - lo");
+  RK_SIDE_REQUIRE(Q >= 0 && h >= 1 && ldq >= h && lde >= h, "Q >= 0, h >= 1, ldq >= h, lde >= h");
+  RK_SIDE_REQUIRE(lo >= 0 && hi >= lo && ldo >= hi - lo, "0 <= lo <= hi, ldo >= hi - lo");
   const int S = hi - lo;
   if (Q == 0 || S == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
@@ -242,20 +215,20 @@ extern "C" int rk_ix_scores(const float *Qn, int32_t Q, int32_t ldq, const float
     hipLaunchKernelGGL((ix_scores_kernel<1, 1, 2>), dim3((S + 255) / 256, 1), dim3(256), 0, st, Qn, Q, ldq, En,
                        lde, h, lo, S, out, ldo);
   } else {                     // 128 x 128
-    IX_REQUIRE((Q + 127) / 128 <= 65535, "Q too large for one call");
+    RK_SIDE_REQUIRE((Q + 127) / 128 <= 65535, "Q too large for one call");
     hipLaunchKernelGGL((ix_scores_kernel<2, 2, 2>), dim3((S + 127) / 128, (Q + 127) / 128), dim3(256), 0, st, Qn,
                        Q, ldq, En, lde, h, lo, S, out, ldo);
   }
-  IX_CHECK_LAUNCH("ix_scores");
+  RK_SIDE_CHECK_LAUNCH("ix_scores");
   return 0;
 }
 
 extern "C" int rk_ix_pool_scores(const float *En, int32_t lde, int32_t h, const int64_t *hist_ptr,
                                  const int64_t *hist_idx, int32_t U, const int64_t *pool_idx,
                                  const int64_t *pool_cnt, int32_t pool_ld, float scale, float *out, void *stream) {
-  IX_REQUIRE(h >= 1 && lde >= h && U >= 0 && pool_ld >= 0, "h >= 1, lde >= h, U >= 0, pool_ld >= 0");
-  IX_REQUIRE(U <= 65535, "at most 65535 users per call");
-  IX_REQUIRE(!isnan(scale), "scale is NaN");
+  RK_SIDE_REQUIRE(h >= 1 && lde >= h && U >= 0 && pool_ld >= 0, "h >= 1, lde >= h, U >= 0, pool_ld >= 0");
+  RK_SIDE_REQUIRE(U <= 65535, "at most 65535 users per call");
+  RK_SIDE_REQUIRE(!isnan(scale), "scale is NaN");
   if (U == 0 || pool_ld == 0) return 0;
   const int iscale = (scale >= 0.f && scale <= 64.f && scale == floorf(scale)) ? (int)scale : -1;
   const dim3 grid((pool_ld + 255) / 256, U);
@@ -264,10 +237,10 @@ extern "C" int rk_ix_pool_scores(const float *En, int32_t lde, int32_t h, const 
     hipLaunchKernelGGL(ix_pool_scores_kernel<POOL_T>, grid, dim3(256), POOL_T * h * sizeof(float), st, En, lde, h,
                        hist_ptr, hist_idx, pool_idx, pool_cnt, pool_ld, scale, iscale, out);
   } else {
-    IX_REQUIRE((size_t)h * sizeof(float) <= POOL_LDS_MAX, "h > 16384");
+    RK_SIDE_REQUIRE((size_t)h * sizeof(float) <= POOL_LDS_MAX, "h > 16384");
     hipLaunchKernelGGL(ix_pool_scores_kernel<1>, grid, dim3(256), h * sizeof(float), st, En, lde, h, hist_ptr,
                        hist_idx, pool_idx, pool_cnt, pool_ld, scale, iscale, out);
   }
-  IX_CHECK_LAUNCH("ix_pool_scores");
+  RK_SIDE_CHECK_LAUNCH("ix_pool_scores");
   return 0;
 }

@@ -16,37 +16,10 @@
 //                  that fall in its columns
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/recoder_rp3.h"
-
-static thread_local char g_rp3_err[512] = "";
-
-static void rp3_set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_rp3_err, sizeof(g_rp3_err), fmt, ap);
-  va_end(ap);
-}
-
-#define RP3_REQUIRE(cond, msg)                                             \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      rp3_set_error("%s: %s", __func__, msg);                              \
-      return -2;                                                           \
-    }                                                                      \
-  } while (0)
-
-#define RP3_CHECK_LAUNCH(name)                                             \
-  do {                                                                     \
-    hipError_t e__ = hipGetLastError();                                    \
-    if (e__ != hipSuccess) {                                               \
-      rp3_set_error("%s: %s", name, hipGetErrorString(e__));               \
-      return -1;                                                           \
-    }                                                                      \
-  } while (0)
+#include "side_error.h"
 
 namespace {
 
@@ -353,7 +326,7 @@ extern "C" {
 
 int rk_rp3_version(void) { return 100; }
 
-const char *rk_rp3_last_error(void) { return g_rp3_err; }
+const char *rk_rp3_last_error(void) { return g_rk_side_err; }
 
 int rk_rp3_max_neighbours(void) { return FT_MAX_K; }
 
@@ -361,7 +334,7 @@ int rk_rp3_lds_items(void) { return FT_LDS_ITEMS; }
 
 int64_t rk_rp3_fit_workspace_bytes(int32_t n_items) {
   if (n_items < 1) {
-    rp3_set_error("%s: n_items must be >= 1", __func__);
+    rk_side_set_error("%s: n_items must be >= 1", __func__);
     return -2;
   }
   if (n_items <= FT_LDS_ITEMS) return 256;
@@ -372,18 +345,18 @@ int rk_rp3_fit(const int64_t *t_indptr, const int32_t *t_indices, const int64_t 
                const int32_t *u_indices, int32_t n_users, int32_t n_items, const float *user_w,
                const float *row_scale, const float *col_scale, int32_t K, int32_t row_lo, int32_t row_hi,
                int32_t *nbr_ids, float *nbr_w, int32_t *nbr_count, void *ws, int64_t ws_bytes, void *stream) {
-  RP3_REQUIRE(t_indptr && t_indices && u_indptr && u_indices && user_w && row_scale && col_scale && nbr_ids &&
+  RK_SIDE_REQUIRE(t_indptr && t_indices && u_indptr && u_indices && user_w && row_scale && col_scale && nbr_ids &&
                   nbr_w && nbr_count && ws, "null pointer");
-  RP3_REQUIRE(n_users >= 0 && n_items >= 1 && n_items < INT_MAX - 2048, "bad sizes");
-  RP3_REQUIRE(K >= 1 && K <= FT_MAX_K, "K outside [1, rk_rp3_max_neighbours()]");
-  RP3_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= n_items, "bad row range");
-  RP3_REQUIRE(ws_bytes >= rk_rp3_fit_workspace_bytes(n_items), "workspace too small");
-  RP3_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
+  RK_SIDE_REQUIRE(n_users >= 0 && n_items >= 1 && n_items < INT_MAX - 2048, "bad sizes");
+  RK_SIDE_REQUIRE(K >= 1 && K <= FT_MAX_K, "K outside [1, rk_rp3_max_neighbours()]");
+  RK_SIDE_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= n_items, "bad row range");
+  RK_SIDE_REQUIRE(ws_bytes >= rk_rp3_fit_workspace_bytes(n_items), "workspace too small");
+  RK_SIDE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
   if (row_lo == row_hi) return 0;
   hipStream_t s = (hipStream_t)stream;
   int *counter = (int *)ws;
   if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
-    rp3_set_error("%s: hipMemsetAsync failed", __func__);
+    rk_side_set_error("%s: hipMemsetAsync failed", __func__);
     return -1;
   }
   const int rows = row_hi - row_lo;
@@ -400,22 +373,22 @@ int rk_rp3_fit(const int64_t *t_indptr, const int32_t *t_indices, const int64_t 
                        u_indices, n_users, n_items, user_w, row_scale, col_scale, K, row_lo, row_hi, nbr_ids, nbr_w,
                        nbr_count, counter, acc, cand, stride, (int)ch);
   }
-  RP3_CHECK_LAUNCH("rp3_fit_kernel");
+  RK_SIDE_CHECK_LAUNCH("rp3_fit_kernel");
   return 0;
 }
 
 int rk_rp3_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
                   int32_t n_items, const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count,
                   int32_t K, int32_t lo, int32_t hi, float *out, int64_t ldo, void *stream) {
-  RP3_REQUIRE(indptr && indices && nbr_ids && nbr_w && nbr_count && out, "null pointer");
-  RP3_REQUIRE(n_rows >= 0 && n_items >= 1 && K >= 1 && K <= FT_MAX_K, "bad sizes");
-  RP3_REQUIRE(0 <= lo && lo < hi && hi <= n_items && ldo >= hi - lo, "bad strip");
+  RK_SIDE_REQUIRE(indptr && indices && nbr_ids && nbr_w && nbr_count && out, "null pointer");
+  RK_SIDE_REQUIRE(n_rows >= 0 && n_items >= 1 && K >= 1 && K <= FT_MAX_K, "bad sizes");
+  RK_SIDE_REQUIRE(0 <= lo && lo < hi && hi <= n_items && ldo >= hi - lo, "bad strip");
   if (n_rows == 0) return 0;
   const int width = hi - lo;
   const dim3 grid(n_rows, (width + SC_TILE - 1) / SC_TILE);
   hipLaunchKernelGGL(rp3_scores_kernel, grid, dim3(SC_WAVES * 64), 0, (hipStream_t)stream, indptr, indices, data,
                      n_items, nbr_ids, nbr_w, nbr_count, K, lo, width, out, ldo);
-  RP3_CHECK_LAUNCH("rp3_scores_kernel");
+  RK_SIDE_CHECK_LAUNCH("rp3_scores_kernel");
   return 0;
 }
 

@@ -16,37 +16,10 @@
 //                   user's ascending indices by a binary search that starts behind the last one
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/recoder_slim.h"
-
-static thread_local char g_slim_err[512] = "";
-
-static void slim_set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_slim_err, sizeof(g_slim_err), fmt, ap);
-  va_end(ap);
-}
-
-#define SLIM_REQUIRE(cond, msg)                                            \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      slim_set_error("%s: %s", __func__, msg);                             \
-      return -2;                                                           \
-    }                                                                      \
-  } while (0)
-
-#define SLIM_CHECK_LAUNCH(name)                                            \
-  do {                                                                     \
-    hipError_t e__ = hipGetLastError();                                    \
-    if (e__ != hipSuccess) {                                               \
-      slim_set_error("%s: %s", name, hipGetErrorString(e__));              \
-      return -1;                                                           \
-    }                                                                      \
-  } while (0)
+#include "side_error.h"
 
 namespace {
 
@@ -275,7 +248,7 @@ extern "C" {
 
 int rk_slim_version(void) { return 100; }
 
-const char *rk_slim_last_error(void) { return g_slim_err; }
+const char *rk_slim_last_error(void) { return g_rk_side_err; }
 
 int rk_slim_max_neighbours(void) { return SL_MAX_K; }
 
@@ -283,7 +256,7 @@ int rk_slim_lds_candidates(void) { return SL_LDS_CANDS; }
 
 int64_t rk_slim_fit_workspace_bytes(int32_t n_items) {
   if (n_items < 1) {
-    slim_set_error("%s: n_items must be >= 1", __func__);
+    rk_side_set_error("%s: n_items must be >= 1", __func__);
     return -2;
   }
   if (n_items <= SL_LDS_CANDS) return 256;              // (at most n - 1 candidates: the LDS always holds them)
@@ -294,20 +267,20 @@ int rk_slim_fit(const float *G, int64_t ldg, int32_t n_items, const float *inv_d
                 int32_t max_sweeps, float tol, int32_t col_lo, int32_t col_hi, int32_t *nbr_ids, float *nbr_w,
                 int32_t *nbr_count, int32_t *col_sweeps, int32_t *col_support, void *ws, int64_t ws_bytes,
                 void *stream) {
-  SLIM_REQUIRE(G && inv_denom && nbr_ids && nbr_w && nbr_count && col_sweeps && col_support && ws, "null pointer");
-  SLIM_REQUIRE(n_items >= 1 && n_items < INT_MAX - 2048 && ldg >= n_items, "bad sizes");
-  SLIM_REQUIRE(K >= 1 && K <= SL_MAX_K, "K outside [1, rk_slim_max_neighbours()]");
-  SLIM_REQUIRE(l1 >= 0.f && l1 < INFINITY, "l1 must be finite and >= 0");
-  SLIM_REQUIRE(tol >= 0.f, "tol must be >= 0");
-  SLIM_REQUIRE(max_sweeps >= 1, "max_sweeps must be >= 1");
-  SLIM_REQUIRE(0 <= col_lo && col_lo <= col_hi && col_hi <= n_items, "bad column range");
-  SLIM_REQUIRE(ws_bytes >= rk_slim_fit_workspace_bytes(n_items), "workspace too small");
-  SLIM_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
+  RK_SIDE_REQUIRE(G && inv_denom && nbr_ids && nbr_w && nbr_count && col_sweeps && col_support && ws, "null pointer");
+  RK_SIDE_REQUIRE(n_items >= 1 && n_items < INT_MAX - 2048 && ldg >= n_items, "bad sizes");
+  RK_SIDE_REQUIRE(K >= 1 && K <= SL_MAX_K, "K outside [1, rk_slim_max_neighbours()]");
+  RK_SIDE_REQUIRE(l1 >= 0.f && l1 < INFINITY, "l1 must be finite and >= 0");
+  RK_SIDE_REQUIRE(tol >= 0.f, "tol must be >= 0");
+  RK_SIDE_REQUIRE(max_sweeps >= 1, "max_sweeps must be >= 1");
+  RK_SIDE_REQUIRE(0 <= col_lo && col_lo <= col_hi && col_hi <= n_items, "bad column range");
+  RK_SIDE_REQUIRE(ws_bytes >= rk_slim_fit_workspace_bytes(n_items), "workspace too small");
+  RK_SIDE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
   if (col_lo == col_hi) return 0;
   hipStream_t s = (hipStream_t)stream;
   int *counter = (int *)ws;
   if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
-    slim_set_error("%s: hipMemsetAsync failed", __func__);
+    rk_side_set_error("%s: hipMemsetAsync failed", __func__);
     return -1;
   }
   const int cols = col_hi - col_lo;
@@ -315,22 +288,22 @@ int rk_slim_fit(const float *G, int64_t ldg, int32_t n_items, const float *inv_d
   hipLaunchKernelGGL(slim_fit_kernel, dim3(groups), dim3(64), 0, s, G, ldg, n_items, inv_denom, l1, K, max_sweeps,
                      tol, col_lo, col_hi, nbr_ids, nbr_w, nbr_count, col_sweeps, col_support, counter,
                      (float *)((char *)ws + 256), sl_stride(n_items));
-  SLIM_CHECK_LAUNCH("slim_fit_kernel");
+  RK_SIDE_CHECK_LAUNCH("slim_fit_kernel");
   return 0;
 }
 
 int rk_slim_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
                    int32_t n_items, const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count,
                    int32_t K, int32_t lo, int32_t hi, float *out, int64_t ldo, void *stream) {
-  SLIM_REQUIRE(indptr && indices && nbr_ids && nbr_w && nbr_count && out, "null pointer");
-  SLIM_REQUIRE(n_rows >= 0 && n_items >= 1 && K >= 1 && K <= SL_MAX_K, "bad sizes");
-  SLIM_REQUIRE(0 <= lo && lo < hi && hi <= n_items && ldo >= hi - lo, "bad strip");
+  RK_SIDE_REQUIRE(indptr && indices && nbr_ids && nbr_w && nbr_count && out, "null pointer");
+  RK_SIDE_REQUIRE(n_rows >= 0 && n_items >= 1 && K >= 1 && K <= SL_MAX_K, "bad sizes");
+  RK_SIDE_REQUIRE(0 <= lo && lo < hi && hi <= n_items && ldo >= hi - lo, "bad strip");
   if (n_rows == 0) return 0;
   const int width = hi - lo;
   const dim3 grid(n_rows, (width + SC_THREADS - 1) / SC_THREADS);
   hipLaunchKernelGGL(slim_scores_kernel, grid, dim3(SC_THREADS), 0, (hipStream_t)stream, indptr, indices, data,
                      nbr_ids, nbr_w, nbr_count, K, lo, width, out, ldo);
-  SLIM_CHECK_LAUNCH("slim_scores_kernel");
+  RK_SIDE_CHECK_LAUNCH("slim_scores_kernel");
   return 0;
 }
 

@@ -14,38 +14,11 @@
 //                        both operands staged in LDS 32 k at a time, every output one k-ascending chain
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "common.h"
 #include "../../include/recoder_svd.h"
-
-static thread_local char g_svd_err[512] = "";
-
-static void svd_set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_svd_err, sizeof(g_svd_err), fmt, ap);
-  va_end(ap);
-}
-
-#define SVD_REQUIRE(cond, msg)                                             \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      svd_set_error("%s: %s", __func__, msg);                              \
-      return -2;                                                           \
-    }                                                                      \
-  } while (0)
-
-#define SVD_CHECK_LAUNCH(name)                                             \
-  do {                                                                     \
-    hipError_t e__ = hipGetLastError();                                    \
-    if (e__ != hipSuccess) {                                               \
-      svd_set_error("%s: %s", name, hipGetErrorString(e__));               \
-      return -1;                                                           \
-    }                                                                      \
-  } while (0)
+#include "side_error.h"
 
 namespace {
 
@@ -397,27 +370,27 @@ extern "C" {
 
 int rk_svd_version(void) { return 100; }
 
-const char *rk_svd_last_error(void) { return g_svd_err; }
+const char *rk_svd_last_error(void) { return g_rk_side_err; }
 
 int rk_svd_max_l(void) { return MAX_L; }
 
 int rk_svd_gaussian(float *out, int32_t rows, int32_t l, int32_t ld, uint64_t seed, void *stream) {
-  SVD_REQUIRE(out != nullptr, "null pointer");
-  SVD_REQUIRE(rows >= 0 && l >= 1 && ld >= l, "bad sizes");
+  RK_SIDE_REQUIRE(out != nullptr, "null pointer");
+  RK_SIDE_REQUIRE(rows >= 0 && l >= 1 && ld >= l, "bad sizes");
   const int64_t n = (int64_t)rows * l;
   if (n == 0) return 0;
-  SVD_REQUIRE((n + 255) / 256 < ((int64_t)1 << 31), "too many elements for one launch");
+  RK_SIDE_REQUIRE((n + 255) / 256 < ((int64_t)1 << 31), "too many elements for one launch");
   hipLaunchKernelGGL(svd_gaussian_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n,
                      l, ld, seed);
-  SVD_CHECK_LAUNCH("svd_gaussian_kernel");
+  RK_SIDE_CHECK_LAUNCH("svd_gaussian_kernel");
   return 0;
 }
 
 int rk_svd_spmm(const int64_t *indptr, const int32_t *indices, const float *data, int32_t row_lo, int32_t row_hi,
                 const float *F, int32_t ldf, int32_t l, float *Y, int32_t ldy, void *stream) {
-  SVD_REQUIRE(indptr && indices && F && Y, "null pointer");
-  SVD_REQUIRE(0 <= row_lo && row_lo <= row_hi, "bad row range");
-  SVD_REQUIRE(l >= 1 && l <= MAX_L && ldf >= l && ldy >= l, "bad sizes");
+  RK_SIDE_REQUIRE(indptr && indices && F && Y, "null pointer");
+  RK_SIDE_REQUIRE(0 <= row_lo && row_lo <= row_hi, "bad row range");
+  RK_SIDE_REQUIRE(l >= 1 && l <= MAX_L && ldf >= l && ldy >= l, "bad sizes");
   if (row_lo == row_hi) return 0;
   hipStream_t st = (hipStream_t)stream;
   const bool vec = l % 4 == 0 && ldf % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(F) & 15) == 0 &&
@@ -427,13 +400,13 @@ int rk_svd_spmm(const int64_t *indptr, const int32_t *indices, const float *data
   else if (vec) spmm_launch<true, 1>(indptr, indices, data, row_lo, row_hi, F, ldf, l, Y, ldy, st);
   else if (two) spmm_launch<false, 2>(indptr, indices, data, row_lo, row_hi, F, ldf, l, Y, ldy, st);
   else spmm_launch<false, 1>(indptr, indices, data, row_lo, row_hi, F, ldf, l, Y, ldy, st);
-  SVD_CHECK_LAUNCH("rk_svd_spmm");
+  RK_SIDE_CHECK_LAUNCH("rk_svd_spmm");
   return 0;
 }
 
 int64_t rk_svd_chol_inverse_workspace_bytes(int32_t l) {
   if (l < 1 || l > MAX_L) {
-    svd_set_error("%s: l must be in 1..%d", __func__, MAX_L);
+    rk_side_set_error("%s: l must be in 1..%d", __func__, MAX_L);
     return -2;
   }
   return l <= CH_LDS_L ? 0 : (int64_t)l * l * (int64_t)sizeof(double);
@@ -441,27 +414,27 @@ int64_t rk_svd_chol_inverse_workspace_bytes(int32_t l) {
 
 int rk_svd_chol_inverse(const float *G, int32_t l, float *Rinv, void *ws, int64_t ws_bytes, int32_t *status,
                         void *stream) {
-  SVD_REQUIRE(G && Rinv && status, "null pointer");
-  SVD_REQUIRE(l >= 1 && l <= MAX_L, "bad sizes");
+  RK_SIDE_REQUIRE(G && Rinv && status, "null pointer");
+  RK_SIDE_REQUIRE(l >= 1 && l <= MAX_L, "bad sizes");
   const int64_t need = rk_svd_chol_inverse_workspace_bytes(l);
-  SVD_REQUIRE(need == 0 || (ws != nullptr && ws_bytes >= need), "workspace too small");
-  SVD_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "workspace must be 16-byte aligned");
+  RK_SIDE_REQUIRE(need == 0 || (ws != nullptr && ws_bytes >= need), "workspace too small");
+  RK_SIDE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "workspace must be 16-byte aligned");
   hipLaunchKernelGGL(svd_chol_inverse_kernel, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, G, l, Rinv,
                      (double *)ws, status);
-  SVD_CHECK_LAUNCH("svd_chol_inverse_kernel");
+  RK_SIDE_CHECK_LAUNCH("svd_chol_inverse_kernel");
   return 0;
 }
 
 int rk_svd_rotate(const float *Y, int32_t rows, int32_t l, int32_t ldy, const float *M, int32_t l2, int32_t ldm,
                   float *Out, int32_t ldo, void *stream) {
-  SVD_REQUIRE(Y && M && Out, "null pointer");
-  SVD_REQUIRE(rows >= 0 && l >= 1 && l <= MAX_L && l2 >= 1 && l2 <= MAX_L, "bad sizes");
-  SVD_REQUIRE(ldy >= l && ldm >= l2 && ldo >= l2, "bad leading dimensions");
-  SVD_REQUIRE(Out != Y, "the rotation is out of place");
+  RK_SIDE_REQUIRE(Y && M && Out, "null pointer");
+  RK_SIDE_REQUIRE(rows >= 0 && l >= 1 && l <= MAX_L && l2 >= 1 && l2 <= MAX_L, "bad sizes");
+  RK_SIDE_REQUIRE(ldy >= l && ldm >= l2 && ldo >= l2, "bad leading dimensions");
+  RK_SIDE_REQUIRE(Out != Y, "the rotation is out of place");
   if (rows == 0) return 0;
   const dim3 grid((unsigned)(((int64_t)rows + RT_ROWS - 1) / RT_ROWS), (l2 + RT_COLS - 1) / RT_COLS);
   hipLaunchKernelGGL(svd_rotate_kernel, grid, dim3(256), 0, (hipStream_t)stream, Y, rows, l, ldy, M, l2, ldm, Out, ldo);
-  SVD_CHECK_LAUNCH("svd_rotate_kernel");
+  RK_SIDE_CHECK_LAUNCH("svd_rotate_kernel");
   return 0;
 }
 

@@ -10,38 +10,11 @@
 // same code in eager and replayed steps, so a row's outputs depend on its own inputs alone.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "common.h"
 #include "../../include/recoder_vae.h"
-
-static thread_local char g_vae_err[512] = "";
-
-static void vae_set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_vae_err, sizeof(g_vae_err), fmt, ap);
-  va_end(ap);
-}
-
-#define VAE_REQUIRE(cond, msg)                                             \
-  do {                                                                     \
-    if (!(cond)) {                                                         \
-      vae_set_error("%s: %s", __func__, msg);                              \
-      return -2;                                                           \
-    }                                                                      \
-  } while (0)
-
-#define VAE_CHECK_LAUNCH(name)                                             \
-  do {                                                                     \
-    hipError_t e__ = hipGetLastError();                                    \
-    if (e__ != hipSuccess) {                                               \
-      vae_set_error("%s: %s", name, hipGetErrorString(e__));               \
-      return -1;                                                           \
-    }                                                                      \
-  } while (0)
+#include "side_error.h"
 
 namespace {
 
@@ -125,33 +98,33 @@ __global__ __launch_bounds__(256) void vae_sample_bwd_kernel(const float *__rest
 
 extern "C" int rk_vae_version(void) { return 100; }
 
-extern "C" const char *rk_vae_last_error(void) { return g_vae_err; }
+extern "C" const char *rk_vae_last_error(void) { return g_rk_side_err; }
 
 extern "C" int rk_vae_sample(const float *E, int32_t B, int32_t d, int32_t train, const float *eps_in, uint64_t seed,
                              uint64_t rng_step, const int64_t *users, int32_t row_off, const int64_t *cursor,
                              int32_t cursor_off, const float *beta_table, float beta, float *z, float *eps_out,
                              float *kl_part, void *stream_) {
-  VAE_REQUIRE(B >= 0 && d >= 1 && row_off >= 0, "B >= 0, d >= 1 and row_off >= 0");
-  VAE_REQUIRE(E != nullptr && z != nullptr, "E and z are required");
-  VAE_REQUIRE(!train || eps_out != nullptr, "training mode needs eps_out (the backward reads it)");
+  RK_SIDE_REQUIRE(B >= 0 && d >= 1 && row_off >= 0, "B >= 0, d >= 1 and row_off >= 0");
+  RK_SIDE_REQUIRE(E != nullptr && z != nullptr, "E and z are required");
+  RK_SIDE_REQUIRE(!train || eps_out != nullptr, "training mode needs eps_out (the backward reads it)");
   if (B == 0) return 0;
   const rk_cur_t cur = {cursor, cursor_off};
   hipLaunchKernelGGL(vae_sample_kernel, dim3(rk_cdiv(B, ROWS_PER_WG)), dim3(64 * ROWS_PER_WG), 0,
                      (hipStream_t)stream_, E, B, d, train, eps_in, seed, rng_step, users, row_off, cur, beta_table,
                      beta, z, eps_out, kl_part);
-  VAE_CHECK_LAUNCH("vae_sample");
+  RK_SIDE_CHECK_LAUNCH("vae_sample");
   return 0;
 }
 
 extern "C" int rk_vae_sample_bwd(const float *E, const float *eps, const float *dz, int32_t B, int32_t d, float inv,
                                  const int64_t *cursor, int32_t cursor_off, const float *beta_table, float beta,
                                  float *dE, void *stream_) {
-  VAE_REQUIRE(B >= 0 && d >= 1, "B >= 0 and d >= 1");
-  VAE_REQUIRE(E != nullptr && eps != nullptr && dz != nullptr && dE != nullptr, "E, eps, dz and dE are required");
+  RK_SIDE_REQUIRE(B >= 0 && d >= 1, "B >= 0 and d >= 1");
+  RK_SIDE_REQUIRE(E != nullptr && eps != nullptr && dz != nullptr && dE != nullptr, "E, eps, dz and dE are required");
   if (B == 0) return 0;
   const rk_cur_t cur = {cursor, cursor_off};
   hipLaunchKernelGGL(vae_sample_bwd_kernel, dim3(rk_cdiv(B, ROWS_PER_WG)), dim3(64 * ROWS_PER_WG), 0,
                      (hipStream_t)stream_, E, eps, dz, B, d, inv, cur, beta_table, beta, dE);
-  VAE_CHECK_LAUNCH("vae_sample_bwd");
+  RK_SIDE_CHECK_LAUNCH("vae_sample_bwd");
   return 0;
 }

@@ -16,6 +16,9 @@ import torch
 from . import _lib
 from ._lib import RkBlock, SCAN_CHUNK, check, ptr
 
+# HBM of one MI355X: a fit whose buffers pass it is refused before any device is touched
+DEVICE_HBM_BYTES = 288 * 2 ** 30
+
 
 def cdiv(a, b):
   return (a + b - 1) // b

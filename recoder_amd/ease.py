@@ -15,24 +15,15 @@ import math
 
 import torch
 
-from . import _ease_lib
-from .als import check_not_distributed as _als_check_not_distributed
-from .device import current_stream
+from . import _ease_lib, als
+from ._lib import ptr
+from .device import DEVICE_HBM_BYTES, current_stream
 
-# HBM of one MI355X: a catalogue whose n x n matrix passes it is refused before any device is touched
-DEVICE_HBM_BYTES = 288 * 2 ** 30
 _INV_NB, _INV_TILE = 64, 128       # (the block width and update tile of rk_ease_spd_inverse)
 
 
-def _ptr(t):
-  return None if t is None else t.data_ptr()
-
-
 def check_not_distributed():
-  try:
-    _als_check_not_distributed()
-  except NotImplementedError:
-    raise NotImplementedError("train_ease runs on one GPU: a multi-GPU EASE fit is not implemented")
+  als.check_not_distributed("train_ease runs on one GPU: a multi-GPU EASE fit is not implemented")
 
 
 def check_reg(reg):
@@ -88,8 +79,8 @@ def gram(ucsr, icsr, reg, out=None):
   if out is None:
     out = torch.empty(n, n, dtype=torch.float32, device=ucsr.indptr.device)
   assert out.shape == (n, n) and out.dtype == torch.float32 and out.stride(1) == 1
-  _ease_lib.check(lib.rk_ease_gram(_ptr(icsr.indptr), _ptr(icsr.indices), _ptr(icsr.data), _ptr(ucsr.indptr),
-                                   _ptr(ucsr.indices), _ptr(ucsr.data), n_users, n, float(reg), _ptr(out),
+  _ease_lib.check(lib.rk_ease_gram(ptr(icsr.indptr), ptr(icsr.indices), ptr(icsr.data), ptr(ucsr.indptr),
+                                   ptr(ucsr.indices), ptr(ucsr.data), n_users, n, float(reg), ptr(out),
                                    out.stride(0), current_stream()), "rk_ease_gram")
   return out
 
@@ -102,7 +93,7 @@ def spd_inverse_async(A, status, ws=None):
   need = lib.rk_ease_spd_inverse_workspace_bytes(n)
   if ws is None or ws.numel() < need:
     ws = torch.empty(need, dtype=torch.uint8, device=A.device)
-  _ease_lib.check(lib.rk_ease_spd_inverse(_ptr(A), n, A.stride(0), _ptr(ws), ws.numel(), _ptr(status),
+  _ease_lib.check(lib.rk_ease_spd_inverse(ptr(A), n, A.stride(0), ptr(ws), ws.numel(), ptr(status),
                                           current_stream()), "rk_ease_spd_inverse")
   return ws
 
@@ -131,7 +122,7 @@ def finalize(P, out=None):
   out = P if out is None else out
   assert P.shape == out.shape == (n, n) and P.stride(1) == 1 and out.stride(1) == 1
   diag = torch.empty(n, dtype=torch.float32, device=P.device)
-  _ease_lib.check(lib.rk_ease_finalize(_ptr(P), n, P.stride(0), _ptr(out), out.stride(0), _ptr(diag),
+  _ease_lib.check(lib.rk_ease_finalize(ptr(P), n, P.stride(0), ptr(out), out.stride(0), ptr(diag),
                                        current_stream()), "rk_ease_finalize")
   return out, diag
 
@@ -148,8 +139,8 @@ def scores(csr, W, lo=0, hi=None, out=None, ld=None, n_rows=None):
     ld = hi - lo if ld is None else ld
     out = torch.empty(n_rows, ld, dtype=torch.float32, device=W.device)
   ld = out.stride(0) if ld is None else ld
-  _ease_lib.check(lib.rk_ease_scores(_ptr(csr.indptr), _ptr(csr.indices), _ptr(csr.data), n_rows, _ptr(W),
-                                     W.stride(0), lo, hi, _ptr(out), ld, current_stream()), "rk_ease_scores")
+  _ease_lib.check(lib.rk_ease_scores(ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), n_rows, ptr(W),
+                                     W.stride(0), lo, hi, ptr(out), ld, current_stream()), "rk_ease_scores")
   return out
 
 

@@ -33,7 +33,7 @@ from .device import Block, DeviceCSR, require_gpu
 from .engine import FusedEngine
 from .losses import MSELoss, MultinomialNLLLoss
 from .metrics import RecommenderEvaluator
-from .nn import (DynamicAutoencoder, FactorizationModel, MatrixFactorization, RandomWalkItemModel,
+from .nn import (DynamicAutoencoder, FactorizationModel, ItemItemModel, MatrixFactorization, RandomWalkItemModel,
                  ShallowAutoencoder, SparseLinearModel, VariationalAutoencoder)
 from .recommender import InferenceRecommender
 
@@ -425,6 +425,25 @@ class Recoder(object):
                 eval_batch_size=eval_batch_size)
     self._sync_user_rows()
 
+  def _scores_from_csr_rows(self):
+    """True for the item-item models (nn.ItemItemModel): scores are the users' CSR rows times W, no encoder."""
+    return isinstance(self.model, ItemItemModel)
+
+  def _size_hints(self, train_dataset):
+    """(num_users, num_items) before the model is initialised: from the dataset's ids where unknown."""
+    n_users, n_items = self.num_users, self.num_items
+    if n_users is None and len(train_dataset.users):
+      n_users = int(np.max(train_dataset.users)) + 1
+    if n_items is None and len(train_dataset.items):
+      n_items = int(np.max(train_dataset.items)) + 1
+    return n_users, n_items
+
+  def _reset_optimizers(self):
+    """A fresh optimizer at the next __init_training: Adam moments of an earlier train() do not describe
+    the tables a closed-form fit leaves."""
+    self.optimizer = self.sparse_optimizer = None
+    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+
   def train_als(self, train_dataset, num_iterations=10, reg=100.0, cg_steps=3):
     """Implicit-feedback alternating least squares for a MatrixFactorization with activation 'none'
     (recoder_amd/als.py): minimises the configured MSELoss(confidence=alpha, reduction='sum') over the
@@ -436,9 +455,7 @@ class Recoder(object):
     alpha = als.check_config(self.model, self.loss, self.loss_params, num_iterations, reg, cg_steps)
     als.check_not_distributed()
     log.info("ALS: %d iterations, reg %g, confidence %g, %d CG steps", num_iterations, reg, alpha, cg_steps)
-    # (a fresh optimizer: Adam moments of an earlier train() do not describe the ALS tables)
-    self.optimizer = self.sparse_optimizer = None
-    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    self._reset_optimizers()
     self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
     ucsr, icsr = als.csr_pair(als.host_matrix(train_dataset), self.num_users, self.num_items, self.device)
     m = self.model
@@ -462,17 +479,11 @@ class Recoder(object):
     from . import als, svd
     h, l = svd.check_config(self.model, oversample, num_power_iterations, seed)
     svd.check_not_distributed()
-    n_users, n_items = self.num_users, self.num_items
-    if n_users is None and len(train_dataset.users):
-      n_users = int(np.max(train_dataset.users)) + 1
-    if n_items is None and len(train_dataset.items):
-      n_items = int(np.max(train_dataset.items)) + 1
+    n_users, n_items = self._size_hints(train_dataset)
     svd.check_rank(l, n_users or 0, n_items or 0)
     svd.check_memory(n_users, n_items, l, 0, free_bytes=float("inf"))
     log.info("PureSVD: h %d, l %d, %d power iterations, seed %d", h, l, num_power_iterations, seed)
-    # (a fresh optimizer: Adam moments of an earlier train() do not describe these tables)
-    self.optimizer = self.sparse_optimizer = None
-    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    self._reset_optimizers()
     self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
     svd.check_rank(l, self.num_users, self.num_items)
     host = als.host_matrix(train_dataset)
@@ -499,16 +510,13 @@ class Recoder(object):
       raise ValueError("train_ease fits a ShallowAutoencoder, not %s" % type(self.model).__name__)
     reg = ease.check_reg(self.model.reg if reg is None else reg)
     ease.check_not_distributed()
-    n_hint = self.num_items
-    if n_hint is None and len(train_dataset.items):
-      n_hint = int(np.max(train_dataset.items)) + 1
+    n_hint = self._size_hints(train_dataset)[1]
     if n_hint:
       # (before init_model allocates the n x n parameter: a 1 M-item catalogue gets a ValueError, not an OOM)
       ease.check_memory(n_hint, free_bytes=float("inf"))
     log.info("EASE: reg %g", reg)
     self.model.reg = reg
-    self.optimizer = self.sparse_optimizer = None
-    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    self._reset_optimizers()
     first = not self.__model_initialized
     if first:
       require_gpu()
@@ -536,18 +544,13 @@ class Recoder(object):
     alpha, beta, K = rp3.check_config(m, m.alpha if alpha is None else alpha, m.beta if beta is None else beta,
                                       m.neighbours if neighbours is None else neighbours)
     rp3.check_not_distributed()
-    n_hint, u_hint = self.num_items, self.num_users
-    if n_hint is None and len(train_dataset.items):
-      n_hint = int(np.max(train_dataset.items)) + 1
-    if u_hint is None and len(train_dataset.users):
-      u_hint = int(np.max(train_dataset.users)) + 1
+    u_hint, n_hint = self._size_hints(train_dataset)
     if n_hint:
       # (before init_model allocates: a catalogue that cannot fit gets a ValueError, not an OOM)
       rp3.check_memory(u_hint or 0, n_hint, K, 0, free_bytes=float("inf"))
     log.info("RP3beta: alpha %g, beta %g, %d neighbours", alpha, beta, K)
     m.alpha, m.beta = alpha, beta
-    self.optimizer = self.sparse_optimizer = None
-    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    self._reset_optimizers()
     if not self.__model_initialized:
       require_gpu()
       m.neighbours = K
@@ -585,11 +588,7 @@ class Recoder(object):
         m, m.l1_reg if l1_reg is None else l1_reg, m.l2_reg if l2_reg is None else l2_reg,
         m.neighbours if neighbours is None else neighbours, max_sweeps, tol)
     slim.check_not_distributed()
-    n_hint, u_hint = self.num_items, self.num_users
-    if n_hint is None and len(train_dataset.items):
-      n_hint = int(np.max(train_dataset.items)) + 1
-    if u_hint is None and len(train_dataset.users):
-      u_hint = int(np.max(train_dataset.users)) + 1
+    u_hint, n_hint = self._size_hints(train_dataset)
     if n_hint:
       # (before init_model allocates: a catalogue whose Gram cannot fit gets a ValueError, not an OOM)
       slim.check_memory(u_hint or 0, n_hint, K, 0, free_bytes=float("inf"))
@@ -597,8 +596,7 @@ class Recoder(object):
     slim.check_values(host)
     log.info("SLIM: l1_reg %g, l2_reg %g, %d neighbours, at most %d sweeps, tol %g", l1, l2, K, max_sweeps, tol)
     m.l1_reg, m.l2_reg = l1, l2
-    self.optimizer = self.sparse_optimizer = None
-    self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
+    self._reset_optimizers()
     if not self.__model_initialized:
       require_gpu()
       m.neighbours = K
@@ -1306,21 +1304,8 @@ class Recoder(object):
     blk, B, n_items = self._input_block(users_interactions)
     ld = blk.ld_cap
     out = torch.empty(B, ld, dtype=torch.float32, device=self.device)
-    if isinstance(self.model, ShallowAutoencoder):
-      from . import ease
-      ease.scores(self._eval_ws["dcsr"], self.model.item_weights.data, 0, n_items, out=out, ld=ld, n_rows=B)
-      return out[:, :n_items], blk, B
-    if isinstance(self.model, RandomWalkItemModel):
-      from . import rp3
-      m = self.model
-      rp3.scores(self._eval_ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, 0, n_items,
-                 out=out, ld=ld, n_rows=B)
-      return out[:, :n_items], blk, B
-    if isinstance(self.model, SparseLinearModel):
-      from . import slim
-      m = self.model
-      slim.scores(self._eval_ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, 0, n_items,
-                  out=out, ld=ld, n_rows=B)
+    if self._scores_from_csr_rows():
+      self.model.csr_scores(self._eval_ws["dcsr"], 0, n_items, out, ld, B)
       return out[:, :n_items], blk, B
     engine.predict_scores(blk, 0, B, out, ld, blk)
     return out[:, :n_items], blk, B
@@ -1358,21 +1343,19 @@ class Recoder(object):
     from .device import current_stream
     lib = _lib.load()
     engine = self._engine()
-    rp3_model = isinstance(self.model, RandomWalkItemModel)
-    slim_model = isinstance(self.model, SparseLinearModel)
-    ease_model = isinstance(self.model, ShallowAutoencoder) or rp3_model or slim_model     # (scores from the CSR rows, no encoder)
-    if (getattr(engine, "generic", False) and not ease_model) or k > lib.rk_topk_max_k():
+    csr_model = self._scores_from_csr_rows()
+    if (getattr(engine, "generic", False) and not csr_model) or k > lib.rk_topk_max_k():
       return self._recommend_dense(users_interactions, k)
     blk, B, n_items = self._input_block(users_interactions)
     ws = self._eval_ws
-    z = None if ease_model else engine.encode_eval(blk, 0, B)
+    z = None if csr_model else engine.encode_eval(blk, 0, B)
     strip = max(k, min(n_items, int(self.eval_strip_items)))
     bounds = [(lo, min(n_items, lo + strip)) for lo in range(0, n_items, strip)]
     if len(bounds) > 1 and bounds[-1][1] - bounds[-1][0] < k:      # a last strip shorter than k:
       lo0 = bounds[-2][0]                                         # merge it into the one before
       bounds = bounds[:-2] + [(lo0, n_items)]
     ns = len(bounds)
-    if ns > 1 and not ease_model and os.environ.get("RK_EVAL_FUSED", "1") != "0" and \
+    if ns > 1 and not csr_model and os.environ.get("RK_EVAL_FUSED", "1") != "0" and \
         hasattr(engine, "recommend_fused"):
       # catalogues of more than one strip: the top-k filter rides in the decode's epilogue (no score
       # matrix, no passes over it): a strided sample of the catalogue bounds every row's k-th best
@@ -1396,21 +1379,9 @@ class Recoder(object):
     cand_idx, cand_val = ws["cand"][0][:B], ws["cand"][1][:B]
     scores = ws["scores"]
     for s, (lo, hi) in enumerate(bounds):
-      if ease_model:
-        # a ShallowAutoencoder's, RandomWalkItemModel's or SparseLinearModel's strip of scores: the users' CSR rows times W[:, lo:hi]
-        if rp3_model:
-          from . import rp3
-          m = self.model
-          rp3.scores(ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, lo, hi, out=scores,
-                     ld=ld, n_rows=B)
-        elif slim_model:
-          from . import slim
-          m = self.model
-          slim.scores(ws["dcsr"], m.item_neighbours, m.item_weights.data, m.neighbour_counts, lo, hi, out=scores,
-                      ld=ld, n_rows=B)
-        else:
-          from . import ease
-          ease.scores(ws["dcsr"], self.model.item_weights.data, lo, hi, out=scores, ld=ld, n_rows=B)
+      if csr_model:
+        # an item-item model's strip of scores: the users' CSR rows times W[:, lo:hi]
+        self.model.csr_scores(ws["dcsr"], lo, hi, scores, ld, B)
         _lib.check(lib.rk_topk_masked(scores.data_ptr(), B, hi - lo, ld, blk.ref, 0, k, lo, 1,
                                       cand_idx[:, s * k:].data_ptr(), cand_val[:, s * k:].data_ptr(),
                                       ns * k, current_stream()), "rk_topk_masked")

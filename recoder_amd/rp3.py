@@ -19,26 +19,17 @@ import math
 import numpy as np
 import torch
 
-from . import _rp3_lib
-from .als import check_not_distributed as _als_check_not_distributed
-from .device import current_stream
+from . import _neighbours, _rp3_lib, als
+from ._lib import ptr
+from .device import DEVICE_HBM_BYTES, current_stream
 
-# HBM of one MI355X
-DEVICE_HBM_BYTES = 288 * 2 ** 30
 MAX_NEIGHBOURS = 1024      # rk_rp3_max_neighbours()
 LDS_ITEMS = 12288          # rk_rp3_lds_items()
 _GROUPS, _WAVES = 512, 16  # (resident workgroups and waves per workgroup of rk_rp3_fit)
 
 
-def _ptr(t):
-  return None if t is None else t.data_ptr()
-
-
 def check_not_distributed():
-  try:
-    _als_check_not_distributed()
-  except NotImplementedError:
-    raise NotImplementedError("train_rp3beta runs on one GPU: a multi-GPU RP3beta fit is not implemented")
+  als.check_not_distributed("train_rp3beta runs on one GPU: a multi-GPU RP3beta fit is not implemented")
 
 
 def check_config(model, alpha, beta, neighbours):
@@ -54,10 +45,7 @@ def check_params(alpha, beta, neighbours):
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
         not (math.isfinite(float(v)) and float(v) >= 0):
       raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
-  if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or \
-      not 1 <= neighbours <= MAX_NEIGHBOURS:
-    raise ValueError("neighbours must be an integer in [1, %d] (got %r)" % (MAX_NEIGHBOURS, neighbours))
-  return float(alpha), float(beta), int(neighbours)
+  return float(alpha), float(beta), _neighbours.check_neighbours(neighbours, MAX_NEIGHBOURS)
 
 
 def _power(x, e):
@@ -131,9 +119,9 @@ def fit_rows(ucsr, icsr, user_w, row_scale, col_scale, ids, w, count, row_lo=0, 
   need = lib.rk_rp3_fit_workspace_bytes(n)
   if ws is None or ws.numel() < need:
     ws = torch.empty(need, dtype=torch.uint8, device=ids.device)
-  _rp3_lib.check(lib.rk_rp3_fit(_ptr(icsr.indptr), _ptr(icsr.indices), _ptr(ucsr.indptr), _ptr(ucsr.indices),
-                                n_users, n, _ptr(user_w), _ptr(row_scale), _ptr(col_scale), K, row_lo, row_hi,
-                                _ptr(ids), _ptr(w), _ptr(count), _ptr(ws), ws.numel(), current_stream()),
+  _rp3_lib.check(lib.rk_rp3_fit(ptr(icsr.indptr), ptr(icsr.indices), ptr(ucsr.indptr), ptr(ucsr.indices),
+                                n_users, n, ptr(user_w), ptr(row_scale), ptr(col_scale), K, row_lo, row_hi,
+                                ptr(ids), ptr(w), ptr(count), ptr(ws), ws.numel(), current_stream()),
                  "rk_rp3_fit")
   return ws
 
@@ -142,21 +130,7 @@ def scores(csr, ids, w, count, lo=0, hi=None, out=None, ld=None, n_rows=None):
   """out[u, c] = sum_i x_ui W[i, lo + c] over the stored entries of CSR row u, ascending, W the sparse
   matrix the kept neighbours spell (rk_rp3_scores).  ``csr``: anything with int64 ``indptr``, int32
   ``indices`` and fp32 ``data`` (or None) on the device."""
-  lib = _rp3_lib.load()
-  n, K = ids.shape
-  hi = n if hi is None else hi
-  n_rows = csr.shape[0] if n_rows is None else n_rows
-  assert ids.dtype == torch.int32 and w.dtype == torch.float32 and count.dtype == torch.int32
-  assert ids.is_contiguous() and w.is_contiguous() and w.shape == (n, K) and count.shape == (n,)
-  assert 0 <= lo < hi <= n and csr.shape[1] <= n
-  if out is None:
-    ld = hi - lo if ld is None else ld
-    out = torch.empty(n_rows, ld, dtype=torch.float32, device=ids.device)
-  ld = out.stride(0) if ld is None else ld
-  _rp3_lib.check(lib.rk_rp3_scores(_ptr(csr.indptr), _ptr(csr.indices), _ptr(csr.data), n_rows, n, _ptr(ids),
-                                   _ptr(w), _ptr(count), K, lo, hi, _ptr(out), ld, current_stream()),
-                 "rk_rp3_scores")
-  return out
+  return _neighbours.scores(_rp3_lib, "rk_rp3_scores", csr, ids, w, count, lo, hi, out, ld, n_rows)
 
 
 # ---------------------------------------------------------------------- fit

@@ -21,26 +21,17 @@ import math
 import numpy as np
 import torch
 
-from . import _slim_lib
-from .als import check_not_distributed as _als_check_not_distributed
-from .device import current_stream
+from . import _neighbours, _slim_lib, als
+from ._lib import ptr
+from .device import DEVICE_HBM_BYTES, current_stream
 
-# HBM of one MI355X
-DEVICE_HBM_BYTES = 288 * 2 ** 30
 MAX_NEIGHBOURS = 1024      # rk_slim_max_neighbours()
 LDS_CANDIDATES = 960       # rk_slim_lds_candidates()
 _GROUPS, _ARRAYS = 2048, 5  # (resident workgroups of rk_slim_fit and the state arrays of a column)
 
 
-def _ptr(t):
-  return None if t is None else t.data_ptr()
-
-
 def check_not_distributed():
-  try:
-    _als_check_not_distributed()
-  except NotImplementedError:
-    raise NotImplementedError("train_slim runs on one GPU: a multi-GPU SLIM fit is not implemented")
+  als.check_not_distributed("train_slim runs on one GPU: a multi-GPU SLIM fit is not implemented")
 
 
 def check_config(model, l1_reg, l2_reg, neighbours, max_sweeps=50, tol=1e-5):
@@ -56,12 +47,10 @@ def check_params(l1_reg, l2_reg, neighbours, max_sweeps=50, tol=1e-5):
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
         not (math.isfinite(float(v)) and float(v) >= 0):
       raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
-  if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or \
-      not 1 <= neighbours <= MAX_NEIGHBOURS:
-    raise ValueError("neighbours must be an integer in [1, %d] (got %r)" % (MAX_NEIGHBOURS, neighbours))
+  neighbours = _neighbours.check_neighbours(neighbours, MAX_NEIGHBOURS)
   if isinstance(max_sweeps, bool) or not isinstance(max_sweeps, (int, np.integer)) or not 1 <= max_sweeps < 2 ** 31:
     raise ValueError("max_sweeps must be an integer >= 1 (got %r)" % (max_sweeps,))
-  return float(l1_reg), float(l2_reg), int(neighbours), int(max_sweeps), float(tol)
+  return float(l1_reg), float(l2_reg), neighbours, int(max_sweeps), float(tol)
 
 
 def check_values(host):
@@ -140,9 +129,9 @@ def fit_columns(G, inv, l1_reg, ids, w, count, sweeps, support, max_sweeps=50, t
   need = lib.rk_slim_fit_workspace_bytes(n)
   if ws is None or ws.numel() < need:
     ws = torch.empty(need, dtype=torch.uint8, device=ids.device)
-  _slim_lib.check(lib.rk_slim_fit(_ptr(G), G.stride(0), n, _ptr(inv), float(l1_reg), K, int(max_sweeps), float(tol),
-                                  col_lo, col_hi, _ptr(ids), _ptr(w), _ptr(count), _ptr(sweeps), _ptr(support),
-                                  _ptr(ws), ws.numel(), current_stream()), "rk_slim_fit")
+  _slim_lib.check(lib.rk_slim_fit(ptr(G), G.stride(0), n, ptr(inv), float(l1_reg), K, int(max_sweeps), float(tol),
+                                  col_lo, col_hi, ptr(ids), ptr(w), ptr(count), ptr(sweeps), ptr(support),
+                                  ptr(ws), ws.numel(), current_stream()), "rk_slim_fit")
   return ws
 
 
@@ -150,21 +139,7 @@ def scores(csr, ids, w, count, lo=0, hi=None, out=None, ld=None, n_rows=None):
   """out[u, c] = sum_k x_uk W[k, lo + c] over the kept entries of column lo + c, ascending, that CSR row u
   stores (rk_slim_scores).  ``csr``: anything with int64 ``indptr``, int32 ``indices`` and fp32 ``data``
   (or None) on the device."""
-  lib = _slim_lib.load()
-  n, K = ids.shape
-  hi = n if hi is None else hi
-  n_rows = csr.shape[0] if n_rows is None else n_rows
-  assert ids.dtype == torch.int32 and w.dtype == torch.float32 and count.dtype == torch.int32
-  assert ids.is_contiguous() and w.is_contiguous() and w.shape == (n, K) and count.shape == (n,)
-  assert 0 <= lo < hi <= n and csr.shape[1] <= n
-  if out is None:
-    ld = hi - lo if ld is None else ld
-    out = torch.empty(n_rows, ld, dtype=torch.float32, device=ids.device)
-  ld = out.stride(0) if ld is None else ld
-  _slim_lib.check(lib.rk_slim_scores(_ptr(csr.indptr), _ptr(csr.indices), _ptr(csr.data), n_rows, n, _ptr(ids),
-                                     _ptr(w), _ptr(count), K, lo, hi, _ptr(out), ld, current_stream()),
-                  "rk_slim_scores")
-  return out
+  return _neighbours.scores(_slim_lib, "rk_slim_scores", csr, ids, w, count, lo, hi, out, ld, n_rows)
 
 
 # ---------------------------------------------------------------------- fit

@@ -21,18 +21,13 @@ import numpy as np
 import torch
 
 from . import _svd_lib, als
-from .device import current_stream
+from ._lib import ptr
+from .device import DEVICE_HBM_BYTES, current_stream
 from .nn import MatrixFactorization
 
 MAX_L = 512                      # rk_svd_max_l()
 LONG_ROW = _svd_lib.LONG_ROW     # rows this long take the sparse product's 16-wave path
 _CHOL_LDS_L = 128                # (up to here rk_svd_chol_inverse needs no workspace)
-# HBM of one MI355X: a fit whose buffers pass it is refused before any device is touched
-DEVICE_HBM_BYTES = 288 * 2 ** 30
-
-
-def _ptr(t):
-  return None if t is None else t.data_ptr()
 
 
 def _is_int(v):
@@ -63,10 +58,7 @@ def check_config(model, oversample, num_power_iterations, seed):
 
 
 def check_not_distributed():
-  try:
-    als.check_not_distributed()
-  except NotImplementedError:
-    raise NotImplementedError("train_svd runs on one GPU: a multi-GPU PureSVD fit is not implemented")
+  als.check_not_distributed("train_svd runs on one GPU: a multi-GPU PureSVD fit is not implemented")
 
 
 def check_rank(l, n_users, n_items):
@@ -108,7 +100,7 @@ def gaussian(rows, l, seed, out=None):
     out = torch.empty(rows, l, dtype=torch.float32, device="cuda")
   assert out.shape == (rows, l) and out.dtype == torch.float32 and (out.stride(1) == 1 or l == 1)
   ld = out.stride(0) if rows > 1 else l
-  _svd_lib.check(lib.rk_svd_gaussian(_ptr(out), rows, l, ld, int(seed) & (2 ** 64 - 1), current_stream()),
+  _svd_lib.check(lib.rk_svd_gaussian(ptr(out), rows, l, ld, int(seed) & (2 ** 64 - 1), current_stream()),
                  "rk_svd_gaussian")
   return out
 
@@ -126,8 +118,8 @@ def spmm(csr, F, out=None, row_lo=0, row_hi=None):
   assert (F.stride(1) == 1 and out.stride(1) == 1) or l == 1
   ldf = F.stride(0) if F.shape[0] > 1 else l
   ldy = out.stride(0) if out.shape[0] > 1 else l
-  _svd_lib.check(lib.rk_svd_spmm(_ptr(csr.indptr), _ptr(csr.indices), _ptr(csr.data), row_lo, row_hi, _ptr(F),
-                                 ldf, l, _ptr(out), ldy, current_stream()), "rk_svd_spmm")
+  _svd_lib.check(lib.rk_svd_spmm(ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), row_lo, row_hi, ptr(F),
+                                 ldf, l, ptr(out), ldy, current_stream()), "rk_svd_spmm")
   return out
 
 
@@ -146,7 +138,7 @@ def chol_inverse(G, status, ws=None):
   if ws is None or ws.numel() < need:
     ws = chol_workspace(l, G.device)
   Rinv = torch.empty(l, l, dtype=torch.float32, device=G.device)
-  _svd_lib.check(lib.rk_svd_chol_inverse(_ptr(G), l, _ptr(Rinv), _ptr(ws), ws.numel(), _ptr(status),
+  _svd_lib.check(lib.rk_svd_chol_inverse(ptr(G), l, ptr(Rinv), ptr(ws), ws.numel(), ptr(status),
                                          current_stream()), "rk_svd_chol_inverse")
   return Rinv
 
@@ -164,7 +156,7 @@ def rotate(Y, M, out=None):
   ldy = Y.stride(0) if rows > 1 else l
   ldm = M.stride(0) if l > 1 else l2
   ldo = out.stride(0) if rows > 1 else l2
-  _svd_lib.check(lib.rk_svd_rotate(_ptr(Y), rows, l, ldy, _ptr(M), l2, ldm, _ptr(out), ldo, current_stream()),
+  _svd_lib.check(lib.rk_svd_rotate(ptr(Y), rows, l, ldy, ptr(M), l2, ldm, ptr(out), ldo, current_stream()),
                  "rk_svd_rotate")
   return out
 

@@ -4,56 +4,18 @@ library's exports alone; ExactEmbeddingsIndex builds, saves and loads without a 
 loudly when asked to search without one."""
 import os
 import pickle
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.abi_util import built  # noqa: F401  (built: a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INDEX_HEADER = os.path.join(ROOT, "include", "recoder_index.h")
-TRAIN_HEADERS = [os.path.join(ROOT, "include", "recoder_hip.h"), os.path.join(ROOT, "include", "recoder_hip_probe.h")]
-
-
-def _declared(paths):
-  src = "".join(open(p).read() for p in paths)
-  src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-  return sorted(set(re.findall(r"\b(rk_[a-z0-9_]+)\s*\(", src)))
-
-
-def _exports(path):
-  out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-  return sorted(l.split()[-1] for l in out.splitlines() if " T " in l)
-
-
-@pytest.fixture(scope="module")
-def built():
-  from recoder_amd.build import INDEX_LIB, LIB, build_library
-  build_library(verbose=False)
-  return LIB, INDEX_LIB
 
 
 def test_build_library_produces_both_libraries(built):
-  for path in built:
+  for path in (built.LIB, built.INDEX_LIB):
     assert os.path.exists(path), path
-
-
-def test_index_library_exports_exactly_its_header(built):
-  from recoder_amd import _index_lib
-  declared = _declared([INDEX_HEADER])
-  assert declared and all(s.startswith("rk_ix_") for s in declared)
-  assert _exports(built[1]) == declared
-  assert sorted(_index_lib.SIGNATURES) == declared
-  lib = _index_lib.load()
-  assert lib.rk_ix_version() >= 100
-  assert isinstance(lib.rk_ix_last_error(), bytes)
-
-
-def test_training_library_exports_are_unchanged(built):
-  exported = _exports(built[0])
-  assert exported == _declared(TRAIN_HEADERS)
-  assert len(exported) == 80
-  assert not any(s.startswith("rk_ix_") for s in exported)
 
 
 def test_build_load_round_trip_without_gpu(tmp_path):
