@@ -39,6 +39,35 @@
  *     are sorted by id.
  *   - rk_rp3_scores: one ascending f32 fmaf chain per output, from +0, over the user's stored
  *     entries: a score depends neither on the strip nor on the user's position in the batch.
+ *
+ * UserKNN (rk_rp3_user_*): the user-neighbourhood model, served from the training matrix X itself.  It
+ * lives in this library because it is the fit's row pass turned round: the same hand-out of rows through
+ * a counter, the same LDS / workspace split of the accumulator, the same exact selection and compaction
+ * (one device function in rp3.hip, shared by both kernels).  With H_v the items of training user v and
+ * H_q the stored items of a query row q (values play no part in the similarity):
+ *   c_qv   = |H_q and H_v|                                          (an integer, exact)
+ *   sim_qv = c_qv / (qn[q] * un[v] + shrink)                        (cosine with qn = |H_q|^1/2, un = |H_v|^1/2)
+ *   q keeps its N largest sim_qv > 0 by (sim descending, v ascending), stored with ascending v
+ *   scores(q, j) = sum over the kept v, ascending, of sim_qv * x_vj
+ * qn and un are INPUTS made on the host (float64 square roots rounded once to f32): no sqrt runs on the
+ * device.  A training user whose row equals the query is a neighbour like any other (the interface
+ * carries no user ids).
+ *
+ * Numerics of rk_rp3_user_* (bitwise repeatable; a row's result depends on the data alone)
+ *   - c_qv is counted with 32-bit integer atomic adds on the workgroup's own accumulator row: integer
+ *     adds commute, so the order in which the waves arrive changes nothing.
+ *   - sim = c / ((qn * un) + shrink): the product, the sum and the quotient are three separate f32
+ *     operations, each correctly rounded.  The product and the sum are compiled under
+ *     "#pragma clang fp contract(off)" (hipcc's default would fuse them into one fma); the quotient is
+ *     __fdiv_rn, and the library is built without -ffast-math and with hipcc's default
+ *     -fhip-fp32-correctly-rounded-divide-sqrt, so that no approximate reciprocal stands in for it.
+ *   - selection and compaction: the fit's, ties at the N-th value to the lower user ids.
+ *   - rk_rp3_user_scores: one f32 fmaf chain per output, from +0, over the kept neighbours in ascending
+ *     v.  The split: a workgroup takes one query and one tile of 8192 columns, each of its 8 waves owns
+ *     1024 consecutive columns of the tile and walks ALL the query's neighbours in ascending order, 64 at a
+ *     time (lane l finds by binary search where neighbour l's ascending row enters and leaves the wave's
+ *     columns; then the wave takes the 64 one after the other).  A column's chain therefore stays inside
+ *     one wave, in neighbour order, whatever lo, hi and the query's position in the batch.
  */
 #ifndef RECODER_RP3_H
 #define RECODER_RP3_H
@@ -54,7 +83,7 @@ extern "C" {
 int rk_rp3_version(void);
 const char *rk_rp3_last_error(void);
 
-/* the largest K of rk_rp3_fit / rk_rp3_scores (1024) */
+/* the largest K of rk_rp3_fit / rk_rp3_scores and the largest N of rk_rp3_user_* (1024) */
 int rk_rp3_max_neighbours(void);
 
 /* the largest n_items whose row accumulators live in LDS; a larger catalogue keeps one n-float row
@@ -92,6 +121,40 @@ int rk_rp3_fit(const int64_t *t_indptr, const int32_t *t_indices, const int64_t 
 int rk_rp3_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
                   int32_t n_items, const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count,
                   int32_t K, int32_t lo, int32_t hi, float *out, int64_t ldo, void *stream);
+
+/* bytes of workspace rk_rp3_user_neighbours needs for n_users training users (host arithmetic; > 0;
+ * < 0 on bad arguments): the counter alone up to rk_rp3_lds_items() users, above it one row of counts
+ * and one list of touched users per resident workgroup */
+int64_t rk_rp3_user_workspace_bytes(int32_t n_users);
+
+/*
+ * The neighbour lists of the query rows [row_lo, row_hi): one fused pass per row (count, scale, select,
+ * compact).  (q_*): the query CSR's indptr and indices (row_hi <= its rows; an item outside [0, n_items)
+ * adds nothing); (t_*): the item-major CSR of X (n_items rows, columns = training users).  un [n_users],
+ * qn [query rows] as above, shrink finite and >= 0, 1 <= N <= rk_rp3_max_neighbours().
+ *   nbr_ids   int32 [query rows, N]  the kept v of row q, ascending; -1 past nbr_count[q]
+ *   nbr_sim   f32   [query rows, N]  their sim_qv; +0 past nbr_count[q]
+ *   nbr_count int32 [query rows]     how many were kept (<= N)
+ * Rows outside [row_lo, row_hi) are not touched.  Rows are handed to the resident workgroups through one
+ * counter in the workspace, as in rk_rp3_fit.  ws must be 256-byte aligned.
+ */
+int rk_rp3_user_neighbours(const int64_t *q_indptr, const int32_t *q_indices, const int64_t *t_indptr,
+                           const int32_t *t_indices, int32_t n_users, int32_t n_items, const float *un,
+                           const float *qn, float shrink, int32_t N, int32_t row_lo, int32_t row_hi,
+                           int32_t *nbr_ids, float *nbr_sim, int32_t *nbr_count, void *ws, int64_t ws_bytes,
+                           void *stream);
+
+/*
+ * out[q][c] = sum over the kept neighbours (v, sim) of row q, ascending, of sim * X[v][lo + c] for q in
+ * [0, n_rows) and c in [0, hi - lo); columns nobody reaches are +0.  (u_*): the user-major CSR of X (n_users
+ * rows, columns = items ascending); u_data NULL: every value is 1.0.  A neighbour id outside [0, n_users)
+ * adds nothing.  0 <= lo < hi <= n_items.  out [n_rows, ldo], ldo >= hi - lo; columns past hi - lo are
+ * left as they are.  The layout is what rk_topk_masked reads.
+ */
+int rk_rp3_user_scores(const int32_t *nbr_ids, const float *nbr_sim, const int32_t *nbr_count, int32_t n_rows,
+                       int32_t N, const int64_t *u_indptr, const int32_t *u_indices, const float *u_data,
+                       int32_t n_users, int32_t n_items, int32_t lo, int32_t hi, float *out, int64_t ldo,
+                       void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -8,7 +8,7 @@ Drop-in for the reference's training path: ``Recoder`` / ``FactorizationModel``
 # in checkpoints as 'recoder_version' (model.py:207)
 __version__ = "0.4.0"
 
-__all__ = ["ShallowAutoencoder", "RandomWalkItemModel", "SparseLinearModel"]
+__all__ = ["ShallowAutoencoder", "RandomWalkItemModel", "SparseLinearModel", "UserNeighbourhoodModel"]
 
 
 def __getattr__(name):
@@ -22,4 +22,7 @@ def __getattr__(name):
   if name == "SparseLinearModel":
     from .nn import SparseLinearModel
     return SparseLinearModel
+  if name == "UserNeighbourhoodModel":
+    from .nn import UserNeighbourhoodModel
+    return UserNeighbourhoodModel
   raise AttributeError("module %r has no attribute %r" % (__name__, name))

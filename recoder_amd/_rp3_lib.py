@@ -1,12 +1,12 @@
 """ctypes binding of librecoder_rp3.so (the C ABI in include/recoder_rp3.h): the RP3beta kernels
-for recoder_amd.rp3.  Like _lib.py: plain pointers and sizes, no torch types across the boundary,
+for recoder_amd.rp3 and the user-neighbourhood kernels for recoder_amd.userknn.  Like _lib.py: plain pointers and sizes, no torch types across the boundary,
 no CPU fallback."""
 import os
 
 # PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
 import torch  # noqa: F401
 
-from ctypes import c_char_p, c_int32, c_int64, c_void_p
+from ctypes import c_char_p, c_float, c_int32, c_int64, c_void_p
 
 from ._lib import checker, loader
 
@@ -25,6 +25,11 @@ SIGNATURES = {
   "rk_rp3_fit": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P,
                            c_int64, _P]),
   "rk_rp3_scores": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P]),
+  "rk_rp3_user_workspace_bytes": (c_int64, [c_int32]),
+  "rk_rp3_user_neighbours": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, _P, _P, c_float, c_int32, c_int32, c_int32, _P,
+                                       _P, _P, _P, c_int64, _P]),
+  "rk_rp3_user_scores": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P,
+                                   c_int64, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

@@ -16,7 +16,9 @@ librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencod
 librecoder_svd.so  the randomized truncated SVD behind PureSVD for MatrixFactorization
                    (include/recoder_svd.h), likewise a library of its own
 librecoder_rp3.so  the RP3beta item-graph fit and its scores for RandomWalkItemModel
-                   (include/recoder_rp3.h), likewise a library of its own
+                   (include/recoder_rp3.h), likewise a library of its own.  It also holds the
+                   user-neighbourhood kernels of UserNeighbourhoodModel (rk_rp3_user_*): they share
+                   the fit's row hand-out and selection, which live in this translation unit
 librecoder_slim.so  the SLIM coordinate-descent fit and its scores for SparseLinearModel
                    (include/recoder_slim.h), likewise a library of its own
 

@@ -14,6 +14,17 @@
 //   rk_rp3_scores  one workgroup per (user, tile of 8192 columns held in LDS); each of its 8 waves owns
 //                  1024 columns and walks the user's entries in order, adding x * w of the neighbours
 //                  that fall in its columns
+//
+// UserKNN, the user-neighbourhood model served from the training matrix itself:
+//   rk_rp3_user_neighbours  one workgroup per query row at a time, rows handed out through the same counter.
+//                  accumulate: c[v] = |H_q and H_v| by integer atomics on the workgroup's own accumulator
+//                    (LDS, or a workspace row that also lists the users it touches: a user's first touch is
+//                    the add that returns 0); an item with few users belongs to one wave, an item with many
+//                    is walked by all sixteen
+//                  scale: sim = c / (qn[q] * un[v] + shrink); select, compact: the fit's (ft_select_store)
+//   rk_rp3_user_scores  rk_rp3_scores' tiling: one workgroup per (query, tile of 8192 columns in LDS), a wave owns
+//                  1024 columns and walks the query's neighbours in order; 64 neighbours at a time, a lane
+//                  finds by binary search where its neighbour's row enters and leaves the wave's columns
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -71,6 +82,102 @@ __device__ void ft_pick(const int *hist, int need, int lane, bool desc, int *o) 
     }
     run += h[q];
   }
+}
+
+// What a row's pass does once its values stand in acc (every thread of the workgroup calls it): select,
+// compact and store row ``row`` of the [*, K] lists.  On entry acc[j] holds the value of every candidate j
+// (for_cands(f) calls f(j) once per candidate, spread over the threads), hist the histogram of the top
+// byte of the values > 0 and sh[5] is 0; n bounds the ids.  kid / kw: FT_MAX_K entries; sh[1..5] are used.
+template <class ForCands>
+__device__ __forceinline__ void ft_select_store(const float *acc, ForCands for_cands, int K, int n, int row,
+                                                int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_w,
+                                                int32_t *__restrict__ nbr_count, int *hist, int *sh, int *kid,
+                                                float *kw, int tid, int lane, int wv) {
+  // ---- select: T = the K-th largest value's bits, need = how many equal to T are kept, J = up to which id
+  uint32_t T = 0, tmask = 0;
+  int need = K, J = INT_MAX;
+  bool all = false;
+#pragma unroll 1
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (shift != 24) {
+      if (tid < 256) hist[tid] = 0;
+      __syncthreads();
+      for_cands([&](int j) {
+        const float w = acc[j];
+        const uint32_t k = f2u(w);
+        if (w > 0.f && (k & tmask) == T) atomicAdd(&hist[(k >> shift) & 255], 1);
+      });
+      __syncthreads();
+    }
+    if (wv == 0) ft_pick(hist, need, lane, true, sh + 1);
+    __syncthreads();
+    if (shift == 24 && sh[4] <= K) {
+      all = true;
+      break;
+    }
+    T |= (uint32_t)sh[1] << shift;
+    tmask |= 255u << shift;
+    need = sh[2];
+  }
+  if (!all && sh[3] > need) {
+    uint32_t jp = 0, jm = 0;
+#pragma unroll 1
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      if (((uint32_t)(n - 1) >> shift) != 0) {      // (otherwise: every id has zeros here)
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for_cands([&](int j) {
+          if (f2u(acc[j]) == T && ((uint32_t)j & jm) == jp) atomicAdd(&hist[((uint32_t)j >> shift) & 255], 1);
+        });
+        __syncthreads();
+        if (wv == 0) ft_pick(hist, need, lane, false, sh + 1);
+        __syncthreads();
+        jp |= (uint32_t)sh[1] << shift;
+        need = sh[2];
+      }
+      jm |= 255u << shift;
+    }
+    J = (int)jp;
+  }
+
+  // ---- compact: gather (any order), sort by id, store
+  for_cands([&](int j) {
+    const float w = acc[j];
+    const uint32_t k = f2u(w);
+    if (w > 0.f && (all || k > T || (k == T && j <= J))) {
+      const int pos = atomicAdd(&sh[5], 1);
+      if (pos < FT_MAX_K) {
+        kid[pos] = j;
+        kw[pos] = w;
+      }
+    }
+  });
+  __syncthreads();
+  const int kept = sh[5] < K ? sh[5] : K;
+  int P = 1;
+  while (P < kept) P <<= 1;
+  if (tid >= kept && tid < P) kid[tid] = INT_MAX;
+  __syncthreads();
+  for (int k2 = 2; k2 <= P; k2 <<= 1)
+    for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
+      const int o = tid ^ j2;
+      if (tid < P && o > tid) {
+        const int a = kid[tid], b = kid[o];
+        if ((a > b) == ((tid & k2) == 0)) {
+          kid[tid] = b;
+          kid[o] = a;
+          const float wa = kw[tid];
+          kw[tid] = kw[o];
+          kw[o] = wa;
+        }
+      }
+      __syncthreads();
+    }
+  for (int c = tid; c < K; c += FT_THREADS) {
+    nbr_ids[(int64_t)row * K + c] = c < kept ? kid[c] : -1;
+    nbr_w[(int64_t)row * K + c] = c < kept ? kw[c] : 0.f;
+  }
+  if (tid == 0) nbr_count[row] = kept;
 }
 
 template <bool WS>
@@ -182,92 +289,133 @@ __global__ __launch_bounds__(FT_THREADS) void rp3_fit_kernel(
     });
     __syncthreads();
 
-    // ---- select: T = the K-th largest value's bits, need = how many equal to T are kept, J = up to which id
-    uint32_t T = 0, tmask = 0;
-    int need = K, J = INT_MAX;
-    bool all = false;
-#pragma unroll 1
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (shift != 24) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        for_cands([&](int j) {
-          const float w = acc[j];
-          const uint32_t k = f2u(w);
-          if (w > 0.f && (k & tmask) == T) atomicAdd(&hist[(k >> shift) & 255], 1);
-        });
-        __syncthreads();
-      }
-      if (wv == 0) ft_pick(hist, need, lane, true, sh + 1);
-      __syncthreads();
-      if (shift == 24 && sh[4] <= K) {
-        all = true;
-        break;
-      }
-      T |= (uint32_t)sh[1] << shift;
-      tmask |= 255u << shift;
-      need = sh[2];
+    ft_select_store(acc, for_cands, K, n, i, nbr_ids, nbr_w, nbr_count, hist, sh, kid, kw, tid, lane, wv);
+    if (WS) for_cands([&](int j) { acc[j] = -0.f; });
+  }
+}
+
+// ----------------------------------------------------------- user neighbours
+constexpr int UN_WIDE = 256;                  // an item with at least this many users is walked by every wave
+
+// c / ((qs * u) + shrink): three f32 operations, each correctly rounded.  hipcc's default -ffp-contract=fast
+// would fuse the product and the sum into one fma (__fmul_rn / __fadd_rn are plain * and + to it), hence the pragma
+__device__ inline float un_sim(float c, float qs, float u, float shrink) {
+#pragma clang fp contract(off)
+  const float prod = qs * u;
+  const float den = prod + shrink;
+  return __fdiv_rn(c, den);
+}
+
+// (the accumulator row holds counts while a row accumulates and the similarities afterwards: one 32-bit
+// word per user either way, so that ft_select_store reads it as the fit's)
+template <bool WS>
+__global__ __launch_bounds__(FT_THREADS) void rp3_user_neighbours_kernel(
+    const int64_t *__restrict__ q_indptr, const int32_t *__restrict__ q_indices,
+    const int64_t *__restrict__ t_indptr, const int32_t *__restrict__ t_indices, int n_users, int n,
+    const float *__restrict__ un, const float *__restrict__ qn, float shrink, int K, int row_lo, int row_hi,
+    int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_sim, int32_t *__restrict__ nbr_count, int *counter,
+    float *ws_acc, int *ws_cand, int64_t acc_stride) {
+  __shared__ float lds_acc[WS ? 1 : FT_LDS_ITEMS];
+  __shared__ int kid[FT_MAX_K];
+  __shared__ float kw[FT_MAX_K];
+  __shared__ int hist[256];
+  __shared__ int sh[8];          // 0: the row's offset; 1..4: ft_pick's answer; 5: entries gathered; 6: users touched
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float *acc = WS ? ws_acc + (int64_t)blockIdx.x * acc_stride : lds_acc;
+  int *cand = WS ? ws_cand + (int64_t)blockIdx.x * acc_stride : nullptr;
+
+  auto for_cands = [&](auto f) {
+    if (!WS) {
+      for (int v = tid; v < n_users; v += FT_THREADS) f(v);
+    } else {
+      const int c = sh[6] < acc_stride ? sh[6] : (int)acc_stride;
+      for (int s = tid; s < c; s += FT_THREADS) f(cand[s]);
     }
-    if (!all && sh[3] > need) {
-      uint32_t jp = 0, jm = 0;
-#pragma unroll 1
-      for (int shift = 24; shift >= 0; shift -= 8) {
-        if (((uint32_t)(n - 1) >> shift) != 0) {      // (otherwise: every id has zeros here)
-          if (tid < 256) hist[tid] = 0;
-          __syncthreads();
-          for_cands([&](int j) {
-            if (f2u(acc[j]) == T && ((uint32_t)j & jm) == jp) atomicAdd(&hist[((uint32_t)j >> shift) & 255], 1);
-          });
-          __syncthreads();
-          if (wv == 0) ft_pick(hist, need, lane, false, sh + 1);
-          __syncthreads();
-          jp |= (uint32_t)sh[1] << shift;
-          need = sh[2];
-        }
-        jm |= 255u << shift;
-      }
-      J = (int)jp;
+  };
+
+  if (WS)
+    for (int v = tid; v < n_users; v += FT_THREADS) acc[v] = 0.f;
+
+  for (;;) {
+    __syncthreads();
+    if (tid == 0) {
+      sh[0] = atomicAdd(counter, 1);
+      sh[6] = 0;
+    }
+    __syncthreads();
+    const int64_t q64 = (int64_t)row_lo + sh[0];
+    if (q64 >= row_hi) break;
+    const int q = (int)q64;
+    if (!WS) {
+      for (int v = tid; v < n_users; v += FT_THREADS) acc[v] = 0.f;
+      __syncthreads();
     }
 
-    // ---- compact: gather (any order), sort by id, store
-    for_cands([&](int j) {
-      const float w = acc[j];
-      const uint32_t k = f2u(w);
-      if (w > 0.f && (all || k > T || (k == T && j <= J))) {
-        const int pos = atomicAdd(&sh[5], 1);
-        if (pos < FT_MAX_K) {
-          kid[pos] = j;
-          kw[pos] = w;
+    // ---- accumulate: (row start, row end) of 64 query items at a time; integer adds commute, so who
+    // adds first changes nothing
+    const int64_t e0 = q_indptr[q], e1 = q_indptr[q + 1];
+    for (int64_t eb = e0; eb < e1; eb += 64) {
+      const int cnt = e1 - eb < 64 ? (int)(e1 - eb) : 64;
+      int64_t r0 = 0, r1 = 0;
+      if (lane < cnt) {
+        const int it = q_indices[eb + lane];
+        if (it >= 0 && it < n) {               // (an item outside the catalogue adds nothing)
+          r0 = t_indptr[it];
+          r1 = t_indptr[it + 1];
         }
       }
-    });
-    __syncthreads();
-    const int kept = sh[5] < K ? sh[5] : K;
-    int P = 1;
-    while (P < kept) P <<= 1;
-    if (tid >= kept && tid < P) kid[tid] = INT_MAX;
-    __syncthreads();
-    for (int k2 = 2; k2 <= P; k2 <<= 1)
-      for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-        const int o = tid ^ j2;
-        if (tid < P && o > tid) {
-          const int a = kid[tid], b = kid[o];
-          if ((a > b) == ((tid & k2) == 0)) {
-            kid[tid] = b;
-            kid[o] = a;
-            const float wa = kw[tid];
-            kw[tid] = kw[o];
-            kw[o] = wa;
+      for (int l = 0; l < cnt; ++l) {
+        const int64_t p0 = __shfl(r0, l, 64), p1 = __shfl(r1, l, 64);
+        const bool wide = p1 - p0 >= UN_WIDE;                    // (the same answer in every wave)
+        if (!wide && (l & (FT_WAVES - 1)) != wv) continue;
+        const int step = wide ? FT_THREADS : 64;
+        for (int64_t pb = p0 + (wide ? wv * 64 : 0); pb < p1; pb += step) {      // (wave-uniform bounds)
+          const int64_t p = pb + lane;
+          int v = -1;
+          if (p < p1) {
+            v = t_indices[p];
+            if (v < 0 || v >= n_users) v = -1;                  // (a bad index adds nothing)
+          }
+          if (WS) {
+            const bool first = v >= 0 && atomicAdd(reinterpret_cast<unsigned int *>(acc + v), 1u) == 0u;
+            const unsigned long long m = __ballot(first);
+            if (m) {
+              int base = 0;
+              if (lane == 0) base = atomicAdd(&sh[6], __popcll(m));
+              base = __shfl(base, 0, 64);
+              const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+              if (first && pos < acc_stride) cand[pos] = v;
+            }
+          } else {
+            if (v >= 0) atomicAdd(reinterpret_cast<unsigned int *>(acc + v), 1u);
           }
         }
-        __syncthreads();
       }
-    for (int c = tid; c < K; c += FT_THREADS) {
-      nbr_ids[(int64_t)i * K + c] = c < kept ? kid[c] : -1;
-      nbr_w[(int64_t)i * K + c] = c < kept ? kw[c] : 0.f;
     }
-    if (tid == 0) nbr_count[i] = kept;
-    if (WS) for_cands([&](int j) { acc[j] = -0.f; });
+    if (tid < 256) hist[tid] = 0;
+    if (tid == 0) sh[5] = 0;
+    if (WS) __threadfence();                   // (the adds were made in L2: nothing of this row is read before them)
+    __syncthreads();
+
+    // ---- scale, and the histogram of the top byte
+    const float qs = qn[q];
+    for_cands([&](int v) {
+      // (workspace: the count is read where the atomics made it, past this CU's L1)
+      const uint32_t c = WS ? __hip_atomic_load(reinterpret_cast<unsigned int *>(acc + v), __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_AGENT)
+                            : f2u(acc[v]);
+      float w = 0.f;
+      if (c) w = un_sim((float)c, qs, un[v], shrink);
+      acc[v] = w;
+      if (w > 0.f) atomicAdd(&hist[f2u(w) >> 24], 1);
+    });
+    __syncthreads();
+
+    ft_select_store(acc, for_cands, K, n_users, q, nbr_ids, nbr_sim, nbr_count, hist, sh, kid, kw, tid, lane, wv);
+    if (WS)
+      for_cands([&](int v) {
+        __hip_atomic_store(reinterpret_cast<unsigned int *>(acc + v), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      });
   }
 }
 
@@ -319,12 +467,66 @@ __global__ __launch_bounds__(SC_WAVES * 64) void rp3_scores_kernel(
   for (int c = threadIdx.x; c < w; c += SC_WAVES * 64) row[c] = tile[c];
 }
 
+// first position in [a, b) of the ascending idx whose value is >= key
+__device__ inline int64_t sc_lower_bound(const int32_t *__restrict__ idx, int64_t a, int64_t b, int64_t key) {
+  while (a < b) {
+    const int64_t m = a + ((b - a) >> 1);
+    if (idx[m] < key) a = m + 1; else b = m;
+  }
+  return a;
+}
+
+__global__ __launch_bounds__(SC_WAVES * 64) void rp3_user_scores_kernel(
+    const int32_t *__restrict__ nbr_ids, const float *__restrict__ nbr_sim, const int32_t *__restrict__ nbr_count,
+    int K, const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const float *__restrict__ data,
+    int n_users, int lo, int width, float *__restrict__ out, int64_t ldo) {
+  __shared__ float tile[SC_TILE];
+  const int q = blockIdx.x;                             // (queries fastest: neighbours' rows are shared)
+  const int t0 = blockIdx.y * SC_TILE;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t wlo = (int64_t)lo + t0 + wv * SC_SUB;
+  const int64_t whi = wlo + SC_SUB < (int64_t)lo + width ? wlo + SC_SUB : (int64_t)lo + width;
+  float *mine = tile + wv * SC_SUB;
+  for (int c = lane; c < SC_SUB; c += 64) mine[c] = 0.f;
+  if (wlo < whi) {
+    int nc = nbr_count[q];
+    nc = nc < 0 ? 0 : (nc > K ? K : nc);
+    const int64_t base = (int64_t)q * K;
+    for (int sb = 0; sb < nc; sb += 64) {
+      const int cnt = nc - sb < 64 ? nc - sb : 64;
+      int64_t a = 0, b = 0;
+      float sv = 0.f;
+      if (lane < cnt) {
+        const int v = nbr_ids[base + sb + lane];
+        if (v >= 0 && v < n_users) {           // (a bad id adds nothing)
+          const int64_t r1 = indptr[v + 1];
+          a = sc_lower_bound(indices, indptr[v], r1, wlo);
+          b = sc_lower_bound(indices, a, r1, whi);
+          sv = nbr_sim[base + sb + lane];
+        }
+      }
+      for (int l = 0; l < cnt; ++l) {          // neighbours ascending: a column's chain stays in this wave
+        const int64_t p0 = __shfl(a, l, 64), p1 = __shfl(b, l, 64);
+        const float s = __shfl(sv, l, 64);
+        for (int64_t p = p0 + lane; p < p1; p += 64) {  // items of one row are distinct: no two lanes meet
+          const int64_t j = indices[p] - wlo;
+          if (j >= 0 && j < SC_SUB) mine[j] = fmaf(s, data ? data[p] : 1.f, mine[j]);   // (holds for an ascending row)
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int w = width - t0 < SC_TILE ? width - t0 : SC_TILE;
+  float *row = out + (int64_t)q * ldo + t0;
+  for (int c = threadIdx.x; c < w; c += SC_WAVES * 64) row[c] = tile[c];
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------ ABI
 extern "C" {
 
-int rk_rp3_version(void) { return 100; }
+int rk_rp3_version(void) { return 101; }
 
 const char *rk_rp3_last_error(void) { return g_rk_side_err; }
 
@@ -389,6 +591,69 @@ int rk_rp3_scores(const int64_t *indptr, const int32_t *indices, const float *da
   hipLaunchKernelGGL(rp3_scores_kernel, grid, dim3(SC_WAVES * 64), 0, (hipStream_t)stream, indptr, indices, data,
                      n_items, nbr_ids, nbr_w, nbr_count, K, lo, width, out, ldo);
   RK_SIDE_CHECK_LAUNCH("rp3_scores_kernel");
+  return 0;
+}
+
+int64_t rk_rp3_user_workspace_bytes(int32_t n_users) {
+  if (n_users < 1) {
+    rk_side_set_error("%s: n_users must be >= 1", __func__);
+    return -2;
+  }
+  if (n_users <= FT_LDS_ITEMS) return 256;
+  return 256 + (int64_t)FT_GROUPS * 2 * ft_acc_stride(n_users) * 4;
+}
+
+int rk_rp3_user_neighbours(const int64_t *q_indptr, const int32_t *q_indices, const int64_t *t_indptr,
+                           const int32_t *t_indices, int32_t n_users, int32_t n_items, const float *un,
+                           const float *qn, float shrink, int32_t N, int32_t row_lo, int32_t row_hi,
+                           int32_t *nbr_ids, float *nbr_sim, int32_t *nbr_count, void *ws, int64_t ws_bytes,
+                           void *stream) {
+  RK_SIDE_REQUIRE(q_indptr && q_indices && t_indptr && t_indices && un && qn && nbr_ids && nbr_sim && nbr_count && ws,
+                  "null pointer");
+  RK_SIDE_REQUIRE(n_users >= 1 && n_users < INT_MAX - 2048 && n_items >= 1, "bad sizes");
+  RK_SIDE_REQUIRE(N >= 1 && N <= FT_MAX_K, "N outside [1, rk_rp3_max_neighbours()]");
+  RK_SIDE_REQUIRE(shrink >= 0.f && shrink <= 3.0e38f, "shrink must be finite and >= 0");
+  RK_SIDE_REQUIRE(0 <= row_lo && row_lo <= row_hi, "bad row range");
+  RK_SIDE_REQUIRE(ws_bytes >= rk_rp3_user_workspace_bytes(n_users), "workspace too small");
+  RK_SIDE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
+  if (row_lo == row_hi) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  int *counter = (int *)ws;
+  if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
+    rk_side_set_error("%s: hipMemsetAsync failed", __func__);
+    return -1;
+  }
+  const int rows = row_hi - row_lo;
+  const int groups = rows < FT_GROUPS ? rows : FT_GROUPS;
+  if (n_users <= FT_LDS_ITEMS) {
+    hipLaunchKernelGGL(rp3_user_neighbours_kernel<false>, dim3(groups), dim3(FT_THREADS), 0, s, q_indptr, q_indices,
+                       t_indptr, t_indices, n_users, n_items, un, qn, shrink, N, row_lo, row_hi, nbr_ids, nbr_sim,
+                       nbr_count, counter, (float *)nullptr, (int *)nullptr, (int64_t)0);
+  } else {
+    const int64_t stride = ft_acc_stride(n_users);
+    float *acc = (float *)((char *)ws + 256);
+    int *cand = (int *)(acc + (int64_t)FT_GROUPS * stride);
+    hipLaunchKernelGGL(rp3_user_neighbours_kernel<true>, dim3(groups), dim3(FT_THREADS), 0, s, q_indptr, q_indices,
+                       t_indptr, t_indices, n_users, n_items, un, qn, shrink, N, row_lo, row_hi, nbr_ids, nbr_sim,
+                       nbr_count, counter, acc, cand, stride);
+  }
+  RK_SIDE_CHECK_LAUNCH("rp3_user_neighbours_kernel");
+  return 0;
+}
+
+int rk_rp3_user_scores(const int32_t *nbr_ids, const float *nbr_sim, const int32_t *nbr_count, int32_t n_rows,
+                       int32_t N, const int64_t *u_indptr, const int32_t *u_indices, const float *u_data,
+                       int32_t n_users, int32_t n_items, int32_t lo, int32_t hi, float *out, int64_t ldo,
+                       void *stream) {
+  RK_SIDE_REQUIRE(nbr_ids && nbr_sim && nbr_count && u_indptr && u_indices && out, "null pointer");
+  RK_SIDE_REQUIRE(n_rows >= 0 && n_users >= 1 && n_items >= 1 && N >= 1 && N <= FT_MAX_K, "bad sizes");
+  RK_SIDE_REQUIRE(0 <= lo && lo < hi && hi <= n_items && ldo >= hi - lo, "bad strip");
+  if (n_rows == 0) return 0;
+  const int width = hi - lo;
+  const dim3 grid(n_rows, (width + SC_TILE - 1) / SC_TILE);
+  hipLaunchKernelGGL(rp3_user_scores_kernel, grid, dim3(SC_WAVES * 64), 0, (hipStream_t)stream, nbr_ids, nbr_sim,
+                     nbr_count, N, u_indptr, u_indices, u_data, n_users, lo, width, out, ldo);
+  RK_SIDE_CHECK_LAUNCH("rp3_user_scores_kernel");
   return 0;
 }
 

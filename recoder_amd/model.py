@@ -33,8 +33,8 @@ from .device import Block, DeviceCSR, require_gpu
 from .engine import FusedEngine
 from .losses import MSELoss, MultinomialNLLLoss
 from .metrics import RecommenderEvaluator
-from .nn import (DynamicAutoencoder, FactorizationModel, ItemItemModel, MatrixFactorization, RandomWalkItemModel,
-                 ShallowAutoencoder, SparseLinearModel, VariationalAutoencoder)
+from .nn import (CsrScoresModel, DynamicAutoencoder, FactorizationModel, MatrixFactorization, RandomWalkItemModel,
+                 ShallowAutoencoder, SparseLinearModel, UserNeighbourhoodModel, VariationalAutoencoder)
 from .recommender import InferenceRecommender
 
 log = logging.getLogger("recoder_amd")
@@ -88,6 +88,7 @@ class Recoder(object):
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
+    self.userknn_info = None    # train_userknn: what the last UserKNN fit reported
     self.__model_initialized = False
     self.__optimizer_state_dict = None
     self.__sparse_optimizer_state_dict = None
@@ -378,6 +379,9 @@ class Recoder(object):
     if isinstance(self.model, SparseLinearModel):
       raise ValueError("a SparseLinearModel is fitted by coordinate descent on the Gram matrix: call "
                        "train_slim(train_dataset)")
+    if isinstance(self.model, UserNeighbourhoodModel):
+      raise ValueError("a UserNeighbourhoodModel is its training matrix, there is nothing to descend on: call "
+                       "train_userknn(train_dataset)")
     if num_sampling_users == 0:
       num_sampling_users = batch_size
     if eval_batch_size is None:
@@ -426,8 +430,9 @@ class Recoder(object):
     self._sync_user_rows()
 
   def _scores_from_csr_rows(self):
-    """True for the item-item models (nn.ItemItemModel): scores are the users' CSR rows times W, no encoder."""
-    return isinstance(self.model, ItemItemModel)
+    """True for the models without an encoder (nn.CsrScoresModel: the item-item models, scores = the users' CSR
+    rows times W, and the user-neighbourhood model): scores come from ``model.csr_scores``."""
+    return isinstance(self.model, CsrScoresModel)
 
   def _size_hints(self, train_dataset):
     """(num_users, num_items) before the model is initialised: from the dataset's ids where unknown."""
@@ -609,6 +614,43 @@ class Recoder(object):
     _, _, _, info = slim.fit(pair, l1, l2, K, max_sweeps, tol,
                              out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))
     self.slim_info = info
+    self._weights_written()
+    return dict(info)
+
+  def train_userknn(self, train_dataset, neighbours=None, shrink=None):
+    """The "fit" of a UserNeighbourhoodModel (recoder_amd/userknn.py): the model takes the dataset's
+    interaction matrix X, as both CSRs with the values as stored, and the users' norms.  At serving time a
+    query keeps its ``neighbours`` most similar training users by ``|H_q and H_v| / (sqrt(|H_q|) sqrt(|H_v|) +
+    shrink)`` over the item sets and scores ``sum of sim * X[v, :]``; a training user identical to the query is
+    not excluded.  ``None`` takes the model's value; explicit values are stored back into the model, so that
+    a checkpoint's ``model_params`` describe it.  Another call replaces the matrix: that is how new
+    interactions take effect.  The configured ``loss`` plays no part.  Builds a fresh optimizer of
+    ``optimizer_type`` so that ``save_state`` works.  Returns (and keeps in ``userknn_info``) n_users, n, nnz,
+    neighbours, shrink and fit_ms (HIP events)."""
+    from . import als, userknn
+    m = self.model
+    N, shrink = userknn.check_config(m, m.neighbours if neighbours is None else neighbours,
+                                     m.shrink if shrink is None else shrink)
+    userknn.check_not_distributed()
+    host = als.host_matrix(train_dataset)
+    u_hint, n_hint = self._size_hints(train_dataset)
+    if u_hint and n_hint:
+      # (before init_model allocates: a matrix that cannot fit gets a ValueError, not an OOM)
+      userknn.check_memory(u_hint, n_hint, N, host.nnz, free_bytes=float("inf"))
+    log.info("UserKNN: %d neighbours, shrink %g", N, shrink)
+    m.neighbours, m.shrink = N, shrink
+    self._reset_optimizers()
+    if not self.__model_initialized:
+      require_gpu()
+      m.nnz = int(host.nnz)
+    elif (m.num_users, m.nnz) != (self.num_users, int(host.nnz)):
+      m.allocate(self.num_users, host.nnz, self.device)
+    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
+    m = self.model
+    userknn.check_memory(self.num_users, self.num_items, N, host.nnz)
+    pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
+    _, info = userknn.fit(pair, N, shrink, model=m)
+    self.userknn_info = info
     self._weights_written()
     return dict(info)
 

@@ -403,16 +403,22 @@ def dense_to_csr(input, input_items, n):
   return SimpleNamespace(indptr=indptr, indices=indices.contiguous(), data=vals.contiguous(), shape=(B, n))
 
 
-class ItemItemModel(FactorizationModel):
-  """What the item-item models share: ``scores = input @ W`` for a fitted [num_items, num_items] W that a
-  subclass stores in its own way.  A subclass gives ``csr_scores`` (its HIP scores kernel) and
-  ``_dense_w`` (W as a dense matrix, for ``torch_forward``)."""
+class CsrScoresModel(FactorizationModel):
+  """A model without an encoder: a user's scores come from the user's CSR row alone.  ``Recoder.predict`` and
+  ``Recoder.recommend_array`` hand such a model the batch's device CSR, strip by strip."""
 
   def csr_scores(self, csr, lo, hi, out, ld, n_rows):
-    """out[u, c] = (row u of ``csr``) @ W[:, lo + c] for c < hi - lo and u < n_rows, ``out`` f32 with row
-    stride ``ld`` (None with ``out`` None: a new [n_rows, hi - lo] tensor); returns ``out``.  This is what
-    ``Recoder.predict`` and ``Recoder.recommend_array`` call, whatever the class."""
+    """out[u, c] = the score of item lo + c for row u of ``csr``, for c < hi - lo and u < n_rows, ``out`` f32
+    with row stride ``ld`` (None with ``out`` None: a new [n_rows, hi - lo] tensor); returns ``out``.  This
+    is what ``Recoder.predict`` and ``Recoder.recommend_array`` call, whatever the class; the strips of one
+    batch are calls with the same ``csr`` object."""
     raise NotImplementedError
+
+
+class ItemItemModel(CsrScoresModel):
+  """What the item-item models share: ``scores = input @ W`` for a fitted [num_items, num_items] W that a
+  subclass stores in its own way.  A subclass gives ``csr_scores`` (its HIP scores kernel: out[u, c] =
+  (row u of ``csr``) @ W[:, lo + c]) and ``_dense_w`` (W as a dense matrix, for ``torch_forward``)."""
 
   def _dense_w(self):
     raise NotImplementedError
@@ -613,3 +619,150 @@ class SparseLinearModel(_NeighbourListModel):
     cols = torch.arange(n, device=ids.device)[:, None].expand(n, K)
     W[ids[live], cols[live]] = self.item_weights.data.to(dtype)[live]
     return W
+
+
+class UserNeighbourhoodModel(CsrScoresModel):
+  """UserKNN: user-based cosine neighbourhoods over the training matrix X (recoder_amd/userknn.py).  A query's
+  similarity to training user v is ``|H_q and H_v| / (sqrt(|H_q|) sqrt(|H_v|) + shrink)`` over the item SETS
+  (values play no part), it keeps its ``neighbours`` most similar users (ties to the lower ids) and its scores
+  are ``sum over them of sim * X[v, :]`` with the stored training values.  Neighbours are found at serving
+  time from the history the caller passes, so users the fit has never seen are served like any other.  A
+  training user identical to the query is not excluded: it takes one of the slots and contributes only
+  items that the masked top-k removes.
+
+  The model IS the training matrix, "fitted" by ``Recoder.train_userknn``: both of its CSRs
+  (``user_indptr`` int64 [num_users + 1], ``user_indices`` int32 [nnz]; ``item_indptr`` int64
+  [num_items + 1], ``item_indices`` int32 [nnz]) and ``user_norms`` f32 [num_users] are buffers and
+  ``interaction_values`` f32 [nnz] (user-major order) is the one parameter, so all six are in
+  ``state_dict()``; empty until fitted.  ``neighbours`` and ``shrink`` travel in ``model_params()``, with the
+  sizes a checkpoint's tensors have.  ``Recoder.train`` refuses this model and points at ``train_userknn``.
+  """
+
+  def __init__(self, neighbours=400, shrink=10.0):
+    super().__init__()
+    self.neighbours = neighbours
+    self.shrink = shrink
+    self.num_items = self.num_users = None
+    self.nnz = 0
+    self.interaction_values = None
+    self.neighbour_passes = 0      # rk_rp3_user_neighbours calls so far (one per batch, whatever the strips)
+    self._batch = None             # (the csr of the last batch, its rows, its neighbour lists, the workspace)
+    self._validate()
+
+  def _validate(self):
+    from .userknn import check_params
+    self.neighbours, self.shrink = check_params(self.neighbours, self.shrink)
+
+  def init_model(self, num_items=None, num_users=None):
+    self._validate()
+    self.num_items = num_items
+    self.allocate(self.num_users if num_users is None else num_users, self.nnz, None)
+
+  def allocate(self, num_users, nnz, device):
+    """(Re-)create the six tensors for ``num_users`` users and ``nnz`` entries: an empty matrix."""
+    U, n, nnz = int(num_users or 0), int(self.num_items), int(nnz)
+    self.num_users, self.nnz, self._batch = U, nnz, None
+    for name in ("user_indptr", "user_indices", "item_indptr", "item_indices", "user_norms"):
+      self._buffers.pop(name, None)
+    self.register_buffer("user_indptr", torch.zeros(U + 1, dtype=torch.int64, device=device))
+    self.register_buffer("user_indices", torch.zeros(max(1, nnz), dtype=torch.int32, device=device))
+    self.register_buffer("item_indptr", torch.zeros(n + 1, dtype=torch.int64, device=device))
+    self.register_buffer("item_indices", torch.zeros(max(1, nnz), dtype=torch.int32, device=device))
+    self.register_buffer("user_norms", torch.zeros(U, dtype=torch.float32, device=device))
+    self.interaction_values = nn.Parameter(torch.zeros(max(1, nnz), device=device), requires_grad=False)
+
+  def store(self, ucsr, icsr, un):
+    """Copy the (user-major, item-major) device CSR pair of X and the users' norms into the tensors."""
+    assert ucsr.shape == (self.num_users, self.num_items) and ucsr.nnz == self.nnz
+    self.user_indptr.copy_(ucsr.indptr)
+    self.item_indptr.copy_(icsr.indptr)
+    self.user_indices.copy_(ucsr.indices)
+    self.item_indices.copy_(icsr.indices)
+    self.user_norms.copy_(un)
+    if ucsr.data is None:
+      self.interaction_values.data.fill_(1.0)
+    else:
+      self.interaction_values.data.copy_(ucsr.data)
+    self._batch = None
+
+  def model_params(self):
+    return {"neighbours": int(self.neighbours), "shrink": float(self.shrink), "num_users": self.num_users,
+            "nnz": int(self.nnz)}
+
+  def load_model_params(self, model_params):
+    self.neighbours = int(model_params["neighbours"])
+    self.shrink = float(model_params["shrink"])
+    self.num_users = model_params.get("num_users")
+    self.nnz = int(model_params.get("nnz", 0))
+    self._validate()
+
+  def _load_from_state_dict(self, *args, **kwargs):
+    self._batch = None
+    return super()._load_from_state_dict(*args, **kwargs)
+
+  def _csrs(self):
+    from types import SimpleNamespace
+    U, n = self.num_users, self.num_items
+    return (SimpleNamespace(indptr=self.user_indptr, indices=self.user_indices, data=self.interaction_values.data,
+                            shape=(U, n)),
+            SimpleNamespace(indptr=self.item_indptr, indices=self.item_indices, data=None, shape=(n, U)))
+
+  def batch_neighbours(self, csr, n_rows=None):
+    """(ids, sim, count) of the rows of ``csr``: computed once per ``csr`` object (rk_rp3_user_neighbours) and
+    kept until another batch arrives, so that the strips of one batch share them."""
+    from . import userknn
+    n_rows = csr.shape[0] if n_rows is None else n_rows
+    b = self._batch
+    if b is not None and b[0] is csr and b[1] == n_rows:
+      return b[2]
+    qn = userknn.query_norms(csr)
+    *nbr, ws = userknn.neighbours(csr, self._csrs()[1], self.user_norms, self.neighbours, self.shrink, qn=qn,
+                                  row_hi=n_rows, ws=None if b is None else b[3])
+    self.neighbour_passes += 1
+    self._batch = (csr, n_rows, tuple(nbr), ws)
+    return self._batch[2]
+
+  def csr_scores(self, csr, lo, hi, out, ld, n_rows):
+    from . import userknn
+    if not self.num_users:
+      raise ValueError("the UserNeighbourhoodModel holds no training matrix: call train_userknn first")
+    nbr = self.batch_neighbours(csr, n_rows)
+    return userknn.scores(nbr, self._csrs()[0], lo, hi, out=out, ld=ld, n_rows=n_rows)    # (rk_rp3_user_scores)
+
+  def forward(self, input, input_users=None, input_items=None, target_users=None,
+              target_items=None):
+    """The scores of a dense batch on the HIP kernels (``csr_scores`` over the input's non-zeros); no
+    autograd.  On the host (no device tensors) it is ``torch_forward``."""
+    if not input.is_cuda:
+      with torch.no_grad():
+        return self.torch_forward(input, input_users, input_items, target_users, target_items)
+    n = self.num_items
+    csr = dense_to_csr(input, input_items, n)
+    out = self.csr_scores(csr, 0, n, None, None, input.shape[0])
+    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
+
+  def torch_forward(self, input, input_users=None, input_items=None, target_users=None,
+                    target_items=None):
+    """The same model in torch ops on the dense X (small matrices only; host tensors): f32 similarities,
+    a stable descending sort for the cut, a dense product for the scores."""
+    U, n = self.num_users, self.num_items
+    dev = input.device
+    rows = torch.repeat_interleave(torch.arange(U, device=dev), self.user_indptr[1:] - self.user_indptr[:-1])
+    cols = self.user_indices[:self.nnz].to(torch.int64)
+    X = torch.zeros(U, n, dtype=torch.float32, device=dev)
+    X[rows, cols] = self.interaction_values.data[:self.nnz].to(torch.float32)
+    B = torch.zeros(U, n, dtype=torch.float32, device=dev)
+    B[rows, cols] = 1.0
+    H = torch.zeros(input.shape[0], n, dtype=torch.float32, device=dev)
+    nz = (input != 0).to(torch.float32)
+    if input_items is None:
+      H[:, :nz.shape[1]] = nz
+    else:
+      H[:, input_items.to(torch.int64)] = nz
+    qn = torch.sqrt(H.sum(1).double()).float()
+    c = H @ B.t()
+    sim = torch.where(c > 0, c / (qn[:, None] * self.user_norms[None, :] + self.shrink), torch.zeros_like(c))
+    order = torch.sort(sim, dim=1, descending=True, stable=True)[1][:, :self.neighbours]
+    kept = torch.zeros_like(sim).scatter_(1, order, sim.gather(1, order))
+    out = kept @ X
+    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
