@@ -32,6 +32,30 @@
  *   - rk_als_solve: a row's result depends only on its CSR row, G, v, the fixed table, the biases
  *     and its own current value: any [row_lo, row_hi) gives bitwise the rows of the full solve,
  *     whatever path (stashed or streamed factor rows, G from LDS or from memory) a row takes.
+ *
+ * BPR pairwise ranking (Rendle, Freudenthaler, Gantner & Schmidt-Thieme 2009) for the same model, the
+ * rk_als_bpr_* functions: a triple t = (u, i, j) scores x_t = p_u . (q_i - q_j) + b_i - b_j, its loss is
+ * softplus(-x_t), its gradient weight g_t = sigma(-x_t).  One step is synchronous mini-batch SGD over T
+ * triples, every gradient taken at the tables as they stand at the start of the step:
+ *   p_u += lr (sum_{t: u_t = u} g_t (q_i - q_j) - reg c_u p_u)          c_u: valid triples that hold u
+ *   q_i += lr (sum_{t: i_t = i} g_t p_u - sum_{t: j_t = i} g_t p_u - reg c_i q_i)   (b_i likewise, +-g_t)
+ * with c_i the occurrences of item i in either role; no division by T.  sample, grad, a stable sort of
+ * the keys (the caller's: T user keys, 2T item keys) and apply make one step; no floating-point atomics.
+ *   - Counter RNG: mix(z) is splitmix64's output function (z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) *
+ *     0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31), all modulo 2^64.
+ *     key(seed, step, slot) = mix(mix(seed) ^ (step << 32 | slot)); draw d is mix(key + d), and it maps
+ *     to [0, range) as (high 32 bits * range) >> 32.  That map is biased: a value's probability differs
+ *     from 1 / range by at most 2^-32 (nothing for a power-of-two range).
+ *   - Draw 0 picks a stored entry e in [0, nnz), nnz < 2^31; the user is the row that holds e, the
+ *     positive is indices[e].  Draws 1..32 pick j in [0, n_items) until j is not in the user's row (rows
+ *     ascending); when all 32 are, neg[t] = -1 and the slot is invalid: it adds nothing anywhere.
+ *   - rk_als_bpr_grad: lane l of the triple's wave owns dimensions k = l + 64 m.  d_k = q_ik - q_jk (one
+ *     rounding); the dot is each lane's fmaf chain over m ascending from +0, then an xor butterfly over
+ *     lane distances 32, 16, 8, 4, 2, 1; then + b_i, then - b_j.  With e = exp(-|x|): g = e / (1 + e) for
+ *     x >= 0, 1 / (1 + e) otherwise; loss = max(-x, 0) + log1p(e).
+ *   - rk_als_bpr_apply: a row's sum is one fmaf chain per element over its segment of the sorted keys in
+ *     the order given (ascending slot when the sort is stable), from +0; then
+ *     new = fmaf(lr, fmaf(-(reg * c), old, sum), old).  One wave owns a row; nobody else writes it.
  */
 #ifndef RECODER_ALS_H
 #define RECODER_ALS_H
@@ -91,6 +115,48 @@ int rk_als_objective(const int64_t *indptr, const int32_t *indices, const float 
                      int32_t cols, const float *X, int32_t ldx, const float *Y, int32_t ldy, int32_t h,
                      const float *bias, float alpha, float reg, const float *Gx, const float *Gy,
                      const float *sx, const float *cy, void *ws, int64_t ws_bytes, double *out, void *stream);
+
+/*
+ * bytes of the buffers one BPR step over T triples at embedding size h needs from its caller, each
+ * rounded up to 256: users, pos, neg (int32 [T]), g, loss (f32 [T]), D, P (f32 [T, h]):
+ * 5 * round256(4 T) + 2 * round256(4 T h).  1 <= T <= 2^24; < 0 on bad arguments.  (The caller's sort
+ * of the keys needs its own room.)
+ */
+int64_t rk_als_bpr_workspace_bytes(int32_t T, int32_t h);
+
+/*
+ * users[t], pos[t], neg[t] (int32 [T]) for the slots t < T of step `step` >= 0 under `seed`, from the
+ * user x item CSR (int64 indptr [n_users + 1], int32 indices ascending within a row, nnz =
+ * indptr[n_users], 1 <= nnz < 2^31): see the draws above.  Integer arithmetic only; stored values play
+ * no part.
+ */
+int rk_als_bpr_sample(const int64_t *indptr, const int32_t *indices, int32_t n_users, int32_t n_items,
+                      int64_t nnz, int64_t seed, int32_t step, int32_t T, int32_t *users, int32_t *pos,
+                      int32_t *neg, void *stream);
+
+/*
+ * For every slot t < T: g[t] = sigma(-x_t), loss[t] = softplus(-x_t) and the staging rows D[t, :] =
+ * q_i - q_j, P[t, :] = p_u (f32 [T, h], leading dimension h) from X [n_users, ldx], Y [n_items, ldy]
+ * and bias [n_items].  A slot with neg[t] < 0 (or an id outside the tables) is invalid: g, loss and
+ * both rows are +0.  x (f32 [T]; NULL: not wanted) receives the scores x_t, for tests and measurements.
+ * One wave per triple.
+ */
+int rk_als_bpr_grad(const int32_t *users, const int32_t *pos, const int32_t *neg, int32_t T, int32_t n_users,
+                    int32_t n_items, const float *X, int32_t ldx, const float *Y, int32_t ldy, const float *bias,
+                    int32_t h, float *g, float *loss, float *x, float *D, float *P, void *stream);
+
+/*
+ * The update of one table from the sorted keys of a step.  keys (int32 [n], ascending): the row of
+ * every entry; order (int64 [n]): the entry's position before the sort, as a device sort returns it.
+ * roles == 1 (users): n = T, entry t is slot t, V = D, bias NULL.  roles == 2 (items): n = 2 T, entry
+ * 2 t is slot t's positive (weight +g_t) and entry 2 t + 1 its negative (weight -g_t), V = P, bias the
+ * item bias, updated like a table column with V = 1.  Keys outside [0, n_rows) are skipped: give the
+ * entries of an invalid slot the key n_rows.  table [n_rows, ldt] is updated in place; rows without a
+ * key are not touched.  One wave per distinct key.
+ */
+int rk_als_bpr_apply(const int32_t *keys, const int64_t *order, int32_t n, int32_t roles, const float *g,
+                     const float *V, int32_t h, float lr, float reg, int32_t n_rows, float *table, int32_t ldt,
+                     float *bias, void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

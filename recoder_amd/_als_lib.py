@@ -1,6 +1,6 @@
 """ctypes binding of librecoder_als.so (the C ABI in include/recoder_als.h): implicit-feedback ALS
-for recoder_amd.als.  Like _lib.py: plain pointers and sizes, no torch types across the boundary,
-no CPU fallback."""
+for recoder_amd.als and the BPR step (rk_als_bpr_*) for recoder_amd.bpr.  Like _lib.py: plain pointers
+and sizes, no torch types across the boundary, no CPU fallback."""
 import os
 
 # PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
@@ -30,6 +30,12 @@ SIGNATURES = {
   "rk_als_objective_workspace_bytes": (c_int64, [c_int32]),
   "rk_als_objective": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32, _P, c_float,
                                  c_float, _P, _P, _P, _P, _P, c_int64, _P, _P]),
+  "rk_als_bpr_workspace_bytes": (c_int64, [c_int32, c_int32]),
+  "rk_als_bpr_sample": (c_int32, [_P, _P, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P]),
+  "rk_als_bpr_grad": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, c_int32,
+                                _P, _P, _P, _P, _P, _P]),
+  "rk_als_bpr_apply": (c_int32, [_P, _P, c_int32, c_int32, _P, _P, c_int32, c_float, c_float, c_int32, _P,
+                                 c_int32, _P, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

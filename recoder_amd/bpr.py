@@ -1,0 +1,262 @@
+"""BPR-MF: Bayesian personalised ranking (Rendle, Freudenthaler, Gantner & Schmidt-Thieme 2009) for
+``MatrixFactorization``, on the rk_als_bpr_* kernels of librecoder_als.so (include/recoder_als.h).
+
+The model is a ``MatrixFactorization`` with ``activation_type="none"``: p = ``user_embedding_layer.weight``,
+q = ``item_embedding_layer.weight``, b = ``bias``.  A triple t = (u, i, j) -- a stored entry (u, i) drawn
+uniformly, an item j the user does not hold drawn uniformly -- scores x_t = p_u . (q_i - q_j) + b_i - b_j;
+its loss is softplus(-x_t).  One step is synchronous mini-batch SGD over T triples, every gradient taken
+at the tables as they stand at the start of the step, with g_t = sigma(-x_t):
+
+    p_u += lr (sum_{t: u_t = u} g_t (q_i - q_j) - reg c_u p_u)
+    q_i += lr (sum_{t: i_t = i} g_t p_u - sum_{t: j_t = i} g_t p_u - reg c_i q_i)      (b_i likewise)
+
+c counts the batch's valid triples that hold the row (an item in either role); nothing is divided by T.
+The stored entries are edges: their values play no part.  A step is sample, grad, two stable sorts of
+the keys (torch.sort on the device: plumbing) and two applies; its result depends on the data and the
+seed alone, bit for bit.
+
+``Recoder.train_bpr`` is the public entry point; the functions below are the layer under it (and what
+the tests and tools/bpr_bench.py drive directly).
+"""
+import math
+
+import numpy as np
+import scipy.sparse as sp
+import torch
+
+from . import _als_lib, als
+from ._lib import ptr
+from .device import DEVICE_HBM_BYTES, current_stream
+from .nn import MatrixFactorization
+
+MAX_H = als.MAX_H         # rk_als_max_h()
+MAX_BATCH = 1 << 24       # (the kernels' limit on T)
+MAX_DRAWS = 32            # negatives drawn per slot before it is given up
+
+
+def check_not_distributed():
+  als.check_not_distributed("train_bpr runs on one GPU: multi-GPU BPR is not implemented")
+
+
+def _number(name, v, lo_open):
+  if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+      not math.isfinite(float(v)) or float(v) < 0 or (lo_open and float(v) == 0):
+    raise ValueError("%s must be finite and %s 0 (got %r)" % (name, ">" if lo_open else ">=", v))
+  return float(v)
+
+
+def _count(name, v, lo, hi=None):
+  if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+    raise ValueError("%s must be an integer %s (got %r)"
+                     % (name, ">= %d" % lo if hi is None else "in %d..%d" % (lo, hi), v))
+  return int(v)
+
+
+def check_config(model, num_epochs, batch_size, lr, reg, seed):
+  """The BPR contract, checked before any GPU work; returns (num_epochs, batch_size, lr, reg, seed)."""
+  if not isinstance(model, MatrixFactorization):
+    raise ValueError("train_bpr trains a MatrixFactorization, not %s" % type(model).__name__)
+  if model.activation_type != "none":
+    raise ValueError("train_bpr needs activation_type='none' (got %r)" % (model.activation_type,))
+  if model.dropout_prob and model.dropout_prob > 0:
+    raise ValueError("train_bpr needs dropout_prob == 0 (got %r)" % (model.dropout_prob,))
+  h = model.embedding_size
+  if not isinstance(h, (int, np.integer)) or not 1 <= h <= MAX_H:
+    raise ValueError("train_bpr supports embedding sizes 1..%d (got %r)" % (MAX_H, h))
+  if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not -2 ** 63 <= seed < 2 ** 63:
+    raise ValueError("seed must be an integer that fits 64 bits (got %r)" % (seed,))
+  return (_count("num_epochs", num_epochs, 0), _count("batch_size", batch_size, 1, MAX_BATCH),
+          _number("lr", lr, True), _number("reg", reg, False), int(seed))
+
+
+def steps_per_epoch(nnz, batch_size):
+  return -(-int(nnz) // int(batch_size))
+
+
+def check_data(nnz, n_items, num_epochs, batch_size):
+  """What the sampler needs of the matrix; returns the steps of one epoch."""
+  nnz = int(nnz)
+  if nnz >= 2 ** 31:
+    raise ValueError("train_bpr draws a stored entry with 32-bit arithmetic: nnz must be below 2^31 (got %d)" % nnz)
+  if nnz < 1 or n_items < 1:
+    raise ValueError("train_bpr needs at least one stored entry to sample from (got nnz = %d)" % nnz)
+  steps = steps_per_epoch(nnz, batch_size)
+  if steps * int(num_epochs) >= 2 ** 31:
+    raise ValueError("num_epochs * ceil(nnz / batch_size) must be below 2^31 (got %d steps)" % (steps * num_epochs))
+  return steps
+
+
+def _round256(x):
+  return -(-int(x) // 256) * 256
+
+
+def workspace_bytes(T, h):
+  """rk_als_bpr_workspace_bytes(T, h), restated on the host (the memory check needs no library)."""
+  T, h = int(T), int(h)
+  if not (1 <= T <= MAX_BATCH and 1 <= h <= MAX_H):
+    return -2
+  return 5 * _round256(4 * T) + 2 * _round256(4 * T * h)
+
+
+def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True):
+  """Device bytes of a fit: the tables and the bias (unless the caller already holds them), the user-major
+  CSR (int64 indptr, int32 indices), the step's workspace, and the keys of both sorts with what
+  torch.sort returns and holds meanwhile (3 T entries: an int32 key in, an int32 key and an int64
+  position out, as much again for its scratch)."""
+  n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
+  model = (n_users + n_items) * h * 4 + n_items * 4 if allocate_model else 0
+  csr = (n_users + 1) * 8 + max(1, nnz) * 4
+  return model + csr + workspace_bytes(T, h) + 2 * 3 * T * (4 + 4 + 8)
+
+
+def check_memory(n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True):
+  """ValueError naming the sizes and the bytes needed when the fit cannot fit: against one device's whole
+  HBM without touching a device, then (``free_bytes`` None: asked from the current device) against
+  what is free."""
+  n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
+  if workspace_bytes(T, h) < 0:
+    raise ValueError("BPR needs 1 <= batch_size <= %d and 1 <= h <= %d (got %d, %d)" % (MAX_BATCH, MAX_H, T, h))
+  whole = required_bytes(n_users, n_items, h, nnz, T, True)
+  if whole > DEVICE_HBM_BYTES:
+    raise ValueError("BPR over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes: "
+                     "more than one device's memory (%d bytes); multi-device fits are not implemented"
+                     % (n_users, n_items, h, nnz, T, whole, DEVICE_HBM_BYTES))
+  need = required_bytes(n_users, n_items, h, nnz, T, allocate_model)
+  if free_bytes is None:
+    free_bytes = torch.cuda.mem_get_info()[0]
+  if need > free_bytes:
+    raise ValueError("BPR over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes "
+                     "of device memory, %d are free" % (n_users, n_items, h, nnz, T, need, free_bytes))
+  return need
+
+
+def user_csr(m, n_users, n_items, device):
+  """The user x item CSR padded to the tables' row count, uploaded once (rows ascending: the sampler
+  searches them)."""
+  m = sp.csr_matrix(m)
+  if m.shape[0] > n_users or m.shape[1] > n_items:
+    raise ValueError("interaction matrix %s larger than the tables (%d users, %d items)"
+                     % (m.shape, n_users, n_items))
+  if not m.has_sorted_indices:
+    m = m.copy()
+    m.sort_indices()
+  indptr = np.concatenate([m.indptr, np.full(n_users - m.shape[0], m.indptr[-1], m.indptr.dtype)])
+  return als.AlsCSR(sp.csr_matrix((m.data, m.indices, indptr), shape=(n_users, n_items)), device)
+
+
+# ------------------------------------------------------------------ kernels
+class Workspace:
+  """One allocation of rk_als_bpr_workspace_bytes(T, h), cut into the step's buffers."""
+
+  def __init__(self, T, h, device):
+    need = _als_lib.load().rk_als_bpr_workspace_bytes(T, h)
+    assert need == workspace_bytes(T, h) and need > 0, (need, T, h)
+    self.T, self.h = T, h
+    self.raw = torch.empty(need, dtype=torch.uint8, device=device)
+    off = 0
+
+    def cut(nbytes, dtype, shape):
+      nonlocal off
+      v = self.raw[off:off + nbytes].view(dtype).view(shape)
+      off += _round256(nbytes)
+      return v
+    self.users, self.pos, self.neg = (cut(4 * T, torch.int32, (T,)) for _ in range(3))
+    self.g, self.loss = (cut(4 * T, torch.float32, (T,)) for _ in range(2))
+    self.D, self.P = (cut(4 * T * h, torch.float32, (T, h)) for _ in range(2))
+
+
+def _i32(t, n):
+  assert t.dtype == torch.int32 and t.shape == (n,) and t.is_contiguous(), (t.dtype, t.shape)
+
+
+def _f32(t, shape):
+  assert t.dtype == torch.float32 and tuple(t.shape) == tuple(shape) and t.is_contiguous(), (t.dtype, t.shape)
+
+
+def sample(csr, seed, step, users, pos, neg):
+  """users / pos / neg (int32 [T], filled in place) of step ``step`` under ``seed`` (rk_als_bpr_sample)."""
+  T = users.shape[0]
+  for t in (users, pos, neg):
+    _i32(t, T)
+  if csr.nnz >= 2 ** 31:
+    raise ValueError("the BPR sampler needs nnz below 2^31 (got %d)" % csr.nnz)
+  lib = _als_lib.load()
+  _als_lib.check(lib.rk_als_bpr_sample(ptr(csr.indptr), ptr(csr.indices), csr.shape[0], csr.shape[1], csr.nnz,
+                                       int(seed), int(step), T, ptr(users), ptr(pos), ptr(neg),
+                                       current_stream()), "rk_als_bpr_sample")
+
+
+def grad(users, pos, neg, X, Y, bias, g, loss, D, P, x=None):
+  """g, loss [T] and the staging rows D = q_i - q_j, P = p_u [T, h] of the triples (rk_als_bpr_grad); ``x``
+  [T], when given, receives the scores."""
+  T, h = users.shape[0], X.shape[1]
+  for t in (users, pos, neg):
+    _i32(t, T)
+  _f32(g, (T,)), _f32(loss, (T,)), _f32(D, (T, h)), _f32(P, (T, h)), _f32(bias, (Y.shape[0],))
+  if x is not None:
+    _f32(x, (T,))
+  assert X.dtype == Y.dtype == torch.float32 and Y.shape[1] == h and X.stride(1) == 1 and Y.stride(1) == 1
+  lib = _als_lib.load()
+  _als_lib.check(lib.rk_als_bpr_grad(ptr(users), ptr(pos), ptr(neg), T, X.shape[0], Y.shape[0], ptr(X),
+                                     X.stride(0), ptr(Y), Y.stride(0), ptr(bias), h, ptr(g), ptr(loss), ptr(x),
+                                     ptr(D), ptr(P), current_stream()), "rk_als_bpr_grad")
+
+
+def sorted_keys(users, pos, neg, n_users, n_items):
+  """((user keys, order), (item keys, order)): the T user keys and the 2T item keys -- slot t as positive,
+  slot t as negative, slot t + 1 ... -- stably sorted by row on the device, so that a row's entries stay
+  in ascending slot order; an invalid slot's entries carry the key past the table, and sort last."""
+  valid = neg >= 0
+  ukey = torch.where(valid, users, torch.full_like(users, n_users))
+  ikey = torch.where(valid[:, None], torch.stack([pos, neg], dim=1), torch.full_like(pos, n_items)[:, None])
+  uk, uo = torch.sort(ukey, stable=True)
+  ik, io = torch.sort(ikey.reshape(-1), stable=True)
+  return (uk, uo), (ik, io)
+
+
+def apply(keys, order, roles, g, V, lr, reg, table, bias=None):
+  """The update of ``table`` (and ``bias``) in place from the sorted keys (rk_als_bpr_apply)."""
+  n, (T, h) = keys.shape[0], V.shape
+  _i32(keys, n)
+  assert order.dtype == torch.int64 and order.shape == (n,) and order.is_contiguous() and n == roles * T
+  _f32(g, (T,)), _f32(V, (T, h))
+  assert table.dtype == torch.float32 and table.shape[1] == h and table.stride(1) == 1
+  if bias is not None:
+    _f32(bias, (table.shape[0],))
+  lib = _als_lib.load()
+  _als_lib.check(lib.rk_als_bpr_apply(ptr(keys), ptr(order), n, roles, ptr(g), ptr(V), h, float(lr), float(reg),
+                                      table.shape[0], ptr(table), table.stride(0), ptr(bias), current_stream()),
+                 "rk_als_bpr_apply")
+
+
+def step(X, Y, bias, ucsr, ws, seed, step_index, lr, reg):
+  """One BPR step on the tables in place; the triples, g and loss of the step stay in ``ws``."""
+  sample(ucsr, seed, step_index, ws.users, ws.pos, ws.neg)
+  grad(ws.users, ws.pos, ws.neg, X, Y, bias, ws.g, ws.loss, ws.D, ws.P)
+  (uk, uo), (ik, io) = sorted_keys(ws.users, ws.pos, ws.neg, X.shape[0], Y.shape[0])
+  apply(uk, uo, 1, ws.g, ws.D, lr, reg, X)
+  apply(ik, io, 2, ws.g, ws.P, lr, reg, Y, bias)
+
+
+# ---------------------------------------------------------------------- fit
+def fit(X, Y, bias, ucsr, num_epochs, batch_size, lr, reg, seed=0, first_step=0):
+  """num_epochs epochs of ceil(nnz / batch_size) steps on the tables X [users, h], Y [items, h] and bias
+  [items] (in place, f32, row-major); step s of the fit draws as step ``first_step + s``.  Returns the mean
+  loss per valid triple of each epoch (floats; nan for an epoch without one).  One host synchronisation
+  per epoch, to read that epoch's sums."""
+  steps = check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size)
+  check_memory(X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False)
+  ws = Workspace(int(batch_size), X.shape[1], X.device)
+  hist = []
+  s = int(first_step)
+  for _ in range(num_epochs):
+    total = torch.zeros((), dtype=torch.float64, device=X.device)
+    count = torch.zeros((), dtype=torch.int64, device=X.device)
+    for _ in range(steps):
+      step(X, Y, bias, ucsr, ws, seed, s, lr, reg)
+      total += ws.loss.sum(dtype=torch.float64)
+      count += (ws.neg >= 0).sum()
+      s += 1
+    total, count = torch.stack([total, count.double()]).cpu().tolist()      # (the synchronisation)
+    hist.append(total / count if count else float("nan"))
+  return hist

@@ -8,7 +8,8 @@ librecoder_hip.so  the training and recommend path (include/recoder_hip.h)
 librecoder_index.so  exact item similarity (include/recoder_index.h), a library of its
                    own so that the training library's exported symbol set stays as it is
 librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recoder_als.h),
-                   likewise a library of its own
+                   likewise a library of its own.  It also holds the BPR pairwise-ranking step of the
+                   same model (rk_als_bpr_*: sample, grad, apply)
 librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own
 librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencoder

@@ -9,6 +9,15 @@
 //                     workgroup of 16 waves each, the entries split between the waves
 //   rk_als_objective  the sparse part of L, one wave per row, per-row float64 partials; one
 //                     workgroup adds them and the Gram terms in a fixed order
+//
+// BPR pairwise ranking for the same model (rk_als_bpr_*): one synchronous mini-batch SGD step is
+//   rk_als_bpr_sample  one thread per slot: a stored entry and a rejected-until-unseen negative, from
+//                      a counter hash of (seed, step, slot, draw); integer arithmetic only
+//   rk_als_bpr_grad    one wave per triple: x, g = sigma(-x), softplus(-x), and the staging rows
+//                      D[t] = q_i - q_j, P[t] = p_u (the apply step then updates the tables in place)
+//   rk_als_bpr_apply   one wave per distinct row of the sorted keys: the row's segment summed in
+//                      ascending slot order, one fmaf chain per element, then the row's own update.
+//                      No atomics: nobody else writes the row
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -528,6 +537,193 @@ __global__ __launch_bounds__(256) void als_objective_final_kernel(const double *
   if (tid == 0) out[0] = red[0];
 }
 
+// ------------------------------------------------------------------------ bpr
+// The counter RNG, restated here (this translation unit does not include csrc/common.h): splitmix64's
+// output function, z += 0x9E3779B97F4A7C15, two xor-shift-multiplies, a last xor-shift.
+__host__ __device__ __forceinline__ uint64_t bpr_mix(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// draw d of (seed, step, slot) mapped to [0, range): the high 32 bits times range, shifted down
+__host__ __device__ __forceinline__ uint32_t bpr_draw(uint64_t slot_key, uint32_t d, uint32_t range) {
+  const uint64_t r = bpr_mix(slot_key + d);
+  return (uint32_t)(((r >> 32) * (uint64_t)range) >> 32);
+}
+
+constexpr int BPR_MAX_DRAWS = 32;
+
+__global__ __launch_bounds__(256) void als_bpr_sample_kernel(const int64_t *__restrict__ indptr,
+                                                             const int32_t *__restrict__ indices, int n_users,
+                                                             int n_items, uint32_t nnz, uint64_t seed_key,
+                                                             uint32_t step, int T, int32_t *__restrict__ users,
+                                                             int32_t *__restrict__ pos, int32_t *__restrict__ neg) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= T) return;
+  const uint64_t key = bpr_mix(seed_key ^ (((uint64_t)step << 32) | (uint32_t)t));
+  const int64_t e = (int64_t)bpr_draw(key, 0, nnz);
+  // the row that holds e: the last u with indptr[u] <= e (empty rows share their successor's start)
+  int lo = 0, hi = n_users;                 // (indptr[lo] <= e < indptr[hi] throughout)
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (indptr[mid] <= e) lo = mid; else hi = mid;
+  }
+  const int u = lo;
+  const int64_t r0 = indptr[u], r1 = indptr[u + 1];
+  int j = -1;
+  for (int d = 1; d <= BPR_MAX_DRAWS; ++d) {
+    const int c = (int)bpr_draw(key, (uint32_t)d, (uint32_t)n_items);
+    int64_t a = r0, b = r1;                 // first position in [r0, r1) with indices[.] >= c
+    while (a < b) {
+      const int64_t mid = a + ((b - a) >> 1);
+      if (indices[mid] < c) a = mid + 1; else b = mid;
+    }
+    if (!(a < r1 && indices[a] == c)) {
+      j = c;
+      break;
+    }
+  }
+  users[t] = u;
+  pos[t] = indices[e];
+  neg[t] = j;
+}
+
+// One wave per triple.  Lane l owns dimensions k = l + 64 t: d_k = q_ik - q_jk (one rounding), the dot
+// is the lane's fmaf chain over t ascending from +0, then the xor butterfly of wave_sum, then + b_i,
+// then - b_j.  A slot with neg < 0 (or an id outside the tables) is invalid: g, loss and both rows +0.
+template <int NT>
+__global__ __launch_bounds__(256) void als_bpr_grad_kernel(const int32_t *__restrict__ users,
+                                                           const int32_t *__restrict__ pos,
+                                                           const int32_t *__restrict__ neg, int T, int n_users,
+                                                           int n_items, const float *__restrict__ X, int ldx,
+                                                           const float *__restrict__ Y, int ldy,
+                                                           const float *__restrict__ bias, int h,
+                                                           float *__restrict__ g, float *__restrict__ loss,
+                                                           float *__restrict__ xout, float *__restrict__ D,
+                                                           float *__restrict__ P) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const int u = users[t], i = pos[t], j = neg[t];
+  const bool ok = u >= 0 && u < n_users && i >= 0 && i < n_items && j >= 0 && j < n_items;   // (wave-uniform)
+  float p[NT], d[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int k = lane + 64 * q;
+    const bool in = ok && k < h;
+    p[q] = in ? X[(int64_t)u * ldx + k] : 0.f;
+    const float qi = in ? Y[(int64_t)i * ldy + k] : 0.f;
+    const float qj = in ? Y[(int64_t)j * ldy + k] : 0.f;
+    d[q] = qi - qj;
+  }
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int k = lane + 64 * q;
+    if (k < h) {
+      D[(int64_t)t * h + k] = d[q];
+      P[(int64_t)t * h + k] = p[q];
+    }
+  }
+  if (!ok) {
+    if (lane == 0) {
+      g[t] = loss[t] = 0.f;
+      if (xout) xout[t] = 0.f;
+    }
+    return;
+  }
+  const float x = (wave_dot<NT>(p, d) + bias[i]) - bias[j];
+  if (lane == 0) {
+    // sigma(-x) and softplus(-x) = max(-x, 0) + log1p(exp(-|x|)) through e = exp(-|x|) <= 1
+    const float e = expf(-fabsf(x));
+    g[t] = x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);
+    loss[t] = fmaxf(-x, 0.f) + log1pf(e);
+    if (xout) xout[t] = x;
+  }
+}
+
+// One wave per sorted position s; the wave at the head of a segment of equal keys owns that row, the
+// others leave.  order[s] is the entry's position before the sort: slot t = order / roles, and with
+// roles == 2 (the item side) an odd position is the slot's negative, which enters with -g.
+//   acc_k = fmaf(+-g_t, V[t, k], acc_k) over the segment, from +0;  c = the segment's length
+//   new_k = fmaf(lr, fmaf(-(reg * c), old_k, acc_k), old_k)           (the bias likewise, V = 1)
+constexpr int BPR_UNROLL = 4;
+
+template <int NT>
+__global__ __launch_bounds__(256) void als_bpr_apply_kernel(const int32_t *__restrict__ keys,
+                                                            const int64_t *__restrict__ order, int n, int roles,
+                                                            const float *__restrict__ g,
+                                                            const float *__restrict__ V, int h, float lr,
+                                                            float reg, int n_rows, float *__restrict__ table,
+                                                            int ldt, float *__restrict__ bias) {
+  const int lane = threadIdx.x & 63;
+  const int s0 = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s0 >= n) return;
+  const int key = keys[s0];
+  if (key < 0 || key >= n_rows) return;                  // (the invalid slots' sentinel, sorted last)
+  if (s0 > 0 && keys[s0 - 1] == key) return;             // (not a head)
+  // the segment's length: 64 keys at a time, the first lane whose key differs
+  int c = 0;
+  for (;;) {
+    const int s = s0 + c + lane;
+    const bool same = s < n && keys[s] == key;
+    const uint64_t m = __ballot(!same);
+    if (m) {
+      c += __ffsll((unsigned long long)m) - 1;
+      break;
+    }
+    c += 64;
+  }
+  float acc[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) acc[q] = 0.f;
+  float bacc = 0.f;
+  const int64_t slots = roles == 2 ? n >> 1 : n;
+  for (int a0 = 0; a0 < c; a0 += BPR_UNROLL) {
+    float v[BPR_UNROLL][NT], w[BPR_UNROLL];
+#pragma unroll
+    for (int r = 0; r < BPR_UNROLL; ++r) {
+      const bool in = a0 + r < c;
+      const int64_t e = in ? order[s0 + a0 + r] : 0;
+      const int64_t t = roles == 2 ? e >> 1 : e;
+      const bool ok = in && e >= 0 && t < slots;         // (an order outside the batch adds nothing)
+      const float gt = ok ? g[t] : 0.f;
+      w[r] = (roles == 2 && (e & 1)) ? -gt : gt;
+#pragma unroll
+      for (int q = 0; q < NT; ++q) {
+        const int k = lane + 64 * q;
+        v[r][q] = (ok && k < h) ? V[t * h + k] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < BPR_UNROLL; ++r) {
+      if (a0 + r < c) {                                  // (wave-uniform: a tail entry must not touch the chain)
+#pragma unroll
+        for (int q = 0; q < NT; ++q) acc[q] = fmaf(w[r], v[r][q], acc[q]);
+        bacc += w[r];
+      }
+    }
+  }
+  const float rc = reg * (float)c;
+  float *row = table + (int64_t)key * ldt;
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int k = lane + 64 * q;
+    if (k < h) {
+      const float old = row[k];
+      row[k] = fmaf(lr, fmaf(-rc, old, acc[q]), old);
+    }
+  }
+  if (bias && lane == 0) {
+    const float old = bias[key];
+    bias[key] = fmaf(lr, fmaf(-rc, old, bacc), old);
+  }
+}
+
+int64_t bpr_round256(int64_t x) { return (x + 255) / 256 * 256; }
+constexpr int BPR_MAX_T = 1 << 24;
+
 int nt_of(int h) { return h <= 64 ? 1 : h <= 128 ? 2 : h <= 256 ? 4 : 8; }
 
 }  // namespace
@@ -633,5 +829,71 @@ extern "C" int rk_als_objective(const int64_t *indptr, const int32_t *indices, c
   hipLaunchKernelGGL(als_objective_final_kernel, dim3(1), dim3(256), 0, st, part, rows, cols, h, bias, reg, Gx, Gy,
                      sx, cy, out);
   RK_SIDE_CHECK_LAUNCH("als_objective_final");
+  return 0;
+}
+
+extern "C" int64_t rk_als_bpr_workspace_bytes(int32_t T, int32_t h) {
+  if (T < 1 || T > BPR_MAX_T || h < 1 || h > MAX_H) return -2;
+  return 5 * bpr_round256((int64_t)T * 4) + 2 * bpr_round256((int64_t)T * h * 4);
+}
+
+extern "C" int rk_als_bpr_sample(const int64_t *indptr, const int32_t *indices, int32_t n_users, int32_t n_items,
+                                 int64_t nnz, int64_t seed, int32_t step, int32_t T, int32_t *users, int32_t *pos,
+                                 int32_t *neg, void *stream) {
+  RK_SIDE_REQUIRE(n_users >= 1 && n_items >= 1, "n_users >= 1, n_items >= 1");
+  RK_SIDE_REQUIRE(nnz >= 1 && nnz < ((int64_t)1 << 31), "1 <= nnz < 2^31");
+  RK_SIDE_REQUIRE(step >= 0 && T >= 1 && T <= BPR_MAX_T, "step >= 0, 1 <= T <= 2^24");
+  RK_SIDE_REQUIRE(indptr && indices && users && pos && neg, "null pointer");
+  hipLaunchKernelGGL(als_bpr_sample_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     indptr, indices, n_users, n_items, (uint32_t)nnz, bpr_mix((uint64_t)seed), (uint32_t)step, T,
+                     users, pos, neg);
+  RK_SIDE_CHECK_LAUNCH("als_bpr_sample");
+  return 0;
+}
+
+#define ALS_BPR_GRAD_LAUNCH(NT)                                                                                   \
+  hipLaunchKernelGGL(als_bpr_grad_kernel<NT>, grid, dim3(256), 0, st, users, pos, neg, T, n_users, n_items, X, ldx, \
+                     Y, ldy, bias, h, g, loss, x, D, P)
+
+extern "C" int rk_als_bpr_grad(const int32_t *users, const int32_t *pos, const int32_t *neg, int32_t T,
+                               int32_t n_users, int32_t n_items, const float *X, int32_t ldx, const float *Y,
+                               int32_t ldy, const float *bias, int32_t h, float *g, float *loss, float *x, float *D,
+                               float *P, void *stream) {
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldx >= h && ldy >= h, "1 <= h <= 512, ldx >= h, ldy >= h");
+  RK_SIDE_REQUIRE(T >= 1 && T <= BPR_MAX_T && n_users >= 1 && n_items >= 1, "1 <= T <= 2^24, n_users, n_items >= 1");
+  RK_SIDE_REQUIRE(users && pos && neg && X && Y && bias && g && loss && D && P, "null pointer");
+  const dim3 grid((unsigned)((T + 3) / 4));
+  hipStream_t st = (hipStream_t)stream;
+  switch (nt_of(h)) {
+    case 1: ALS_BPR_GRAD_LAUNCH(1); break;
+    case 2: ALS_BPR_GRAD_LAUNCH(2); break;
+    case 4: ALS_BPR_GRAD_LAUNCH(4); break;
+    default: ALS_BPR_GRAD_LAUNCH(8); break;
+  }
+  RK_SIDE_CHECK_LAUNCH("als_bpr_grad");
+  return 0;
+}
+
+#define ALS_BPR_APPLY_LAUNCH(NT)                                                                                 \
+  hipLaunchKernelGGL(als_bpr_apply_kernel<NT>, grid, dim3(256), 0, st, keys, order, n, roles, g, V, h, lr, reg,  \
+                     n_rows, table, ldt, bias)
+
+extern "C" int rk_als_bpr_apply(const int32_t *keys, const int64_t *order, int32_t n, int32_t roles, const float *g,
+                                const float *V, int32_t h, float lr, float reg, int32_t n_rows, float *table,
+                                int32_t ldt, float *bias, void *stream) {
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldt >= h, "1 <= h <= 512, ldt >= h");
+  RK_SIDE_REQUIRE(roles == 1 || roles == 2, "roles is 1 (users) or 2 (items: positive, negative)");
+  RK_SIDE_REQUIRE(n >= roles && n % roles == 0 && n / roles <= BPR_MAX_T, "n = roles * T, 1 <= T <= 2^24");
+  RK_SIDE_REQUIRE(n_rows >= 1, "n_rows >= 1");
+  RK_SIDE_REQUIRE(keys && order && g && V && table, "null pointer");
+  const dim3 grid((unsigned)((n + 3) / 4));
+  hipStream_t st = (hipStream_t)stream;
+  switch (nt_of(h)) {
+    case 1: ALS_BPR_APPLY_LAUNCH(1); break;
+    case 2: ALS_BPR_APPLY_LAUNCH(2); break;
+    case 4: ALS_BPR_APPLY_LAUNCH(4); break;
+    default: ALS_BPR_APPLY_LAUNCH(8); break;
+  }
+  RK_SIDE_CHECK_LAUNCH("als_bpr_apply");
   return 0;
 }

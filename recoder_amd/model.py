@@ -85,6 +85,7 @@ class Recoder(object):
     self.last_epoch_losses = None
     self.loss_history = []      # per-epoch arrays of the per-step training losses
     self.als_history = []       # train_als: the ALS objective after each iteration
+    self.bpr_history = []       # train_bpr: the mean loss per valid triple of each epoch
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -468,6 +469,31 @@ class Recoder(object):
                                m.bias.data, ucsr, icsr, alpha, float(reg), int(cg_steps), int(num_iterations))
     self._weights_written()
     return list(self.als_history)
+
+  def train_bpr(self, train_dataset, num_epochs=40, batch_size=1024, lr=0.1, reg=0.01, seed=0):
+    """BPR-MF (Rendle et al. 2009) for a MatrixFactorization with activation 'none' (recoder_amd/bpr.py):
+    pairwise ranking on sampled triples (user, a stored item, an item the user does not hold), loss
+    softplus(-(x_ui - x_uj)), synchronous mini-batch SGD with learning rate ``lr`` and an L2 pull ``reg``
+    on every row a triple touches, the bias trained with the item table.  An epoch is
+    ceil(nnz / batch_size) steps of ``batch_size`` triples; the draws are a pure function of ``seed``,
+    the step (counted from 0 in every call) and the slot, so a fixed seed gives the same bits.  The
+    stored values and the configured ``loss`` play no part.  Builds a fresh optimizer of
+    ``optimizer_type``, so that ``save_state``, ``train`` and ``train_als`` work on the tables it leaves.
+    Returns (and keeps in ``bpr_history``) the mean loss per valid triple of each epoch."""
+    from . import als, bpr
+    num_epochs, batch_size, lr, reg, seed = bpr.check_config(self.model, num_epochs, batch_size, lr, reg, seed)
+    bpr.check_not_distributed()
+    log.info("BPR: %d epochs of batches of %d, lr %g, reg %g, seed %d", num_epochs, batch_size, lr, reg, seed)
+    self._reset_optimizers()
+    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
+    host = als.host_matrix(train_dataset)
+    bpr.check_data(host.nnz, self.num_items, num_epochs, batch_size)
+    ucsr = bpr.user_csr(host, self.num_users, self.num_items, self.device)
+    m = self.model
+    self.bpr_history = bpr.fit(m.user_embedding_layer.weight.data, m.item_embedding_layer.weight.data,
+                               m.bias.data, ucsr, num_epochs, batch_size, lr, reg, seed)
+    self._weights_written()
+    return list(self.bpr_history)
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
