@@ -27,7 +27,8 @@
  * The three weight vectors of rk_rp3_fit are INPUTS, made on the host: no pow runs on the device.
  * RP3beta passes user_w[v] = r_v^-alpha, row_scale[i] = d_i^-alpha, col_scale[j] = d_j^-beta.  The
  * same kernel therefore also gives P3alpha (col_scale = 1, i.e. beta = 0) and weighted cosine kNN
- * (user_w = 1, row_scale = col_scale = d^-1/2): the driver builds neither.
+ * (user_w = 1, row_scale = col_scale = d^-1/2): the driver builds neither.  (That cosine is the
+ * degenerate one: no shrink term, no stored values, no set similarity -- those are rk_rp3_item_fit.)
  *
  * Numerics (f32; every call is bitwise repeatable and a row's result depends on the data alone)
  *   - S_ij is ONE f32 add chain from +0 of user_w[v] over the users v of item i, ascending, that also
@@ -68,6 +69,33 @@
  *     time (lane l finds by binary search where neighbour l's ascending row enters and leaves the wave's
  *     columns; then the wave takes the 64 one after the other).  A column's chain therefore stays inside
  *     one wave, in neighbour order, whatever lo, hi and the query's position in the batch.
+ *
+ * ItemKNN (rk_rp3_item_*): the shrunk item-neighbourhood model, rk_rp3_fit's row pass (the same hand-out, the
+ * same LDS / workspace split with its -0 first-touch fill, the same selection and compaction) with the two
+ * things rk_rp3_fit's separable scale cannot spell: stored VALUES in the dot product and a denominator that
+ * is not a product of a row and a column factor.  With a_vi the stored (possibly feature-weighted) value of
+ * user v for item i, and j the own item, the one whose list is built (column j of W):
+ *   s_ij   = sum over the users v of item j, ascending, that also hold i, of a_vj * a_vi
+ *   form 0 (product): den = own[j] * oth[i] + shrink            cosine: own = oth = |a|;
+ *                                                               asymmetric: own = |a_j|^(2(1-alpha)), oth = |a_i|^(2 alpha)
+ *   form 1 (sum):     den = own[j] + oth[i] + g * s_ij + shrink Tversky on binary data: own = beta d_j,
+ *                                                               oth = alpha d_i, g = 1 - alpha - beta
+ *                                                               (Jaccard: alpha = beta = 1; Dice: alpha = beta = 1/2)
+ *   sim_ij = s_ij / den where s_ij > 0 and den > 0, +0 otherwise; sim_jj = 0
+ *   column j keeps its K largest sim_ij > 0 by (sim descending, i ascending), stored with ascending i
+ *   scores(u, j) = sum over the kept i of column j that u holds of x_ui * sim_ij    (rk_slim_scores: the
+ *                  lists are per column, as SparseLinearModel's)
+ * own and oth are INPUTS made on the host (float64, rounded once): no sqrt or pow runs on the device.
+ *
+ * Numerics of rk_rp3_item_fit (bitwise repeatable; a column's result depends on the data alone)
+ *   - s_ij is ONE f32 fmaf(a_vj, a_vi, acc) chain from +0, users ascending; no atomics on data (a column of
+ *     the accumulator has one owning wave, which takes the users one after the other).  With NULL data the
+ *     chain is adds of 1.0: an exact count.  Every product must be >= +0 (values >= 0): the workspace form
+ *     recognises a column's first touch from its -0 fill.
+ *   - den: form 0 (own[j] * oth[i]) + shrink; form 1 ((own[j] + oth[i]) + (g * s_ij)) + shrink.  Every
+ *     operation is a separately rounded f32 operation, compiled under "#pragma clang fp contract(off)"; the
+ *     quotient is __fdiv_rn (see rk_rp3_user_neighbours).
+ *   - selection and compaction: the fit's, ties at the K-th value to the lower ids.
  */
 #ifndef RECODER_RP3_H
 #define RECODER_RP3_H
@@ -155,6 +183,30 @@ int rk_rp3_user_scores(const int32_t *nbr_ids, const float *nbr_sim, const int32
                        int32_t N, const int64_t *u_indptr, const int32_t *u_indices, const float *u_data,
                        int32_t n_users, int32_t n_items, int32_t lo, int32_t hi, float *out, int64_t ldo,
                        void *stream);
+
+/* bytes of workspace rk_rp3_item_fit needs for n_items (host arithmetic; > 0; < 0 on bad arguments): what
+ * rk_rp3_fit_workspace_bytes gives */
+int64_t rk_rp3_item_workspace_bytes(int32_t n_items);
+
+/*
+ * Columns [col_lo, col_hi) of the ItemKNN model: one fused pass per own item j (accumulate, scale, select,
+ * compact).  (t_*): the item-major CSR (n_items rows, columns = users); (u_*): the user-major CSR (n_users
+ * rows, columns = items) of the SAME matrix, values included.  t_data and u_data are either both NULL (every
+ * value is 1.0) or both given (finite, >= 0).  own [n_items] and oth [n_items] are >= 0; form is 0 (product)
+ * or 1 (sum); g and shrink are finite, shrink >= 0.  1 <= K <= rk_rp3_max_neighbours(),
+ * 0 <= col_lo <= col_hi <= n_items.
+ *   nbr_ids   int32 [n_items, K]  the kept i of column j, ascending; -1 past nbr_count[j]
+ *   nbr_w     f32   [n_items, K]  their sim_ij; +0 past nbr_count[j]
+ *   nbr_count int32 [n_items]     how many were kept (<= K)
+ * Columns outside [col_lo, col_hi) are not touched.  Columns are handed to the resident workgroups through
+ * one counter in the workspace, as rk_rp3_fit's rows are: any column range, in any hand-out order, gives the
+ * same bits.  ws must be 256-byte aligned.
+ */
+int rk_rp3_item_fit(const int64_t *t_indptr, const int32_t *t_indices, const float *t_data, const int64_t *u_indptr,
+                    const int32_t *u_indices, const float *u_data, int32_t n_users, int32_t n_items,
+                    const float *own, const float *oth, int32_t form, float g, float shrink, int32_t K,
+                    int32_t col_lo, int32_t col_hi, int32_t *nbr_ids, float *nbr_w, int32_t *nbr_count, void *ws,
+                    int64_t ws_bytes, void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -8,7 +8,8 @@ Drop-in for the reference's training path: ``Recoder`` / ``FactorizationModel``
 # in checkpoints as 'recoder_version' (model.py:207)
 __version__ = "0.4.0"
 
-__all__ = ["ShallowAutoencoder", "RandomWalkItemModel", "SparseLinearModel", "UserNeighbourhoodModel"]
+__all__ = ["ShallowAutoencoder", "RandomWalkItemModel", "SparseLinearModel", "UserNeighbourhoodModel",
+           "ItemNeighbourhoodModel"]
 
 
 def __getattr__(name):
@@ -25,4 +26,7 @@ def __getattr__(name):
   if name == "UserNeighbourhoodModel":
     from .nn import UserNeighbourhoodModel
     return UserNeighbourhoodModel
+  if name == "ItemNeighbourhoodModel":
+    from .nn import ItemNeighbourhoodModel
+    return ItemNeighbourhoodModel
   raise AttributeError("module %r has no attribute %r" % (__name__, name))

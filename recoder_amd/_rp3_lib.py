@@ -1,5 +1,6 @@
 """ctypes binding of librecoder_rp3.so (the C ABI in include/recoder_rp3.h): the RP3beta kernels
-for recoder_amd.rp3 and the user-neighbourhood kernels for recoder_amd.userknn.  Like _lib.py: plain pointers and sizes, no torch types across the boundary,
+for recoder_amd.rp3, the user-neighbourhood kernels for recoder_amd.userknn and the item-neighbourhood fit for
+recoder_amd.itemknn.  Like _lib.py: plain pointers and sizes, no torch types across the boundary,
 no CPU fallback."""
 import os
 
@@ -30,6 +31,9 @@ SIGNATURES = {
                                        _P, _P, _P, c_int64, _P]),
   "rk_rp3_user_scores": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P,
                                    c_int64, _P]),
+  "rk_rp3_item_workspace_bytes": (c_int64, [c_int32]),
+  "rk_rp3_item_fit": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, c_int32, c_float, c_float, c_int32,
+                                c_int32, c_int32, _P, _P, _P, _P, c_int64, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

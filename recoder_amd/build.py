@@ -19,7 +19,9 @@ librecoder_svd.so  the randomized truncated SVD behind PureSVD for MatrixFactori
 librecoder_rp3.so  the RP3beta item-graph fit and its scores for RandomWalkItemModel
                    (include/recoder_rp3.h), likewise a library of its own.  It also holds the
                    user-neighbourhood kernels of UserNeighbourhoodModel (rk_rp3_user_*): they share
-                   the fit's row hand-out and selection, which live in this translation unit
+                   the fit's row hand-out and selection, which live in this translation unit, and so
+                   does the item-neighbourhood fit of ItemNeighbourhoodModel (rk_rp3_item_*), whose
+                   scores are rk_slim_scores
 librecoder_slim.so  the SLIM coordinate-descent fit and its scores for SparseLinearModel
                    (include/recoder_slim.h), likewise a library of its own
 

@@ -15,6 +15,14 @@
 //                  1024 columns and walks the user's entries in order, adding x * w of the neighbours
 //                  that fall in its columns
 //
+// ItemKNN, the shrunk item-neighbourhood model (cosine, asymmetric cosine, Tversky / Jaccard / Dice):
+//   rk_rp3_item_fit  rk_rp3_fit's row pass for the own item j (hand-out, LDS / workspace split, first touch, selection):
+//                  accumulate: the walked user's own value a_vj travels with (user, row start, row end) and a
+//                    column i the wave owns takes fmaf(a_vj, a_vi, acc): one fmaf chain per column, ascending
+//                    users, no atomics on data; without values (a template parameter) the chain is adds of 1.0
+//                  scale: s / (own[j] * oth[i] + shrink) or s / (own[j] + oth[i] + g * s + shrink): the shrink
+//                    term and the co-count in the denominator are what rk_rp3_fit's separable scale cannot spell
+//
 // UserKNN, the user-neighbourhood model served from the training matrix itself:
 //   rk_rp3_user_neighbours  one workgroup per query row at a time, rows handed out through the same counter.
 //                  accumulate: c[v] = |H_q and H_v| by integer atomics on the workgroup's own accumulator
@@ -419,6 +427,140 @@ __global__ __launch_bounds__(FT_THREADS) void rp3_user_neighbours_kernel(
   }
 }
 
+// ------------------------------------------------------------------ item fit
+// s / den, den = (own * oth) + shrink (form 0) or ((own + oth) + (g * s)) + shrink (form 1): every operation a
+// separately rounded f32 operation (see un_sim for the pragma), +0 unless s > 0 and den > 0
+__device__ inline float it_sim(float s, float own, float oth, int form, float g, float shrink) {
+#pragma clang fp contract(off)
+  float den;
+  if (form == 0) {
+    const float prod = own * oth;
+    den = prod + shrink;
+  } else {
+    const float sum = own + oth;
+    const float gs = g * s;
+    const float t = sum + gs;
+    den = t + shrink;
+  }
+  return s > 0.f && den > 0.f ? __fdiv_rn(s, den) : 0.f;
+}
+
+// (rp3_fit_kernel's structure; DATA false: t_data / u_data are not read and every value is 1.0)
+template <bool WS, bool DATA>
+__global__ __launch_bounds__(FT_THREADS) void rp3_item_fit_kernel(
+    const int64_t *__restrict__ t_indptr, const int32_t *__restrict__ t_indices, const float *__restrict__ t_data,
+    const int64_t *__restrict__ u_indptr, const int32_t *__restrict__ u_indices, const float *__restrict__ u_data,
+    int n_users, int n, const float *__restrict__ own, const float *__restrict__ oth, int form, float g,
+    float shrink, int K, int col_lo, int col_hi, int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_w,
+    int32_t *__restrict__ nbr_count, int *counter, float *ws_acc, int *ws_cand, int64_t acc_stride, int ch) {
+  __shared__ float lds_acc[WS ? 1 : FT_LDS_ITEMS];
+  __shared__ int kid[FT_MAX_K];
+  __shared__ float kw[FT_MAX_K];
+  __shared__ int hist[256];
+  __shared__ int wcnt[FT_WAVES];
+  __shared__ int sh[8];          // 0: the column's offset; 1..4: ft_pick's answer; 5: entries gathered
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float *acc = WS ? ws_acc + (int64_t)blockIdx.x * acc_stride : lds_acc;
+  int *cand = WS ? ws_cand + (int64_t)blockIdx.x * FT_WAVES * ch : nullptr;
+  int *mylist = WS ? cand + (int64_t)wv * ch : nullptr;
+
+  auto for_cands = [&](auto f) {
+    if (!WS) {
+      for (int i = tid; i < n; i += FT_THREADS) f(i);
+    } else {
+#pragma unroll 1
+      for (int w = 0; w < FT_WAVES; ++w) {
+        const int c = wcnt[w];
+        const int *L = cand + (int64_t)w * ch;
+        for (int s = tid; s < c; s += FT_THREADS) f(L[s]);
+      }
+    }
+  };
+
+  if (WS)
+    for (int c = tid; c < n; c += FT_THREADS) acc[c] = -0.f;
+
+  for (;;) {
+    __syncthreads();
+    if (tid == 0) sh[0] = atomicAdd(counter, 1);
+    __syncthreads();
+    const int64_t j64 = (int64_t)col_lo + sh[0];
+    if (j64 >= col_hi) break;
+    const int j = (int)j64;
+    if (!WS) {
+      for (int c = tid; c < n; c += FT_THREADS) acc[c] = 0.f;
+      __syncthreads();
+    }
+
+    // ---- accumulate: (user, row start, row end, the own item's value) fetched 64 at a time
+    int mycnt = 0;
+    const int64_t e0 = t_indptr[j], e1 = t_indptr[j + 1];
+    for (int64_t eb = e0; eb < e1; eb += 64) {
+      const int cnt = e1 - eb < 64 ? (int)(e1 - eb) : 64;
+      int64_t r0 = 0, r1 = 0;
+      float av = 0.f;
+      if (lane < cnt) {
+        const int u = t_indices[eb + lane];
+        if (u >= 0 && u < n_users) {           // (a bad index reads nothing)
+          r0 = u_indptr[u];
+          r1 = u_indptr[u + 1];
+          if (DATA) av = t_data[eb + lane];
+        }
+      }
+      for (int l = 0; l < cnt; ++l) {
+        const int64_t p0 = __shfl(r0, l, 64), p1 = __shfl(r1, l, 64);
+        const float a = DATA ? __shfl(av, l, 64) : 1.f;
+        for (int64_t p = p0; p < p1; p += 64) {       // (wave-uniform bounds)
+          const int64_t q = p + lane;
+          int c = 0;
+          float x = 1.f;
+          bool mine = false;
+          if (q < p1) {
+            c = u_indices[q];
+            mine = c >= 0 && c < n && ((c >> 6) & (FT_WAVES - 1)) == wv;
+            if (DATA && mine) x = u_data[q];
+          }
+          if (WS) {
+            // (rp3_fit_kernel's first touch: a product is >= +0, so fmaf(a, x, +0) is bitwise the chain's start)
+            bool first = false;
+            if (mine) {
+              const float old = acc[c];
+              first = f2u(old) == FT_UNTOUCHED;
+              acc[c] = DATA ? fmaf(a, x, first ? 0.f : old) : (first ? 0.f : old) + 1.f;
+            }
+            const unsigned long long m = __ballot(first);
+            if (first) {
+              const int pos = mycnt + __popcll(m & ((1ull << lane) - 1ull));
+              if (pos < ch) mylist[pos] = c;
+            }
+            mycnt += __popcll(m);
+            __threadfence_block();
+          } else {
+            if (mine) acc[c] = DATA ? fmaf(a, x, acc[c]) : acc[c] + 1.f;
+          }
+        }
+      }
+    }
+    if (WS && lane == 0) wcnt[wv] = mycnt < ch ? mycnt : ch;
+    if (tid < 256) hist[tid] = 0;
+    if (tid == 0) sh[5] = 0;
+    __syncthreads();
+
+    // ---- scale, and the histogram of the top byte
+    const float oj = own[j];
+    for_cands([&](int i) {
+      float w = it_sim(acc[i], oj, oth[i], form, g, shrink);
+      if (i == j) w = 0.f;
+      acc[i] = w;
+      if (w > 0.f) atomicAdd(&hist[f2u(w) >> 24], 1);
+    });
+    __syncthreads();
+
+    ft_select_store(acc, for_cands, K, n, j, nbr_ids, nbr_w, nbr_count, hist, sh, kid, kw, tid, lane, wv);
+    if (WS) for_cands([&](int i) { acc[i] = -0.f; });
+  }
+}
+
 // --------------------------------------------------------------------- scores
 constexpr int SC_WAVES = 8;
 constexpr int SC_SUB = 1024;                  // columns a wave owns
@@ -526,7 +668,7 @@ __global__ __launch_bounds__(SC_WAVES * 64) void rp3_user_scores_kernel(
 // ------------------------------------------------------------------------ ABI
 extern "C" {
 
-int rk_rp3_version(void) { return 101; }
+int rk_rp3_version(void) { return 102; }
 
 const char *rk_rp3_last_error(void) { return g_rk_side_err; }
 
@@ -576,6 +718,57 @@ int rk_rp3_fit(const int64_t *t_indptr, const int32_t *t_indices, const int64_t 
                        nbr_count, counter, acc, cand, stride, (int)ch);
   }
   RK_SIDE_CHECK_LAUNCH("rp3_fit_kernel");
+  return 0;
+}
+
+int64_t rk_rp3_item_workspace_bytes(int32_t n_items) {
+  if (n_items < 1) {
+    rk_side_set_error("%s: n_items must be >= 1", __func__);
+    return -2;
+  }
+  return rk_rp3_fit_workspace_bytes(n_items);
+}
+
+int rk_rp3_item_fit(const int64_t *t_indptr, const int32_t *t_indices, const float *t_data, const int64_t *u_indptr,
+                    const int32_t *u_indices, const float *u_data, int32_t n_users, int32_t n_items,
+                    const float *own, const float *oth, int32_t form, float g, float shrink, int32_t K,
+                    int32_t col_lo, int32_t col_hi, int32_t *nbr_ids, float *nbr_w, int32_t *nbr_count, void *ws,
+                    int64_t ws_bytes, void *stream) {
+  RK_SIDE_REQUIRE(t_indptr && t_indices && u_indptr && u_indices && own && oth && nbr_ids && nbr_w && nbr_count && ws,
+                  "null pointer");
+  RK_SIDE_REQUIRE((t_data == nullptr) == (u_data == nullptr), "t_data and u_data must be given together or both be NULL");
+  RK_SIDE_REQUIRE(n_users >= 0 && n_items >= 1 && n_items < INT_MAX - 2048, "bad sizes");
+  RK_SIDE_REQUIRE(form == 0 || form == 1, "form must be 0 (product) or 1 (sum)");
+  RK_SIDE_REQUIRE(g >= -3.0e38f && g <= 3.0e38f, "g must be finite");
+  RK_SIDE_REQUIRE(shrink >= 0.f && shrink <= 3.0e38f, "shrink must be finite and >= 0");
+  RK_SIDE_REQUIRE(K >= 1 && K <= FT_MAX_K, "K outside [1, rk_rp3_max_neighbours()]");
+  RK_SIDE_REQUIRE(0 <= col_lo && col_lo <= col_hi && col_hi <= n_items, "bad column range");
+  RK_SIDE_REQUIRE(ws_bytes >= rk_rp3_item_workspace_bytes(n_items), "workspace too small");
+  RK_SIDE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
+  if (col_lo == col_hi) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  int *counter = (int *)ws;
+  if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
+    rk_side_set_error("%s: hipMemsetAsync failed", __func__);
+    return -1;
+  }
+  const int cols = col_hi - col_lo;
+  const int groups = cols < FT_GROUPS ? cols : FT_GROUPS;
+  const bool data = t_data != nullptr;
+  auto launch = [&](auto kernel, float *acc, int *cand, int64_t stride, int ch) {
+    hipLaunchKernelGGL(kernel, dim3(groups), dim3(FT_THREADS), 0, s, t_indptr, t_indices, t_data, u_indptr, u_indices,
+                       u_data, n_users, n_items, own, oth, form, g, shrink, K, col_lo, col_hi, nbr_ids, nbr_w, nbr_count,
+                       counter, acc, cand, stride, ch);
+  };
+  if (n_items <= FT_LDS_ITEMS) {
+    launch(data ? rp3_item_fit_kernel<false, true> : rp3_item_fit_kernel<false, false>, nullptr, nullptr, 0, 0);
+  } else {
+    const int64_t stride = ft_acc_stride(n_items), ch = ft_list_stride(n_items);
+    float *acc = (float *)((char *)ws + 256);
+    launch(data ? rp3_item_fit_kernel<true, true> : rp3_item_fit_kernel<true, false>, acc,
+           (int *)(acc + (int64_t)FT_GROUPS * stride), stride, (int)ch);
+  }
+  RK_SIDE_CHECK_LAUNCH("rp3_item_fit_kernel");
   return 0;
 }
 

@@ -33,8 +33,9 @@ from .device import Block, DeviceCSR, require_gpu
 from .engine import FusedEngine
 from .losses import MSELoss, MultinomialNLLLoss
 from .metrics import RecommenderEvaluator
-from .nn import (CsrScoresModel, DynamicAutoencoder, FactorizationModel, MatrixFactorization, RandomWalkItemModel,
-                 ShallowAutoencoder, SparseLinearModel, UserNeighbourhoodModel, VariationalAutoencoder)
+from .nn import (CsrScoresModel, DynamicAutoencoder, FactorizationModel, ItemNeighbourhoodModel, MatrixFactorization,
+                 RandomWalkItemModel, ShallowAutoencoder, SparseLinearModel, UserNeighbourhoodModel,
+                 VariationalAutoencoder)
 from .recommender import InferenceRecommender
 
 log = logging.getLogger("recoder_amd")
@@ -90,6 +91,7 @@ class Recoder(object):
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
     self.userknn_info = None    # train_userknn: what the last UserKNN fit reported
+    self.itemknn_info = None    # train_itemknn: what the last ItemKNN fit reported
     self.__model_initialized = False
     self.__optimizer_state_dict = None
     self.__sparse_optimizer_state_dict = None
@@ -380,6 +382,9 @@ class Recoder(object):
     if isinstance(self.model, SparseLinearModel):
       raise ValueError("a SparseLinearModel is fitted by coordinate descent on the Gram matrix: call "
                        "train_slim(train_dataset)")
+    if isinstance(self.model, ItemNeighbourhoodModel):
+      raise ValueError("an ItemNeighbourhoodModel is fitted in closed form from the items' co-occurrences: call "
+                       "train_itemknn(train_dataset)")
     if isinstance(self.model, UserNeighbourhoodModel):
       raise ValueError("a UserNeighbourhoodModel is its training matrix, there is nothing to descend on: call "
                        "train_userknn(train_dataset)")
@@ -594,6 +599,51 @@ class Recoder(object):
     pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
     _, _, _, info = rp3.fit(pair, alpha, beta, K, out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))
     self.rp3_info = info
+    self._weights_written()
+    return dict(info)
+
+  def train_itemknn(self, train_dataset, neighbours=None, shrink=None, similarity=None, feature_weighting=None):
+    """The closed-form ItemKNN fit of an ItemNeighbourhoodModel (recoder_amd/itemknn.py): column j of W keeps
+    the ``neighbours`` largest ``s_ij / (denominator + shrink)``, ``s_ij = sum over the users v of i and j of
+    a_vi a_vj`` over the dataset's interaction matrix (values as stored, finite and >= 0: ValueError
+    otherwise; re-weighted by ``feature_weighting`` for the two cosines, taken as 1 by the set similarities).
+    ``None`` takes the model's value; explicit values are stored back into the model, so that a checkpoint's
+    ``model_params`` describe the weights it holds, and another ``neighbours`` re-allocates the model's
+    tensors.  The alpha / beta values of the asymmetric and Tversky similarities are the model's.  The
+    configured ``loss`` plays no part.  Builds a fresh optimizer of ``optimizer_type`` so that ``save_state``
+    works.  Returns (and keeps in ``itemknn_info``) n, nnz, neighbours, shrink, similarity, feature_weighting,
+    kept (entries kept over all columns) and fit_ms (HIP events)."""
+    from . import als, itemknn
+    m = self.model
+    if not isinstance(m, ItemNeighbourhoodModel):
+      raise ValueError("train_itemknn fits an ItemNeighbourhoodModel, not %s" % type(m).__name__)
+    K, shrink, similarity, feature_weighting, aa, ta, tb = itemknn.check_config(
+        m, m.neighbours if neighbours is None else neighbours, m.shrink if shrink is None else shrink,
+        m.similarity if similarity is None else similarity,
+        m.feature_weighting if feature_weighting is None else feature_weighting)
+    itemknn.check_not_distributed()
+    u_hint, n_hint = self._size_hints(train_dataset)
+    if n_hint:
+      # (before init_model allocates: a catalogue that cannot fit gets a ValueError, not an OOM)
+      itemknn.check_memory(u_hint or 0, n_hint, K, 0, free_bytes=float("inf"))
+    host = als.host_matrix(train_dataset)
+    itemknn.check_values(host)
+    log.info("ItemKNN: %s similarity, feature weighting %s, %d neighbours, shrink %g", similarity,
+             feature_weighting, K, shrink)
+    m.shrink, m.similarity, m.feature_weighting = shrink, similarity, feature_weighting
+    self._reset_optimizers()
+    if not self.__model_initialized:
+      require_gpu()
+      m.neighbours = K
+    elif K != m.item_weights.shape[1]:
+      m.allocate(K, self.device)
+    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
+    m = self.model
+    itemknn.check_memory(self.num_users, self.num_items, K, host.nnz, allocate_model=False)
+    pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
+    _, _, _, info = itemknn.fit(pair, K, shrink, similarity, feature_weighting, aa, ta, tb,
+                                out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))
+    self.itemknn_info = info
     self._weights_written()
     return dict(info)
 

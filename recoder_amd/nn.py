@@ -570,7 +570,23 @@ class RandomWalkItemModel(_NeighbourListModel):
     return W
 
 
-class SparseLinearModel(_NeighbourListModel):
+class _ColumnListModel(_NeighbourListModel):
+  """The neighbour-list models whose lists spell the COLUMNS of W: row j of the three tensors holds the kept k
+  of column j, ``W[item_neighbours[j, s], j] = item_weights[j, s]`` (the layout rk_slim_scores reads)."""
+
+  def dense_weights(self, dtype=torch.float32):
+    """W [num_items, num_items]: the kept entries scattered into a dense matrix, ``W[item_neighbours[j, s], j]
+    = item_weights[j, s]`` (small catalogues only)."""
+    n, K = self.item_weights.shape
+    W = torch.zeros(n, n, dtype=dtype, device=self.item_weights.device)
+    ids = self.item_neighbours.to(torch.int64)
+    live = torch.arange(K, device=ids.device)[None, :] < self.neighbour_counts.to(torch.int64)[:, None]
+    cols = torch.arange(n, device=ids.device)[:, None].expand(n, K)
+    W[ids[live], cols[live]] = self.item_weights.data.to(dtype)[live]
+    return W
+
+
+class SparseLinearModel(_ColumnListModel):
   """SLIM (Ning & Karypis 2011): the learned sparse item-item model ``scores = input @ W``, column j of W
   the non-negative elastic-net regression of item j on the other items,
   ``min over w >= 0, w_j = 0 of 1/2 |x_j - X w|^2 + l2_reg/2 |w|^2 + l1_reg |w|_1``, cut to its ``neighbours``
@@ -609,16 +625,54 @@ class SparseLinearModel(_NeighbourListModel):
     self.neighbours = int(model_params["neighbours"])
     self._validate()
 
-  def dense_weights(self, dtype=torch.float32):
-    """W [num_items, num_items]: the kept entries scattered into a dense matrix, ``W[item_neighbours[j, s], j]
-    = item_weights[j, s]`` (small catalogues only)."""
-    n, K = self.item_weights.shape
-    W = torch.zeros(n, n, dtype=dtype, device=self.item_weights.device)
-    ids = self.item_neighbours.to(torch.int64)
-    live = torch.arange(K, device=ids.device)[None, :] < self.neighbour_counts.to(torch.int64)[:, None]
-    cols = torch.arange(n, device=ids.device)[:, None].expand(n, K)
-    W[ids[live], cols[live]] = self.item_weights.data.to(dtype)[live]
-    return W
+
+class ItemNeighbourhoodModel(_ColumnListModel):
+  """ItemKNN (the shrunk item-neighbourhood baseline of Dacrema et al. 2019): ``scores = input @ W``, column j
+  of W the ``neighbours`` items most similar to item j, ``W[i, j] = s_ij / (denominator + shrink)`` with
+  ``s_ij = sum over the users v of i and j of a_vi a_vj``, fitted by ``Recoder.train_itemknn``
+  (recoder_amd/itemknn.py).  ``similarity``: "cosine" (``|a_i| |a_j|``), "asymmetric" (Aiolli 2013:
+  ``|a_j|^(2(1 - asymmetric_alpha)) |a_i|^(2 asymmetric_alpha)``), or, on the binary matrix, "tversky"
+  (``s + tversky_alpha |i \\ j| + tversky_beta |j \\ i|``), "jaccard" (alpha = beta = 1) and "dice" (alpha = beta =
+  1/2).  ``feature_weighting`` ("none", "tfidf", "bm25") re-weights the stored values for the two cosines.
+  ``shrink`` **matters**: without it a pair that one user shares gets similarity 1 and the model ranks far
+  below popularity on sparse data.
+
+  Three tensors, all in ``state_dict()``, laid out as ``SparseLinearModel``'s, per COLUMN of W:
+  ``item_neighbours`` int32 [num_items, neighbours] (the kept i of column j, ascending, -1 where a column has
+  fewer), ``item_weights`` f32 of the same shape and ``neighbour_counts`` int32 [num_items]; empty until
+  fitted.  The seven settings travel in ``model_params()``.  ``Recoder.train`` refuses this model and points
+  at ``train_itemknn``.
+  """
+  fit_module = "itemknn"
+  _PARAMS = ("neighbours", "shrink", "similarity", "feature_weighting", "asymmetric_alpha", "tversky_alpha",
+             "tversky_beta")
+
+  def __init__(self, neighbours=200, shrink=300.0, similarity="cosine", feature_weighting="none",
+               asymmetric_alpha=0.5, tversky_alpha=1.0, tversky_beta=1.0):
+    super().__init__()
+    self.neighbours = neighbours
+    self.shrink = shrink
+    self.similarity = similarity
+    self.feature_weighting = feature_weighting
+    self.asymmetric_alpha = asymmetric_alpha
+    self.tversky_alpha = tversky_alpha
+    self.tversky_beta = tversky_beta
+    self.num_items = None
+    self.item_weights = None
+    self._validate()
+
+  def _validate(self):
+    from .itemknn import check_params
+    for name, v in zip(self._PARAMS, check_params(*(getattr(self, name) for name in self._PARAMS))):
+      setattr(self, name, v)
+
+  def model_params(self):
+    return {name: getattr(self, name) for name in self._PARAMS}
+
+  def load_model_params(self, model_params):
+    for name in self._PARAMS:
+      setattr(self, name, model_params[name])
+    self._validate()
 
 
 class UserNeighbourhoodModel(CsrScoresModel):
