@@ -1,38 +1,36 @@
-// RP3beta: the sparse item-graph model (include/recoder_rp3.h, librecoder_rp3.so).
+// The neighbour-list models (include/recoder_rp3.h, librecoder_rp3.so): RP3beta, ItemKNN and UserKNN.
 //
-//   rk_rp3_fit     one workgroup (16 waves) per source item i at a time, rows handed out through a counter.
-//                  accumulate: every wave walks the users of item i in order and adds user_w[v] to the
-//                    columns of user v it owns (64-column granules, round robin over the waves): one add
-//                    chain per column, ascending users, no atomics on data.  The accumulators are a row in
-//                    LDS (n <= FT_LDS_ITEMS) or a row of the workspace; the workspace path also lists the
-//                    columns it touches (a column's first touch is seen from its -0 fill), so that
-//                    everything after costs the row's candidates, not n
-//                  scale: W = (row_scale[i] * S) * col_scale[j], the diagonal 0
-//                  select: radix selection (4 x 8 bits) of the K-th largest float, then of the id up to which
-//                    values equal to it are kept
-//                  compact: the kept entries gathered in LDS, sorted by id (bitonic), written with padding
-//   rk_rp3_scores  one workgroup per (user, tile of 8192 columns held in LDS); each of its 8 waves owns
-//                  1024 columns and walks the user's entries in order, adding x * w of the neighbours
-//                  that fall in its columns
+// The three fits are one row pass (FtPass) with a model's accumulate and scale plugged in: one workgroup
+// (16 waves) per row at a time, rows handed out through a counter.
+//   accumulate: a row's values, one 32-bit word per candidate, in LDS (n <= FT_LDS_ITEMS) or in a row of the
+//     workspace; the workspace form also lists the words it touches (a word's first touch is seen from its
+//     fill), so that everything after costs the row's candidates, not n
+//   scale: every candidate's word becomes the row's value for it
+//   select: radix selection (4 x 8 bits) of the K-th largest float, then of the id up to which values equal to
+//     it are kept
+//   compact: the kept entries gathered in LDS, sorted by id (bitonic), written with padding
 //
-// ItemKNN, the shrunk item-neighbourhood model (cosine, asymmetric cosine, Tversky / Jaccard / Dice):
-//   rk_rp3_item_fit  rk_rp3_fit's row pass for the own item j (hand-out, LDS / workspace split, first touch, selection):
-//                  accumulate: the walked user's own value a_vj travels with (user, row start, row end) and a
-//                    column i the wave owns takes fmaf(a_vj, a_vi, acc): one fmaf chain per column, ascending
-//                    users, no atomics on data; without values (a template parameter) the chain is adds of 1.0
-//                  scale: s / (own[j] * oth[i] + shrink) or s / (own[j] + oth[i] + g * s + shrink): the shrink
-//                    term and the co-count in the denominator are what rk_rp3_fit's separable scale cannot spell
+//   rk_rp3_fit (RP3beta, the sparse item-graph model), source item i:
+//     accumulate: ft_walk_users; every wave walks the users of item i in order and adds user_w[v] to the
+//       columns of user v it owns: one add chain per column, ascending users, no atomics on data
+//     scale: W = (row_scale[i] * S) * col_scale[j], the diagonal 0
+//   rk_rp3_item_fit (ItemKNN: cosine, asymmetric cosine, Tversky / Jaccard / Dice), own item j:
+//     accumulate: ft_walk_users; the walked user's own value a_vj travels with it and a column i takes
+//       fmaf(a_vj, a_vi, acc); without values (a template parameter) the chain is adds of 1.0
+//     scale: s / (own[j] * oth[i] + shrink) or s / (own[j] + oth[i] + g * s + shrink): the shrink term and the
+//       co-count in the denominator are what rk_rp3_fit's separable scale cannot spell
+//   rk_rp3_user_neighbours (UserKNN, served from the training matrix itself), query row q:
+//     accumulate: its own; c[v] = |H_q and H_v| by integer atomics on the workgroup's accumulators (a user's
+//       first touch is the add that returns 0); an item with few users belongs to one wave, an item with many
+//       is walked by all sixteen
+//     scale: sim = c / (qn[q] * un[v] + shrink)
 //
-// UserKNN, the user-neighbourhood model served from the training matrix itself:
-//   rk_rp3_user_neighbours  one workgroup per query row at a time, rows handed out through the same counter.
-//                  accumulate: c[v] = |H_q and H_v| by integer atomics on the workgroup's own accumulator
-//                    (LDS, or a workspace row that also lists the users it touches: a user's first touch is
-//                    the add that returns 0); an item with few users belongs to one wave, an item with many
-//                    is walked by all sixteen
-//                  scale: sim = c / (qn[q] * un[v] + shrink); select, compact: the fit's (ft_select_store)
-//   rk_rp3_user_scores  rk_rp3_scores' tiling: one workgroup per (query, tile of 8192 columns in LDS), a wave owns
-//                  1024 columns and walks the query's neighbours in order; 64 neighbours at a time, a lane
-//                  finds by binary search where its neighbour's row enters and leaves the wave's columns
+// The two scores kernels share their tiling (sc_begin, sc_store): one workgroup per (row, tile of 8192 columns
+// held in LDS), each of its 8 waves owns 1024 columns.
+//   rk_rp3_scores  a wave walks the user's entries in order, adding x * w of the neighbours that fall in its
+//                  columns
+//   rk_rp3_user_scores  a wave walks the query's neighbours in order; 64 neighbours at a time, a lane finds by
+//                  binary search where its neighbour's row enters and leaves the wave's columns
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -188,6 +186,178 @@ __device__ __forceinline__ void ft_select_store(const float *acc, ForCands for_c
   if (tid == 0) nbr_count[row] = kept;
 }
 
+// ------------------------------------------------------------------ row pass
+// What the three fit kernels share.  A workgroup takes rows from a counter until none is left; a row's
+// values are accumulated (by the model's own code) in n 32-bit words, a row in LDS or (WS) the workgroup's
+// row of the workspace; finish() turns them into the row's values and hands them to ft_select_store.  WS
+// also lists the words a row touches, so that everything after the accumulate costs the row's candidates,
+// not n: a word's first touch is seen from its fill, and finish() puts the touched words back at it.
+//   COUNTS false (RP3beta, ItemKNN): f32 sums, fill -0, a candidate list per wave (its entries in cnt[wave])
+//   COUNTS true (UserKNN): integer counts made by atomics in L2, fill 0, one list (its entries in cnt[0]);
+//     the counts are read and cleared at agent scope, past this CU's L1
+template <bool WS>
+struct FtState {                 // the workgroup's LDS
+  int kid[FT_MAX_K];
+  float kw[FT_MAX_K];
+  int hist[256];
+  int cnt[FT_WAVES];
+  int sh[8];                     // 0: the row's offset; 1..4: ft_pick's answer; 5: entries gathered
+  float acc[WS ? 1 : FT_LDS_ITEMS];      // (last: in front, WS's one unused word takes the arrays off their alignment
+};                                       // and the selection past 64 VGPRs, the two-workgroups-per-CU budget)
+
+template <bool WS, bool COUNTS>
+struct FtPass {
+  static constexpr int LISTS = COUNTS ? 1 : FT_WAVES;
+  FtState<WS> &S;
+  const int n, ch, tid, lane, wv;          // ch: entries of one candidate list
+  float *acc;
+  int *cand;
+
+  __device__ __forceinline__ FtPass(FtState<WS> &S, int n, float *ws_acc, int *ws_cand, int64_t acc_stride, int ch)
+      : S(S), n(n), ch(ch), tid(threadIdx.x), lane(tid & 63), wv(tid >> 6),
+        acc(WS ? ws_acc + (int64_t)blockIdx.x * acc_stride : S.acc),
+        cand(WS ? ws_cand + (int64_t)blockIdx.x * LISTS * ch : nullptr) {
+    if (WS)
+      for (int c = tid; c < n; c += FT_THREADS) acc[c] = COUNTS ? 0.f : -0.f;
+  }
+
+  // f(j) once per candidate j of the row, spread over the threads
+  template <class F>
+  __device__ __forceinline__ void for_cands(F f) const {
+    if (!WS) {
+      for (int j = tid; j < n; j += FT_THREADS) f(j);
+    } else {
+#pragma unroll 1
+      for (int l = 0; l < LISTS; ++l) {
+        const int c = S.cnt[l] < ch ? S.cnt[l] : ch;
+        const int *L = cand + (int64_t)l * ch;
+        for (int s = tid; s < c; s += FT_THREADS) f(L[s]);
+      }
+    }
+  }
+
+  // the workgroup's next row of [lo, hi), its accumulators at their start; -1 when none is left
+  __device__ __forceinline__ int next_row(int *counter, int lo, int hi) {
+    __syncthreads();
+    if (tid == 0) {
+      S.sh[0] = atomicAdd(counter, 1);
+      if (COUNTS) S.cnt[0] = 0;
+    }
+    __syncthreads();
+    const int64_t row = (int64_t)lo + S.sh[0];
+    if (row >= hi) return -1;
+    if (!WS) {
+      for (int c = tid; c < n; c += FT_THREADS) acc[c] = 0.f;
+      __syncthreads();
+    }
+    return (int)row;
+  }
+
+  // After the accumulate: candidate j's word becomes scale(j, the word's bits), the row's value; then
+  // select, compact and store the row (ft_select_store) and leave the touched words at their fill.
+  template <class Scale>
+  __device__ __forceinline__ void finish(Scale scale, int K, int row, int32_t *__restrict__ nbr_ids,
+                                         float *__restrict__ nbr_w, int32_t *__restrict__ nbr_count) {
+    if (tid < 256) S.hist[tid] = 0;
+    if (tid == 0) S.sh[5] = 0;
+    if (WS && COUNTS) __threadfence();         // (the adds were made in L2: nothing of this row is read before them)
+    __syncthreads();
+
+    // ---- scale, and the histogram of the top byte
+    for_cands([&](int j) {
+      const uint32_t a = WS && COUNTS ? __hip_atomic_load(reinterpret_cast<unsigned int *>(acc + j), __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_AGENT)
+                                      : f2u(acc[j]);
+      const float w = scale(j, a);
+      acc[j] = w;
+      if (w > 0.f) atomicAdd(&S.hist[f2u(w) >> 24], 1);
+    });
+    __syncthreads();
+
+    ft_select_store(acc, [&](auto f) { for_cands(f); }, K, n, row, nbr_ids, nbr_w, nbr_count, S.hist, S.sh, S.kid,
+                    S.kw, tid, lane, wv);
+    if (WS)
+      for_cands([&](int j) {
+        if (COUNTS)
+          __hip_atomic_store(reinterpret_cast<unsigned int *>(acc + j), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else
+          acc[j] = -0.f;
+      });
+  }
+};
+
+// The accumulate of the two item models: every wave walks the users of item ``row`` in order and updates the
+// columns of each user that it owns (64-column granules, round robin over the waves): one chain per column,
+// ascending users, no atomics on data.  (user, row start, row end, m.payload) are fetched 64 at a time, as
+// rk_ease_gram does, and a column takes m.update(its value so far, the user's payload, m.value(the entry)).
+template <bool WS, class Model>
+__device__ __forceinline__ void ft_walk_users(FtPass<WS, false> &ps, const Model &m, int row,
+                                              const int64_t *__restrict__ t_indptr,
+                                              const int32_t *__restrict__ t_indices,
+                                              const int64_t *__restrict__ u_indptr,
+                                              const int32_t *__restrict__ u_indices, int n_users) {
+  const int lane = ps.lane, wv = ps.wv, n = ps.n, ch = ps.ch;
+  float *acc = ps.acc;
+  int *mylist = WS ? ps.cand + (int64_t)wv * ch : nullptr;
+  int mycnt = 0;
+  const int64_t e0 = t_indptr[row], e1 = t_indptr[row + 1];
+  for (int64_t eb = e0; eb < e1; eb += 64) {
+    const int cnt = e1 - eb < 64 ? (int)(e1 - eb) : 64;
+    int64_t r0 = 0, r1 = 0;
+    float pay = 0.f;
+    if (lane < cnt) {
+      const int u = t_indices[eb + lane];
+      if (u >= 0 && u < n_users) {           // (a bad index reads nothing)
+        r0 = u_indptr[u];
+        r1 = u_indptr[u + 1];
+        pay = m.payload(eb + lane, u);
+      }
+    }
+    for (int l = 0; l < cnt; ++l) {
+      const int64_t p0 = __shfl(r0, l, 64), p1 = __shfl(r1, l, 64);
+      const float a = __shfl(pay, l, 64);
+      for (int64_t p = p0; p < p1; p += 64) {       // (wave-uniform bounds)
+        const int64_t q = p + lane;
+        int c = 0;
+        float x = 1.f;
+        bool mine = false;
+        if (q < p1) {
+          c = u_indices[q];
+          mine = c >= 0 && c < n && ((c >> 6) & (FT_WAVES - 1)) == wv;
+          if (mine) x = m.value(q);
+        }
+        // columns of one user are distinct: no two lanes meet.  A first touch starts the chain from +0: an
+        // update's term is >= +0, so that is bitwise the chain of the LDS form
+        bool first = false;
+        if (mine) {
+          const float old = acc[c];
+          first = WS && f2u(old) == FT_UNTOUCHED;
+          acc[c] = m.update(first ? 0.f : old, a, x);
+        }
+        if (WS) {
+          const unsigned long long mask = __ballot(first);
+          if (first) {
+            const int pos = mycnt + __popcll(mask & ((1ull << lane) - 1ull));
+            if (pos < ch) mylist[pos] = c;
+          }
+          mycnt += __popcll(mask);
+          // the next user's updates may come from other lanes of this wave: the fence keeps them behind these stores
+          __threadfence_block();
+        }
+      }
+    }
+  }
+  if (WS && lane == 0) ps.S.cnt[wv] = mycnt;
+}
+
+// --------------------------------------------------------------------- RP3beta
+struct Rp3Walk {                 // the walked user's weight travels with it and is added to every column
+  const float *__restrict__ user_w;
+  __device__ __forceinline__ float payload(int64_t, int u) const { return user_w[u]; }
+  __device__ __forceinline__ float value(int64_t) const { return 1.f; }
+  __device__ __forceinline__ float update(float s, float w, float) const { return s + w; }
+};
+
 template <bool WS>
 __global__ __launch_bounds__(FT_THREADS) void rp3_fit_kernel(
     const int64_t *__restrict__ t_indptr, const int32_t *__restrict__ t_indices,
@@ -195,114 +365,66 @@ __global__ __launch_bounds__(FT_THREADS) void rp3_fit_kernel(
     const float *__restrict__ user_w, const float *__restrict__ row_scale, const float *__restrict__ col_scale,
     int K, int row_lo, int row_hi, int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_w,
     int32_t *__restrict__ nbr_count, int *counter, float *ws_acc, int *ws_cand, int64_t acc_stride, int ch) {
-  __shared__ float lds_acc[WS ? 1 : FT_LDS_ITEMS];
-  __shared__ int kid[FT_MAX_K];
-  __shared__ float kw[FT_MAX_K];
-  __shared__ int hist[256];
-  __shared__ int wcnt[FT_WAVES];
-  __shared__ int sh[8];          // 0: the row's offset; 1..4: ft_pick's answer; 5: entries gathered
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  float *acc = WS ? ws_acc + (int64_t)blockIdx.x * acc_stride : lds_acc;
-  int *cand = WS ? ws_cand + (int64_t)blockIdx.x * FT_WAVES * ch : nullptr;
-  int *mylist = WS ? cand + (int64_t)wv * ch : nullptr;
-
-  auto for_cands = [&](auto f) {
-    if (!WS) {
-      for (int j = tid; j < n; j += FT_THREADS) f(j);
-    } else {
-#pragma unroll 1
-      for (int w = 0; w < FT_WAVES; ++w) {
-        const int c = wcnt[w];
-        const int *L = cand + (int64_t)w * ch;
-        for (int s = tid; s < c; s += FT_THREADS) f(L[s]);
-      }
-    }
-  };
-
-  if (WS)
-    for (int c = tid; c < n; c += FT_THREADS) acc[c] = -0.f;
-
-  for (;;) {
-    __syncthreads();
-    if (tid == 0) sh[0] = atomicAdd(counter, 1);
-    __syncthreads();
-    const int64_t i64 = (int64_t)row_lo + sh[0];
-    if (i64 >= row_hi) break;
-    const int i = (int)i64;
-    if (!WS) {
-      for (int c = tid; c < n; c += FT_THREADS) acc[c] = 0.f;
-      __syncthreads();
-    }
-
-    // ---- accumulate: (user, row start, row end, weight) fetched 64 at a time, as rk_ease_gram does
-    int mycnt = 0;
-    const int64_t e0 = t_indptr[i], e1 = t_indptr[i + 1];
-    for (int64_t eb = e0; eb < e1; eb += 64) {
-      const int cnt = e1 - eb < 64 ? (int)(e1 - eb) : 64;
-      int64_t r0 = 0, r1 = 0;
-      float uw = 0.f;
-      if (lane < cnt) {
-        const int u = t_indices[eb + lane];
-        if (u >= 0 && u < n_users) {           // (a bad index reads nothing)
-          r0 = u_indptr[u];
-          r1 = u_indptr[u + 1];
-          uw = user_w[u];
-        }
-      }
-      for (int l = 0; l < cnt; ++l) {
-        const int64_t p0 = __shfl(r0, l, 64), p1 = __shfl(r1, l, 64);
-        const float w = __shfl(uw, l, 64);
-        for (int64_t p = p0; p < p1; p += 64) {       // (wave-uniform bounds)
-          const int64_t q = p + lane;
-          int c = 0;
-          bool mine = false;
-          if (q < p1) {
-            c = u_indices[q];
-            mine = c >= 0 && c < n && ((c >> 6) & (FT_WAVES - 1)) == wv;
-          }
-          if (WS) {
-            // columns of one user are distinct: no two lanes meet.  The next user's adds may come from
-            // other lanes of this wave: the fence keeps them behind these stores
-            bool first = false;
-            if (mine) {
-              const float old = acc[c];
-              first = f2u(old) == FT_UNTOUCHED;
-              acc[c] = (first ? 0.f : old) + w;
-            }
-            const unsigned long long m = __ballot(first);
-            if (first) {
-              const int pos = mycnt + __popcll(m & ((1ull << lane) - 1ull));
-              if (pos < ch) mylist[pos] = c;
-            }
-            mycnt += __popcll(m);
-            __threadfence_block();
-          } else {
-            if (mine) acc[c] += w;
-          }
-        }
-      }
-    }
-    if (WS && lane == 0) wcnt[wv] = mycnt < ch ? mycnt : ch;
-    if (tid < 256) hist[tid] = 0;
-    if (tid == 0) sh[5] = 0;
-    __syncthreads();
-
-    // ---- scale, and the histogram of the top byte
+  __shared__ FtState<WS> S;
+  FtPass<WS, false> ps(S, n, ws_acc, ws_cand, acc_stride, ch);
+  const Rp3Walk walk{user_w};
+  for (int i; (i = ps.next_row(counter, row_lo, row_hi)) >= 0;) {
+    ft_walk_users(ps, walk, i, t_indptr, t_indices, u_indptr, u_indices, n_users);
     const float rs = row_scale[i];
-    for_cands([&](int j) {
-      float w = __fmul_rn(__fmul_rn(rs, acc[j]), col_scale[j]);
-      if (j == i) w = 0.f;
-      acc[j] = w;
-      if (w > 0.f) atomicAdd(&hist[f2u(w) >> 24], 1);
-    });
-    __syncthreads();
-
-    ft_select_store(acc, for_cands, K, n, i, nbr_ids, nbr_w, nbr_count, hist, sh, kid, kw, tid, lane, wv);
-    if (WS) for_cands([&](int j) { acc[j] = -0.f; });
+    ps.finish([&](int j, uint32_t s) {
+      return j == i ? 0.f : __fmul_rn(__fmul_rn(rs, __uint_as_float(s)), col_scale[j]);
+    }, K, i, nbr_ids, nbr_w, nbr_count);
   }
 }
 
-// ----------------------------------------------------------- user neighbours
+// --------------------------------------------------------------------- ItemKNN
+// s / den, den = (own * oth) + shrink (form 0) or ((own + oth) + (g * s)) + shrink (form 1): every operation a
+// separately rounded f32 operation (see un_sim for the pragma), +0 unless s > 0 and den > 0
+__device__ inline float it_sim(float s, float own, float oth, int form, float g, float shrink) {
+#pragma clang fp contract(off)
+  float den;
+  if (form == 0) {
+    const float prod = own * oth;
+    den = prod + shrink;
+  } else {
+    const float sum = own + oth;
+    const float gs = g * s;
+    const float t = sum + gs;
+    den = t + shrink;
+  }
+  return s > 0.f && den > 0.f ? __fdiv_rn(s, den) : 0.f;
+}
+
+// the walked user's value for the own item travels with it: one fmaf chain per column; DATA false: t_data /
+// u_data are not read, every value is 1.0 and the chain is adds of 1.0
+template <bool DATA>
+struct ItemWalk {
+  const float *__restrict__ t_data, *__restrict__ u_data;
+  __device__ __forceinline__ float payload(int64_t e, int) const { return DATA ? t_data[e] : 1.f; }
+  __device__ __forceinline__ float value(int64_t q) const { return DATA ? u_data[q] : 1.f; }
+  __device__ __forceinline__ float update(float s, float a, float x) const { return DATA ? fmaf(a, x, s) : s + 1.f; }
+};
+
+template <bool WS, bool DATA>
+__global__ __launch_bounds__(FT_THREADS) void rp3_item_fit_kernel(
+    const int64_t *__restrict__ t_indptr, const int32_t *__restrict__ t_indices, const float *__restrict__ t_data,
+    const int64_t *__restrict__ u_indptr, const int32_t *__restrict__ u_indices, const float *__restrict__ u_data,
+    int n_users, int n, const float *__restrict__ own, const float *__restrict__ oth, int form, float g,
+    float shrink, int K, int col_lo, int col_hi, int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_w,
+    int32_t *__restrict__ nbr_count, int *counter, float *ws_acc, int *ws_cand, int64_t acc_stride, int ch) {
+  __shared__ FtState<WS> S;
+  FtPass<WS, false> ps(S, n, ws_acc, ws_cand, acc_stride, ch);
+  const ItemWalk<DATA> walk{t_data, u_data};
+  for (int j; (j = ps.next_row(counter, col_lo, col_hi)) >= 0;) {
+    ft_walk_users(ps, walk, j, t_indptr, t_indices, u_indptr, u_indices, n_users);
+    const float oj = own[j];
+    ps.finish([&](int i, uint32_t s) {
+      return i == j ? 0.f : it_sim(__uint_as_float(s), oj, oth[i], form, g, shrink);
+    }, K, j, nbr_ids, nbr_w, nbr_count);
+  }
+}
+
+// --------------------------------------------------------------------- UserKNN
 constexpr int UN_WIDE = 256;                  // an item with at least this many users is walked by every wave
 
 // c / ((qs * u) + shrink): three f32 operations, each correctly rounded.  hipcc's default -ffp-contract=fast
@@ -314,8 +436,9 @@ __device__ inline float un_sim(float c, float qs, float u, float shrink) {
   return __fdiv_rn(c, den);
 }
 
-// (the accumulator row holds counts while a row accumulates and the similarities afterwards: one 32-bit
-// word per user either way, so that ft_select_store reads it as the fit's)
+// (a word holds a count while a row accumulates and the similarity afterwards.  The accumulate is this
+// kernel's own: integer adds commute, so an item with few users belongs to one wave, an item with many is
+// walked by all sixteen, and a user's first touch is the add that returns 0)
 template <bool WS>
 __global__ __launch_bounds__(FT_THREADS) void rp3_user_neighbours_kernel(
     const int64_t *__restrict__ q_indptr, const int32_t *__restrict__ q_indices,
@@ -323,44 +446,12 @@ __global__ __launch_bounds__(FT_THREADS) void rp3_user_neighbours_kernel(
     const float *__restrict__ un, const float *__restrict__ qn, float shrink, int K, int row_lo, int row_hi,
     int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_sim, int32_t *__restrict__ nbr_count, int *counter,
     float *ws_acc, int *ws_cand, int64_t acc_stride) {
-  __shared__ float lds_acc[WS ? 1 : FT_LDS_ITEMS];
-  __shared__ int kid[FT_MAX_K];
-  __shared__ float kw[FT_MAX_K];
-  __shared__ int hist[256];
-  __shared__ int sh[8];          // 0: the row's offset; 1..4: ft_pick's answer; 5: entries gathered; 6: users touched
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  float *acc = WS ? ws_acc + (int64_t)blockIdx.x * acc_stride : lds_acc;
-  int *cand = WS ? ws_cand + (int64_t)blockIdx.x * acc_stride : nullptr;
-
-  auto for_cands = [&](auto f) {
-    if (!WS) {
-      for (int v = tid; v < n_users; v += FT_THREADS) f(v);
-    } else {
-      const int c = sh[6] < acc_stride ? sh[6] : (int)acc_stride;
-      for (int s = tid; s < c; s += FT_THREADS) f(cand[s]);
-    }
-  };
-
-  if (WS)
-    for (int v = tid; v < n_users; v += FT_THREADS) acc[v] = 0.f;
-
-  for (;;) {
-    __syncthreads();
-    if (tid == 0) {
-      sh[0] = atomicAdd(counter, 1);
-      sh[6] = 0;
-    }
-    __syncthreads();
-    const int64_t q64 = (int64_t)row_lo + sh[0];
-    if (q64 >= row_hi) break;
-    const int q = (int)q64;
-    if (!WS) {
-      for (int v = tid; v < n_users; v += FT_THREADS) acc[v] = 0.f;
-      __syncthreads();
-    }
-
-    // ---- accumulate: (row start, row end) of 64 query items at a time; integer adds commute, so who
-    // adds first changes nothing
+  __shared__ FtState<WS> S;
+  FtPass<WS, true> ps(S, n_users, ws_acc, ws_cand, acc_stride, (int)acc_stride);
+  const int lane = ps.lane, wv = ps.wv;
+  float *acc = ps.acc;
+  for (int q; (q = ps.next_row(counter, row_lo, row_hi)) >= 0;) {
+    // ---- accumulate: (row start, row end) of 64 query items at a time
     const int64_t e0 = q_indptr[q], e1 = q_indptr[q + 1];
     for (int64_t eb = e0; eb < e1; eb += 64) {
       const int cnt = e1 - eb < 64 ? (int)(e1 - eb) : 64;
@@ -389,10 +480,10 @@ __global__ __launch_bounds__(FT_THREADS) void rp3_user_neighbours_kernel(
             const unsigned long long m = __ballot(first);
             if (m) {
               int base = 0;
-              if (lane == 0) base = atomicAdd(&sh[6], __popcll(m));
+              if (lane == 0) base = atomicAdd(&S.cnt[0], __popcll(m));
               base = __shfl(base, 0, 64);
               const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-              if (first && pos < acc_stride) cand[pos] = v;
+              if (first && pos < ps.ch) ps.cand[pos] = v;
             }
           } else {
             if (v >= 0) atomicAdd(reinterpret_cast<unsigned int *>(acc + v), 1u);
@@ -400,164 +491,9 @@ __global__ __launch_bounds__(FT_THREADS) void rp3_user_neighbours_kernel(
         }
       }
     }
-    if (tid < 256) hist[tid] = 0;
-    if (tid == 0) sh[5] = 0;
-    if (WS) __threadfence();                   // (the adds were made in L2: nothing of this row is read before them)
-    __syncthreads();
-
-    // ---- scale, and the histogram of the top byte
     const float qs = qn[q];
-    for_cands([&](int v) {
-      // (workspace: the count is read where the atomics made it, past this CU's L1)
-      const uint32_t c = WS ? __hip_atomic_load(reinterpret_cast<unsigned int *>(acc + v), __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT)
-                            : f2u(acc[v]);
-      float w = 0.f;
-      if (c) w = un_sim((float)c, qs, un[v], shrink);
-      acc[v] = w;
-      if (w > 0.f) atomicAdd(&hist[f2u(w) >> 24], 1);
-    });
-    __syncthreads();
-
-    ft_select_store(acc, for_cands, K, n_users, q, nbr_ids, nbr_sim, nbr_count, hist, sh, kid, kw, tid, lane, wv);
-    if (WS)
-      for_cands([&](int v) {
-        __hip_atomic_store(reinterpret_cast<unsigned int *>(acc + v), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      });
-  }
-}
-
-// ------------------------------------------------------------------ item fit
-// s / den, den = (own * oth) + shrink (form 0) or ((own + oth) + (g * s)) + shrink (form 1): every operation a
-// separately rounded f32 operation (see un_sim for the pragma), +0 unless s > 0 and den > 0
-__device__ inline float it_sim(float s, float own, float oth, int form, float g, float shrink) {
-#pragma clang fp contract(off)
-  float den;
-  if (form == 0) {
-    const float prod = own * oth;
-    den = prod + shrink;
-  } else {
-    const float sum = own + oth;
-    const float gs = g * s;
-    const float t = sum + gs;
-    den = t + shrink;
-  }
-  return s > 0.f && den > 0.f ? __fdiv_rn(s, den) : 0.f;
-}
-
-// (rp3_fit_kernel's structure; DATA false: t_data / u_data are not read and every value is 1.0)
-template <bool WS, bool DATA>
-__global__ __launch_bounds__(FT_THREADS) void rp3_item_fit_kernel(
-    const int64_t *__restrict__ t_indptr, const int32_t *__restrict__ t_indices, const float *__restrict__ t_data,
-    const int64_t *__restrict__ u_indptr, const int32_t *__restrict__ u_indices, const float *__restrict__ u_data,
-    int n_users, int n, const float *__restrict__ own, const float *__restrict__ oth, int form, float g,
-    float shrink, int K, int col_lo, int col_hi, int32_t *__restrict__ nbr_ids, float *__restrict__ nbr_w,
-    int32_t *__restrict__ nbr_count, int *counter, float *ws_acc, int *ws_cand, int64_t acc_stride, int ch) {
-  __shared__ float lds_acc[WS ? 1 : FT_LDS_ITEMS];
-  __shared__ int kid[FT_MAX_K];
-  __shared__ float kw[FT_MAX_K];
-  __shared__ int hist[256];
-  __shared__ int wcnt[FT_WAVES];
-  __shared__ int sh[8];          // 0: the column's offset; 1..4: ft_pick's answer; 5: entries gathered
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  float *acc = WS ? ws_acc + (int64_t)blockIdx.x * acc_stride : lds_acc;
-  int *cand = WS ? ws_cand + (int64_t)blockIdx.x * FT_WAVES * ch : nullptr;
-  int *mylist = WS ? cand + (int64_t)wv * ch : nullptr;
-
-  auto for_cands = [&](auto f) {
-    if (!WS) {
-      for (int i = tid; i < n; i += FT_THREADS) f(i);
-    } else {
-#pragma unroll 1
-      for (int w = 0; w < FT_WAVES; ++w) {
-        const int c = wcnt[w];
-        const int *L = cand + (int64_t)w * ch;
-        for (int s = tid; s < c; s += FT_THREADS) f(L[s]);
-      }
-    }
-  };
-
-  if (WS)
-    for (int c = tid; c < n; c += FT_THREADS) acc[c] = -0.f;
-
-  for (;;) {
-    __syncthreads();
-    if (tid == 0) sh[0] = atomicAdd(counter, 1);
-    __syncthreads();
-    const int64_t j64 = (int64_t)col_lo + sh[0];
-    if (j64 >= col_hi) break;
-    const int j = (int)j64;
-    if (!WS) {
-      for (int c = tid; c < n; c += FT_THREADS) acc[c] = 0.f;
-      __syncthreads();
-    }
-
-    // ---- accumulate: (user, row start, row end, the own item's value) fetched 64 at a time
-    int mycnt = 0;
-    const int64_t e0 = t_indptr[j], e1 = t_indptr[j + 1];
-    for (int64_t eb = e0; eb < e1; eb += 64) {
-      const int cnt = e1 - eb < 64 ? (int)(e1 - eb) : 64;
-      int64_t r0 = 0, r1 = 0;
-      float av = 0.f;
-      if (lane < cnt) {
-        const int u = t_indices[eb + lane];
-        if (u >= 0 && u < n_users) {           // (a bad index reads nothing)
-          r0 = u_indptr[u];
-          r1 = u_indptr[u + 1];
-          if (DATA) av = t_data[eb + lane];
-        }
-      }
-      for (int l = 0; l < cnt; ++l) {
-        const int64_t p0 = __shfl(r0, l, 64), p1 = __shfl(r1, l, 64);
-        const float a = DATA ? __shfl(av, l, 64) : 1.f;
-        for (int64_t p = p0; p < p1; p += 64) {       // (wave-uniform bounds)
-          const int64_t q = p + lane;
-          int c = 0;
-          float x = 1.f;
-          bool mine = false;
-          if (q < p1) {
-            c = u_indices[q];
-            mine = c >= 0 && c < n && ((c >> 6) & (FT_WAVES - 1)) == wv;
-            if (DATA && mine) x = u_data[q];
-          }
-          if (WS) {
-            // (rp3_fit_kernel's first touch: a product is >= +0, so fmaf(a, x, +0) is bitwise the chain's start)
-            bool first = false;
-            if (mine) {
-              const float old = acc[c];
-              first = f2u(old) == FT_UNTOUCHED;
-              acc[c] = DATA ? fmaf(a, x, first ? 0.f : old) : (first ? 0.f : old) + 1.f;
-            }
-            const unsigned long long m = __ballot(first);
-            if (first) {
-              const int pos = mycnt + __popcll(m & ((1ull << lane) - 1ull));
-              if (pos < ch) mylist[pos] = c;
-            }
-            mycnt += __popcll(m);
-            __threadfence_block();
-          } else {
-            if (mine) acc[c] = DATA ? fmaf(a, x, acc[c]) : acc[c] + 1.f;
-          }
-        }
-      }
-    }
-    if (WS && lane == 0) wcnt[wv] = mycnt < ch ? mycnt : ch;
-    if (tid < 256) hist[tid] = 0;
-    if (tid == 0) sh[5] = 0;
-    __syncthreads();
-
-    // ---- scale, and the histogram of the top byte
-    const float oj = own[j];
-    for_cands([&](int i) {
-      float w = it_sim(acc[i], oj, oth[i], form, g, shrink);
-      if (i == j) w = 0.f;
-      acc[i] = w;
-      if (w > 0.f) atomicAdd(&hist[f2u(w) >> 24], 1);
-    });
-    __syncthreads();
-
-    ft_select_store(acc, for_cands, K, n, j, nbr_ids, nbr_w, nbr_count, hist, sh, kid, kw, tid, lane, wv);
-    if (WS) for_cands([&](int i) { acc[i] = -0.f; });
+    ps.finish([&](int v, uint32_t c) { return c ? un_sim((float)c, qs, un[v], shrink) : 0.f; }, K, q, nbr_ids, nbr_sim,
+              nbr_count);
   }
 }
 
@@ -566,18 +502,36 @@ constexpr int SC_WAVES = 8;
 constexpr int SC_SUB = 1024;                  // columns a wave owns
 constexpr int SC_TILE = SC_WAVES * SC_SUB;    // 32 KB of LDS
 
+// a scores workgroup's start: the calling wave's columns of the tile (returned) at 0, [wlo, whi) their range
+// in the catalogue (empty past the strip's end)
+__device__ __forceinline__ float *sc_begin(float *tile, int lo, int width, int64_t &wlo, int64_t &whi) {
+  const int t0 = blockIdx.y * SC_TILE;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  wlo = (int64_t)lo + t0 + wv * SC_SUB;
+  whi = wlo + SC_SUB < (int64_t)lo + width ? wlo + SC_SUB : (int64_t)lo + width;
+  float *mine = tile + wv * SC_SUB;
+  for (int c = lane; c < SC_SUB; c += 64) mine[c] = 0.f;
+  return mine;
+}
+
+// ... and its end: the tile's columns inside the strip written to row ``r`` of out
+__device__ __forceinline__ void sc_store(const float *tile, int r, int width, float *__restrict__ out, int64_t ldo) {
+  __syncthreads();
+  const int t0 = blockIdx.y * SC_TILE;
+  const int w = width - t0 < SC_TILE ? width - t0 : SC_TILE;
+  float *row = out + (int64_t)r * ldo + t0;
+  for (int c = threadIdx.x; c < w; c += SC_WAVES * 64) row[c] = tile[c];
+}
+
 __global__ __launch_bounds__(SC_WAVES * 64) void rp3_scores_kernel(
     const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const float *__restrict__ data,
     int n_items, const int32_t *__restrict__ nbr_ids, const float *__restrict__ nbr_w,
     const int32_t *__restrict__ nbr_count, int K, int lo, int width, float *__restrict__ out, int64_t ldo) {
   __shared__ float tile[SC_TILE];
   const int u = blockIdx.x;                             // (users fastest: neighbours share a column tile)
-  const int t0 = blockIdx.y * SC_TILE;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t wlo = (int64_t)lo + t0 + wv * SC_SUB;
-  const int64_t whi = wlo + SC_SUB < (int64_t)lo + width ? wlo + SC_SUB : (int64_t)lo + width;
-  float *mine = tile + wv * SC_SUB;
-  for (int c = lane; c < SC_SUB; c += 64) mine[c] = 0.f;
+  const int lane = threadIdx.x & 63;
+  int64_t wlo, whi;
+  float *mine = sc_begin(tile, lo, width, wlo, whi);
   if (wlo < whi) {
     const int64_t e0 = indptr[u], e1 = indptr[u + 1];
     for (int64_t eb = e0; eb < e1; eb += 64) {
@@ -603,10 +557,7 @@ __global__ __launch_bounds__(SC_WAVES * 64) void rp3_scores_kernel(
       }
     }
   }
-  __syncthreads();
-  const int w = width - t0 < SC_TILE ? width - t0 : SC_TILE;
-  float *row = out + (int64_t)u * ldo + t0;
-  for (int c = threadIdx.x; c < w; c += SC_WAVES * 64) row[c] = tile[c];
+  sc_store(tile, u, width, out, ldo);
 }
 
 // first position in [a, b) of the ascending idx whose value is >= key
@@ -624,12 +575,9 @@ __global__ __launch_bounds__(SC_WAVES * 64) void rp3_user_scores_kernel(
     int n_users, int lo, int width, float *__restrict__ out, int64_t ldo) {
   __shared__ float tile[SC_TILE];
   const int q = blockIdx.x;                             // (queries fastest: neighbours' rows are shared)
-  const int t0 = blockIdx.y * SC_TILE;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t wlo = (int64_t)lo + t0 + wv * SC_SUB;
-  const int64_t whi = wlo + SC_SUB < (int64_t)lo + width ? wlo + SC_SUB : (int64_t)lo + width;
-  float *mine = tile + wv * SC_SUB;
-  for (int c = lane; c < SC_SUB; c += 64) mine[c] = 0.f;
+  const int lane = threadIdx.x & 63;
+  int64_t wlo, whi;
+  float *mine = sc_begin(tile, lo, width, wlo, whi);
   if (wlo < whi) {
     int nc = nbr_count[q];
     nc = nc < 0 ? 0 : (nc > K ? K : nc);
@@ -657,10 +605,39 @@ __global__ __launch_bounds__(SC_WAVES * 64) void rp3_user_scores_kernel(
       }
     }
   }
-  __syncthreads();
-  const int w = width - t0 < SC_TILE ? width - t0 : SC_TILE;
-  float *row = out + (int64_t)q * ldo + t0;
-  for (int c = threadIdx.x; c < w; c += SC_WAVES * 64) row[c] = tile[c];
+  sc_store(tile, q, width, out, ldo);
+}
+
+// What the three fits do on the host after their own argument checks (fn: the entry point, for the
+// messages; n: the accumulators of a row; need: the entry point's workspace bytes): the workspace checks,
+// nothing for an empty range, the counter at 0, then launch(kernel, groups, counter, acc, cand, stride, ch)
+// with the LDS form (no accumulators in the workspace) or with the workspace form, whose accumulator rows
+// and candidate lists follow the counter's 256 bytes.
+template <class Kernel, class Launch>
+int ft_run(const char *fn, const char *kernel_name, Kernel lds_form, Kernel ws_form, int n, int lo, int hi, void *ws,
+           int64_t ws_bytes, int64_t need, hipStream_t s, Launch launch) {
+  const char *bad = ws_bytes < need ? "workspace too small"
+                    : (reinterpret_cast<uintptr_t>(ws) & 255) != 0 ? "workspace must be 256-byte aligned" : nullptr;
+  if (bad) {
+    rk_side_set_error("%s: %s", fn, bad);
+    return -2;
+  }
+  if (lo == hi) return 0;
+  int *counter = (int *)ws;
+  if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
+    rk_side_set_error("%s: hipMemsetAsync failed", fn);
+    return -1;
+  }
+  const int groups = hi - lo < FT_GROUPS ? hi - lo : FT_GROUPS;
+  if (n <= FT_LDS_ITEMS) {
+    launch(lds_form, groups, counter, (float *)nullptr, (int *)nullptr, (int64_t)0, 0);
+  } else {
+    const int64_t stride = ft_acc_stride(n);
+    float *acc = (float *)((char *)ws + 256);
+    launch(ws_form, groups, counter, acc, (int *)(acc + (int64_t)FT_GROUPS * stride), stride, (int)ft_list_stride(n));
+  }
+  RK_SIDE_CHECK_LAUNCH(kernel_name);
+  return 0;
 }
 
 }  // namespace
@@ -694,31 +671,14 @@ int rk_rp3_fit(const int64_t *t_indptr, const int32_t *t_indices, const int64_t 
   RK_SIDE_REQUIRE(n_users >= 0 && n_items >= 1 && n_items < INT_MAX - 2048, "bad sizes");
   RK_SIDE_REQUIRE(K >= 1 && K <= FT_MAX_K, "K outside [1, rk_rp3_max_neighbours()]");
   RK_SIDE_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= n_items, "bad row range");
-  RK_SIDE_REQUIRE(ws_bytes >= rk_rp3_fit_workspace_bytes(n_items), "workspace too small");
-  RK_SIDE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
-  if (row_lo == row_hi) return 0;
   hipStream_t s = (hipStream_t)stream;
-  int *counter = (int *)ws;
-  if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
-    rk_side_set_error("%s: hipMemsetAsync failed", __func__);
-    return -1;
-  }
-  const int rows = row_hi - row_lo;
-  const int groups = rows < FT_GROUPS ? rows : FT_GROUPS;
-  if (n_items <= FT_LDS_ITEMS) {
-    hipLaunchKernelGGL(rp3_fit_kernel<false>, dim3(groups), dim3(FT_THREADS), 0, s, t_indptr, t_indices, u_indptr,
-                       u_indices, n_users, n_items, user_w, row_scale, col_scale, K, row_lo, row_hi, nbr_ids, nbr_w,
-                       nbr_count, counter, (float *)nullptr, (int *)nullptr, (int64_t)0, 0);
-  } else {
-    const int64_t stride = ft_acc_stride(n_items), ch = ft_list_stride(n_items);
-    float *acc = (float *)((char *)ws + 256);
-    int *cand = (int *)(acc + (int64_t)FT_GROUPS * stride);
-    hipLaunchKernelGGL(rp3_fit_kernel<true>, dim3(groups), dim3(FT_THREADS), 0, s, t_indptr, t_indices, u_indptr,
-                       u_indices, n_users, n_items, user_w, row_scale, col_scale, K, row_lo, row_hi, nbr_ids, nbr_w,
-                       nbr_count, counter, acc, cand, stride, (int)ch);
-  }
-  RK_SIDE_CHECK_LAUNCH("rp3_fit_kernel");
-  return 0;
+  return ft_run(__func__, "rp3_fit_kernel", rp3_fit_kernel<false>, rp3_fit_kernel<true>, n_items, row_lo, row_hi, ws,
+                ws_bytes, rk_rp3_fit_workspace_bytes(n_items), s,
+                [&](auto kernel, int groups, int *counter, float *acc, int *cand, int64_t stride, int ch) {
+                  hipLaunchKernelGGL(kernel, dim3(groups), dim3(FT_THREADS), 0, s, t_indptr, t_indices, u_indptr,
+                                     u_indices, n_users, n_items, user_w, row_scale, col_scale, K, row_lo, row_hi,
+                                     nbr_ids, nbr_w, nbr_count, counter, acc, cand, stride, ch);
+                });
 }
 
 int64_t rk_rp3_item_workspace_bytes(int32_t n_items) {
@@ -743,33 +703,17 @@ int rk_rp3_item_fit(const int64_t *t_indptr, const int32_t *t_indices, const flo
   RK_SIDE_REQUIRE(shrink >= 0.f && shrink <= 3.0e38f, "shrink must be finite and >= 0");
   RK_SIDE_REQUIRE(K >= 1 && K <= FT_MAX_K, "K outside [1, rk_rp3_max_neighbours()]");
   RK_SIDE_REQUIRE(0 <= col_lo && col_lo <= col_hi && col_hi <= n_items, "bad column range");
-  RK_SIDE_REQUIRE(ws_bytes >= rk_rp3_item_workspace_bytes(n_items), "workspace too small");
-  RK_SIDE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
-  if (col_lo == col_hi) return 0;
   hipStream_t s = (hipStream_t)stream;
-  int *counter = (int *)ws;
-  if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
-    rk_side_set_error("%s: hipMemsetAsync failed", __func__);
-    return -1;
-  }
-  const int cols = col_hi - col_lo;
-  const int groups = cols < FT_GROUPS ? cols : FT_GROUPS;
   const bool data = t_data != nullptr;
-  auto launch = [&](auto kernel, float *acc, int *cand, int64_t stride, int ch) {
-    hipLaunchKernelGGL(kernel, dim3(groups), dim3(FT_THREADS), 0, s, t_indptr, t_indices, t_data, u_indptr, u_indices,
-                       u_data, n_users, n_items, own, oth, form, g, shrink, K, col_lo, col_hi, nbr_ids, nbr_w, nbr_count,
-                       counter, acc, cand, stride, ch);
-  };
-  if (n_items <= FT_LDS_ITEMS) {
-    launch(data ? rp3_item_fit_kernel<false, true> : rp3_item_fit_kernel<false, false>, nullptr, nullptr, 0, 0);
-  } else {
-    const int64_t stride = ft_acc_stride(n_items), ch = ft_list_stride(n_items);
-    float *acc = (float *)((char *)ws + 256);
-    launch(data ? rp3_item_fit_kernel<true, true> : rp3_item_fit_kernel<true, false>, acc,
-           (int *)(acc + (int64_t)FT_GROUPS * stride), stride, (int)ch);
-  }
-  RK_SIDE_CHECK_LAUNCH("rp3_item_fit_kernel");
-  return 0;
+  return ft_run(__func__, "rp3_item_fit_kernel",
+                data ? rp3_item_fit_kernel<false, true> : rp3_item_fit_kernel<false, false>,
+                data ? rp3_item_fit_kernel<true, true> : rp3_item_fit_kernel<true, false>, n_items, col_lo, col_hi, ws,
+                ws_bytes, rk_rp3_item_workspace_bytes(n_items), s,
+                [&](auto kernel, int groups, int *counter, float *acc, int *cand, int64_t stride, int ch) {
+                  hipLaunchKernelGGL(kernel, dim3(groups), dim3(FT_THREADS), 0, s, t_indptr, t_indices, t_data,
+                                     u_indptr, u_indices, u_data, n_users, n_items, own, oth, form, g, shrink, K, col_lo,
+                                     col_hi, nbr_ids, nbr_w, nbr_count, counter, acc, cand, stride, ch);
+                });
 }
 
 int rk_rp3_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
@@ -807,31 +751,15 @@ int rk_rp3_user_neighbours(const int64_t *q_indptr, const int32_t *q_indices, co
   RK_SIDE_REQUIRE(N >= 1 && N <= FT_MAX_K, "N outside [1, rk_rp3_max_neighbours()]");
   RK_SIDE_REQUIRE(shrink >= 0.f && shrink <= 3.0e38f, "shrink must be finite and >= 0");
   RK_SIDE_REQUIRE(0 <= row_lo && row_lo <= row_hi, "bad row range");
-  RK_SIDE_REQUIRE(ws_bytes >= rk_rp3_user_workspace_bytes(n_users), "workspace too small");
-  RK_SIDE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
-  if (row_lo == row_hi) return 0;
   hipStream_t s = (hipStream_t)stream;
-  int *counter = (int *)ws;
-  if (hipMemsetAsync(counter, 0, sizeof(int), s) != hipSuccess) {
-    rk_side_set_error("%s: hipMemsetAsync failed", __func__);
-    return -1;
-  }
-  const int rows = row_hi - row_lo;
-  const int groups = rows < FT_GROUPS ? rows : FT_GROUPS;
-  if (n_users <= FT_LDS_ITEMS) {
-    hipLaunchKernelGGL(rp3_user_neighbours_kernel<false>, dim3(groups), dim3(FT_THREADS), 0, s, q_indptr, q_indices,
-                       t_indptr, t_indices, n_users, n_items, un, qn, shrink, N, row_lo, row_hi, nbr_ids, nbr_sim,
-                       nbr_count, counter, (float *)nullptr, (int *)nullptr, (int64_t)0);
-  } else {
-    const int64_t stride = ft_acc_stride(n_users);
-    float *acc = (float *)((char *)ws + 256);
-    int *cand = (int *)(acc + (int64_t)FT_GROUPS * stride);
-    hipLaunchKernelGGL(rp3_user_neighbours_kernel<true>, dim3(groups), dim3(FT_THREADS), 0, s, q_indptr, q_indices,
-                       t_indptr, t_indices, n_users, n_items, un, qn, shrink, N, row_lo, row_hi, nbr_ids, nbr_sim,
-                       nbr_count, counter, acc, cand, stride);
-  }
-  RK_SIDE_CHECK_LAUNCH("rp3_user_neighbours_kernel");
-  return 0;
+  return ft_run(__func__, "rp3_user_neighbours_kernel", rp3_user_neighbours_kernel<false>,
+                rp3_user_neighbours_kernel<true>, n_users, row_lo, row_hi, ws, ws_bytes,
+                rk_rp3_user_workspace_bytes(n_users), s,
+                [&](auto kernel, int groups, int *counter, float *acc, int *cand, int64_t stride, int) {
+                  hipLaunchKernelGGL(kernel, dim3(groups), dim3(FT_THREADS), 0, s, q_indptr, q_indices, t_indptr,
+                                     t_indices, n_users, n_items, un, qn, shrink, N, row_lo, row_hi, nbr_ids, nbr_sim,
+                                     nbr_count, counter, acc, cand, stride);      // (one list of stride entries)
+                });
 }
 
 int rk_rp3_user_scores(const int32_t *nbr_ids, const float *nbr_sim, const int32_t *nbr_count, int32_t n_rows,

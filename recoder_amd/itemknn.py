@@ -25,15 +25,13 @@ runs on the device.
 ``Recoder.train_itemknn`` is the public entry point; the functions below are the layer under it (and what the
 tests and tools/itemknn_bench.py drive directly).
 """
-import math
-
 import numpy as np
 import scipy.sparse as sp
 import torch
 
 from . import _neighbours, _rp3_lib, _slim_lib, als
 from ._lib import ptr
-from .device import DEVICE_HBM_BYTES, current_stream
+from .device import current_stream
 from .rp3 import LDS_ITEMS, MAX_NEIGHBOURS      # rk_rp3_lds_items(), rk_rp3_max_neighbours()
 from .rp3 import workspace_bytes                # (rk_rp3_item_workspace_bytes is rk_rp3_fit_workspace_bytes)
 
@@ -57,19 +55,12 @@ def check_config(model, neighbours, shrink, similarity, feature_weighting):
                       model.tversky_alpha, model.tversky_beta)
 
 
-def _number(name, v, lo=0.0, hi=math.inf):
-  if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
-      not (math.isfinite(float(v)) and lo <= float(v) <= hi):
-    raise ValueError("%s must be finite and %s (got %r)" % (name, ">= 0" if hi == math.inf else
-                                                            "in [%g, %g]" % (lo, hi), v))
-  return float(v)
-
-
 def check_params(neighbours, shrink, similarity="cosine", feature_weighting="none", asymmetric_alpha=0.5,
                  tversky_alpha=1.0, tversky_beta=1.0):
   """(neighbours, shrink, similarity, feature_weighting, asymmetric_alpha, tversky_alpha, tversky_beta), checked."""
   K = _neighbours.check_neighbours(neighbours, MAX_NEIGHBOURS)
-  shrink = _number("shrink", shrink)
+  number = _neighbours.check_number
+  shrink = number("shrink", shrink)
   if similarity not in SIMILARITIES:
     raise ValueError("similarity must be one of %s (got %r)" % (", ".join(SIMILARITIES), similarity))
   if feature_weighting not in FEATURE_WEIGHTINGS:
@@ -78,8 +69,8 @@ def check_params(neighbours, shrink, similarity="cosine", feature_weighting="non
   if similarity in SET_SIMILARITIES and feature_weighting != "none":
     raise ValueError("the %s similarity is over item sets, on the binary matrix: feature_weighting %r has nothing "
                      "to weigh (use \"none\")" % (similarity, feature_weighting))
-  return (K, shrink, similarity, feature_weighting, _number("asymmetric_alpha", asymmetric_alpha, 0.0, 1.0),
-          _number("tversky_alpha", tversky_alpha), _number("tversky_beta", tversky_beta))
+  return (K, shrink, similarity, feature_weighting, number("asymmetric_alpha", asymmetric_alpha, 0.0, 1.0),
+          number("tversky_alpha", tversky_alpha), number("tversky_beta", tversky_beta))
 
 
 def check_values(host):
@@ -146,20 +137,12 @@ def check_memory(n_users, n_items, K, nnz, free_bytes=None, allocate_model=True)
   n_users, n, K, nnz = int(n_users), int(n_items), int(K), int(nnz)
   if n < 1:
     raise ValueError("ItemKNN needs at least one item (got n = %d)" % n)
-  whole = required_bytes(n_users, n, K, nnz, True)
-  if whole > DEVICE_HBM_BYTES:
-    raise ValueError("ItemKNN over %d users x %d items with %d neighbours and %d entries needs %d bytes: more "
-                     "than one device's memory (%d bytes); multi-device fits are not implemented"
-                     % (n_users, n, K, nnz, whole, DEVICE_HBM_BYTES))
-  if n * K >= 2 ** 40:
-    raise ValueError("ItemKNN over n = %d items with %d neighbours is outside the kernels' index range" % (n, K))
-  need = required_bytes(n_users, n, K, nnz, allocate_model)
-  if free_bytes is None:
-    free_bytes = torch.cuda.mem_get_info()[0]
-  if need > free_bytes:
-    raise ValueError("ItemKNN over %d users x %d items with %d neighbours and %d entries needs %d bytes of "
-                     "device memory, %d are free" % (n_users, n, K, nnz, need, free_bytes))
-  return need
+  what = "ItemKNN over %(users)d users x %(n)d items with %(K)d neighbours and %(nnz)d entries needs %(need)d bytes"
+  return _neighbours.check_memory(
+      lambda allocate: required_bytes(n_users, n, K, nnz, allocate), dict(users=n_users, n=n, K=K, nnz=nnz),
+      what + ": more than one device's memory (%(hbm)d bytes); multi-device fits are not implemented",
+      what + " of device memory, %(free)d are free", free_bytes, allocate_model,
+      "ItemKNN over n = %(n)d items with %(K)d neighbours is outside the kernels' index range")
 
 
 # ------------------------------------------------------------------ kernels
@@ -172,15 +155,11 @@ def fit_columns(ucsr, icsr, u_data, t_data, own, oth, form, g, shrink, ids, w, c
   assert icsr.shape == (n, n_users)
   K = ids.shape[1]
   col_hi = n if col_hi is None else col_hi
-  assert ids.shape == (n, K) and ids.dtype == torch.int32 and ids.is_contiguous()
-  assert w.shape == (n, K) and w.dtype == torch.float32 and w.is_contiguous()
-  assert count.shape == (n,) and count.dtype == torch.int32
+  _neighbours.lists(n, K, ids.device, (ids, w, count))
   assert own.shape == (n,) and oth.shape == (n,) and own.dtype == oth.dtype == torch.float32
   for d in (u_data, t_data):
     assert d is None or (d.dtype == torch.float32 and d.numel() >= ucsr.nnz and d.is_contiguous())
-  need = lib.rk_rp3_item_workspace_bytes(n)
-  if ws is None or ws.numel() < need:
-    ws = torch.empty(need, dtype=torch.uint8, device=ids.device)
+  ws = _neighbours.workspace(ws, lib.rk_rp3_item_workspace_bytes(n), ids.device)
   _rp3_lib.check(lib.rk_rp3_item_fit(ptr(icsr.indptr), ptr(icsr.indices), ptr(t_data), ptr(ucsr.indptr),
                                      ptr(ucsr.indices), ptr(u_data), n_users, n, ptr(own), ptr(oth), int(form),
                                      float(g), float(shrink), K, col_lo, col_hi, ptr(ids), ptr(w), ptr(count),
@@ -233,16 +212,9 @@ def fit(csr_pair, neighbours, shrink, similarity="cosine", feature_weighting="no
   if u_data is not None:
     u_data, t_data = torch.from_numpy(u_data).to(dev), torch.from_numpy(t_data).to(dev)
   own, oth = torch.from_numpy(own).to(dev), torch.from_numpy(oth).to(dev)
-  if out is None:
-    out = (torch.empty(n, K, dtype=torch.int32, device=dev), torch.empty(n, K, dtype=torch.float32, device=dev),
-           torch.empty(n, dtype=torch.int32, device=dev))
-  ids, w, count = out
-  ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-  ev[0].record()
-  fit_columns(ucsr, icsr, u_data, t_data, own, oth, form, g, shrink, ids, w, count)
-  ev[1].record()
-  kept = int(count.sum(dtype=torch.int64).item())      # (the synchronisation)
-  ev[1].synchronize()
+  ids, w, count = _neighbours.lists(n, K, dev, out)
+  kept, fit_ms = _neighbours.timed_fit(
+      lambda: fit_columns(ucsr, icsr, u_data, t_data, own, oth, form, g, shrink, ids, w, count), count)
   info = dict(n=int(n), nnz=int(ucsr.nnz), neighbours=K, shrink=shrink, similarity=similarity,
-              feature_weighting=feature_weighting, kept=kept, fit_ms=ev[0].elapsed_time(ev[1]))
+              feature_weighting=feature_weighting, kept=kept, fit_ms=fit_ms)
   return ids, w, count, info

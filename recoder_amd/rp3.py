@@ -14,14 +14,12 @@ anywhere, so catalogues ``ShallowAutoencoder`` refuses fit.
 ``Recoder.train_rp3beta`` is the public entry point; the functions below are the layer under it (and
 what the tests and tools/rp3_bench.py drive directly).
 """
-import math
-
 import numpy as np
 import torch
 
 from . import _neighbours, _rp3_lib, als
 from ._lib import ptr
-from .device import DEVICE_HBM_BYTES, current_stream
+from .device import DEVICE_HBM_BYTES, current_stream  # noqa: F401 (the bound of check_memory, for callers)
 
 MAX_NEIGHBOURS = 1024      # rk_rp3_max_neighbours()
 LDS_ITEMS = 12288          # rk_rp3_lds_items()
@@ -41,11 +39,8 @@ def check_config(model, alpha, beta, neighbours):
 
 
 def check_params(alpha, beta, neighbours):
-  for name, v in (("alpha", alpha), ("beta", beta)):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
-        not (math.isfinite(float(v)) and float(v) >= 0):
-      raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
-  return float(alpha), float(beta), _neighbours.check_neighbours(neighbours, MAX_NEIGHBOURS)
+  return (_neighbours.check_number("alpha", alpha), _neighbours.check_number("beta", beta),
+          _neighbours.check_neighbours(neighbours, MAX_NEIGHBOURS))
 
 
 def _power(x, e):
@@ -88,20 +83,12 @@ def check_memory(n_users, n_items, K, nnz, free_bytes=None, allocate_model=True)
   n_users, n, K, nnz = int(n_users), int(n_items), int(K), int(nnz)
   if n < 1:
     raise ValueError("RP3beta needs at least one item (got n = %d)" % n)
-  whole = required_bytes(n_users, n, K, nnz, True)
-  if whole > DEVICE_HBM_BYTES:
-    raise ValueError("RP3beta over %d users x %d items with %d neighbours and %d entries needs %d bytes: more "
-                     "than one device's memory (%d bytes); multi-device fits are not implemented"
-                     % (n_users, n, K, nnz, whole, DEVICE_HBM_BYTES))
-  if n * K >= 2 ** 40:
-    raise ValueError("RP3beta over n = %d items with %d neighbours is outside the kernels' index range" % (n, K))
-  need = required_bytes(n_users, n, K, nnz, allocate_model)
-  if free_bytes is None:
-    free_bytes = torch.cuda.mem_get_info()[0]
-  if need > free_bytes:
-    raise ValueError("RP3beta over %d users x %d items with %d neighbours and %d entries needs %d bytes of "
-                     "device memory, %d are free" % (n_users, n, K, nnz, need, free_bytes))
-  return need
+  what = "RP3beta over %(users)d users x %(n)d items with %(K)d neighbours and %(nnz)d entries needs %(need)d bytes"
+  return _neighbours.check_memory(
+      lambda allocate: required_bytes(n_users, n, K, nnz, allocate), dict(users=n_users, n=n, K=K, nnz=nnz),
+      what + ": more than one device's memory (%(hbm)d bytes); multi-device fits are not implemented",
+      what + " of device memory, %(free)d are free", free_bytes, allocate_model,
+      "RP3beta over n = %(n)d items with %(K)d neighbours is outside the kernels' index range")
 
 
 # ------------------------------------------------------------------ kernels
@@ -112,13 +99,9 @@ def fit_rows(ucsr, icsr, user_w, row_scale, col_scale, ids, w, count, row_lo=0, 
   assert icsr.shape == (n, n_users)
   K = ids.shape[1]
   row_hi = n if row_hi is None else row_hi
-  assert ids.shape == (n, K) and ids.dtype == torch.int32 and ids.is_contiguous()
-  assert w.shape == (n, K) and w.dtype == torch.float32 and w.is_contiguous()
-  assert count.shape == (n,) and count.dtype == torch.int32
+  _neighbours.lists(n, K, ids.device, (ids, w, count))
   assert user_w.shape == (n_users,) and row_scale.shape == (n,) and col_scale.shape == (n,)
-  need = lib.rk_rp3_fit_workspace_bytes(n)
-  if ws is None or ws.numel() < need:
-    ws = torch.empty(need, dtype=torch.uint8, device=ids.device)
+  ws = _neighbours.workspace(ws, lib.rk_rp3_fit_workspace_bytes(n), ids.device)
   _rp3_lib.check(lib.rk_rp3_fit(ptr(icsr.indptr), ptr(icsr.indices), ptr(ucsr.indptr), ptr(ucsr.indices),
                                 n_users, n, ptr(user_w), ptr(row_scale), ptr(col_scale), K, row_lo, row_hi,
                                 ptr(ids), ptr(w), ptr(count), ptr(ws), ws.numel(), current_stream()),
@@ -154,16 +137,7 @@ def fit(csr_pair, alpha, beta, neighbours, out=None):
   check_memory(n_users, n, K, ucsr.nnz, allocate_model=out is None)
   dev = ucsr.indptr.device
   uw, rs, cs = (torch.from_numpy(a).to(dev) for a in host_weights(csr_pair, alpha, beta))
-  if out is None:
-    out = (torch.empty(n, K, dtype=torch.int32, device=dev), torch.empty(n, K, dtype=torch.float32, device=dev),
-           torch.empty(n, dtype=torch.int32, device=dev))
-  ids, w, count = out
-  ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-  ev[0].record()
-  fit_rows(ucsr, icsr, uw, rs, cs, ids, w, count)
-  ev[1].record()
-  kept = int(count.sum(dtype=torch.int64).item())      # (the synchronisation)
-  ev[1].synchronize()
-  info = dict(n=int(n), nnz=int(ucsr.nnz), alpha=alpha, beta=beta, neighbours=K, kept=kept,
-              fit_ms=ev[0].elapsed_time(ev[1]))
+  ids, w, count = _neighbours.lists(n, K, dev, out)
+  kept, fit_ms = _neighbours.timed_fit(lambda: fit_rows(ucsr, icsr, uw, rs, cs, ids, w, count), count)
+  info = dict(n=int(n), nnz=int(ucsr.nnz), alpha=alpha, beta=beta, neighbours=K, kept=kept, fit_ms=fit_ms)
   return ids, w, count, info

@@ -16,14 +16,12 @@ divided by U:  l1_reg = U * alpha * l1_ratio,  l2_reg = U * alpha * (1 - l1_rati
 ``Recoder.train_slim`` is the public entry point; the functions below are the layer under it (and what
 the tests and tools/slim_bench.py drive directly).
 """
-import math
-
 import numpy as np
 import torch
 
 from . import _neighbours, _slim_lib, als
 from ._lib import ptr
-from .device import DEVICE_HBM_BYTES, current_stream
+from .device import current_stream
 
 MAX_NEIGHBOURS = 1024      # rk_slim_max_neighbours()
 LDS_CANDIDATES = 960       # rk_slim_lds_candidates()
@@ -43,14 +41,12 @@ def check_config(model, l1_reg, l2_reg, neighbours, max_sweeps=50, tol=1e-5):
 
 
 def check_params(l1_reg, l2_reg, neighbours, max_sweeps=50, tol=1e-5):
-  for name, v in (("l1_reg", l1_reg), ("l2_reg", l2_reg), ("tol", tol)):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
-        not (math.isfinite(float(v)) and float(v) >= 0):
-      raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
+  l1_reg, l2_reg, tol = (_neighbours.check_number(name, v) for name, v in
+                         (("l1_reg", l1_reg), ("l2_reg", l2_reg), ("tol", tol)))
   neighbours = _neighbours.check_neighbours(neighbours, MAX_NEIGHBOURS)
   if isinstance(max_sweeps, bool) or not isinstance(max_sweeps, (int, np.integer)) or not 1 <= max_sweeps < 2 ** 31:
     raise ValueError("max_sweeps must be an integer >= 1 (got %r)" % (max_sweeps,))
-  return float(l1_reg), float(l2_reg), neighbours, int(max_sweeps), float(tol)
+  return l1_reg, l2_reg, neighbours, int(max_sweeps), tol
 
 
 def check_values(host):
@@ -95,20 +91,13 @@ def check_memory(n_users, n_items, K, nnz, free_bytes=None, allocate_model=True)
   n_users, n, K, nnz = int(n_users), int(n_items), int(K), int(nnz)
   if n < 1:
     raise ValueError("SLIM needs at least one item (got n = %d)" % n)
-  whole = required_bytes(n_users, n, K, nnz, True)
-  if whole > DEVICE_HBM_BYTES:
-    raise ValueError("SLIM over %d users x %d items with %d neighbours and %d entries needs %d bytes, %d of them "
-                     "for its n x n fp32 Gram (the limit EASE has): more than one device's memory (%d bytes); "
-                     "multi-device fits are not implemented"
-                     % (n_users, n, K, nnz, whole, n * n * 4, DEVICE_HBM_BYTES))
-  need = required_bytes(n_users, n, K, nnz, allocate_model)
-  if free_bytes is None:
-    free_bytes = torch.cuda.mem_get_info()[0]
-  if need > free_bytes:
-    raise ValueError("SLIM over %d users x %d items with %d neighbours and %d entries needs %d bytes of device "
-                     "memory (%d for the n x n Gram), %d are free"
-                     % (n_users, n, K, nnz, need, n * n * 4, free_bytes))
-  return need
+  what = "SLIM over %(users)d users x %(n)d items with %(K)d neighbours and %(nnz)d entries needs %(need)d bytes"
+  return _neighbours.check_memory(
+      lambda allocate: required_bytes(n_users, n, K, nnz, allocate),
+      dict(users=n_users, n=n, K=K, nnz=nnz, gram=n * n * 4),
+      what + ", %(gram)d of them for its n x n fp32 Gram (the limit EASE has): more than one device's memory "
+      "(%(hbm)d bytes); multi-device fits are not implemented",
+      what + " of device memory (%(gram)d for the n x n Gram), %(free)d are free", free_bytes, allocate_model)
 
 
 # ------------------------------------------------------------------ kernels
@@ -122,13 +111,10 @@ def fit_columns(G, inv, l1_reg, ids, w, count, sweeps, support, max_sweeps=50, t
   col_hi = n if col_hi is None else col_hi
   assert G.shape == (n, n) and G.dtype == torch.float32 and G.stride(1) == 1
   assert inv.shape == (n,) and inv.dtype == torch.float32
-  assert ids.shape == (n, K) and ids.dtype == torch.int32 and ids.is_contiguous()
-  assert w.shape == (n, K) and w.dtype == torch.float32 and w.is_contiguous()
-  for t in (count, sweeps, support):
+  _neighbours.lists(n, K, ids.device, (ids, w, count))
+  for t in (sweeps, support):
     assert t.shape == (n,) and t.dtype == torch.int32
-  need = lib.rk_slim_fit_workspace_bytes(n)
-  if ws is None or ws.numel() < need:
-    ws = torch.empty(need, dtype=torch.uint8, device=ids.device)
+  ws = _neighbours.workspace(ws, lib.rk_slim_fit_workspace_bytes(n), ids.device)
   _slim_lib.check(lib.rk_slim_fit(ptr(G), G.stride(0), n, ptr(inv), float(l1_reg), K, int(max_sweeps), float(tol),
                                   col_lo, col_hi, ptr(ids), ptr(w), ptr(count), ptr(sweeps), ptr(support),
                                   ptr(ws), ws.numel(), current_stream()), "rk_slim_fit")
@@ -158,10 +144,7 @@ def fit(csr_pair, l1_reg, l2_reg, neighbours, max_sweeps=50, tol=1e-5, out=None)
   n_users, n = ucsr.shape
   check_memory(n_users, n, K, ucsr.nnz, allocate_model=out is None)
   dev = ucsr.indptr.device
-  if out is None:
-    out = (torch.empty(n, K, dtype=torch.int32, device=dev), torch.empty(n, K, dtype=torch.float32, device=dev),
-           torch.empty(n, dtype=torch.int32, device=dev))
-  ids, w, count = out
+  ids, w, count = _neighbours.lists(n, K, dev, out)
   sweeps = torch.empty(n, dtype=torch.int32, device=dev)
   support = torch.empty(n, dtype=torch.int32, device=dev)
   ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]

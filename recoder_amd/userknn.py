@@ -17,14 +17,12 @@ one of the slots and contributes only items that the masked top-k removes.
 ``Recoder.train_userknn`` is the public entry point; the functions below are the layer under it (and what
 the tests and tools/userknn_bench.py drive directly).
 """
-import math
-
 import numpy as np
 import torch
 
 from . import _neighbours, _rp3_lib, als
 from ._lib import ptr
-from .device import DEVICE_HBM_BYTES, current_stream
+from .device import current_stream
 from .rp3 import LDS_ITEMS as LDS_USERS      # rk_rp3_lds_items(): the users whose counts live in LDS
 from .rp3 import MAX_NEIGHBOURS              # rk_rp3_max_neighbours()
 
@@ -45,10 +43,8 @@ def check_config(model, neighbours, shrink):
 
 
 def check_params(neighbours, shrink):
-  if isinstance(shrink, bool) or not isinstance(shrink, (int, float, np.integer, np.floating)) or \
-      not (math.isfinite(float(shrink)) and float(shrink) >= 0):
-    raise ValueError("shrink must be finite and >= 0 (got %r)" % (shrink,))
-  return _neighbours.check_neighbours(neighbours, MAX_NEIGHBOURS), float(shrink)
+  shrink = _neighbours.check_number("shrink", shrink)
+  return _neighbours.check_neighbours(neighbours, MAX_NEIGHBOURS), shrink
 
 
 def norms(lengths):
@@ -82,17 +78,11 @@ def check_memory(n_users, n_items, N, nnz, free_bytes=None):
   U, n, N, nnz = int(n_users), int(n_items), int(N), int(nnz)
   if U < 1 or n < 1:
     raise ValueError("UserKNN needs at least one user and one item (got %d users x %d items)" % (U, n))
-  need = required_bytes(U, n, N, nnz)
-  if need > DEVICE_HBM_BYTES:
-    raise ValueError("UserKNN over %d users x %d items with %d neighbours and %d entries needs %d bytes: more "
-                     "than one device's memory (%d bytes); multi-device serving is not implemented"
-                     % (U, n, N, nnz, need, DEVICE_HBM_BYTES))
-  if free_bytes is None:
-    free_bytes = torch.cuda.mem_get_info()[0]
-  if need > free_bytes:
-    raise ValueError("UserKNN over %d users x %d items with %d neighbours and %d entries needs %d bytes of "
-                     "device memory, %d are free" % (U, n, N, nnz, need, free_bytes))
-  return need
+  what = "UserKNN over %(users)d users x %(n)d items with %(K)d neighbours and %(nnz)d entries needs %(need)d bytes"
+  return _neighbours.check_memory(
+      lambda allocate: required_bytes(U, n, N, nnz), dict(users=U, n=n, K=N, nnz=nnz),
+      what + ": more than one device's memory (%(hbm)d bytes); multi-device serving is not implemented",
+      what + " of device memory, %(free)d are free", free_bytes)
 
 
 # ------------------------------------------------------------------ kernels
@@ -118,16 +108,8 @@ def neighbours(csr, icsr, un, N, shrink, qn=None, out=None, row_lo=0, row_hi=Non
   assert un.shape == (U,) and un.dtype == torch.float32 and 0 <= row_lo <= row_hi <= Q
   qn = query_norms(csr) if qn is None else qn
   assert qn.shape == (Q,) and qn.dtype == torch.float32
-  if out is None:
-    out = (torch.empty(Q, N, dtype=torch.int32, device=dev), torch.empty(Q, N, dtype=torch.float32, device=dev),
-           torch.empty(Q, dtype=torch.int32, device=dev))
-  ids, sim, count = out
-  assert ids.shape == (Q, N) and ids.dtype == torch.int32 and ids.is_contiguous()
-  assert sim.shape == (Q, N) and sim.dtype == torch.float32 and sim.is_contiguous()
-  assert count.shape == (Q,) and count.dtype == torch.int32
-  need = lib.rk_rp3_user_workspace_bytes(U)
-  if ws is None or ws.numel() < need:
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+  ids, sim, count = _neighbours.lists(Q, N, dev, out)
+  ws = _neighbours.workspace(ws, lib.rk_rp3_user_workspace_bytes(U), dev)
   _rp3_lib.check(lib.rk_rp3_user_neighbours(ptr(csr.indptr), ptr(csr.indices), ptr(icsr.indptr), ptr(icsr.indices),
                                             U, n, ptr(un), ptr(qn), float(shrink), N, row_lo, row_hi, ptr(ids),
                                             ptr(sim), ptr(count), ptr(ws), ws.numel(), current_stream()),

@@ -17,7 +17,6 @@ Data: C2 = synthetic.ml20m_like (116 677 x 20 108, 6.32 M nnz) and msd_like (471
 21.7 M nnz); h in {64, 128, 200}; alpha = 10, reg = 100, 3 CG steps, xavier init from seed 0.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -26,16 +25,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from bench_util import emit  # noqa: E402
 
 ALPHA, REG, CG = 10.0, 100.0, 3
-
-
-def emit(rec, out):
-  line = json.dumps(rec)
-  print(line, flush=True)
-  if out:
-    with open(out, "a") as f:
-      f.write(line + "\n")
 
 
 def init_tables(n_users, n_items, h, dev):

@@ -17,38 +17,19 @@ Data: slice = tests/golden/real_ml20m_slice.npz (10 000 x 7 915, 118 k nnz); c2 
 (116 677 x 20 108, 6.32 M nnz).  Writes profiles/bpr_bench.jsonl unless --out says otherwise.
 """
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
-import scipy.sparse as sp
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_util import emit, load  # noqa: E402
 
 LR, REG, EPOCHS, BATCH = 0.1, 0.01, 40, 1024          # (train_bpr's defaults)
 GRID = [(0.1, 0.01, 64), (0.05, 0.01, 64), (0.2, 0.01, 64), (0.1, 0.002, 64), (0.1, 0.05, 64), (0.1, 0.01, 16),
         (0.1, 0.01, 128)]
-
-
-def emit(rec, out):
-  line = json.dumps(rec)
-  print(line, flush=True)
-  if out:
-    with open(out, "a") as f:
-      f.write(line + "\n")
-
-
-def load(name):
-  if name == "c2":
-    from recoder_amd import synthetic
-    return sp.csr_matrix(synthetic.ml20m_like(seed=0)), None
-  z = np.load(os.path.join(ROOT, "tests", "golden", "real_ml20m_slice.npz"))
-  shape = tuple(int(v) for v in z["shape"])
-  mk = lambda p: sp.csr_matrix((z[p + "/data"], z[p + "/indices"], z[p + "/indptr"]), shape=shape)
-  return mk("x"), mk("y")
 
 
 def init_tables(n_users, n_items, h, dev):

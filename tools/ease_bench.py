@@ -17,38 +17,19 @@ Data: c2 = synthetic.ml20m_like(seed=0) (116 677 x 20 108, 6.32 M nnz); slice =
 tests/golden/real_ml20m_slice.npz (10 000 x 7 915).  reg = 500.
 """
 import argparse
-import json
 import os
 import sys
 import time
 
 import numpy as np
-import scipy.sparse as sp
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_util import emit, load  # noqa: E402
 
 REG, B, K = 500.0, 500, 100
 F32_MATRIX_PEAK_TF = 157.0
-
-
-def emit(rec, out):
-  line = json.dumps(rec)
-  print(line, flush=True)
-  if out:
-    with open(out, "a") as f:
-      f.write(line + "\n")
-
-
-def load(name):
-  if name == "c2":
-    from recoder_amd import synthetic
-    return sp.csr_matrix(synthetic.ml20m_like(seed=0)), None
-  z = np.load(os.path.join(ROOT, "tests", "golden", "real_ml20m_slice.npz"))
-  shape = tuple(int(v) for v in z["shape"])
-  mk = lambda p: sp.csr_matrix((z[p + "/data"], z[p + "/indices"], z[p + "/indptr"]), shape=shape)
-  return mk("x"), mk("y")
 
 
 def timed(fn, reps=1):

@@ -22,7 +22,6 @@ Data: slice = tests/golden/real_ml20m_slice.npz (10 000 x 7 915); c2 = synthetic
 (116 677 x 20 108, 6.32 M nnz: above rk_rp3_lds_items(), so the workspace form).
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -32,6 +31,7 @@ import scipy.sparse as sp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_util import emit, event_ms, guarded, load  # noqa: E402
 
 B, K = 500, 100
 GRID = [(200, 300.0, "cosine", "none"), (200, 0.0, "cosine", "none"), (100, 100.0, "cosine", "none"),
@@ -42,24 +42,6 @@ CPU_SHRINKS = (0.0, 5.0, 20.0, 100.0, 300.0, 1000.0)
 CPU_KINDS = [("cosine", "none", 0.5), ("cosine", "tfidf", 0.5), ("cosine", "bm25", 0.5), ("jaccard", "none", 0.5),
              ("dice", "none", 0.5), ("asymmetric", "none", 0.3), ("asymmetric", "none", 0.5),
              ("asymmetric", "none", 0.7)]
-
-
-def emit(rec, out):
-  line = json.dumps(rec)
-  print(line, flush=True)
-  if out:
-    with open(out, "a") as f:
-      f.write(line + "\n")
-
-
-def load(name):
-  if name == "c2":
-    from recoder_amd import synthetic
-    return sp.csr_matrix(synthetic.ml20m_like(seed=0)), None
-  z = np.load(os.path.join(ROOT, "tests", "golden", "real_ml20m_slice.npz"))
-  shape = tuple(int(v) for v in z["shape"])
-  mk = lambda p: sp.csr_matrix((z[p + "/data"], z[p + "/indices"], z[p + "/indptr"]), shape=shape)
-  return mk("x"), mk("y")
 
 
 # ------------------------------------------------------------------ CPU grid
@@ -97,26 +79,6 @@ def cpu_grid(out, jobs):
 
 
 # ----------------------------------------------------------------------- GPU
-def guarded(fn):
-  try:
-    return fn()
-  except Exception as e:          # (an op this torch build lacks, or no room for the dense matrix: reported, not fatal)
-    print("torch restatement step not available: %s: %s" % (type(e).__name__, e), file=sys.stderr)
-    return None
-
-
-def event_ms(fn, reps=5):
-  import torch
-  fn()
-  a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  a.record()
-  for _ in range(reps):
-    fn()
-  b.record()
-  torch.cuda.synchronize()
-  return a.elapsed_time(b) / reps
-
-
 def serve_time(rec, inp, reps=10):
   rec.recommend_array(inp, K)
   t0 = time.perf_counter()
@@ -153,10 +115,10 @@ def hip_side(x, out, with_rp3):
     def fit():
       state["ws"] = itemknn.fit_columns(*pair, ud, td, own, oth, form, g, p["shrink"], ids, w, count,
                                         ws=state.get("ws"))
-    ms = event_ms(fit)
+    ms = event_ms(fit, 5)
     out.update({tag + "fit_ms": ms, tag + "adds_per_s": adds / (ms * 1e-3), tag + "values": ud is not None})
   uw, rs, cs = (torch.from_numpy(a).to(dev) for a in rp3.host_weights(pair, 0.6, 0.3))
-  rp3_ms = event_ms(lambda: rp3.fit_rows(*pair, uw, rs, cs, ids, w, count, ws=state["ws"]))
+  rp3_ms = event_ms(lambda: rp3.fit_rows(*pair, uw, rs, cs, ids, w, count, ws=state["ws"]), 5)
   out.update(rp3_fit_ms=rp3_ms, fit_vs_rp3_fit=out["fit_ms"] / rp3_ms, tfidf_fit_vs_rp3_fit=out["tfidf_fit_ms"] / rp3_ms)
   users = np.arange(min(B, x.shape[0]))
   inp = UsersInteractions(users, x[users])

@@ -17,7 +17,6 @@ Data: slice = tests/golden/real_ml20m_slice.npz (10 000 x 7 915); c2 = synthetic
 (116 677 x 20 108, 6.32 M nnz: above rk_rp3_lds_items(), so the workspace path).
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -28,36 +27,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_util import emit, guarded, load  # noqa: E402
 
 ALPHA, BETA, NEIGHBOURS, B, K, EASE_REG = 0.6, 0.3, 100, 500, 100, 500.0
 GRID = [(0.6, 0.3, 100), (0.6, 0.2, 100), (0.6, 0.3, 20), (0.6, 0.3, 200), (0.4, 0.3, 100), (0.8, 0.3, 100),
         (0.6, 0.0, 100), (1.0, 0.6, 100)]
-
-
-def emit(rec, out):
-  line = json.dumps(rec)
-  print(line, flush=True)
-  if out:
-    with open(out, "a") as f:
-      f.write(line + "\n")
-
-
-def load(name):
-  if name == "c2":
-    from recoder_amd import synthetic
-    return sp.csr_matrix(synthetic.ml20m_like(seed=0)), None
-  z = np.load(os.path.join(ROOT, "tests", "golden", "real_ml20m_slice.npz"))
-  shape = tuple(int(v) for v in z["shape"])
-  mk = lambda p: sp.csr_matrix((z[p + "/data"], z[p + "/indices"], z[p + "/indptr"]), shape=shape)
-  return mk("x"), mk("y")
-
-
-def guarded(fn):
-  try:
-    return fn()
-  except Exception as e:          # (an op this torch build lacks, or no room for the dense matrix: reported, not fatal)
-    print("torch restatement step not available: %s: %s" % (type(e).__name__, e), file=sys.stderr)
-    return None
 
 
 def serve_time(rec, inp, reps=10):

@@ -19,7 +19,6 @@ Data: slice = tests/golden/real_ml20m_slice.npz (10 000 x 7 915); c2 = synthetic
 No number from this tool exists yet: it has not been run on an MI355X, and it fixes no target.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -30,28 +29,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_util import emit, load  # noqa: E402
 
 L1, L2, NEIGHBOURS, MAX_SWEEPS, TOL, B, K = 1.0, 1000.0, 200, 50, 1e-5, 500, 100
 GRID = [(1.0, 1000.0, 200), (1.0, 1000.0, 100), (1.0, 1000.0, 1024), (2.0, 1000.0, 200), (0.5, 1000.0, 200),
         (1.0, 500.0, 200), (1.0, 2000.0, 200), (5.0, 100.0, 200)]
-
-
-def emit(rec, out):
-  line = json.dumps(rec)
-  print(line, flush=True)
-  if out:
-    with open(out, "a") as f:
-      f.write(line + "\n")
-
-
-def load(name):
-  if name == "c2":
-    from recoder_amd import synthetic
-    return sp.csr_matrix(synthetic.ml20m_like(seed=0)), None
-  z = np.load(os.path.join(ROOT, "tests", "golden", "real_ml20m_slice.npz"))
-  shape = tuple(int(v) for v in z["shape"])
-  mk = lambda p: sp.csr_matrix((z[p + "/data"], z[p + "/indices"], z[p + "/indptr"]), shape=shape)
-  return mk("x"), mk("y")
 
 
 def guarded(fn):

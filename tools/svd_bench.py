@@ -16,7 +16,6 @@ Rank matters: on the very sparse slice PureSVD is at its best at h = 4 (Recall@2
 popularity's 0.108) and falls below popularity from about h = 16 on; --quality prints the curve.  Needs
 the GPU: there is no CPU path."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -27,19 +26,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_util import emit  # noqa: E402
 
 SHAPES = [(4, 20), (64, 80), (200, 216)]
 Q = 6
 HBM_BPS = 8.0e12            # MI355X HBM3E
 F32_MFMA_FLOPS = 157.3e12
-
-
-def emit(rec, out):
-  line = json.dumps(rec)
-  print(line, flush=True)
-  if out:
-    with open(out, "a") as f:
-      f.write(line + "\n")
 
 
 def load_slice():

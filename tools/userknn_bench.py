@@ -17,7 +17,6 @@ Data: slice = tests/golden/real_ml20m_slice.npz (10 000 x 7 915); c2 = synthetic
 (116 677 x 20 108, 6.32 M nnz: more users than rk_rp3_lds_items(), so the workspace path).
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -28,46 +27,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_util import emit, event_ms, guarded, load  # noqa: E402
 
 B, K = 500, 100
 GRID = [(n, s) for n in (100, 200, 400, 800) for s in (0.0, 10.0)]
-
-
-def emit(rec, out):
-  line = json.dumps(rec)
-  print(line, flush=True)
-  if out:
-    with open(out, "a") as f:
-      f.write(line + "\n")
-
-
-def load(name):
-  if name == "c2":
-    from recoder_amd import synthetic
-    return sp.csr_matrix(synthetic.ml20m_like(seed=0)), None
-  z = np.load(os.path.join(ROOT, "tests", "golden", "real_ml20m_slice.npz"))
-  shape = tuple(int(v) for v in z["shape"])
-  mk = lambda p: sp.csr_matrix((z[p + "/data"], z[p + "/indices"], z[p + "/indptr"]), shape=shape)
-  return mk("x"), mk("y")
-
-
-def guarded(fn):
-  try:
-    return fn()
-  except Exception as e:          # (an op this torch build lacks, or no room for the dense matrix: reported, not fatal)
-    print("torch restatement step not available: %s: %s" % (type(e).__name__, e), file=sys.stderr)
-    return None
-
-
-def event_ms(fn, reps=10):
-  fn()
-  a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  a.record()
-  for _ in range(reps):
-    fn()
-  b.record()
-  torch.cuda.synchronize()
-  return a.elapsed_time(b) / reps
 
 
 def serve_time(rec, inp, reps=10):
@@ -97,9 +60,9 @@ def hip_side(x, out, with_rp3):
   def nb():
     *state["nbr"], state["ws"] = userknn.neighbours(q, icsr, m.user_norms, m.neighbours, m.shrink, qn=qn,
                                                     ws=state.get("ws"))
-  nb_ms = event_ms(nb)
+  nb_ms = event_ms(nb, 10)
   buf = torch.empty(len(users), x.shape[1], dtype=torch.float32, device="cuda")
-  sc_ms = event_ms(lambda: userknn.scores(state["nbr"], ucsr, out=buf))
+  sc_ms = event_ms(lambda: userknn.scores(state["nbr"], ucsr, out=buf), 10)
   r = np.diff(x.indptr)[users].astype(np.float64)
   d = np.diff(x.T.tocsr().indptr).astype(np.float64)
   adds = float(sum(d[x.indices[x.indptr[u]:x.indptr[u + 1]]].sum() for u in users))
@@ -138,7 +101,7 @@ def torch_batch(x, N, shrink):
     w, ids = torch.topk(sim, min(N, sim.shape[1]), dim=1)
     kept = torch.zeros_like(sim).scatter_(1, ids, w)
     return torch.sparse.mm(xt, kept.t().contiguous()).t()
-  return event_ms(run, reps=5)
+  return event_ms(run, 5)
 
 
 def torch_side(x, out):
