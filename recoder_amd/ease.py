@@ -26,6 +26,14 @@ def check_not_distributed():
   als.check_not_distributed("train_ease runs on one GPU: a multi-GPU EASE fit is not implemented")
 
 
+def check_config(model, reg):
+  """The EASE contract, checked before any GPU work; returns reg."""
+  from .nn import ShallowAutoencoder
+  if not isinstance(model, ShallowAutoencoder):
+    raise ValueError("train_ease fits a ShallowAutoencoder, not %s" % type(model).__name__)
+  return check_reg(reg)
+
+
 def check_reg(reg):
   reg = float(reg)
   if not (math.isfinite(reg) and reg > 0):

@@ -18,6 +18,7 @@ Two hooks exist because a GPU cannot reproduce the reference's CPU RNG streams
       bottleneck sample of training step ``step`` whose rows are ``users`` (default: counter RNG).
 Either hook turns the HIP-graph replay of the training steps off.
 """
+import functools
 import logging
 import os
 
@@ -33,12 +34,21 @@ from .device import Block, DeviceCSR, require_gpu
 from .engine import FusedEngine
 from .losses import MSELoss, MultinomialNLLLoss
 from .metrics import RecommenderEvaluator
-from .nn import (CsrScoresModel, DynamicAutoencoder, FactorizationModel, ItemNeighbourhoodModel, MatrixFactorization,
-                 RandomWalkItemModel, ShallowAutoencoder, SparseLinearModel, UserNeighbourhoodModel,
+from .nn import (CsrScoresModel, DynamicAutoencoder, FactorizationModel, MatrixFactorization,
                  VariationalAutoencoder)
 from .recommender import InferenceRecommender
 
 log = logging.getLogger("recoder_amd")
+
+
+def _default(value, model, name):
+  """``value``, or the model's ``name`` where it is None.  On a model of another class, which may lack the
+  attribute, that stays None: the fit module's check_config refuses the class before it looks at a number."""
+  return getattr(model, name, None) if value is None else value
+
+
+def _mf_tables(m):
+  return m.user_embedding_layer.weight.data, m.item_embedding_layer.weight.data
 
 
 def _top_sum(degrees, k):
@@ -373,21 +383,8 @@ class Recoder(object):
         lr, weight_decay, batch_size, self.optimizer_type, lr_milestones, self.loss))
 
     self._check_vae()
-    if isinstance(self.model, ShallowAutoencoder):
-      raise ValueError("a ShallowAutoencoder is fitted in closed form: call train_ease(train_dataset) "
-                       "(gradient steps would not keep its zero diagonal)")
-    if isinstance(self.model, RandomWalkItemModel):
-      raise ValueError("a RandomWalkItemModel is fitted in closed form from the interaction graph: call "
-                       "train_rp3beta(train_dataset)")
-    if isinstance(self.model, SparseLinearModel):
-      raise ValueError("a SparseLinearModel is fitted by coordinate descent on the Gram matrix: call "
-                       "train_slim(train_dataset)")
-    if isinstance(self.model, ItemNeighbourhoodModel):
-      raise ValueError("an ItemNeighbourhoodModel is fitted in closed form from the items' co-occurrences: call "
-                       "train_itemknn(train_dataset)")
-    if isinstance(self.model, UserNeighbourhoodModel):
-      raise ValueError("a UserNeighbourhoodModel is its training matrix, there is nothing to descend on: call "
-                       "train_userknn(train_dataset)")
+    if getattr(self.model, "fit_method", None):       # (the closed-form models of nn.py say so themselves)
+      raise ValueError(self.model.fit_sentence % self.model.fit_method)
     if num_sampling_users == 0:
       num_sampling_users = batch_size
     if eval_batch_size is None:
@@ -455,6 +452,60 @@ class Recoder(object):
     self.optimizer = self.sparse_optimizer = None
     self.__optimizer_state_dict = self.__sparse_optimizer_state_dict = None
 
+  def _closed_form_fit(self, mod, train_dataset, keep, check, log_line, fit, hint_check=None, check_values=False,
+                       store=None, place=None, size_check=None, csrs=None, copy=dict):
+    """The one sequence behind the eight ``train_*`` methods below: ``mod`` is the fit module, the callables say
+    what differs, ``cfg`` is what ``check`` returned and ``host()`` the dataset's host matrix, built at the step
+    that first asks for it.  The order decides which exception wins, and a call that raises in A-D leaves the
+    Recoder and the model as they were:
+      A ``check(model)``: the module's check_config, the model's class first;  B ``check_not_distributed``;
+      C ``hint_check(cfg, users, items, host)``: the sizes of ``_size_hints`` against one device's memory, before
+        init_model allocates (a catalogue that cannot fit gets a ValueError, not an OOM);
+      D ``mod.check_values(host())``;  E the log line;  F ``store(cfg)``: hyperparameters back into the model;
+      G fresh optimizers;  H ``place(cfg, first, host)``: on first use (after require_gpu) the size init_model
+        allocates, later a re-allocation when it changed;  I ``__init_training``;
+      J ``size_check(cfg, host)``: the real sizes against what is free;  K the device CSRs (``csrs``);
+      L ``fit(model, csrs, cfg)``, kept in ``self.<keep>``;  M ``_weights_written()``; returns ``copy`` of it."""
+    from . import als
+    cfg = check(self.model)
+    mod.check_not_distributed()
+    host = functools.lru_cache(maxsize=None)(lambda: als.host_matrix(train_dataset))
+    if hint_check is not None:
+      hint_check(cfg, *self._size_hints(train_dataset), host)
+    if check_values:
+      mod.check_values(host())
+    log.info(*log_line(cfg))
+    for name, value in (store(cfg) if store else {}).items():
+      setattr(self.model, name, value)
+    self._reset_optimizers()
+    if place is not None:
+      first = not self.__model_initialized
+      if first:
+        require_gpu()
+      place(cfg, first, host)
+    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
+    if size_check is not None:
+      size_check(cfg, host)
+    pair = (csrs or als.csr_pair)(host(), self.num_users, self.num_items, self.device)
+    setattr(self, keep, fit(self.model, pair, cfg))
+    self._weights_written()
+    return copy(getattr(self, keep))
+
+  def _neighbour_list_fit(self, mod, train_dataset, keep, check, k_at, log_line, store, check_values=False):
+    """``_closed_form_fit`` for the three models stored as [n, K] neighbour lists, K = ``cfg[k_at]``: the same
+    memory checks, the same tensors to (re-)allocate and to hand to ``mod.fit(csrs, *cfg, out=...)``."""
+    def place(cfg, first, host):
+      if first:
+        self.model.neighbours = cfg[k_at]
+      elif cfg[k_at] != self.model.item_weights.shape[1]:
+        self.model.allocate(cfg[k_at], self.device)
+    return self._closed_form_fit(
+        mod, train_dataset, keep, check, log_line, store=store, place=place, check_values=check_values,
+        hint_check=lambda c, u, n, host: n and mod.check_memory(u or 0, n, c[k_at], 0, free_bytes=float("inf")),
+        size_check=lambda c, host: mod.check_memory(self.num_users, self.num_items, c[k_at], host().nnz,
+                                                    allocate_model=False),
+        fit=lambda m, pair, c: mod.fit(pair, *c, out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))[-1])
+
   def train_als(self, train_dataset, num_iterations=10, reg=100.0, cg_steps=3):
     """Implicit-feedback alternating least squares for a MatrixFactorization with activation 'none'
     (recoder_amd/als.py): minimises the configured MSELoss(confidence=alpha, reduction='sum') over the
@@ -463,17 +514,13 @@ class Recoder(object):
     ``optimizer_type``, so that ``save_state`` and ``train`` work on the tables it leaves.  Returns
     (and keeps in ``als_history``) the objective after each iteration."""
     from . import als
-    alpha = als.check_config(self.model, self.loss, self.loss_params, num_iterations, reg, cg_steps)
-    als.check_not_distributed()
-    log.info("ALS: %d iterations, reg %g, confidence %g, %d CG steps", num_iterations, reg, alpha, cg_steps)
-    self._reset_optimizers()
-    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
-    ucsr, icsr = als.csr_pair(als.host_matrix(train_dataset), self.num_users, self.num_items, self.device)
-    m = self.model
-    self.als_history = als.fit(m.user_embedding_layer.weight.data, m.item_embedding_layer.weight.data,
-                               m.bias.data, ucsr, icsr, alpha, float(reg), int(cg_steps), int(num_iterations))
-    self._weights_written()
-    return list(self.als_history)
+    return self._closed_form_fit(
+        als, train_dataset, "als_history", copy=list,
+        check=lambda m: als.check_config(m, self.loss, self.loss_params, num_iterations, reg, cg_steps),
+        log_line=lambda alpha: ("ALS: %d iterations, reg %g, confidence %g, %d CG steps", num_iterations, reg, alpha,
+                                cg_steps),
+        fit=lambda m, pair, alpha: als.fit(*_mf_tables(m), m.bias.data, *pair, alpha, float(reg), int(cg_steps),
+                                           int(num_iterations)))
 
   def train_bpr(self, train_dataset, num_epochs=40, batch_size=1024, lr=0.1, reg=0.01, seed=0):
     """BPR-MF (Rendle et al. 2009) for a MatrixFactorization with activation 'none' (recoder_amd/bpr.py):
@@ -485,20 +532,13 @@ class Recoder(object):
     stored values and the configured ``loss`` play no part.  Builds a fresh optimizer of
     ``optimizer_type``, so that ``save_state``, ``train`` and ``train_als`` work on the tables it leaves.
     Returns (and keeps in ``bpr_history``) the mean loss per valid triple of each epoch."""
-    from . import als, bpr
-    num_epochs, batch_size, lr, reg, seed = bpr.check_config(self.model, num_epochs, batch_size, lr, reg, seed)
-    bpr.check_not_distributed()
-    log.info("BPR: %d epochs of batches of %d, lr %g, reg %g, seed %d", num_epochs, batch_size, lr, reg, seed)
-    self._reset_optimizers()
-    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
-    host = als.host_matrix(train_dataset)
-    bpr.check_data(host.nnz, self.num_items, num_epochs, batch_size)
-    ucsr = bpr.user_csr(host, self.num_users, self.num_items, self.device)
-    m = self.model
-    self.bpr_history = bpr.fit(m.user_embedding_layer.weight.data, m.item_embedding_layer.weight.data,
-                               m.bias.data, ucsr, num_epochs, batch_size, lr, reg, seed)
-    self._weights_written()
-    return list(self.bpr_history)
+    from . import bpr
+    return self._closed_form_fit(
+        bpr, train_dataset, "bpr_history", copy=list, csrs=bpr.user_csr,
+        check=lambda m: bpr.check_config(m, num_epochs, batch_size, lr, reg, seed),
+        log_line=lambda c: ("BPR: %d epochs of batches of %d, lr %g, reg %g, seed %d",) + c,
+        size_check=lambda c, host: bpr.check_data(host().nnz, self.num_items, c[0], c[1]),
+        fit=lambda m, ucsr, c: bpr.fit(*_mf_tables(m), m.bias.data, ucsr, *c))
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
@@ -512,26 +552,22 @@ class Recoder(object):
     milliseconds of the sparse products and of the orthonormalisations (HIP events), those of the host's
     eigendecomposition, and ``ritz_residual`` = max_k |A^T u_k - sigma_k^2 v_k| / sigma_1^2: flat spectra
     converge slowly, and this is the signal to raise ``num_power_iterations``."""
-    from . import als, svd
-    h, l = svd.check_config(self.model, oversample, num_power_iterations, seed)
-    svd.check_not_distributed()
-    n_users, n_items = self._size_hints(train_dataset)
-    svd.check_rank(l, n_users or 0, n_items or 0)
-    svd.check_memory(n_users, n_items, l, 0, free_bytes=float("inf"))
-    log.info("PureSVD: h %d, l %d, %d power iterations, seed %d", h, l, num_power_iterations, seed)
-    self._reset_optimizers()
-    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
-    svd.check_rank(l, self.num_users, self.num_items)
-    host = als.host_matrix(train_dataset)
-    svd.check_memory(self.num_users, self.num_items, l, host.nnz)
-    ucsr, icsr = als.csr_pair(host, self.num_users, self.num_items, self.device)
-    m = self.model
-    info = svd.fit(m.user_embedding_layer.weight.data, m.item_embedding_layer.weight.data, ucsr, icsr,
-                   int(oversample), int(num_power_iterations), int(seed))
-    m.bias.data.zero_()
-    self._weights_written()
-    self.svd_info = info
-    return dict(info)
+    from . import svd
+
+    def sizes(l, n_users, n_items, nnz, **free):
+      svd.check_rank(l, n_users or 0, n_items or 0)
+      svd.check_memory(n_users, n_items, l, nnz, **free)
+
+    def fit(m, pair, c):
+      info = svd.fit(*_mf_tables(m), *pair, int(oversample), int(num_power_iterations), int(seed))
+      m.bias.data.zero_()
+      return info
+    return self._closed_form_fit(
+        svd, train_dataset, "svd_info", fit=fit,
+        check=lambda m: svd.check_config(m, oversample, num_power_iterations, seed),               # c = (h, l)
+        hint_check=lambda c, u, n, host: sizes(c[1], u, n, 0, free_bytes=float("inf")),
+        size_check=lambda c, host: sizes(c[1], self.num_users, self.num_items, host().nnz),
+        log_line=lambda c: ("PureSVD: h %d, l %d, %d power iterations, seed %d",) + c + (num_power_iterations, seed))
 
   def train_ease(self, train_dataset, reg=None):
     """The closed-form EASE fit of a ShallowAutoencoder (recoder_amd/ease.py): ``item_weights`` becomes
@@ -541,28 +577,15 @@ class Recoder(object):
     configured ``loss`` plays no part: EASE minimises the squared error with an L2 penalty by
     construction.  Builds a fresh optimizer of ``optimizer_type`` so that ``save_state`` works.  Returns
     ``info``: n, nnz, reg and the milliseconds of the Gram, the inverse and finalize (HIP events)."""
-    from . import als, ease
-    if not isinstance(self.model, ShallowAutoencoder):
-      raise ValueError("train_ease fits a ShallowAutoencoder, not %s" % type(self.model).__name__)
-    reg = ease.check_reg(self.model.reg if reg is None else reg)
-    ease.check_not_distributed()
-    n_hint = self._size_hints(train_dataset)[1]
-    if n_hint:
-      # (before init_model allocates the n x n parameter: a 1 M-item catalogue gets a ValueError, not an OOM)
-      ease.check_memory(n_hint, free_bytes=float("inf"))
-    log.info("EASE: reg %g", reg)
-    self.model.reg = reg
-    self._reset_optimizers()
-    first = not self.__model_initialized
-    if first:
-      require_gpu()
-      ease.check_memory(n_hint or 1)                 # (the parameter itself is the n x n matrix)
-    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
-    pair = als.csr_pair(als.host_matrix(train_dataset), self.num_users, self.num_items, self.device)
-    _, info = ease.fit(pair, reg, out=self.model.item_weights.data)
-    self.ease_info = info
-    self._weights_written()
-    return {k: v for k, v in info.items() if k != "diag"}
+    from . import ease
+    return self._closed_form_fit(
+        ease, train_dataset, "ease_info", copy=lambda info: {k: v for k, v in info.items() if k != "diag"},
+        check=lambda m: ease.check_config(m, _default(reg, m, "reg")),
+        hint_check=lambda c, u, n, host: n and ease.check_memory(n, free_bytes=float("inf")),
+        log_line=lambda reg: ("EASE: reg %g", reg), store=lambda reg: {"reg": reg},
+        # (first use: the parameter itself is the n x n matrix, and it has to fit what is free)
+        place=lambda reg, first, host: first and ease.check_memory(self._size_hints(train_dataset)[1] or 1),
+        fit=lambda m, pair, reg: ease.fit(pair, reg, out=m.item_weights.data)[-1])
 
   def train_rp3beta(self, train_dataset, alpha=None, beta=None, neighbours=None):
     """The closed-form RP3beta fit of a RandomWalkItemModel (recoder_amd/rp3.py): every item keeps its
@@ -573,34 +596,13 @@ class Recoder(object):
     holds, and another ``neighbours`` re-allocates the model's tensors.  The configured ``loss`` plays no
     part.  Builds a fresh optimizer of ``optimizer_type`` so that ``save_state`` works.  Returns
     ``info``: n, nnz, alpha, beta, neighbours, kept (entries kept over all rows) and fit_ms (HIP events)."""
-    from . import als, rp3
-    m = self.model
-    if not isinstance(m, RandomWalkItemModel):
-      raise ValueError("train_rp3beta fits a RandomWalkItemModel, not %s" % type(m).__name__)
-    alpha, beta, K = rp3.check_config(m, m.alpha if alpha is None else alpha, m.beta if beta is None else beta,
-                                      m.neighbours if neighbours is None else neighbours)
-    rp3.check_not_distributed()
-    u_hint, n_hint = self._size_hints(train_dataset)
-    if n_hint:
-      # (before init_model allocates: a catalogue that cannot fit gets a ValueError, not an OOM)
-      rp3.check_memory(u_hint or 0, n_hint, K, 0, free_bytes=float("inf"))
-    log.info("RP3beta: alpha %g, beta %g, %d neighbours", alpha, beta, K)
-    m.alpha, m.beta = alpha, beta
-    self._reset_optimizers()
-    if not self.__model_initialized:
-      require_gpu()
-      m.neighbours = K
-    elif K != m.item_weights.shape[1]:
-      m.allocate(K, self.device)
-    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
-    m = self.model
-    host = als.host_matrix(train_dataset)
-    rp3.check_memory(self.num_users, self.num_items, K, host.nnz, allocate_model=False)
-    pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
-    _, _, _, info = rp3.fit(pair, alpha, beta, K, out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))
-    self.rp3_info = info
-    self._weights_written()
-    return dict(info)
+    from . import rp3
+    return self._neighbour_list_fit(
+        rp3, train_dataset, "rp3_info", k_at=2,                                            # c = (alpha, beta, K)
+        check=lambda m: rp3.check_config(m, _default(alpha, m, "alpha"), _default(beta, m, "beta"),
+                                         _default(neighbours, m, "neighbours")),
+        log_line=lambda c: ("RP3beta: alpha %g, beta %g, %d neighbours",) + c,
+        store=lambda c: {"alpha": c[0], "beta": c[1]})
 
   def train_itemknn(self, train_dataset, neighbours=None, shrink=None, similarity=None, feature_weighting=None):
     """The closed-form ItemKNN fit of an ItemNeighbourhoodModel (recoder_amd/itemknn.py): column j of W keeps
@@ -613,39 +615,15 @@ class Recoder(object):
     configured ``loss`` plays no part.  Builds a fresh optimizer of ``optimizer_type`` so that ``save_state``
     works.  Returns (and keeps in ``itemknn_info``) n, nnz, neighbours, shrink, similarity, feature_weighting,
     kept (entries kept over all columns) and fit_ms (HIP events)."""
-    from . import als, itemknn
-    m = self.model
-    if not isinstance(m, ItemNeighbourhoodModel):
-      raise ValueError("train_itemknn fits an ItemNeighbourhoodModel, not %s" % type(m).__name__)
-    K, shrink, similarity, feature_weighting, aa, ta, tb = itemknn.check_config(
-        m, m.neighbours if neighbours is None else neighbours, m.shrink if shrink is None else shrink,
-        m.similarity if similarity is None else similarity,
-        m.feature_weighting if feature_weighting is None else feature_weighting)
-    itemknn.check_not_distributed()
-    u_hint, n_hint = self._size_hints(train_dataset)
-    if n_hint:
-      # (before init_model allocates: a catalogue that cannot fit gets a ValueError, not an OOM)
-      itemknn.check_memory(u_hint or 0, n_hint, K, 0, free_bytes=float("inf"))
-    host = als.host_matrix(train_dataset)
-    itemknn.check_values(host)
-    log.info("ItemKNN: %s similarity, feature weighting %s, %d neighbours, shrink %g", similarity,
-             feature_weighting, K, shrink)
-    m.shrink, m.similarity, m.feature_weighting = shrink, similarity, feature_weighting
-    self._reset_optimizers()
-    if not self.__model_initialized:
-      require_gpu()
-      m.neighbours = K
-    elif K != m.item_weights.shape[1]:
-      m.allocate(K, self.device)
-    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
-    m = self.model
-    itemknn.check_memory(self.num_users, self.num_items, K, host.nnz, allocate_model=False)
-    pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
-    _, _, _, info = itemknn.fit(pair, K, shrink, similarity, feature_weighting, aa, ta, tb,
-                                out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))
-    self.itemknn_info = info
-    self._weights_written()
-    return dict(info)
+    from . import itemknn
+    return self._neighbour_list_fit(
+        itemknn, train_dataset, "itemknn_info", k_at=0, check_values=True,  # c = (K, shrink, similarity, weighting, ...)
+        check=lambda m: itemknn.check_config(
+            m, _default(neighbours, m, "neighbours"), _default(shrink, m, "shrink"),
+            _default(similarity, m, "similarity"), _default(feature_weighting, m, "feature_weighting")),
+        log_line=lambda c: ("ItemKNN: %s similarity, feature weighting %s, %d neighbours, shrink %g", c[2], c[3], c[0],
+                            c[1]),
+        store=lambda c: {"shrink": c[1], "similarity": c[2], "feature_weighting": c[3]})
 
   def train_slim(self, train_dataset, l1_reg=None, l2_reg=None, neighbours=None, max_sweeps=50, tol=1e-5):
     """The SLIM fit of a SparseLinearModel (recoder_amd/slim.py): column j of W becomes the non-negative
@@ -661,37 +639,13 @@ class Recoder(object):
     (entries kept over all columns), cut_columns (columns whose support was larger than ``neighbours``),
     unconverged_columns (columns that ran all ``max_sweeps`` sweeps), max_sweeps_run, gram_ms and fit_ms
     (HIP events)."""
-    from . import als, slim
-    m = self.model
-    if not isinstance(m, SparseLinearModel):
-      raise ValueError("train_slim fits a SparseLinearModel, not %s" % type(m).__name__)
-    l1, l2, K, max_sweeps, tol = slim.check_config(
-        m, m.l1_reg if l1_reg is None else l1_reg, m.l2_reg if l2_reg is None else l2_reg,
-        m.neighbours if neighbours is None else neighbours, max_sweeps, tol)
-    slim.check_not_distributed()
-    u_hint, n_hint = self._size_hints(train_dataset)
-    if n_hint:
-      # (before init_model allocates: a catalogue whose Gram cannot fit gets a ValueError, not an OOM)
-      slim.check_memory(u_hint or 0, n_hint, K, 0, free_bytes=float("inf"))
-    host = als.host_matrix(train_dataset)
-    slim.check_values(host)
-    log.info("SLIM: l1_reg %g, l2_reg %g, %d neighbours, at most %d sweeps, tol %g", l1, l2, K, max_sweeps, tol)
-    m.l1_reg, m.l2_reg = l1, l2
-    self._reset_optimizers()
-    if not self.__model_initialized:
-      require_gpu()
-      m.neighbours = K
-    elif K != m.item_weights.shape[1]:
-      m.allocate(K, self.device)
-    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
-    m = self.model
-    slim.check_memory(self.num_users, self.num_items, K, host.nnz, allocate_model=False)
-    pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
-    _, _, _, info = slim.fit(pair, l1, l2, K, max_sweeps, tol,
-                             out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))
-    self.slim_info = info
-    self._weights_written()
-    return dict(info)
+    from . import slim
+    return self._neighbour_list_fit(
+        slim, train_dataset, "slim_info", k_at=2, check_values=True,         # c = (l1, l2, K, max_sweeps, tol)
+        check=lambda m: slim.check_config(m, _default(l1_reg, m, "l1_reg"), _default(l2_reg, m, "l2_reg"),
+                                          _default(neighbours, m, "neighbours"), max_sweeps, tol),
+        log_line=lambda c: ("SLIM: l1_reg %g, l2_reg %g, %d neighbours, at most %d sweeps, tol %g",) + c,
+        store=lambda c: {"l1_reg": c[0], "l2_reg": c[1]})
 
   def train_userknn(self, train_dataset, neighbours=None, shrink=None):
     """The "fit" of a UserNeighbourhoodModel (recoder_amd/userknn.py): the model takes the dataset's
@@ -703,32 +657,24 @@ class Recoder(object):
     interactions take effect.  The configured ``loss`` plays no part.  Builds a fresh optimizer of
     ``optimizer_type`` so that ``save_state`` works.  Returns (and keeps in ``userknn_info``) n_users, n, nnz,
     neighbours, shrink and fit_ms (HIP events)."""
-    from . import als, userknn
-    m = self.model
-    N, shrink = userknn.check_config(m, m.neighbours if neighbours is None else neighbours,
-                                     m.shrink if shrink is None else shrink)
-    userknn.check_not_distributed()
-    host = als.host_matrix(train_dataset)
-    u_hint, n_hint = self._size_hints(train_dataset)
-    if u_hint and n_hint:
-      # (before init_model allocates: a matrix that cannot fit gets a ValueError, not an OOM)
-      userknn.check_memory(u_hint, n_hint, N, host.nnz, free_bytes=float("inf"))
-    log.info("UserKNN: %d neighbours, shrink %g", N, shrink)
-    m.neighbours, m.shrink = N, shrink
-    self._reset_optimizers()
-    if not self.__model_initialized:
-      require_gpu()
-      m.nnz = int(host.nnz)
-    elif (m.num_users, m.nnz) != (self.num_users, int(host.nnz)):
-      m.allocate(self.num_users, host.nnz, self.device)
-    self.__init_training(train_dataset=train_dataset, lr=0.001, weight_decay=0)
-    m = self.model
-    userknn.check_memory(self.num_users, self.num_items, N, host.nnz)
-    pair = als.csr_pair(host, self.num_users, self.num_items, self.device)
-    _, info = userknn.fit(pair, N, shrink, model=m)
-    self.userknn_info = info
-    self._weights_written()
-    return dict(info)
+    from . import userknn
+
+    def place(c, first, host):
+      m, nnz = self.model, int(host().nnz)
+      if first:
+        m.nnz = nnz
+      elif (m.num_users, m.nnz) != (self.num_users, nnz):
+        m.allocate(self.num_users, nnz, self.device)
+    return self._closed_form_fit(
+        userknn, train_dataset, "userknn_info", place=place,                               # c = (N, shrink)
+        check=lambda m: userknn.check_config(m, _default(neighbours, m, "neighbours"),
+                                             _default(shrink, m, "shrink")),
+        hint_check=lambda c, u, n, host: u and n and userknn.check_memory(u, n, c[0], host().nnz,
+                                                                          free_bytes=float("inf")),
+        log_line=lambda c: ("UserKNN: %d neighbours, shrink %g",) + c,
+        store=lambda c: {"neighbours": c[0], "shrink": c[1]},
+        size_check=lambda c, host: userknn.check_memory(self.num_users, self.num_items, c[0], host().nnz),
+        fit=lambda m, pair, c: userknn.fit(pair, *c, model=m)[-1])
 
   def _pick_engine_for(self, train_dataset):
     """Combinations the fused step does not cover train through the generic engine (torch autograd

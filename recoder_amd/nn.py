@@ -405,7 +405,22 @@ def dense_to_csr(input, input_items, n):
 
 class CsrScoresModel(FactorizationModel):
   """A model without an encoder: a user's scores come from the user's CSR row alone.  ``Recoder.predict`` and
-  ``Recoder.recommend_array`` hand such a model the batch's device CSR, strip by strip."""
+  ``Recoder.recommend_array`` hand such a model the batch's device CSR, strip by strip.  A class that
+  ``Recoder.train`` cannot descend on names ``fit_method``, the ``Recoder`` method that fits it, and
+  ``fit_sentence``, what ``train`` raises instead (``%s``: the method)."""
+  fit_method = fit_sentence = None
+
+  def forward(self, input, input_users=None, input_items=None, target_users=None,
+              target_items=None):
+    """The scores of a dense batch on the model's HIP scores kernel (``csr_scores`` over the input's non-zeros as a
+    CSR over the catalogue, ascending); no autograd.  On the host (no device tensors) it is ``torch_forward``."""
+    if not input.is_cuda:
+      with torch.no_grad():
+        return self.torch_forward(input, input_users, input_items, target_users, target_items)
+    n = self.num_items
+    csr = dense_to_csr(input, input_items, n)
+    out = self.csr_scores(csr, 0, n, None, None, input.shape[0])
+    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
 
   def csr_scores(self, csr, lo, hi, out, ld, n_rows):
     """out[u, c] = the score of item lo + c for row u of ``csr``, for c < hi - lo and u < n_rows, ``out`` f32
@@ -422,19 +437,6 @@ class ItemItemModel(CsrScoresModel):
 
   def _dense_w(self):
     raise NotImplementedError
-
-  def forward(self, input, input_users=None, input_items=None, target_users=None,
-              target_items=None):
-    """``input @ W[input_items][:, target_items]`` on the model's HIP scores kernel (``csr_scores``): the
-    dense input's non-zeros as a CSR over the catalogue, ascending; no autograd.  On the host (no device
-    tensors) it is ``torch_forward``."""
-    if not input.is_cuda:
-      with torch.no_grad():
-        return self.torch_forward(input, input_users, input_items, target_users, target_items)
-    n = self.item_weights.shape[0]
-    csr = dense_to_csr(input, input_items, n)
-    out = self.csr_scores(csr, 0, n, None, None, input.shape[0])
-    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
 
   def torch_forward(self, input, input_users=None, input_items=None, target_users=None,
                     target_items=None):
@@ -457,6 +459,9 @@ class ShallowAutoencoder(ItemItemModel):
   ``model_params()``.  Gradient training would not keep the zero diagonal, so ``Recoder.train`` refuses
   this model and points at ``train_ease``.
   """
+  fit_method = "train_ease"
+  fit_sentence = ("a ShallowAutoencoder is fitted in closed form: call %s(train_dataset) "
+                  "(gradient steps would not keep its zero diagonal)")
 
   def __init__(self, reg=500.0):
     super().__init__()
@@ -493,8 +498,10 @@ class _NeighbourListModel(ItemItemModel):
   """An item-item model stored as neighbour lists: ``item_neighbours`` int32 [num_items, neighbours],
   ``item_weights`` f32 of the same shape and ``neighbour_counts`` int32 [num_items].  A subclass names
   ``fit_module``, the module of this package whose ``scores`` reads the lists, and says in
-  ``dense_weights`` which way round they spell W."""
+  ``lists_spell_columns`` which way round they spell W: row j of the tensors is row j of W,
+  ``W[j, item_neighbours[j, s]] = item_weights[j, s]``, or (True) column j."""
   fit_module = None
+  lists_spell_columns = False
 
   def init_model(self, num_items=None, num_users=None):
     self._validate()
@@ -517,6 +524,17 @@ class _NeighbourListModel(ItemItemModel):
     return fit.scores(csr, self.item_neighbours, self.item_weights.data, self.neighbour_counts, lo, hi, out=out,
                       ld=ld, n_rows=n_rows)
 
+  def dense_weights(self, dtype=torch.float32):
+    """W [num_items, num_items]: the kept entries scattered into a dense matrix (small catalogues only)."""
+    n, K = self.item_weights.shape
+    W = torch.zeros(n, n, dtype=dtype, device=self.item_weights.device)
+    ids = self.item_neighbours.to(torch.int64)
+    live = torch.arange(K, device=ids.device)[None, :] < self.neighbour_counts.to(torch.int64)[:, None]
+    own = torch.arange(n, device=ids.device)[:, None].expand(n, K)
+    rows, cols = (ids, own) if self.lists_spell_columns else (own, ids)
+    W[rows[live], cols[live]] = self.item_weights.data.to(dtype)[live]
+    return W
+
   def _dense_w(self):
     return self.dense_weights()
 
@@ -536,6 +554,8 @@ class RandomWalkItemModel(_NeighbourListModel):
   at ``train_rp3beta``.
   """
   fit_module = "rp3"
+  fit_method = "train_rp3beta"
+  fit_sentence = "a RandomWalkItemModel is fitted in closed form from the interaction graph: call %s(train_dataset)"
 
   def __init__(self, alpha=0.6, beta=0.3, neighbours=100):
     super().__init__()
@@ -559,31 +579,11 @@ class RandomWalkItemModel(_NeighbourListModel):
     self.neighbours = int(model_params["neighbours"])
     self._validate()
 
-  def dense_weights(self, dtype=torch.float32):
-    """W [num_items, num_items]: the kept entries scattered into a dense matrix (small catalogues only)."""
-    n, K = self.item_weights.shape
-    W = torch.zeros(n, n, dtype=dtype, device=self.item_weights.device)
-    ids = self.item_neighbours.to(torch.int64)
-    live = torch.arange(K, device=ids.device)[None, :] < self.neighbour_counts.to(torch.int64)[:, None]
-    rows = torch.arange(n, device=ids.device)[:, None].expand(n, K)
-    W[rows[live], ids[live]] = self.item_weights.data.to(dtype)[live]
-    return W
-
 
 class _ColumnListModel(_NeighbourListModel):
   """The neighbour-list models whose lists spell the COLUMNS of W: row j of the three tensors holds the kept k
   of column j, ``W[item_neighbours[j, s], j] = item_weights[j, s]`` (the layout rk_slim_scores reads)."""
-
-  def dense_weights(self, dtype=torch.float32):
-    """W [num_items, num_items]: the kept entries scattered into a dense matrix, ``W[item_neighbours[j, s], j]
-    = item_weights[j, s]`` (small catalogues only)."""
-    n, K = self.item_weights.shape
-    W = torch.zeros(n, n, dtype=dtype, device=self.item_weights.device)
-    ids = self.item_neighbours.to(torch.int64)
-    live = torch.arange(K, device=ids.device)[None, :] < self.neighbour_counts.to(torch.int64)[:, None]
-    cols = torch.arange(n, device=ids.device)[:, None].expand(n, K)
-    W[ids[live], cols[live]] = self.item_weights.data.to(dtype)[live]
-    return W
+  lists_spell_columns = True
 
 
 class SparseLinearModel(_ColumnListModel):
@@ -602,6 +602,8 @@ class SparseLinearModel(_ColumnListModel):
   ``Recoder.train`` refuses this model and points at ``train_slim``.
   """
   fit_module = "slim"
+  fit_method = "train_slim"
+  fit_sentence = "a SparseLinearModel is fitted by coordinate descent on the Gram matrix: call %s(train_dataset)"
 
   def __init__(self, l1_reg=1.0, l2_reg=1000.0, neighbours=200):
     super().__init__()
@@ -644,6 +646,9 @@ class ItemNeighbourhoodModel(_ColumnListModel):
   at ``train_itemknn``.
   """
   fit_module = "itemknn"
+  fit_method = "train_itemknn"
+  fit_sentence = ("an ItemNeighbourhoodModel is fitted in closed form from the items' co-occurrences: call "
+                  "%s(train_dataset)")
   _PARAMS = ("neighbours", "shrink", "similarity", "feature_weighting", "asymmetric_alpha", "tversky_alpha",
              "tversky_beta")
 
@@ -691,6 +696,9 @@ class UserNeighbourhoodModel(CsrScoresModel):
   ``state_dict()``; empty until fitted.  ``neighbours`` and ``shrink`` travel in ``model_params()``, with the
   sizes a checkpoint's tensors have.  ``Recoder.train`` refuses this model and points at ``train_userknn``.
   """
+  fit_method = "train_userknn"
+  fit_sentence = ("a UserNeighbourhoodModel is its training matrix, there is nothing to descend on: call "
+                  "%s(train_dataset)")
 
   def __init__(self, neighbours=400, shrink=10.0):
     super().__init__()
@@ -782,18 +790,6 @@ class UserNeighbourhoodModel(CsrScoresModel):
       raise ValueError("the UserNeighbourhoodModel holds no training matrix: call train_userknn first")
     nbr = self.batch_neighbours(csr, n_rows)
     return userknn.scores(nbr, self._csrs()[0], lo, hi, out=out, ld=ld, n_rows=n_rows)    # (rk_rp3_user_scores)
-
-  def forward(self, input, input_users=None, input_items=None, target_users=None,
-              target_items=None):
-    """The scores of a dense batch on the HIP kernels (``csr_scores`` over the input's non-zeros); no
-    autograd.  On the host (no device tensors) it is ``torch_forward``."""
-    if not input.is_cuda:
-      with torch.no_grad():
-        return self.torch_forward(input, input_users, input_items, target_users, target_items)
-    n = self.num_items
-    csr = dense_to_csr(input, input_items, n)
-    out = self.csr_scores(csr, 0, n, None, None, input.shape[0])
-    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
 
   def torch_forward(self, input, input_users=None, input_items=None, target_users=None,
                     target_items=None):
