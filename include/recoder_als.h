@@ -56,6 +56,23 @@
  *   - rk_als_bpr_apply: a row's sum is one fmaf chain per element over its segment of the sorted keys in
  *     the order given (ascending slot when the sort is stable), from +0; then
  *     new = fmaf(lr, fmaf(-(reg * c), old, sum), old).  One wave owns a row; nobody else writes it.
+ *
+ * LightGCN (He, Deng, Wang, Li, Zhang & Wang 2020) for the same model, the rk_als_lgcn_* functions: the
+ * final tables are the mean over K + 1 layers of the base tables propagated over the symmetrically
+ * normalised user-item graph, trained with the BPR triples above and Adam (recoder_amd/lightgcn.py).
+ *   - rk_als_lgcn_propagate: a column's sum is one fmaf chain over the row's entries in ascending order
+ *     from +0, acc = fmaf(col_scale[col], F[col, k], acc); then * row_scale, then + Acc, then * acc_scale,
+ *     one rounding each.  A row of >= RK_ALS_LGCN_LONG_ROW entries is cut into n = 64 (h <= 128) or 16
+ *     contiguous parts with the bounds e0 + p len / n; each part is such a chain and the parts are added in
+ *     ascending p.  The order depends on the row's length and h alone: any [row_lo, row_hi) gives bitwise
+ *     the rows of the full call, with 16-byte accesses (h, the leading dimensions and the pointers
+ *     allowing) or without.
+ *   - rk_als_lgcn_scatter: rk_als_bpr_apply's chain over a row's segment with the weight -g_t for a user's
+ *     entry and for a positive, +g_t for a negative; then * scale.
+ *   - rk_als_lgcn_adam: grad = fmaf(reg_scale * count, e, H); m = fmaf(b1, m, (1 - b1) * grad);
+ *     v = fmaf(b2, v, ((1 - b2) * grad) * grad); e = fmaf(-step, m / fmaf(sqrt(v), isb2, eps), e) with
+ *     step = lr / (1 - b1^t) and isb2 = 1 / sqrt(1 - b2^t) computed in float64 on the host and rounded once.
+ *   No floating-point atomics anywhere.
  */
 #ifndef RECODER_ALS_H
 #define RECODER_ALS_H
@@ -157,6 +174,42 @@ int rk_als_bpr_grad(const int32_t *users, const int32_t *pos, const int32_t *neg
 int rk_als_bpr_apply(const int32_t *keys, const int64_t *order, int32_t n, int32_t roles, const float *g,
                      const float *V, int32_t h, float lr, float reg, int32_t n_rows, float *table, int32_t ldt,
                      float *bias, void *stream);
+
+/* rows of at least this many stored entries get a workgroup of 16 waves each in rk_als_lgcn_propagate */
+#define RK_ALS_LGCN_LONG_ROW 1024
+
+/*
+ * One propagation of a LightGCN layer over one orientation of the normalised bipartite graph.  For every
+ * row r in [row_lo, row_hi) of the CSR (indptr / indices; there is no value array):
+ *   Out[r, :h] = row_scale[r] * sum_j col_scale[col_j] * F[col_j, :h]     (no entries: +0)
+ *   Acc[r, :h] = (Acc[r, :h] + Out[r, :h]) * acc_scale                    (Acc != NULL)
+ * Out may be NULL when Acc is given (the last layer, where only the layer mean is wanted).  F [>, ldf] is
+ * indexed by the CSR's columns and must not overlap Out or Acc; row_scale and col_scale hold one float per
+ * row and per column.  Rows outside the range are not touched.
+ */
+int rk_als_lgcn_propagate(const int64_t *indptr, const int32_t *indices, const float *row_scale,
+                          const float *col_scale, int32_t row_lo, int32_t row_hi, const float *F, int32_t ldf,
+                          int32_t h, float *Out, int32_t ldo, float *Acc, int32_t lda, float acc_scale,
+                          void *stream);
+
+/*
+ * The gradient with respect to one final table from the sorted keys of a step, in the layout of
+ * rk_als_bpr_apply (keys, order, n = roles * T, roles; V = D for the users, P for the items).  For every
+ * key in [0, n_rows) present: G[key, :h] = scale * sum +-g_t V[t, :h] and count[key] = its entries.
+ * Rows without a key are not touched: the caller zeroes G [n_rows, ldg] and count (int32 [n_rows]) first.
+ */
+int rk_als_lgcn_scatter(const int32_t *keys, const int64_t *order, int32_t n, int32_t roles, const float *g,
+                        const float *V, int32_t h, float scale, int32_t n_rows, float *G, int32_t ldg,
+                        int32_t *count, void *stream);
+
+/*
+ * Adam step t >= 1 on the base table E0 [rows, lde] in place, from H [rows, ldh] (the propagated
+ * gradient), count (int32 [rows]) and the moments M, V (f32 [rows, h], leading dimension h, in place):
+ * see the numerics above.  Every row is updated: a zero gradient still decays the moments.
+ */
+int rk_als_lgcn_adam(float *E0, int32_t lde, const float *H, int32_t ldh, const int32_t *count, float reg_scale,
+                     float *M, float *V, int32_t rows, int32_t h, float lr, float beta1, float beta2, float eps,
+                     int32_t t, void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

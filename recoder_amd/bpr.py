@@ -73,13 +73,14 @@ def steps_per_epoch(nnz, batch_size):
   return -(-int(nnz) // int(batch_size))
 
 
-def check_data(nnz, n_items, num_epochs, batch_size):
-  """What the sampler needs of the matrix; returns the steps of one epoch."""
+def check_data(nnz, n_items, num_epochs, batch_size, method="train_bpr"):
+  """What the sampler needs of the matrix; returns the steps of one epoch.  ``method`` names the caller in the
+  messages (recoder_amd/lightgcn.py draws with the same sampler)."""
   nnz = int(nnz)
   if nnz >= 2 ** 31:
-    raise ValueError("train_bpr draws a stored entry with 32-bit arithmetic: nnz must be below 2^31 (got %d)" % nnz)
+    raise ValueError("%s draws a stored entry with 32-bit arithmetic: nnz must be below 2^31 (got %d)" % (method, nnz))
   if nnz < 1 or n_items < 1:
-    raise ValueError("train_bpr needs at least one stored entry to sample from (got nnz = %d)" % nnz)
+    raise ValueError("%s needs at least one stored entry to sample from (got nnz = %d)" % (method, nnz))
   steps = steps_per_epoch(nnz, batch_size)
   if steps * int(num_epochs) >= 2 ** 31:
     raise ValueError("num_epochs * ceil(nnz / batch_size) must be below 2^31 (got %d steps)" % (steps * num_epochs))

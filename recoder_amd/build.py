@@ -9,7 +9,8 @@ librecoder_index.so  exact item similarity (include/recoder_index.h), a library 
                    own so that the training library's exported symbol set stays as it is
 librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recoder_als.h),
                    likewise a library of its own.  It also holds the BPR pairwise-ranking step of the
-                   same model (rk_als_bpr_*: sample, grad, apply)
+                   same model (rk_als_bpr_*: sample, grad, apply) and the LightGCN kernels
+                   (rk_als_lgcn_*: propagate, scatter, adam) that train it over the user-item graph
 librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own
 librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencoder

@@ -18,6 +18,12 @@
 //   rk_als_bpr_apply   one wave per distinct row of the sorted keys: the row's segment summed in
 //                      ascending slot order, one fmaf chain per element, then the row's own update.
 //                      No atomics: nobody else writes the row
+//
+// LightGCN for the same model (rk_als_lgcn_*): the step of recoder_amd/lightgcn.py adds
+//   rk_als_lgcn_propagate  one group of lanes per CSR row: the scaled sum of the row's gathered table rows,
+//                          lanes own columns; long rows by a workgroup of 16 waves each, in fixed parts
+//   rk_als_lgcn_scatter    the apply's segment walk, writing the gradient rows and the counts
+//   rk_als_lgcn_adam       one elementwise pass: the L2 term and the Adam update of a base table
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -721,6 +727,248 @@ __global__ __launch_bounds__(256) void als_bpr_apply_kernel(const int32_t *__res
   }
 }
 
+// ----------------------------------------------------------------------- lgcn
+// Out[r] = row_scale[r] * sum_j col_scale[col_j] * F[col_j], Acc[r] = (Acc[r] + Out[r]) * acc_scale.
+// A group of G lanes (a power of two, 1..64) owns a row; lane c of the group owns the column chunks
+// c + G q, q < NT, of VEC floats each (VEC 4: one 16-byte access).  A lane walks its row's entries alone
+// -- no cross-lane step -- so a column's sum is one fmaf chain over the entries in ascending order from
+// +0, whatever G and VEC are: the scalar and the 16-byte forms give the same bits.
+// A row of >= RK_ALS_LGCN_LONG_ROW entries is left to a workgroup of 16 waves (the second launch, at most
+// LG_LONG_GRID workgroups that share the rows out by stride): its entries are cut into lg_parts(h)
+// contiguous parts (bounds e0 + p len / parts: a function of the length and h alone), part p is the
+// chain of group p mod (1024 / G), the parts meet in LDS and are added in ascending p.
+constexpr int LG_LONG = RK_ALS_LGCN_LONG_ROW;
+constexpr int LG_LONG_THREADS = 1024;
+constexpr int LG_LONG_GRID = 2048;                       // workgroups of the long-row launch, at most
+__host__ __device__ constexpr int lg_parts(int h) { return h <= 128 ? 64 : 16; }    // (parts * h * 4 <= 32 KiB)
+
+template <int VEC>
+struct LgVec;
+template <>
+struct LgVec<1> {
+  typedef float T;
+  static __device__ __forceinline__ float get(const float &v, int) { return v; }
+  static __device__ __forceinline__ void set(float &v, int, float x) { v = x; }
+  static __device__ __forceinline__ float zero() { return 0.f; }
+};
+template <>
+struct LgVec<4> {
+  typedef float4 T;
+  static __device__ __forceinline__ float get(const float4 &v, int i) {
+    return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
+  }
+  static __device__ __forceinline__ void set(float4 &v, int i, float x) {
+    if (i == 0) v.x = x; else if (i == 1) v.y = x; else if (i == 2) v.z = x; else v.w = x;
+  }
+  static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+};
+
+// acc[q] (+)= the chain over the entries [e0, e1) for the lane's column chunks (chunk index cg + G q < nch)
+template <int VEC, int NT>
+__device__ __forceinline__ void lgcn_walk(const int32_t *__restrict__ indices, const float *__restrict__ col_scale,
+                                          const float *__restrict__ F, int ldf, int64_t e0, int64_t e1, int cg,
+                                          int G, int nch, typename LgVec<VEC>::T (&acc)[NT]) {
+  typedef typename LgVec<VEC>::T V;
+  constexpr int LG_UNROLL = NT * VEC <= 4 ? 8 : 4;      // entries whose gathers are issued together
+  for (int64_t a = e0; a < e1; a += LG_UNROLL) {
+    V v[LG_UNROLL][NT];
+    float w[LG_UNROLL];
+#pragma unroll
+    for (int r = 0; r < LG_UNROLL; ++r) {
+      const bool in = a + r < e1;
+      const int col = in ? indices[a + r] : 0;
+      w[r] = in ? col_scale[col] : 0.f;
+      const float *row = F + (int64_t)col * ldf;
+#pragma unroll
+      for (int q = 0; q < NT; ++q) {
+        const int ch = cg + G * q;
+        v[r][q] = (in && ch < nch) ? *(const V *)(row + (int64_t)ch * VEC) : LgVec<VEC>::zero();
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < LG_UNROLL; ++r) {
+      if (a + r < e1) {                                  // (a tail entry must not touch the chain)
+#pragma unroll
+        for (int q = 0; q < NT; ++q)
+#pragma unroll
+          for (int i = 0; i < VEC; ++i)
+            LgVec<VEC>::set(acc[q], i, fmaf(w[r], LgVec<VEC>::get(v[r][q], i), LgVec<VEC>::get(acc[q], i)));
+      }
+    }
+  }
+}
+
+// the three roundings after the sum: s * row_scale, + Acc, * acc_scale
+template <int VEC>
+__device__ __forceinline__ void lgcn_finish(typename LgVec<VEC>::T s, float rs, int64_t r, int ch,
+                                            float *__restrict__ Out, int ldo, float *__restrict__ Acc, int lda,
+                                            float acc_scale) {
+  typedef typename LgVec<VEC>::T V;
+  V o;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) LgVec<VEC>::set(o, i, rs * LgVec<VEC>::get(s, i));
+  if (Out) *(V *)(Out + r * ldo + (int64_t)ch * VEC) = o;
+  if (Acc) {
+    V *p = (V *)(Acc + r * lda + (int64_t)ch * VEC);
+    const V old = *p;
+    V n;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i)
+      LgVec<VEC>::set(n, i, (LgVec<VEC>::get(old, i) + LgVec<VEC>::get(o, i)) * acc_scale);
+    *p = n;
+  }
+}
+
+template <int VEC, int NT>
+__global__ __launch_bounds__(256) void als_lgcn_propagate_kernel(
+    const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const float *__restrict__ row_scale,
+    const float *__restrict__ col_scale, int row_lo, int row_hi, const float *__restrict__ F, int ldf, int h,
+    int G, float *__restrict__ Out, int ldo, float *__restrict__ Acc, int lda, float acc_scale) {
+  typedef typename LgVec<VEC>::T V;
+  const int nch = (h + VEC - 1) / VEC;                   // (VEC 4: h is a multiple of 4)
+  const int rpb = 256 / G;                               // rows of a workgroup = its groups
+  const int grp = threadIdx.x / G, cg = threadIdx.x % G;
+  const int64_t r = (int64_t)row_lo + (int64_t)blockIdx.x * rpb + grp;
+  if (r >= row_hi) return;
+  const int64_t e0 = indptr[r], e1 = indptr[r + 1];
+  if (e1 - e0 >= LG_LONG) return;                        // (the long kernel's)
+  V acc[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) acc[q] = LgVec<VEC>::zero();
+  lgcn_walk<VEC, NT>(indices, col_scale, F, ldf, e0, e1, cg, G, nch, acc);
+  const float rs = row_scale[r];
+#pragma unroll
+  for (int q = 0; q < NT; ++q)
+    if (cg + G * q < nch) lgcn_finish<VEC>(acc[q], rs, r, cg + G * q, Out, ldo, Acc, lda, acc_scale);
+}
+
+// Workgroups of 16 waves over the long rows: workgroup b looks at the rows row_lo + b, + gridDim.x, ... (two
+// indptr loads each; long rows that sit side by side go to different workgroups) and sums the long ones,
+// one at a time; a short row is als_lgcn_propagate_kernel's.
+template <int VEC, int NT>
+__global__ __launch_bounds__(LG_LONG_THREADS) void als_lgcn_propagate_long_kernel(
+    const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const float *__restrict__ row_scale,
+    const float *__restrict__ col_scale, int row_lo, int row_hi, const float *__restrict__ F, int ldf, int h, int G,
+    float *__restrict__ Out, int ldo, float *__restrict__ Acc, int lda, float acc_scale) {
+  typedef typename LgVec<VEC>::T V;
+  extern __shared__ float4 lg_lds4[];                    // lg_parts(h) x h floats
+  float *part = (float *)lg_lds4;
+  const int nch = (h + VEC - 1) / VEC, parts = lg_parts(h);
+  const int groups = LG_LONG_THREADS / G, grp = threadIdx.x / G, cg = threadIdx.x % G;
+  for (int64_t r = (int64_t)row_lo + blockIdx.x; r < row_hi; r += gridDim.x) {   // (workgroup-uniform throughout)
+    const int64_t e0 = indptr[r], len = indptr[r + 1] - e0;
+    if (len < LG_LONG) continue;
+    for (int p = grp; p < parts; p += groups) {
+      V acc[NT];
+#pragma unroll
+      for (int q = 0; q < NT; ++q) acc[q] = LgVec<VEC>::zero();
+      lgcn_walk<VEC, NT>(indices, col_scale, F, ldf, e0 + len * p / parts, e0 + len * (p + 1) / parts, cg, G, nch,
+                         acc);
+#pragma unroll
+      for (int q = 0; q < NT; ++q)
+        if (cg + G * q < nch) *(V *)(part + (int64_t)p * nch * VEC + (cg + G * q) * VEC) = acc[q];
+    }
+    __syncthreads();
+    const float rs = row_scale[r];
+    for (int ch = threadIdx.x; ch < nch; ch += LG_LONG_THREADS) {
+      V sum = *(const V *)(part + ch * VEC);
+      for (int p = 1; p < parts; ++p) {
+        const V t = *(const V *)(part + (int64_t)p * nch * VEC + ch * VEC);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) LgVec<VEC>::set(sum, i, LgVec<VEC>::get(sum, i) + LgVec<VEC>::get(t, i));
+      }
+      lgcn_finish<VEC>(sum, rs, r, ch, Out, ldo, Acc, lda, acc_scale);
+    }
+    __syncthreads();                                     // (the next long row reuses the parts)
+  }
+}
+
+// rk_als_bpr_apply's segment walk with another ending: G[key] = scale * sum, count[key] = the segment's
+// length.  The weight is -g_t for a user's entry and for a positive, +g_t for a negative.
+template <int NT>
+__global__ __launch_bounds__(256) void als_lgcn_scatter_kernel(const int32_t *__restrict__ keys,
+                                                               const int64_t *__restrict__ order, int n, int roles,
+                                                               const float *__restrict__ g,
+                                                               const float *__restrict__ V, int h, float scale,
+                                                               int n_rows, float *__restrict__ Gt, int ldg,
+                                                               int32_t *__restrict__ count) {
+  const int lane = threadIdx.x & 63;
+  const int s0 = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s0 >= n) return;
+  const int key = keys[s0];
+  if (key < 0 || key >= n_rows) return;                  // (the invalid slots' sentinel, sorted last)
+  if (s0 > 0 && keys[s0 - 1] == key) return;             // (not a head)
+  int c = 0;
+  for (;;) {                                             // the segment's length, 64 keys at a time
+    const int s = s0 + c + lane;
+    const bool same = s < n && keys[s] == key;
+    const uint64_t m = __ballot(!same);
+    if (m) {
+      c += __ffsll((unsigned long long)m) - 1;
+      break;
+    }
+    c += 64;
+  }
+  float acc[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) acc[q] = 0.f;
+  const int64_t slots = roles == 2 ? n >> 1 : n;
+  for (int a0 = 0; a0 < c; a0 += BPR_UNROLL) {
+    float v[BPR_UNROLL][NT], w[BPR_UNROLL];
+#pragma unroll
+    for (int r = 0; r < BPR_UNROLL; ++r) {
+      const bool in = a0 + r < c;
+      const int64_t e = in ? order[s0 + a0 + r] : 0;
+      const int64_t t = roles == 2 ? e >> 1 : e;
+      const bool ok = in && e >= 0 && t < slots;         // (an order outside the batch adds nothing)
+      const float gt = ok ? g[t] : 0.f;
+      w[r] = (roles == 2 && (e & 1)) ? gt : -gt;
+#pragma unroll
+      for (int q = 0; q < NT; ++q) {
+        const int k = lane + 64 * q;
+        v[r][q] = (ok && k < h) ? V[t * h + k] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < BPR_UNROLL; ++r) {
+      if (a0 + r < c) {
+#pragma unroll
+        for (int q = 0; q < NT; ++q) acc[q] = fmaf(w[r], v[r][q], acc[q]);
+      }
+    }
+  }
+  float *row = Gt + (int64_t)key * ldg;
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int k = lane + 64 * q;
+    if (k < h) row[k] = scale * acc[q];
+  }
+  if (lane == 0) count[key] = c;
+}
+
+// One thread per element.  grad = fmaf(reg_scale * count[row], e, H); m = fmaf(b1, m, (1 - b1) grad);
+// v = fmaf(b2, v, ((1 - b2) grad) grad); e = fmaf(-step, m / fmaf(sqrt(v), isb2, eps), e), with
+// step = lr / (1 - b1^t) and isb2 = 1 / sqrt(1 - b2^t) from the host (float64, rounded once).
+__global__ __launch_bounds__(256) void als_lgcn_adam_kernel(float *__restrict__ E0, int lde,
+                                                            const float *__restrict__ H, int ldh,
+                                                            const int32_t *__restrict__ count, float reg_scale,
+                                                            float *__restrict__ M, float *__restrict__ Vv,
+                                                            int rows, int h, float beta1, float beta2,
+                                                            float omb1, float omb2, float eps, float step,
+                                                            float isb2) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);       // a wave per row and 64 columns
+  const int k = blockIdx.y * 64 + (threadIdx.x & 63);
+  if (r >= rows || k >= h) return;
+  const int64_t x = r * h + k;
+  const float e = E0[r * lde + k];
+  const float grad = fmaf(reg_scale * (float)count[r], e, H[r * ldh + k]);
+  const float m = fmaf(beta1, M[x], omb1 * grad);
+  const float v = fmaf(beta2, Vv[x], (omb2 * grad) * grad);
+  M[x] = m;
+  Vv[x] = v;
+  E0[r * lde + k] = fmaf(-step, m / fmaf(sqrtf(v), isb2, eps), e);
+}
+
 int64_t bpr_round256(int64_t x) { return (x + 255) / 256 * 256; }
 constexpr int BPR_MAX_T = 1 << 24;
 
@@ -895,5 +1143,95 @@ extern "C" int rk_als_bpr_apply(const int32_t *keys, const int64_t *order, int32
     default: ALS_BPR_APPLY_LAUNCH(8); break;
   }
   RK_SIDE_CHECK_LAUNCH("als_bpr_apply");
+  return 0;
+}
+
+#define ALS_LGCN_PROP_LAUNCH(VEC, NT)                                                                          \
+  do {                                                                                                         \
+    hipLaunchKernelGGL((als_lgcn_propagate_kernel<VEC, NT>), grid, dim3(256), 0, st, indptr, indices, row_scale, \
+                       col_scale, row_lo, row_hi, F, ldf, h, G, Out, ldo, Acc, lda, acc_scale);                \
+    hipLaunchKernelGGL((als_lgcn_propagate_long_kernel<VEC, NT>), long_grid, dim3(LG_LONG_THREADS), lds, st,   \
+                       indptr, indices, row_scale, col_scale, row_lo, row_hi, F, ldf, h, G, Out, ldo, Acc, lda, \
+                       acc_scale);                                                                             \
+  } while (0)
+
+extern "C" int rk_als_lgcn_propagate(const int64_t *indptr, const int32_t *indices, const float *row_scale,
+                                     const float *col_scale, int32_t row_lo, int32_t row_hi, const float *F,
+                                     int32_t ldf, int32_t h, float *Out, int32_t ldo, float *Acc, int32_t lda,
+                                     float acc_scale, void *stream) {
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldf >= h, "1 <= h <= 512, ldf >= h");
+  RK_SIDE_REQUIRE(row_lo >= 0 && row_hi >= row_lo, "0 <= row_lo <= row_hi");
+  RK_SIDE_REQUIRE(Out || Acc, "at least one of Out / Acc must be set");
+  RK_SIDE_REQUIRE((!Out || ldo >= h) && (!Acc || lda >= h), "ldo >= h, lda >= h");
+  if (row_hi == row_lo) return 0;
+  RK_SIDE_REQUIRE(indptr && indices && row_scale && col_scale && F, "null pointer");
+  // 16-byte accesses when every row of every matrix starts on a 16-byte boundary and holds whole float4s
+  const bool vec = h % 4 == 0 && ldf % 4 == 0 && (uintptr_t)F % 16 == 0 &&
+                   (!Out || (ldo % 4 == 0 && (uintptr_t)Out % 16 == 0)) &&
+                   (!Acc || (lda % 4 == 0 && (uintptr_t)Acc % 16 == 0));
+  const int nch = vec ? h / 4 : h;
+  int G = 1;
+  while (G < 64 && G < nch) G *= 2;
+  const int nt = (nch + G - 1) / G;                      // (vec: 1..2; scalar: 1..8)
+  const int rpb = 256 / G;
+  const dim3 grid((unsigned)(((int64_t)row_hi - row_lo + rpb - 1) / rpb));
+  const dim3 long_grid((unsigned)std::min<int64_t>((int64_t)row_hi - row_lo, LG_LONG_GRID));
+  const size_t lds = (size_t)lg_parts(h) * h * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  if (vec) {
+    if (nt == 1) ALS_LGCN_PROP_LAUNCH(4, 1);
+    else ALS_LGCN_PROP_LAUNCH(4, 2);
+  } else {
+    switch (nt_of(h)) {
+      case 1: ALS_LGCN_PROP_LAUNCH(1, 1); break;
+      case 2: ALS_LGCN_PROP_LAUNCH(1, 2); break;
+      case 4: ALS_LGCN_PROP_LAUNCH(1, 4); break;
+      default: ALS_LGCN_PROP_LAUNCH(1, 8); break;
+    }
+  }
+  RK_SIDE_CHECK_LAUNCH("als_lgcn_propagate");
+  return 0;
+}
+
+#define ALS_LGCN_SCATTER_LAUNCH(NT)                                                                            \
+  hipLaunchKernelGGL(als_lgcn_scatter_kernel<NT>, grid, dim3(256), 0, st, keys, order, n, roles, g, V, h, scale, \
+                     n_rows, G, ldg, count)
+
+extern "C" int rk_als_lgcn_scatter(const int32_t *keys, const int64_t *order, int32_t n, int32_t roles,
+                                   const float *g, const float *V, int32_t h, float scale, int32_t n_rows, float *G,
+                                   int32_t ldg, int32_t *count, void *stream) {
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldg >= h, "1 <= h <= 512, ldg >= h");
+  RK_SIDE_REQUIRE(roles == 1 || roles == 2, "roles is 1 (users) or 2 (items: positive, negative)");
+  RK_SIDE_REQUIRE(n >= roles && n % roles == 0 && n / roles <= BPR_MAX_T, "n = roles * T, 1 <= T <= 2^24");
+  RK_SIDE_REQUIRE(n_rows >= 1, "n_rows >= 1");
+  RK_SIDE_REQUIRE(keys && order && g && V && G && count, "null pointer");
+  const dim3 grid((unsigned)((n + 3) / 4));
+  hipStream_t st = (hipStream_t)stream;
+  switch (nt_of(h)) {
+    case 1: ALS_LGCN_SCATTER_LAUNCH(1); break;
+    case 2: ALS_LGCN_SCATTER_LAUNCH(2); break;
+    case 4: ALS_LGCN_SCATTER_LAUNCH(4); break;
+    default: ALS_LGCN_SCATTER_LAUNCH(8); break;
+  }
+  RK_SIDE_CHECK_LAUNCH("als_lgcn_scatter");
+  return 0;
+}
+
+extern "C" int rk_als_lgcn_adam(float *E0, int32_t lde, const float *H, int32_t ldh, const int32_t *count,
+                                float reg_scale, float *M, float *V, int32_t rows, int32_t h, float lr, float beta1,
+                                float beta2, float eps, int32_t t, void *stream) {
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && lde >= h && ldh >= h, "1 <= h <= 512, lde >= h, ldh >= h");
+  RK_SIDE_REQUIRE(rows >= 0 && t >= 1, "rows >= 0, t >= 1");
+  RK_SIDE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f,
+                  "0 <= beta1, beta2 < 1, eps > 0");
+  if (rows == 0) return 0;
+  RK_SIDE_REQUIRE(E0 && H && count && M && V, "null pointer");
+  // the bias corrections in float64 from the float arguments, each rounded once
+  const float step = (float)((double)lr / (1.0 - pow((double)beta1, (double)t)));
+  const float isb2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)t)));
+  const dim3 grid((unsigned)((rows + 3) / 4), (unsigned)((h + 63) / 64));
+  hipLaunchKernelGGL(als_lgcn_adam_kernel, grid, dim3(256), 0, (hipStream_t)stream, E0, lde, H, ldh, count,
+                     reg_scale, M, V, rows, h, beta1, beta2, 1.f - beta1, 1.f - beta2, eps, step, isb2);
+  RK_SIDE_CHECK_LAUNCH("als_lgcn_adam");
   return 0;
 }

@@ -97,6 +97,8 @@ class Recoder(object):
     self.loss_history = []      # per-epoch arrays of the per-step training losses
     self.als_history = []       # train_als: the ALS objective after each iteration
     self.bpr_history = []       # train_bpr: the mean loss per valid triple of each epoch
+    self.lightgcn_history = []  # train_lightgcn: the mean loss per valid triple of each epoch
+    self.lightgcn_state = None  # train_lightgcn: base tables, Adam moments, step count, num_layers (device; not saved)
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -454,7 +456,7 @@ class Recoder(object):
 
   def _closed_form_fit(self, mod, train_dataset, keep, check, log_line, fit, hint_check=None, check_values=False,
                        store=None, place=None, size_check=None, csrs=None, copy=dict):
-    """The one sequence behind the eight ``train_*`` methods below: ``mod`` is the fit module, the callables say
+    """The one sequence behind the nine ``train_*`` methods below: ``mod`` is the fit module, the callables say
     what differs, ``cfg`` is what ``check`` returned and ``host()`` the dataset's host matrix, built at the step
     that first asks for it.  The order decides which exception wins, and a call that raises in A-D leaves the
     Recoder and the model as they were:
@@ -539,6 +541,37 @@ class Recoder(object):
         log_line=lambda c: ("BPR: %d epochs of batches of %d, lr %g, reg %g, seed %d",) + c,
         size_check=lambda c, host: bpr.check_data(host().nnz, self.num_items, c[0], c[1]),
         fit=lambda m, ucsr, c: bpr.fit(*_mf_tables(m), m.bias.data, ucsr, *c))
+
+  def train_lightgcn(self, train_dataset, num_layers=3, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3, seed=0,
+                     resume=False):
+    """LightGCN (He et al. 2020) for a MatrixFactorization with activation 'none' (recoder_amd/lightgcn.py): the
+    final tables are the mean over ``num_layers`` + 1 layers of trainable base tables propagated over the
+    symmetrically normalised user-item graph of the stored entries, trained on BPR's triples (the draws of
+    ``train_bpr`` for the same seed, step and slot) with Adam at learning rate ``lr`` and the L2 term ``reg`` on
+    the base rows a triple touches.  The base tables of a first call are the tables as they stand; they, both
+    Adam moments, the step count and ``num_layers`` stay in ``lightgcn_state`` (device tensors, not part of a
+    checkpoint), and ``resume=True`` continues from them with the draws, moments and step count one longer
+    call would have had.  The model's tables end as the final tables and the bias as 0: ``save_state``,
+    ``recommend``, ``evaluate``, ``train``, ``train_als`` and ``train_bpr`` take them as they are.  The stored
+    values and the configured ``loss`` play no part.  Returns (and keeps in ``lightgcn_history``) the mean
+    loss per valid triple of each epoch."""
+    from . import lightgcn
+
+    def check(m):
+      c = lightgcn.check_config(m, num_layers, num_epochs, batch_size, lr, reg, seed)
+      if resume:
+        lightgcn.check_resume(self.lightgcn_state, c[0])
+      return c
+
+    def fit(m, pair, c):
+      # (a fresh state replaces the kept one only once the fit's own checks have passed)
+      self.lightgcn_state, hist = lightgcn.fit(*_mf_tables(m), m.bias.data, *pair, *c,
+                                               state=self.lightgcn_state if resume else None)
+      return hist
+    return self._closed_form_fit(
+        lightgcn, train_dataset, "lightgcn_history", copy=list, check=check, fit=fit,
+        log_line=lambda c: ("LightGCN: %d layers, %d epochs of batches of %d, lr %g, reg %g, seed %d",) + c,
+        size_check=lambda c, host: lightgcn.check_data(host().nnz, self.num_items, c[1], c[2]))
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
