@@ -38,6 +38,12 @@
  *   - rk_ease_finalize: one correctly rounded f32 divide per element.
  *   - rk_ease_scores: one ascending f32 fmaf chain per output, from 0, over the user's stored
  *     entries: a score depends neither on the strip nor on the user's position in the batch.
+ *   - rk_ease_lowrank_add: dot = ONE k-ascending f32 fmaf chain  fma(V[i][t], V[j][t], .)  over t = 0 .. k - 1,
+ *     from 0, on v_mfma_f32_32x32x2_f32 (k is never split over waves or workgroups, there are no atomics);
+ *     then  s = alpha * row_scale[i],  p = s * dot  (two f32 multiplies, in this order) and
+ *     A[i][j] = fma(p, col_scale[j], A[i][j]): three roundings after the chain's k.  An element depends on
+ *     neither the tile it falls in nor the row range: a row range gives bitwise the rows of the full call.  A
+ *     scale (or alpha) that is exactly 0 adds +-0: the element keeps its value.
  */
 #ifndef RECODER_EASE_H
 #define RECODER_EASE_H
@@ -94,6 +100,17 @@ int rk_ease_finalize(const float *P, int32_t n, int64_t ldp, float *B, int64_t l
 int rk_ease_scores(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
                    const float *W, int64_t ldw, int32_t lo, int32_t hi, float *out, int64_t ldo,
                    void *stream);
+
+/*
+ * A[i][j] += (alpha * row_scale[i]) * (sum over t < k of V[i][t] * V[j][t]) * col_scale[j] for i in
+ * [row_lo, row_hi) and j in [0, n): a dense rank-k update with diagonal scalings (GF-CF's ideal low-pass
+ * filter, recoder_amd/gfcf.py).  A [n, lda], lda >= n, columns at or past n are not touched; V [n, ldv],
+ * 1 <= k <= 512, ldv >= k, k a multiple of nothing; row_scale, col_scale [n]; 0 <= row_lo <= row_hi <= n (an
+ * empty range does nothing).  No workspace.
+ */
+int rk_ease_lowrank_add(float *A, int32_t n, int64_t lda, const float *V, int32_t k, int64_t ldv,
+                        const float *row_scale, const float *col_scale, float alpha, int32_t row_lo, int32_t row_hi,
+                        void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

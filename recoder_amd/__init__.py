@@ -9,7 +9,7 @@ Drop-in for the reference's training path: ``Recoder`` / ``FactorizationModel``
 __version__ = "0.4.0"
 
 __all__ = ["ShallowAutoencoder", "RandomWalkItemModel", "SparseLinearModel", "UserNeighbourhoodModel",
-           "ItemNeighbourhoodModel"]
+           "ItemNeighbourhoodModel", "GraphFilterModel"]
 
 
 def __getattr__(name):
@@ -29,4 +29,7 @@ def __getattr__(name):
   if name == "ItemNeighbourhoodModel":
     from .nn import ItemNeighbourhoodModel
     return ItemNeighbourhoodModel
+  if name == "GraphFilterModel":
+    from .nn import GraphFilterModel
+    return GraphFilterModel
   raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -14,7 +14,9 @@ librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recode
 librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own
 librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencoder
-                   (include/recoder_ease.h), likewise a library of its own
+                   (include/recoder_ease.h), likewise a library of its own.  It also holds the dense
+                   rank-k update of GraphFilterModel's GF-CF fit (rk_ease_lowrank_add), which shares the
+                   inverse's MFMA tile
 librecoder_svd.so  the randomized truncated SVD behind PureSVD for MatrixFactorization
                    (include/recoder_svd.h), likewise a library of its own
 librecoder_rp3.so  the RP3beta item-graph fit and its scores for RandomWalkItemModel

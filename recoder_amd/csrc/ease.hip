@@ -12,6 +12,9 @@
 //                        every block's update of it is below half an ulp, and uncompensated they all vanish
 //   rk_ease_finalize     B = -P / diag(P) by columns, diagonal 0
 //   rk_ease_scores       sparse row x dense matrix, one thread per output column, users fastest in the grid
+//   rk_ease_lowrank_add  A += diag(alpha a) V V^T diag(b): the inverse's 128 x 128 MFMA tile walked over k in
+//                        slabs of 32, the whole k inside one wave (one chain per output, no atomics), the two
+//                        scalings and the add in the store
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -316,6 +319,73 @@ __global__ __launch_bounds__(256) void ease_scores_kernel(const int64_t *__restr
     if (ok[q]) out[(int64_t)u * ldo + c0 + 256 * q] = acc[q];
 }
 
+// ---------------------------------------------------------------- lowrank add
+constexpr int LR_KS = 32;               // k-slab held in LDS
+constexpr int LR_LD = TILE + 1;         // odd row stride: the transposing store [row][t] -> [t][row] is conflict-free
+
+// A[i][j] += (alpha a_i) (sum_t V[i][t] V[j][t]) b_j for i in [row_lo, row_hi), j < n.  One workgroup (4 waves) per
+// 128 x 128 tile; the rows i0.. and j0.. of V go through LDS as [t][128] slabs of 32 columns of V, zeros past n
+// and past k (so k needs no alignment; a zero pair leaves the chain's value as it is); wave w takes the
+// 64 x 64 quadrant (w >> 1, w & 1) as 2 x 2 accumulators, each ONE k-ascending chain over all the slabs.
+__global__ __launch_bounds__(256) void ease_lowrank_add_kernel(float *__restrict__ A, int n, int64_t lda,
+                                                               const float *__restrict__ V, int k, int64_t ldv,
+                                                               const float *__restrict__ row_scale,
+                                                               const float *__restrict__ col_scale, float alpha,
+                                                               int row_lo, int row_hi) {
+  __shared__ float Vi[LR_KS * LR_LD];
+  __shared__ float Vj[LR_KS * LR_LD];
+  const int i0 = row_lo + blockIdx.y * TILE, j0 = blockIdx.x * TILE;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int m0 = (wv >> 1) * 64, n0 = (wv & 1) * 64, l31 = lane & 31, kh = lane >> 5;
+  f32x16 acc00, acc01, acc10, acc11;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc00[q] = acc01[q] = acc10[q] = acc11[q] = 0.f;
+  for (int t0 = 0; t0 < k; t0 += LR_KS) {
+    if (t0) __syncthreads();            // (the previous slab has been read)
+    // thread e: row e / 32 of the tile, column t0 + e % 32 of V: a wave reads two rows' 128 contiguous bytes
+    for (int e = threadIdx.x; e < TILE * LR_KS; e += 256) {
+      const int r = e >> 5, t = e & 31;
+      const bool tk = t0 + t < k;
+      const int gi = i0 + r, gj = j0 + r;
+      Vi[t * LR_LD + r] = (tk && gi < row_hi) ? V[(int64_t)gi * ldv + t0 + t] : 0.f;
+      Vj[t * LR_LD + r] = (tk && gj < n) ? V[(int64_t)gj * ldv + t0 + t] : 0.f;
+    }
+    __syncthreads();
+    const int kend = min(LR_KS, (k - t0 + 1) & ~1);
+#pragma unroll 4
+    for (int kk = 0; kk < kend; kk += 2) {
+      const float *vi = Vi + (kk + kh) * LR_LD + m0 + l31, *vj = Vj + (kk + kh) * LR_LD + n0 + l31;
+      const float a0 = vi[0], a1 = vi[32], b0 = vj[0], b1 = vj[32];
+      acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc00, 0, 0, 0);
+      acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc01, 0, 0, 0);
+      acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc10, 0, 0, 0);
+      acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11, 0, 0, 0);
+    }
+  }
+  // C/D map of the 32x32 forms: column n = lane & 31, row m = (q & 3) + 8 (q >> 2) + 4 (lane >> 5).
+  // The order the header states: s = alpha * a_i; p = s * dot; A = fma(p, b_j, A) -- three roundings.
+#define EASE_LR_STORE(acc, mi, ni)                                                      \
+  {                                                                                     \
+    const int gj = j0 + n0 + 32 * (ni) + l31;                                           \
+    if (gj < n) {                                                                       \
+      const float b = col_scale[gj];                                                    \
+      _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                  \
+        const int gi = i0 + m0 + 32 * (mi) + (q & 3) + 8 * (q >> 2) + 4 * kh;           \
+        if (gi < row_hi) {                                                              \
+          float *ap = A + (int64_t)gi * lda + gj;                                       \
+          const float p = __fmul_rn(__fmul_rn(alpha, row_scale[gi]), acc[q]);           \
+          *ap = fmaf(p, b, *ap);                                                        \
+        }                                                                               \
+      }                                                                                 \
+    }                                                                                   \
+  }
+  EASE_LR_STORE(acc00, 0, 0)
+  EASE_LR_STORE(acc01, 0, 1)
+  EASE_LR_STORE(acc10, 1, 0)
+  EASE_LR_STORE(acc11, 1, 1)
+#undef EASE_LR_STORE
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------ ABI
@@ -402,6 +472,23 @@ int rk_ease_scores(const int64_t *indptr, const int32_t *indices, const float *d
   hipLaunchKernelGGL(ease_scores_kernel, grid, dim3(256), 0, (hipStream_t)stream, indptr, indices, data, W, ldw, lo,
                      width, out, ldo);
   RK_SIDE_CHECK_LAUNCH("ease_scores_kernel");
+  return 0;
+}
+
+int rk_ease_lowrank_add(float *A, int32_t n, int64_t lda, const float *V, int32_t k, int64_t ldv,
+                        const float *row_scale, const float *col_scale, float alpha, int32_t row_lo, int32_t row_hi,
+                        void *stream) {
+  RK_SIDE_REQUIRE(A && V && row_scale && col_scale, "null pointer");
+  RK_SIDE_REQUIRE(n >= 1 && lda >= n, "bad sizes");
+  RK_SIDE_REQUIRE(k >= 1 && k <= 512 && ldv >= k, "k must be in [1, 512] and ldv >= k");
+  RK_SIDE_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= n, "bad row range");
+  if (row_lo == row_hi) return 0;
+  const int row_tiles = (row_hi - row_lo + TILE - 1) / TILE;
+  RK_SIDE_REQUIRE(row_tiles <= 65535, "n too large for one launch");
+  const dim3 grid((n + TILE - 1) / TILE, row_tiles);
+  hipLaunchKernelGGL(ease_lowrank_add_kernel, grid, dim3(256), 0, (hipStream_t)stream, A, n, lda, V, k, ldv,
+                     row_scale, col_scale, alpha, row_lo, row_hi);
+  RK_SIDE_CHECK_LAUNCH("ease_lowrank_add_kernel");
   return 0;
 }
 

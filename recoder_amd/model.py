@@ -456,7 +456,7 @@ class Recoder(object):
 
   def _closed_form_fit(self, mod, train_dataset, keep, check, log_line, fit, hint_check=None, check_values=False,
                        store=None, place=None, size_check=None, csrs=None, copy=dict):
-    """The one sequence behind the nine ``train_*`` methods below: ``mod`` is the fit module, the callables say
+    """The one sequence behind the ten ``train_*`` methods below: ``mod`` is the fit module, the callables say
     what differs, ``cfg`` is what ``check`` returned and ``host()`` the dataset's host matrix, built at the step
     that first asks for it.  The order decides which exception wins, and a call that raises in A-D leaves the
     Recoder and the model as they were:
@@ -619,6 +619,42 @@ class Recoder(object):
         # (first use: the parameter itself is the n x n matrix, and it has to fit what is free)
         place=lambda reg, first, host: first and ease.check_memory(self._size_hints(train_dataset)[1] or 1),
         fit=lambda m, pair, reg: ease.fit(pair, reg, out=m.item_weights.data)[-1])
+
+  def train_gfcf(self, train_dataset, rank=None, alpha=None, oversample=16, num_power_iterations=6, seed=0):
+    """The closed-form GF-CF fit of a GraphFilterModel (recoder_amd/gfcf.py): ``item_weights`` becomes
+    ``W = Rn^T Rn + alpha * D_I^-1/2 V V^T D_I^1/2`` for ``Rn = D_U^-1/2 R D_I^-1/2``, R the dataset's interaction
+    graph (the stored entries are the edges, as in ``train_rp3beta``; their values play no part in the fit,
+    they weigh the user's history when scoring) and V its top ``rank`` right singular vectors, from the
+    randomized SVD of ``train_svd`` with a sketch of ``rank + oversample`` columns (at most 512),
+    ``num_power_iterations`` power iterations and ``seed``; a fixed seed gives the same bits.  ``None`` takes
+    the model's value; explicit values are stored back into the model, so that a checkpoint's ``model_params``
+    describe the weights it holds.  The n x n matrix has to fit the device (EASE's limit; ValueError
+    otherwise).  The configured ``loss`` plays no part.  Builds a fresh optimizer of ``optimizer_type`` so that
+    ``save_state`` works.  Returns (and keeps in ``gfcf_info``, there with ``V``, the device tensor of the
+    singular vectors) n, nnz, rank, alpha, l, singular_values, ritz_residual (flat spectra converge slowly:
+    the signal to raise ``num_power_iterations``) and gram_ms, svd_ms and filter_ms (HIP events)."""
+    from . import gfcf, svd
+
+    def sizes(c, n_users, n_items, nnz, **kw):
+      gfcf.check_memory(n_users or 0, n_items, c[2], nnz, **kw)
+      svd.check_rank(c[2], n_users or 0, n_items or 0)
+
+    def place(c, first, host):
+      # (first use: the parameter itself is the n x n matrix, and it has to fit what is free)
+      if first:
+        n_users, n_items = self._size_hints(train_dataset)
+        gfcf.check_memory(n_users or 0, n_items or 1, c[2], host().nnz)
+    return self._closed_form_fit(
+        gfcf, train_dataset, "gfcf_info", copy=lambda info: {k: v for k, v in info.items() if k != "V"},
+        check=lambda m: gfcf.check_config(m, _default(rank, m, "rank"), _default(alpha, m, "alpha"), oversample,
+                                          num_power_iterations, seed),                      # c = (rank, alpha, l)
+        hint_check=lambda c, u, n, host: n and sizes(c, u, n, 0, free_bytes=float("inf")),
+        log_line=lambda c: ("GF-CF: rank %d, alpha %g, l %d, %d power iterations, seed %d",) + c
+        + (num_power_iterations, seed),
+        store=lambda c: {"rank": c[0], "alpha": c[1]}, place=place,
+        size_check=lambda c, host: sizes(c, self.num_users, self.num_items, host().nnz, allocate_matrix=False),
+        fit=lambda m, pair, c: gfcf.fit(pair, c[0], c[1], int(oversample), int(num_power_iterations), int(seed),
+                                        out=m.item_weights.data)[-1])
 
   def train_rp3beta(self, train_dataset, alpha=None, beta=None, neighbours=None):
     """The closed-form RP3beta fit of a RandomWalkItemModel (recoder_amd/rp3.py): every item keeps its

@@ -494,6 +494,56 @@ class ShallowAutoencoder(ItemItemModel):
     return self.item_weights
 
 
+class GraphFilterModel(ItemItemModel):
+  """GF-CF (Shen et al. 2021, "How Powerful is Graph Convolution for Recommendation?"): the closed-form
+  graph-filter item model ``scores = input @ item_weights`` with
+  ``W = Rn^T Rn + alpha * D_I^-1/2 V V^T D_I^1/2`` over the normalised user-item graph
+  ``Rn = D_U^-1/2 R D_I^-1/2`` of the stored entries, V the top ``rank`` right singular vectors of Rn: a linear
+  filter plus an ideal low-pass filter, fitted by ``Recoder.train_gfcf`` (recoder_amd/gfcf.py).  W is not
+  symmetric and its diagonal is not zero (the masked top-k removes seen items anyway).
+
+  One parameter, ``item_weights`` [num_items, num_items], zero until fitted; ``rank`` and ``alpha`` travel in
+  ``model_params()``.  The defaults are the best Recall@20 of the float64 grid on the ML-20M slice
+  (profiles/gfcf_quality.jsonl); the paper's are rank 256, alpha 0.3.  There is nothing to descend on:
+  ``Recoder.train`` refuses this model and points at ``train_gfcf``.
+  """
+  fit_method = "train_gfcf"
+  fit_sentence = ("a GraphFilterModel is fitted in closed form from the normalised interaction graph: call "
+                  "%s(train_dataset)")
+
+  def __init__(self, rank=128, alpha=3.0):
+    super().__init__()
+    self.rank = rank
+    self.alpha = alpha
+    self.num_items = None
+    self.item_weights = None
+    self._validate()
+
+  def _validate(self):
+    from .gfcf import check_params
+    self.rank, self.alpha = check_params(self.rank, self.alpha)
+
+  def init_model(self, num_items=None, num_users=None):
+    self._validate()
+    self.num_items = num_items
+    self.item_weights = nn.Parameter(torch.zeros(num_items, num_items), requires_grad=False)
+
+  def model_params(self):
+    return {"rank": int(self.rank), "alpha": float(self.alpha)}
+
+  def load_model_params(self, model_params):
+    self.rank = int(model_params["rank"])
+    self.alpha = float(model_params["alpha"])
+    self._validate()
+
+  def csr_scores(self, csr, lo, hi, out, ld, n_rows):
+    from . import ease
+    return ease.scores(csr, self.item_weights.data, lo, hi, out=out, ld=ld, n_rows=n_rows)     # (rk_ease_scores)
+
+  def _dense_w(self):
+    return self.item_weights
+
+
 class _NeighbourListModel(ItemItemModel):
   """An item-item model stored as neighbour lists: ``item_neighbours`` int32 [num_items, neighbours],
   ``item_weights`` f32 of the same shape and ``neighbour_counts`` int32 [num_items].  A subclass names
