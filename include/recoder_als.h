@@ -211,6 +211,42 @@ int rk_als_lgcn_adam(float *E0, int32_t lde, const float *H, int32_t ldh, const 
                      float *M, float *V, int32_t rows, int32_t h, float lr, float beta1, float beta2, float eps,
                      int32_t t, void *stream);
 
+/* the largest T of rk_als_gcl_contrast (its workspace holds the T x T scores) */
+#define RK_ALS_GCL_MAX_BATCH 4096
+
+/*
+ * rk_als_lgcn_propagate with SimGCL's noise in its epilogue: with x the row rk_als_lgcn_propagate gives, bit
+ * for bit,
+ *   Out[r, :h] = x + eps * sign(x) * u[r] / |u[r]|_2       (sign(0) = 0: a row without entries stays +0)
+ * and Acc accumulates this perturbed Out.  u[r, c] in (0, 1) is a counter hash of (seed, step, view, layer,
+ * side, r, c) kept apart from the sampler's draws; |u[r]| is an integer sum, so Out depends on the key, the
+ * row and h alone -- not on the leading dimensions, the row range or the launch.  eps == 0 gives
+ * rk_als_lgcn_propagate's bits.  step >= 0; view and layer in 0..255; side 0 (user rows) or 1 (item rows).
+ */
+int rk_als_gcl_propagate(const int64_t *indptr, const int32_t *indices, const float *row_scale,
+                         const float *col_scale, int32_t row_lo, int32_t row_hi, const float *F, int32_t ldf,
+                         int32_t h, float *Out, int32_t ldo, float *Acc, int32_t lda, float acc_scale, float eps,
+                         int64_t seed, int32_t step, int32_t view, int32_t layer, int32_t side, void *stream);
+
+/* bytes of rk_als_gcl_contrast's workspace; -2 unless 1 <= T <= RK_ALS_GCL_MAX_BATCH and 1 <= h <= 512 */
+int64_t rk_als_gcl_contrast_workspace_bytes(int32_t T, int32_t h);
+
+/*
+ * SimGCL's contrast between two view tables V1 [n_rows, ld1] and V2 [n_rows, ld2] over keys (int32 [T],
+ * ascending, as rk_als_lgcn_scatter takes them).  Slot t is active when keys[t] lies in [0, n_rows) and differs
+ * from keys[t - 1]; with m active slots, z = v / |v| per row (0 for |v| = 0) and s_rs = z1_r . z2_s / tau,
+ *   loss[0] = (1 / m) sum_r (log sum_s exp(s_rs) - s_rr)     (over active r and s; 0 when m == 0)
+ *   count[0] = m
+ *   G1[key_r, :h] += weight * d loss / d V1[key_r],   G2 likewise      (other rows are not touched)
+ * The gradient of a row with |v| = 0 is taken as 0.  G1 and G2 may be the same table.  The workspace holds
+ * the T x T scores; loss, count, G1 and G2 are device memory.  A fixed summation order: the same inputs give
+ * the same bits.
+ */
+int rk_als_gcl_contrast(const int32_t *keys, int32_t T, int32_t n_rows, const float *V1, int32_t ld1,
+                        const float *V2, int32_t ld2, int32_t h, float tau, float weight, float *G1, int32_t ldg1,
+                        float *G2, int32_t ldg2, void *ws, int64_t ws_bytes, float *loss, int32_t *count,
+                        void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

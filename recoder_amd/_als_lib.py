@@ -1,6 +1,6 @@
 """ctypes binding of librecoder_als.so (the C ABI in include/recoder_als.h): implicit-feedback ALS
-for recoder_amd.als, the BPR step (rk_als_bpr_*) for recoder_amd.bpr and the LightGCN kernels
-(rk_als_lgcn_*) for recoder_amd.lightgcn.  Like _lib.py: plain pointers
+for recoder_amd.als, the BPR step (rk_als_bpr_*) for recoder_amd.bpr the LightGCN kernels
+(rk_als_lgcn_*) for recoder_amd.lightgcn and SimGCL's (rk_als_gcl_*) for recoder_amd.simgcl.  Like _lib.py: plain pointers
 and sizes, no torch types across the boundary, no CPU fallback."""
 import os
 
@@ -19,6 +19,7 @@ _P = c_void_p
 FORCE_STREAM = 1      # RK_ALS_FORCE_STREAM
 G_GLOBAL = 2          # RK_ALS_G_GLOBAL
 LGCN_LONG_ROW = 1024  # RK_ALS_LGCN_LONG_ROW
+GCL_MAX_BATCH = 4096  # RK_ALS_GCL_MAX_BATCH
 
 # name -> (restype, argtypes); every symbol include/recoder_als.h declares
 SIGNATURES = {
@@ -44,6 +45,11 @@ SIGNATURES = {
                                     _P]),
   "rk_als_lgcn_adam": (c_int32, [_P, c_int32, _P, c_int32, _P, c_float, _P, _P, c_int32, c_int32, c_float, c_float,
                                  c_float, c_float, c_int32, _P]),
+  "rk_als_gcl_propagate": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, _P, c_int32, c_int32, _P, c_int32, _P,
+                                     c_int32, c_float, c_float, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
+  "rk_als_gcl_contrast_workspace_bytes": (c_int64, [c_int32, c_int32]),
+  "rk_als_gcl_contrast": (c_int32, [_P, c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32, c_float, c_float, _P,
+                                    c_int32, _P, c_int32, _P, c_int64, _P, _P, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

@@ -24,6 +24,12 @@
 //                          lanes own columns; long rows by a workgroup of 16 waves each, in fixed parts
 //   rk_als_lgcn_scatter    the apply's segment walk, writing the gradient rows and the counts
 //   rk_als_lgcn_adam       one elementwise pass: the L2 term and the Adam update of a base table
+//
+// SimGCL on top of it (rk_als_gcl_*): the step of recoder_amd/simgcl.py adds
+//   rk_als_gcl_propagate   rk_als_lgcn_propagate's row pass (one template) with a counter-hash noise of length
+//                          eps added to every row in the epilogue
+//   rk_als_gcl_contrast    InfoNCE between two view tables over the distinct keys of a step: loss and gradient
+//                          rows, the T x T scores tiled through LDS; fixed summation orders, no atomics
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -798,15 +804,48 @@ __device__ __forceinline__ void lgcn_walk(const int32_t *__restrict__ indices, c
   }
 }
 
-// the three roundings after the sum: s * row_scale, + Acc, * acc_scale
-template <int VEC>
+// SimGCL's noise (rk_als_gcl_propagate; NOISE below): Out[r] = x + eps sign(x) u[r] / |u[r]|_2, x the row as
+// rk_als_lgcn_propagate rounds it.  u[r, c] = m 2^-24 with m the ODD 24-bit integer of a counter hash -- never 0,
+// exact in f32 -- and key a hash of (seed, step, view, layer, side): bit 31 of the low word is the domain
+// tag, a sampler slot is below 2^24.  sum_c m^2 < 2^57 is an INTEGER sum: any lanes, in any order, give
+// the same |u[r]|, so the noise depends on (key, row, h) alone.
+struct GclNoise {
+  uint64_t key;
+  float eps;
+};
+
+uint64_t gcl_key(int64_t seed, int32_t step, int32_t view, int32_t layer, int32_t side) {
+  const uint64_t low = 0x80000000ull | ((uint64_t)view << 16) | ((uint64_t)layer << 8) | (uint64_t)side;
+  return bpr_mix(bpr_mix((uint64_t)seed) ^ (((uint64_t)(uint32_t)step << 32) | low));
+}
+
+__device__ __forceinline__ uint64_t gcl_row_key(uint64_t key, int64_t r) { return bpr_mix(key + (uint64_t)r); }
+
+__device__ __forceinline__ uint32_t gcl_m(uint64_t row_key, int col) {
+  return ((uint32_t)(bpr_mix(row_key + (uint64_t)(uint32_t)col) >> 41) << 1) | 1u;
+}
+
+// eps / |u[r]|: the integer sum rounded once to f32, 2^-48 exact, a square root and a division
+__device__ __forceinline__ float gcl_scale(uint64_t ss, float eps) { return eps / sqrtf((float)ss * 0x1p-48f); }
+
+// the three roundings after the sum: s * row_scale, + Acc, * acc_scale; with NOISE one more before Acc:
+// fmaf(+-nscale, u, x) by the sign of x -- written as fmaf, so that no instance is left to contract it or
+// not -- or (x == 0) x itself as it stands
+template <int VEC, bool NOISE>
 __device__ __forceinline__ void lgcn_finish(typename LgVec<VEC>::T s, float rs, int64_t r, int ch,
                                             float *__restrict__ Out, int ldo, float *__restrict__ Acc, int lda,
-                                            float acc_scale) {
+                                            float acc_scale, const uint32_t (&m)[VEC], float nscale) {
   typedef typename LgVec<VEC>::T V;
   V o;
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) LgVec<VEC>::set(o, i, rs * LgVec<VEC>::get(s, i));
+  for (int i = 0; i < VEC; ++i) {
+    float x = rs * LgVec<VEC>::get(s, i);
+    if constexpr (NOISE) {
+      const float u = (float)m[i] * 0x1p-24f;
+      x = x > 0.f ? fmaf(nscale, u, x) : x < 0.f ? fmaf(-nscale, u, x) : x;
+    }
+    LgVec<VEC>::set(o, i, x);
+  }
   if (Out) *(V *)(Out + r * ldo + (int64_t)ch * VEC) = o;
   if (Acc) {
     V *p = (V *)(Acc + r * lda + (int64_t)ch * VEC);
@@ -819,11 +858,11 @@ __device__ __forceinline__ void lgcn_finish(typename LgVec<VEC>::T s, float rs, 
   }
 }
 
-template <int VEC, int NT>
+template <int VEC, int NT, bool NOISE>
 __global__ __launch_bounds__(256) void als_lgcn_propagate_kernel(
     const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const float *__restrict__ row_scale,
     const float *__restrict__ col_scale, int row_lo, int row_hi, const float *__restrict__ F, int ldf, int h,
-    int G, float *__restrict__ Out, int ldo, float *__restrict__ Acc, int lda, float acc_scale) {
+    int G, float *__restrict__ Out, int ldo, float *__restrict__ Acc, int lda, float acc_scale, GclNoise nz) {
   typedef typename LgVec<VEC>::T V;
   const int nch = (h + VEC - 1) / VEC;                   // (VEC 4: h is a multiple of 4)
   const int rpb = 256 / G;                               // rows of a workgroup = its groups
@@ -837,21 +876,39 @@ __global__ __launch_bounds__(256) void als_lgcn_propagate_kernel(
   for (int q = 0; q < NT; ++q) acc[q] = LgVec<VEC>::zero();
   lgcn_walk<VEC, NT>(indices, col_scale, F, ldf, e0, e1, cg, G, nch, acc);
   const float rs = row_scale[r];
+  uint32_t m[NT][VEC];
+  float nscale = 0.f;
+  if constexpr (NOISE) {                                 // (a row's group leaves or stays as one: its lanes meet here)
+    const uint64_t row_key = gcl_row_key(nz.key, r);
+    uint64_t ss = 0;
+#pragma unroll
+    for (int q = 0; q < NT; ++q)
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        m[q][i] = cg + G * q < nch ? gcl_m(row_key, (cg + G * q) * VEC + i) : 0u;
+        ss += (uint64_t)m[q][i] * m[q][i];
+      }
+    for (int off = 32; off > 0; off >>= 1)
+      if (off < G) ss += __shfl_xor((unsigned long long)ss, off, 64);
+    nscale = gcl_scale(ss, nz.eps);
+  }
 #pragma unroll
   for (int q = 0; q < NT; ++q)
-    if (cg + G * q < nch) lgcn_finish<VEC>(acc[q], rs, r, cg + G * q, Out, ldo, Acc, lda, acc_scale);
+    if (cg + G * q < nch)
+      lgcn_finish<VEC, NOISE>(acc[q], rs, r, cg + G * q, Out, ldo, Acc, lda, acc_scale, m[q], nscale);
 }
 
 // Workgroups of 16 waves over the long rows: workgroup b looks at the rows row_lo + b, + gridDim.x, ... (two
 // indptr loads each; long rows that sit side by side go to different workgroups) and sums the long ones,
 // one at a time; a short row is als_lgcn_propagate_kernel's.
-template <int VEC, int NT>
+template <int VEC, int NT, bool NOISE>
 __global__ __launch_bounds__(LG_LONG_THREADS) void als_lgcn_propagate_long_kernel(
     const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const float *__restrict__ row_scale,
     const float *__restrict__ col_scale, int row_lo, int row_hi, const float *__restrict__ F, int ldf, int h, int G,
-    float *__restrict__ Out, int ldo, float *__restrict__ Acc, int lda, float acc_scale) {
+    float *__restrict__ Out, int ldo, float *__restrict__ Acc, int lda, float acc_scale, GclNoise nz) {
   typedef typename LgVec<VEC>::T V;
   extern __shared__ float4 lg_lds4[];                    // lg_parts(h) x h floats
+  __shared__ unsigned long long lg_ss[LG_LONG_THREADS / 64];      // (NOISE: the waves' sums of m^2)
   float *part = (float *)lg_lds4;
   const int nch = (h + VEC - 1) / VEC, parts = lg_parts(h);
   const int groups = LG_LONG_THREADS / G, grp = threadIdx.x / G, cg = threadIdx.x % G;
@@ -868,7 +925,26 @@ __global__ __launch_bounds__(LG_LONG_THREADS) void als_lgcn_propagate_long_kerne
       for (int q = 0; q < NT; ++q)
         if (cg + G * q < nch) *(V *)(part + (int64_t)p * nch * VEC + (cg + G * q) * VEC) = acc[q];
     }
+    uint64_t row_key = 0;
+    if constexpr (NOISE) {                               // thread c squares column c (h <= 512 < the threads)
+      row_key = gcl_row_key(nz.key, r);
+      uint64_t ss = 0;
+      for (int c = threadIdx.x; c < h; c += LG_LONG_THREADS) {
+        const uint64_t mc = gcl_m(row_key, c);
+        ss += mc * mc;
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor((unsigned long long)ss, off, 64);
+      if ((threadIdx.x & 63) == 0) lg_ss[threadIdx.x >> 6] = ss;
+    }
     __syncthreads();
+    float nscale = 0.f;
+    if constexpr (NOISE) {
+      uint64_t ss = 0;
+#pragma unroll
+      for (int w = 0; w < LG_LONG_THREADS / 64; ++w) ss += lg_ss[w];
+      nscale = gcl_scale(ss, nz.eps);
+    }
     const float rs = row_scale[r];
     for (int ch = threadIdx.x; ch < nch; ch += LG_LONG_THREADS) {
       V sum = *(const V *)(part + ch * VEC);
@@ -877,9 +953,12 @@ __global__ __launch_bounds__(LG_LONG_THREADS) void als_lgcn_propagate_long_kerne
 #pragma unroll
         for (int i = 0; i < VEC; ++i) LgVec<VEC>::set(sum, i, LgVec<VEC>::get(sum, i) + LgVec<VEC>::get(t, i));
       }
-      lgcn_finish<VEC>(sum, rs, r, ch, Out, ldo, Acc, lda, acc_scale);
+      uint32_t m[VEC];
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) m[i] = NOISE ? gcl_m(row_key, ch * VEC + i) : 0u;
+      lgcn_finish<VEC, NOISE>(sum, rs, r, ch, Out, ldo, Acc, lda, acc_scale, m, nscale);
     }
-    __syncthreads();                                     // (the next long row reuses the parts)
+    __syncthreads();                                     // (the next long row reuses the parts and the sums)
   }
 }
 
@@ -967,6 +1046,236 @@ __global__ __launch_bounds__(256) void als_lgcn_adam_kernel(float *__restrict__ 
   M[x] = m;
   Vv[x] = v;
   E0[r * lde + k] = fmaf(-step, m / fmaf(sqrtf(v), isb2, eps), e);
+}
+
+// ------------------------------------------------------------------------ gcl
+// The contrast of SimGCL over the sorted keys of a step (rk_als_gcl_contrast).  Slot t is ACTIVE when its key lies
+// in the table and differs from the key before it; nothing is compacted: an inactive slot holds zero rows
+// and is masked out of every sum, so all sums run over ascending slots and the bits depend on the inputs
+// alone.  With z = v / |v| (0 for |v| = 0) per active slot, S = Z1 Z2^T / tau and m active slots:
+//   als_gcl_gather_kernel  a wave per slot: act, 1 / |v|, the rows of Z1 and Z2
+//   als_gcl_gemm_kernel    64 x 64 (dZ: 16 x 64) tiles, k in steps of 16 through LDS, one fmaf chain per
+//                          output over k ascending: S (SCORES), then dZ1 = (P Z2 - Z2) / (tau m)
+//                          (P = exp(S - lse) formed as the tile is staged) and dZ2 = (P^T Z1 - Z1) / (tau m)
+//   als_gcl_lse_kernel     a wave per row: the row's maximum, then lse = max + log sum exp(S - max)
+//   als_gcl_loss_kernel    one workgroup: m and the loss (1 / m) sum (lse_r - S_rr)
+//   als_gcl_write_kernel   a wave per active slot: dv = (dz - z (z . dz)) / |v| for both views, and
+//                          G[key] += weight dv.  Active keys are distinct: plain stores, no atomics
+constexpr int GCL_MAX_T = RK_ALS_GCL_MAX_BATCH;
+constexpr int GCL_TILE = 64, GCL_DZ_ROWS = 16, GCL_KT = 16, GCL_LD = GCL_TILE + 4;
+
+struct GclWs {
+  float *Z1, *Z2, *dZ1, *dZ2, *S, *inv1, *inv2, *lse, *term;
+  int32_t *act;
+};
+
+int64_t gcl_ws_floats(int64_t T, int64_t h, GclWs *w, float *base) {
+  int64_t off = 0;
+  auto cut = [&](int64_t n) {
+    float *p = base ? base + off : nullptr;
+    off += (n + 63) / 64 * 64;
+    return p;
+  };
+  GclWs v;
+  v.Z1 = cut(T * h), v.Z2 = cut(T * h), v.dZ1 = cut(T * h), v.dZ2 = cut(T * h), v.S = cut(T * T);
+  v.inv1 = cut(T), v.inv2 = cut(T), v.lse = cut(T), v.term = cut(T);
+  v.act = (int32_t *)cut(T);
+  if (w) *w = v;
+  return off;
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void als_gcl_gather_kernel(const int32_t *__restrict__ keys, int T, int n_rows,
+                                                             const float *__restrict__ V1, int ld1,
+                                                             const float *__restrict__ V2, int ld2, int h,
+                                                             GclWs w) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const int key = keys[t];
+  const bool act = key >= 0 && key < n_rows && (t == 0 || keys[t - 1] != key);       // (wave-uniform)
+  float a[NT], b[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int k = lane + 64 * q;
+    a[q] = (act && k < h) ? V1[(int64_t)key * ld1 + k] : 0.f;
+    b[q] = (act && k < h) ? V2[(int64_t)key * ld2 + k] : 0.f;
+  }
+  const float sa = wave_dot<NT>(a, a), sb = wave_dot<NT>(b, b);
+  const float ia = sa > 0.f ? 1.f / sqrtf(sa) : 0.f, ib = sb > 0.f ? 1.f / sqrtf(sb) : 0.f;
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int k = lane + 64 * q;
+    if (k < h) {
+      w.Z1[(int64_t)t * h + k] = a[q] * ia;
+      w.Z2[(int64_t)t * h + k] = b[q] * ib;
+    }
+  }
+  if (lane == 0) {
+    w.inv1[t] = ia;
+    w.inv2[t] = ib;
+    w.act[t] = act ? 1 : 0;
+  }
+}
+
+// C [M, N] tile (blockIdx.y, blockIdx.x) = sum_k A[i, k] B[k, j], k < Kn ascending.
+//   SCORES:  A = Z1 [T, h], B^T = Z2 [T, h] (B[k, j] = Z2[j, k]), C = S = sum / tau                M = N = T, Kn = h
+//   DZ1:     A[i, k] = P[i, k], B = Z2 [T, h], C = dZ1 = (sum - Z2[i]) c                          M = Kn = T, N = h
+//   DZ2:     A[i, k] = P[k, i], B = Z1 [T, h], C = dZ2 = (sum - Z1[i]) c
+// P[r, s] = exp(S[r, s] - lse[r]) for active r and s, else 0; c = 1 / (tau m), m read from mcount.
+enum { GCL_SCORES = 0, GCL_DZ1 = 1, GCL_DZ2 = 2 };
+
+// A tile is TM rows by 64 columns, TM / 16 x 4 outputs a thread: 64 rows for S, 16 for dZ, whose grid is only
+// (h / 64) wide -- at T = 2048, h = 64 that is 128 workgroups, not 32.  The chains do not depend on TM.
+template <int MODE, int TM>
+__global__ __launch_bounds__(256) void als_gcl_gemm_kernel(int T, int h, float tau, const int32_t *__restrict__ mcount,
+                                                           GclWs w) {
+  constexpr int XR = TM / 16;                            // rows of a thread = A elements it stages per k-step
+  __shared__ float As[GCL_KT][GCL_LD], Bs[GCL_KT][GCL_LD];
+  const int M = T, N = MODE == GCL_SCORES ? T : h, Kn = MODE == GCL_SCORES ? h : T;
+  const int i0 = blockIdx.y * TM, j0 = blockIdx.x * GCL_TILE;
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const float *Zb = MODE == GCL_DZ2 ? w.Z1 : w.Z2;
+  float acc[XR][4];
+#pragma unroll
+  for (int a = 0; a < XR; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+  for (int k0 = 0; k0 < Kn; k0 += GCL_KT) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                        // B: 16 x 64
+      const int e = threadIdx.x + 256 * j;
+      if (MODE == GCL_SCORES) {                          // (row-major over k: 16 consecutive k of a row of Z2)
+        const int row = e >> 4, kk = e & 15, k = k0 + kk;
+        Bs[kk][row] = (j0 + row < N && k < Kn) ? w.Z2[(int64_t)(j0 + row) * h + k] : 0.f;
+      } else {                                           // (64 consecutive columns of slot k)
+        const int kk = e >> 6, col = e & 63, k = k0 + kk;
+        Bs[kk][col] = (k < Kn && j0 + col < N) ? Zb[(int64_t)k * h + j0 + col] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < XR; ++j) {                       // A: 16 x TM
+      const int e = threadIdx.x + 256 * j;
+      if (MODE == GCL_SCORES) {
+        const int row = e >> 4, kk = e & 15, k = k0 + kk;
+        As[kk][row] = (i0 + row < M && k < Kn) ? w.Z1[(int64_t)(i0 + row) * h + k] : 0.f;
+      } else {                                           // consecutive lanes along S's rows (its columns s)
+        const int ai = MODE == GCL_DZ1 ? e >> 4 : e % TM, ak = MODE == GCL_DZ1 ? e & 15 : e / TM;
+        const int r = MODE == GCL_DZ1 ? i0 + ai : k0 + ak, sl = MODE == GCL_DZ1 ? k0 + ak : i0 + ai;
+        const bool in = r < T && sl < T && w.act[r] && w.act[sl];
+        As[ak][ai] = in ? expf(w.S[(int64_t)r * T + sl] - w.lse[r]) : 0.f;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < GCL_KT; ++kk) {
+      const float4 b4 = *(const float4 *)&Bs[kk][tx * 4];
+      const float b[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+      for (int x = 0; x < XR; ++x) {
+        const float a = As[kk][ty * XR + x];
+#pragma unroll
+        for (int y = 0; y < 4; ++y) acc[x][y] = fmaf(a, b[y], acc[x][y]);
+      }
+    }
+    __syncthreads();
+  }
+  const float c = MODE == GCL_SCORES ? 1.f / tau : 1.f / (tau * (float)max(mcount[0], 1));
+  float *C = MODE == GCL_SCORES ? w.S : MODE == GCL_DZ1 ? w.dZ1 : w.dZ2;
+#pragma unroll
+  for (int x = 0; x < XR; ++x) {
+    const int i = i0 + ty * XR + x;
+#pragma unroll
+    for (int y = 0; y < 4; ++y) {
+      const int j = j0 + tx * 4 + y;
+      if (i < M && j < N)
+        C[(int64_t)i * N + j] = MODE == GCL_SCORES ? acc[x][y] * c : (acc[x][y] - Zb[(int64_t)i * h + j]) * c;
+    }
+  }
+}
+
+// lane l owns the columns l, l + 64, ...: its maximum, then its chain of exp(S - max) from +0, each met by the
+// xor butterfly; term = lse - S[r, r].  An inactive row: lse = term = 0.
+__global__ __launch_bounds__(256) void als_gcl_lse_kernel(int T, GclWs w) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= T) return;
+  if (!w.act[r]) {                                       // (wave-uniform)
+    if (lane == 0) w.lse[r] = w.term[r] = 0.f;
+    return;
+  }
+  const float *row = w.S + (int64_t)r * T;
+  float mx = -INFINITY;
+  for (int s = lane; s < T; s += 64)
+    if (w.act[s]) mx = fmaxf(mx, row[s]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  float sum = 0.f;                                       // (mx is finite: column r itself is active)
+  for (int s = lane; s < T; s += 64)
+    if (w.act[s]) sum += expf(row[s] - mx);
+  sum = wave_sum(sum);
+  if (lane == 0) {
+    const float lse = mx + logf(sum);
+    w.lse[r] = lse;
+    w.term[r] = lse - row[r];
+  }
+}
+
+// thread t adds the slots t, t + 256, ... in ascending order, then the tree of als_objective_final_kernel
+__global__ __launch_bounds__(256) void als_gcl_loss_kernel(int T, GclWs w, float *__restrict__ loss,
+                                                           int32_t *__restrict__ mcount) {
+  __shared__ float red[256];
+  __shared__ int cnt[256];
+  const int tid = threadIdx.x;
+  float s = 0.f;
+  int c = 0;
+  for (int t = tid; t < T; t += 256) {
+    s += w.term[t];
+    c += w.act[t];
+  }
+  red[tid] = s;
+  cnt[tid] = c;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) {
+      red[tid] += red[tid + off];
+      cnt[tid] += cnt[tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    mcount[0] = cnt[0];
+    loss[0] = cnt[0] > 0 ? red[0] / (float)cnt[0] : 0.f;
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void als_gcl_write_kernel(const int32_t *__restrict__ keys, int T, int h,
+                                                            float weight, GclWs w, float *G1, int ldg1, float *G2,
+                                                            int ldg2) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T || !w.act[t]) return;                       // (wave-uniform)
+  const int key = keys[t];
+#pragma unroll
+  for (int view = 0; view < 2; ++view) {                 // (view 1 after view 0: G1 and G2 may be one table)
+    const float *Z = view ? w.Z2 : w.Z1, *dZ = view ? w.dZ2 : w.dZ1;
+    const float inv = view ? w.inv2[t] : w.inv1[t];
+    float *row = (view ? G2 + (int64_t)key * ldg2 : G1 + (int64_t)key * ldg1);
+    float z[NT], d[NT];
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int k = lane + 64 * q;
+      z[q] = k < h ? Z[(int64_t)t * h + k] : 0.f;
+      d[q] = k < h ? dZ[(int64_t)t * h + k] : 0.f;
+    }
+    const float zd = wave_dot<NT>(z, d);
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int k = lane + 64 * q;
+      if (k < h) row[k] += weight * (fmaf(-zd, z[q], d[q]) * inv);
+    }
+  }
 }
 
 int64_t bpr_round256(int64_t x) { return (x + 255) / 256 * 256; }
@@ -1148,23 +1457,19 @@ extern "C" int rk_als_bpr_apply(const int32_t *keys, const int64_t *order, int32
 
 #define ALS_LGCN_PROP_LAUNCH(VEC, NT)                                                                          \
   do {                                                                                                         \
-    hipLaunchKernelGGL((als_lgcn_propagate_kernel<VEC, NT>), grid, dim3(256), 0, st, indptr, indices, row_scale, \
-                       col_scale, row_lo, row_hi, F, ldf, h, G, Out, ldo, Acc, lda, acc_scale);                \
-    hipLaunchKernelGGL((als_lgcn_propagate_long_kernel<VEC, NT>), long_grid, dim3(LG_LONG_THREADS), lds, st,   \
-                       indptr, indices, row_scale, col_scale, row_lo, row_hi, F, ldf, h, G, Out, ldo, Acc, lda, \
-                       acc_scale);                                                                             \
+    hipLaunchKernelGGL((als_lgcn_propagate_kernel<VEC, NT, NOISE>), grid, dim3(256), 0, st, indptr, indices,   \
+                       row_scale, col_scale, row_lo, row_hi, F, ldf, h, G, Out, ldo, Acc, lda, acc_scale, nz); \
+    hipLaunchKernelGGL((als_lgcn_propagate_long_kernel<VEC, NT, NOISE>), long_grid, dim3(LG_LONG_THREADS), lds, \
+                       st, indptr, indices, row_scale, col_scale, row_lo, row_hi, F, ldf, h, G, Out, ldo, Acc, \
+                       lda, acc_scale, nz);                                                                    \
   } while (0)
 
-extern "C" int rk_als_lgcn_propagate(const int64_t *indptr, const int32_t *indices, const float *row_scale,
-                                     const float *col_scale, int32_t row_lo, int32_t row_hi, const float *F,
-                                     int32_t ldf, int32_t h, float *Out, int32_t ldo, float *Acc, int32_t lda,
-                                     float acc_scale, void *stream) {
-  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldf >= h, "1 <= h <= 512, ldf >= h");
-  RK_SIDE_REQUIRE(row_lo >= 0 && row_hi >= row_lo, "0 <= row_lo <= row_hi");
-  RK_SIDE_REQUIRE(Out || Acc, "at least one of Out / Acc must be set");
-  RK_SIDE_REQUIRE((!Out || ldo >= h) && (!Acc || lda >= h), "ldo >= h, lda >= h");
-  if (row_hi == row_lo) return 0;
-  RK_SIDE_REQUIRE(indptr && indices && row_scale && col_scale && F, "null pointer");
+// the row pass of rk_als_lgcn_propagate (NOISE false) and rk_als_gcl_propagate (true): both launches
+template <bool NOISE>
+void lgcn_propagate_launch(const int64_t *indptr, const int32_t *indices, const float *row_scale,
+                           const float *col_scale, int32_t row_lo, int32_t row_hi, const float *F, int32_t ldf,
+                           int32_t h, float *Out, int32_t ldo, float *Acc, int32_t lda, float acc_scale, GclNoise nz,
+                           hipStream_t st) {
   // 16-byte accesses when every row of every matrix starts on a 16-byte boundary and holds whole float4s
   const bool vec = h % 4 == 0 && ldf % 4 == 0 && (uintptr_t)F % 16 == 0 &&
                    (!Out || (ldo % 4 == 0 && (uintptr_t)Out % 16 == 0)) &&
@@ -1177,7 +1482,6 @@ extern "C" int rk_als_lgcn_propagate(const int64_t *indptr, const int32_t *indic
   const dim3 grid((unsigned)(((int64_t)row_hi - row_lo + rpb - 1) / rpb));
   const dim3 long_grid((unsigned)std::min<int64_t>((int64_t)row_hi - row_lo, LG_LONG_GRID));
   const size_t lds = (size_t)lg_parts(h) * h * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
   if (vec) {
     if (nt == 1) ALS_LGCN_PROP_LAUNCH(4, 1);
     else ALS_LGCN_PROP_LAUNCH(4, 2);
@@ -1189,7 +1493,92 @@ extern "C" int rk_als_lgcn_propagate(const int64_t *indptr, const int32_t *indic
       default: ALS_LGCN_PROP_LAUNCH(1, 8); break;
     }
   }
+}
+
+extern "C" int rk_als_lgcn_propagate(const int64_t *indptr, const int32_t *indices, const float *row_scale,
+                                     const float *col_scale, int32_t row_lo, int32_t row_hi, const float *F,
+                                     int32_t ldf, int32_t h, float *Out, int32_t ldo, float *Acc, int32_t lda,
+                                     float acc_scale, void *stream) {
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldf >= h, "1 <= h <= 512, ldf >= h");
+  RK_SIDE_REQUIRE(row_lo >= 0 && row_hi >= row_lo, "0 <= row_lo <= row_hi");
+  RK_SIDE_REQUIRE(Out || Acc, "at least one of Out / Acc must be set");
+  RK_SIDE_REQUIRE((!Out || ldo >= h) && (!Acc || lda >= h), "ldo >= h, lda >= h");
+  if (row_hi == row_lo) return 0;
+  RK_SIDE_REQUIRE(indptr && indices && row_scale && col_scale && F, "null pointer");
+  lgcn_propagate_launch<false>(indptr, indices, row_scale, col_scale, row_lo, row_hi, F, ldf, h, Out, ldo, Acc, lda,
+                               acc_scale, GclNoise{0, 0.f}, (hipStream_t)stream);
   RK_SIDE_CHECK_LAUNCH("als_lgcn_propagate");
+  return 0;
+}
+
+extern "C" int rk_als_gcl_propagate(const int64_t *indptr, const int32_t *indices, const float *row_scale,
+                                    const float *col_scale, int32_t row_lo, int32_t row_hi, const float *F,
+                                    int32_t ldf, int32_t h, float *Out, int32_t ldo, float *Acc, int32_t lda,
+                                    float acc_scale, float eps, int64_t seed, int32_t step, int32_t view,
+                                    int32_t layer, int32_t side, void *stream) {
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldf >= h, "1 <= h <= 512, ldf >= h");
+  RK_SIDE_REQUIRE(row_lo >= 0 && row_hi >= row_lo, "0 <= row_lo <= row_hi");
+  RK_SIDE_REQUIRE(Out || Acc, "at least one of Out / Acc must be set");
+  RK_SIDE_REQUIRE((!Out || ldo >= h) && (!Acc || lda >= h), "ldo >= h, lda >= h");
+  RK_SIDE_REQUIRE(eps >= 0.f && eps < INFINITY, "eps must be finite and >= 0");
+  RK_SIDE_REQUIRE(step >= 0 && view >= 0 && view <= 255 && layer >= 0 && layer <= 255 && (side == 0 || side == 1),
+                  "step >= 0, view and layer in 0..255, side is 0 (users) or 1 (items)");
+  if (row_hi == row_lo) return 0;
+  RK_SIDE_REQUIRE(indptr && indices && row_scale && col_scale && F, "null pointer");
+  lgcn_propagate_launch<true>(indptr, indices, row_scale, col_scale, row_lo, row_hi, F, ldf, h, Out, ldo, Acc, lda,
+                              acc_scale, GclNoise{gcl_key(seed, step, view, layer, side), eps}, (hipStream_t)stream);
+  RK_SIDE_CHECK_LAUNCH("als_gcl_propagate");
+  return 0;
+}
+
+extern "C" int64_t rk_als_gcl_contrast_workspace_bytes(int32_t T, int32_t h) {
+  if (T < 1 || T > GCL_MAX_T || h < 1 || h > MAX_H) return -2;
+  return gcl_ws_floats(T, h, nullptr, nullptr) * (int64_t)sizeof(float);
+}
+
+#define ALS_GCL_GATHER_LAUNCH(NT) \
+  hipLaunchKernelGGL(als_gcl_gather_kernel<NT>, waves, dim3(256), 0, st, keys, T, n_rows, V1, ld1, V2, ld2, h, w)
+#define ALS_GCL_WRITE_LAUNCH(NT) \
+  hipLaunchKernelGGL(als_gcl_write_kernel<NT>, waves, dim3(256), 0, st, keys, T, h, weight, w, G1, ldg1, G2, ldg2)
+
+extern "C" int rk_als_gcl_contrast(const int32_t *keys, int32_t T, int32_t n_rows, const float *V1, int32_t ld1,
+                                   const float *V2, int32_t ld2, int32_t h, float tau, float weight, float *G1,
+                                   int32_t ldg1, float *G2, int32_t ldg2, void *ws, int64_t ws_bytes, float *loss,
+                                   int32_t *count, void *stream) {
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ld1 >= h && ld2 >= h && ldg1 >= h && ldg2 >= h,
+                  "1 <= h <= 512, ld1, ld2, ldg1, ldg2 >= h");
+  RK_SIDE_REQUIRE(T >= 1 && T <= GCL_MAX_T && n_rows >= 1, "1 <= T <= 4096, n_rows >= 1");
+  RK_SIDE_REQUIRE(tau > 0.f && tau < INFINITY && weight >= 0.f && weight < INFINITY,
+                  "tau must be finite and > 0, weight finite and >= 0");
+  RK_SIDE_REQUIRE(ws && ws_bytes >= rk_als_gcl_contrast_workspace_bytes(T, h), "workspace too small");
+  RK_SIDE_REQUIRE((uintptr_t)ws % 16 == 0, "the workspace must start on a 16-byte boundary");
+  RK_SIDE_REQUIRE(keys && V1 && V2 && G1 && G2 && loss && count, "null pointer");
+  GclWs w;
+  gcl_ws_floats(T, h, &w, (float *)ws);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 waves((unsigned)((T + 3) / 4));
+  const unsigned tt = (unsigned)((T + GCL_TILE - 1) / GCL_TILE), th = (unsigned)((h + GCL_TILE - 1) / GCL_TILE);
+  const unsigned td = (unsigned)((T + GCL_DZ_ROWS - 1) / GCL_DZ_ROWS);
+  switch (nt_of(h)) {
+    case 1: ALS_GCL_GATHER_LAUNCH(1); break;
+    case 2: ALS_GCL_GATHER_LAUNCH(2); break;
+    case 4: ALS_GCL_GATHER_LAUNCH(4); break;
+    default: ALS_GCL_GATHER_LAUNCH(8); break;
+  }
+  RK_SIDE_CHECK_LAUNCH("als_gcl_gather");
+  hipLaunchKernelGGL((als_gcl_gemm_kernel<GCL_SCORES, GCL_TILE>), dim3(tt, tt), dim3(256), 0, st, T, h, tau, count, w);
+  hipLaunchKernelGGL(als_gcl_lse_kernel, waves, dim3(256), 0, st, T, w);
+  hipLaunchKernelGGL(als_gcl_loss_kernel, dim3(1), dim3(256), 0, st, T, w, loss, count);
+  hipLaunchKernelGGL((als_gcl_gemm_kernel<GCL_DZ1, GCL_DZ_ROWS>), dim3(th, td), dim3(256), 0, st, T, h, tau, count, w);
+  hipLaunchKernelGGL((als_gcl_gemm_kernel<GCL_DZ2, GCL_DZ_ROWS>), dim3(th, td), dim3(256), 0, st, T, h, tau, count, w);
+  RK_SIDE_CHECK_LAUNCH("als_gcl_gemm");
+  switch (nt_of(h)) {
+    case 1: ALS_GCL_WRITE_LAUNCH(1); break;
+    case 2: ALS_GCL_WRITE_LAUNCH(2); break;
+    case 4: ALS_GCL_WRITE_LAUNCH(4); break;
+    default: ALS_GCL_WRITE_LAUNCH(8); break;
+  }
+  RK_SIDE_CHECK_LAUNCH("als_gcl_write");
   return 0;
 }
 

@@ -37,30 +37,32 @@ def check_not_distributed():
   als.check_not_distributed("train_lightgcn runs on one GPU: multi-GPU LightGCN is not implemented")
 
 
-def check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed):
+def check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed, method="train_lightgcn",
+                 max_batch=bpr.MAX_BATCH):
   """The LightGCN contract, checked before any GPU work; returns (num_layers, num_epochs, batch_size, lr, reg,
-  seed)."""
+  seed).  ``method`` names the caller in the messages and ``max_batch`` bounds its batches
+  (recoder_amd/simgcl.py trains the same model under the same contract)."""
   if not isinstance(model, MatrixFactorization):
-    raise ValueError("train_lightgcn trains a MatrixFactorization, not %s" % type(model).__name__)
+    raise ValueError("%s trains a MatrixFactorization, not %s" % (method, type(model).__name__))
   if model.activation_type != "none":
-    raise ValueError("train_lightgcn needs activation_type='none' (got %r)" % (model.activation_type,))
+    raise ValueError("%s needs activation_type='none' (got %r)" % (method, model.activation_type))
   if model.dropout_prob and model.dropout_prob > 0:
-    raise ValueError("train_lightgcn needs dropout_prob == 0 (got %r)" % (model.dropout_prob,))
+    raise ValueError("%s needs dropout_prob == 0 (got %r)" % (method, model.dropout_prob))
   h = model.embedding_size
   if not isinstance(h, (int, np.integer)) or not 1 <= h <= MAX_H:
-    raise ValueError("train_lightgcn supports embedding sizes 1..%d (got %r)" % (MAX_H, h))
+    raise ValueError("%s supports embedding sizes 1..%d (got %r)" % (method, MAX_H, h))
   if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not -2 ** 63 <= seed < 2 ** 63:
     raise ValueError("seed must be an integer that fits 64 bits (got %r)" % (seed,))
   return (_count("num_layers", num_layers, 1, MAX_LAYERS), _count("num_epochs", num_epochs, 0),
-          _count("batch_size", batch_size, 1, bpr.MAX_BATCH), _number("lr", lr, True), _number("reg", reg, False),
+          _count("batch_size", batch_size, 1, max_batch), _number("lr", lr, True), _number("reg", reg, False),
           int(seed))
 
 
-def check_resume(state, num_layers, shapes=None):
+def check_resume(state, num_layers, shapes=None, method="train_lightgcn"):
   """ValueError unless ``state`` (a ``lightgcn_state``) can continue a fit with ``num_layers`` layers on base
   tables of ``shapes`` = ((users, h), (items, h)) (None: not known yet)."""
   if state is None:
-    raise ValueError("resume=True needs the state of an earlier train_lightgcn on this Recoder (there is none)")
+    raise ValueError("resume=True needs the state of an earlier %s on this Recoder (there is none)" % method)
   if state["num_layers"] != num_layers:
     raise ValueError("resume=True continues a fit with num_layers = %d (got %d)" % (state["num_layers"], num_layers))
   if shapes is not None:

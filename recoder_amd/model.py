@@ -99,6 +99,8 @@ class Recoder(object):
     self.bpr_history = []       # train_bpr: the mean loss per valid triple of each epoch
     self.lightgcn_history = []  # train_lightgcn: the mean loss per valid triple of each epoch
     self.lightgcn_state = None  # train_lightgcn: base tables, Adam moments, step count, num_layers (device; not saved)
+    self.simgcl_history = []    # train_simgcl: (mean BPR loss per valid triple, mean NCE per step) of each epoch
+    self.simgcl_state = None    # train_simgcl: base tables, Adam moments, step count, num_layers (device; not saved)
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -456,7 +458,7 @@ class Recoder(object):
 
   def _closed_form_fit(self, mod, train_dataset, keep, check, log_line, fit, hint_check=None, check_values=False,
                        store=None, place=None, size_check=None, csrs=None, copy=dict):
-    """The one sequence behind the ten ``train_*`` methods below: ``mod`` is the fit module, the callables say
+    """The one sequence behind the eleven ``train_*`` methods below: ``mod`` is the fit module, the callables say
     what differs, ``cfg`` is what ``check`` returned and ``host()`` the dataset's host matrix, built at the step
     that first asks for it.  The order decides which exception wins, and a call that raises in A-D leaves the
     Recoder and the model as they were:
@@ -572,6 +574,42 @@ class Recoder(object):
         lightgcn, train_dataset, "lightgcn_history", copy=list, check=check, fit=fit,
         log_line=lambda c: ("LightGCN: %d layers, %d epochs of batches of %d, lr %g, reg %g, seed %d",) + c,
         size_check=lambda c, host: lightgcn.check_data(host().nnz, self.num_items, c[1], c[2]))
+
+  def train_simgcl(self, train_dataset, num_layers=2, num_epochs=10, batch_size=1024, lr=0.002, reg=1e-3,
+                   cl_weight=0.1, cl_eps=0.2, cl_temperature=0.2, seed=0, resume=False):
+    """SimGCL (Yu et al. 2022) for a MatrixFactorization with activation 'none' (recoder_amd/simgcl.py):
+    LightGCN's propagation with the mean over the layers 1..``num_layers`` (layer 0 is left out), trained on
+    BPR's triples (the draws of ``train_bpr`` and ``train_lightgcn`` for the same seed, step and slot) plus
+    ``cl_weight`` times an InfoNCE term at temperature ``cl_temperature`` between two views of the batch's
+    distinct users and of its distinct positive items; a view adds a random vector of length ``cl_eps``, in the
+    orthant of the row, to every row after every layer.  No graph is augmented.  Adam at learning rate ``lr``,
+    the L2 term ``reg`` on the base rows a triple touches; ``batch_size`` is at most ``simgcl.MAX_BATCH``.  The
+    base tables of a first call are the tables as they stand; they, both Adam moments, the step count and
+    ``num_layers`` stay in ``simgcl_state`` (device tensors, not part of a checkpoint), and ``resume=True``
+    continues from them with the draws, noise, moments and step count one longer call would have had.  The
+    model's tables end as the clean tables and the bias as 0: ``save_state``, ``recommend``, ``evaluate``,
+    ``train``, ``train_als`` and ``train_bpr`` take them as they are.  The stored values and the configured
+    ``loss`` play no part.  Returns (and keeps in ``simgcl_history``) one (mean BPR loss per valid triple, mean
+    NCE_users + NCE_items per step) pair per epoch."""
+    from . import simgcl
+
+    def check(m):
+      c = simgcl.check_config(m, num_layers, num_epochs, batch_size, lr, reg, cl_weight, cl_eps, cl_temperature,
+                              seed)
+      if resume:
+        simgcl.check_resume(self.simgcl_state, c[0])
+      return c
+
+    def fit(m, pair, c):
+      # (a fresh state replaces the kept one only once the fit's own checks have passed)
+      self.simgcl_state, hist = simgcl.fit(*_mf_tables(m), m.bias.data, *pair, *c,
+                                           state=self.simgcl_state if resume else None)
+      return hist
+    return self._closed_form_fit(
+        simgcl, train_dataset, "simgcl_history", copy=list, check=check, fit=fit,
+        log_line=lambda c: ("SimGCL: %d layers, %d epochs of batches of %d, lr %g, reg %g, cl_weight %g, eps %g, "
+                            "temperature %g, seed %d",) + c,
+        size_check=lambda c, host: simgcl.check_data(host().nnz, self.num_items, c[1], c[2]))
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
