@@ -247,6 +247,28 @@ int rk_als_gcl_contrast(const int32_t *keys, int32_t T, int32_t n_rows, const fl
                         float *G2, int32_t ldg2, void *ws, int64_t ws_bytes, float *loss, int32_t *count,
                         void *stream);
 
+/* bytes of rk_als_dau_grad's workspace; -2 unless 1 <= T <= RK_ALS_GCL_MAX_BATCH and 1 <= h <= 512 */
+int64_t rk_als_dau_workspace_bytes(int32_t T, int32_t h);
+
+/*
+ * DirectAU's loss and its gradient rows over the T slots (users[t], items[t]) of a step, at the final tables
+ * X [n_users, ldx] and Y [n_items, ldy].  Slot t is valid when both ids lie in their tables; with m valid slots,
+ * a_t = X[users[t]] / |.|, b_t = Y[items[t]] / |.| (0 for a row of norm 0), and for either side's rows z
+ *   e_pq = exp(-2 |z_p - z_q|^2) (|z|^2 taken as 1, or 0 for a zero row),  E = sum_{p < q} e_pq over valid slots
+ * (a repeated id is a slot of its own):
+ *   loss[0] = (1 / m) sum_t |a_t - b_t|^2                     (0 when m == 0)
+ *   loss[1] = log(2 E / (m (m - 1))) over the a_t,  loss[2] likewise over the b_t      (0 when m < 2)
+ *   count[0] = m,  valid[t] = 1.0 or 0.0
+ *   DU[t, :h] = d (loss[0] + (gamma / 2) (loss[1] + loss[2])) / d X[users[t]] taken through slot t alone,
+ *   DI[t, :h] likewise for Y[items[t]]: rk_als_lgcn_scatter with roles = 1 and g = valid sums them per row.
+ * The rows of an invalid slot are 0, and so is the row of a table row of norm 0.  DU, DI (f32 [T, h]), valid
+ * (f32 [T]), loss (f32 [3]) and count (int32 [1]) are device memory; the workspace holds one T x T tile of the
+ * e_pq, used for the users and then for the items.  A fixed summation order: the same inputs give the same bits.
+ */
+int rk_als_dau_grad(const int32_t *users, const int32_t *items, int32_t T, int32_t n_users, int32_t n_items,
+                    const float *X, int32_t ldx, const float *Y, int32_t ldy, int32_t h, float gamma, void *ws,
+                    int64_t ws_bytes, float *DU, float *DI, float *valid, float *loss, int32_t *count, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

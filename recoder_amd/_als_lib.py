@@ -1,7 +1,7 @@
 """ctypes binding of librecoder_als.so (the C ABI in include/recoder_als.h): implicit-feedback ALS
 for recoder_amd.als, the BPR step (rk_als_bpr_*) for recoder_amd.bpr the LightGCN kernels
-(rk_als_lgcn_*) for recoder_amd.lightgcn and SimGCL's (rk_als_gcl_*) for recoder_amd.simgcl.  Like _lib.py: plain pointers
-and sizes, no torch types across the boundary, no CPU fallback."""
+(rk_als_lgcn_*) for recoder_amd.lightgcn, SimGCL's (rk_als_gcl_*) for recoder_amd.simgcl and DirectAU's
+(rk_als_dau_*) for recoder_amd.directau.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
 import os
 
 # PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
@@ -50,6 +50,9 @@ SIGNATURES = {
   "rk_als_gcl_contrast_workspace_bytes": (c_int64, [c_int32, c_int32]),
   "rk_als_gcl_contrast": (c_int32, [_P, c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32, c_float, c_float, _P,
                                     c_int32, _P, c_int32, _P, c_int64, _P, _P, _P]),
+  "rk_als_dau_workspace_bytes": (c_int64, [c_int32, c_int32]),
+  "rk_als_dau_grad": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32, c_float, _P,
+                                c_int64, _P, _P, _P, _P, _P, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

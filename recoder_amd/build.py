@@ -12,7 +12,9 @@ librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recode
                    same model (rk_als_bpr_*: sample, grad, apply) and the LightGCN kernels
                    (rk_als_lgcn_*: propagate, scatter, adam) that train it over the user-item graph
                    and SimGCL's on top of them (rk_als_gcl_*: the propagation with noise in its epilogue,
-                   the contrast between two views)
+                   the contrast between two views) and DirectAU's (rk_als_dau_workspace_bytes,
+                   rk_als_dau_grad: the alignment and uniformity loss with its gradient rows, on the contrast's
+                   tile code)
 librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own
 librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencoder

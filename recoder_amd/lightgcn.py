@@ -38,10 +38,11 @@ def check_not_distributed():
 
 
 def check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed, method="train_lightgcn",
-                 max_batch=bpr.MAX_BATCH):
+                 max_batch=bpr.MAX_BATCH, min_layers=1):
   """The LightGCN contract, checked before any GPU work; returns (num_layers, num_epochs, batch_size, lr, reg,
-  seed).  ``method`` names the caller in the messages and ``max_batch`` bounds its batches
-  (recoder_amd/simgcl.py trains the same model under the same contract)."""
+  seed).  ``method`` names the caller in the messages, ``max_batch`` bounds its batches and ``min_layers`` its
+  layers (recoder_amd/simgcl.py and recoder_amd/directau.py train the same model under the same contract; the
+  latter also without a layer)."""
   if not isinstance(model, MatrixFactorization):
     raise ValueError("%s trains a MatrixFactorization, not %s" % (method, type(model).__name__))
   if model.activation_type != "none":
@@ -53,7 +54,7 @@ def check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed, metho
     raise ValueError("%s supports embedding sizes 1..%d (got %r)" % (method, MAX_H, h))
   if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not -2 ** 63 <= seed < 2 ** 63:
     raise ValueError("seed must be an integer that fits 64 bits (got %r)" % (seed,))
-  return (_count("num_layers", num_layers, 1, MAX_LAYERS), _count("num_epochs", num_epochs, 0),
+  return (_count("num_layers", num_layers, min_layers, MAX_LAYERS), _count("num_epochs", num_epochs, 0),
           _count("batch_size", batch_size, 1, max_batch), _number("lr", lr, True), _number("reg", reg, False),
           int(seed))
 

@@ -101,6 +101,8 @@ class Recoder(object):
     self.lightgcn_state = None  # train_lightgcn: base tables, Adam moments, step count, num_layers (device; not saved)
     self.simgcl_history = []    # train_simgcl: (mean BPR loss per valid triple, mean NCE per step) of each epoch
     self.simgcl_state = None    # train_simgcl: base tables, Adam moments, step count, num_layers (device; not saved)
+    self.directau_history = []  # train_directau: (alignment, uniformity users, uniformity items) means of each epoch
+    self.directau_state = None  # train_directau: base tables, Adam moments, step count, num_layers (device; not saved)
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -458,7 +460,7 @@ class Recoder(object):
 
   def _closed_form_fit(self, mod, train_dataset, keep, check, log_line, fit, hint_check=None, check_values=False,
                        store=None, place=None, size_check=None, csrs=None, copy=dict):
-    """The one sequence behind the eleven ``train_*`` methods below: ``mod`` is the fit module, the callables say
+    """The one sequence behind the twelve ``train_*`` methods below: ``mod`` is the fit module, the callables say
     what differs, ``cfg`` is what ``check`` returned and ``host()`` the dataset's host matrix, built at the step
     that first asks for it.  The order decides which exception wins, and a call that raises in A-D leaves the
     Recoder and the model as they were:
@@ -610,6 +612,42 @@ class Recoder(object):
         log_line=lambda c: ("SimGCL: %d layers, %d epochs of batches of %d, lr %g, reg %g, cl_weight %g, eps %g, "
                             "temperature %g, seed %d",) + c,
         size_check=lambda c, host: simgcl.check_data(host().nnz, self.num_items, c[1], c[2]))
+
+  def train_directau(self, train_dataset, num_layers=2, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3,
+                     gamma=0.2, seed=0, resume=False):
+    """DirectAU (Wang et al. 2022) for a MatrixFactorization with activation 'none' (recoder_amd/directau.py):
+    no negatives are drawn.  A step takes the (user, stored item) pairs of BPR's draws (those of ``train_bpr``,
+    ``train_lightgcn`` and ``train_simgcl`` for the same seed, step and slot), normalises their rows of the final
+    tables to unit length and descends the mean squared distance of a pair (alignment) plus ``gamma`` / 2 times
+    the uniformity -- the logarithm of the mean of exp(-2 distance^2) over the pairs of slots -- of the batch's
+    user rows and of its item rows.  The final tables are LightGCN's mean over ``num_layers`` + 1 layers;
+    ``num_layers = 0`` trains the tables themselves (DirectAU-MF) and propagates nothing.  Adam at learning rate
+    ``lr``, the L2 term ``reg`` on the base rows a slot touches; ``batch_size`` is at most ``directau.MAX_BATCH``.
+    The base tables of a first call are the tables as they stand; they, both Adam moments, the step count and
+    ``num_layers`` stay in ``directau_state`` (device tensors, not part of a checkpoint), and ``resume=True``
+    continues from them with the draws, moments and step count one longer call would have had.  The model's
+    tables end as the final tables, un-normalised (a user scores by the plain dot product, as in the paper's
+    code), and the bias as 0: ``save_state``, ``recommend``, ``evaluate``, ``train``, ``train_als`` and
+    ``train_bpr`` take them as they are.  The stored values and the configured ``loss`` play no part.  Returns
+    (and keeps in ``directau_history``) one (alignment, uniformity of the users, uniformity of the items) triple
+    of per-step means per epoch."""
+    from . import directau
+
+    def check(m):
+      c = directau.check_config(m, num_layers, num_epochs, batch_size, lr, reg, gamma, seed)
+      if resume:
+        directau.check_resume(self.directau_state, c[0])
+      return c
+
+    def fit(m, pair, c):
+      # (a fresh state replaces the kept one only once the fit's own checks have passed)
+      self.directau_state, hist = directau.fit(*_mf_tables(m), m.bias.data, *pair, *c,
+                                               state=self.directau_state if resume else None)
+      return hist
+    return self._closed_form_fit(
+        directau, train_dataset, "directau_history", copy=list, check=check, fit=fit,
+        log_line=lambda c: ("DirectAU: %d layers, %d epochs of batches of %d, lr %g, reg %g, gamma %g, seed %d",) + c,
+        size_check=lambda c, host: directau.check_data(host().nnz, self.num_items, c[1], c[2]))
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
