@@ -203,14 +203,18 @@ def grad(users, pos, neg, X, Y, bias, g, loss, D, P, x=None):
                                      ptr(D), ptr(P), current_stream()), "rk_als_bpr_grad")
 
 
+def masked_keys(ids, valid, n_rows):
+  """``ids`` with the key past the table (it sorts last) where ``valid`` is false."""
+  return torch.where(valid, ids, torch.full_like(ids, n_rows))
+
+
 def sorted_keys(users, pos, neg, n_users, n_items):
   """((user keys, order), (item keys, order)): the T user keys and the 2T item keys -- slot t as positive,
   slot t as negative, slot t + 1 ... -- stably sorted by row on the device, so that a row's entries stay
   in ascending slot order; an invalid slot's entries carry the key past the table, and sort last."""
   valid = neg >= 0
-  ukey = torch.where(valid, users, torch.full_like(users, n_users))
   ikey = torch.where(valid[:, None], torch.stack([pos, neg], dim=1), torch.full_like(pos, n_items)[:, None])
-  uk, uo = torch.sort(ukey, stable=True)
+  uk, uo = torch.sort(masked_keys(users, valid, n_users), stable=True)
   ik, io = torch.sort(ikey.reshape(-1), stable=True)
   return (uk, uo), (ik, io)
 

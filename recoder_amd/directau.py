@@ -22,8 +22,8 @@ import torch
 from . import _als_lib, als, bpr, lightgcn, simgcl
 from ._lib import ptr
 from .bpr import _f32, _i32, _number
-from .device import DEVICE_HBM_BYTES, current_stream
-from .lightgcn import _table, adam, new_state, scatter
+from .device import current_stream
+from .lightgcn import _table, new_state, scatter  # noqa: F401  (new_state: this module's too)
 
 MAX_H = als.MAX_H                         # rk_als_max_h()
 MAX_LAYERS = lightgcn.MAX_LAYERS
@@ -41,8 +41,7 @@ def check_not_distributed():
 def check_config(model, num_layers, num_epochs, batch_size, lr, reg, gamma, seed):
   """The DirectAU contract, checked before any GPU work; returns (num_layers, num_epochs, batch_size, lr, reg,
   gamma, seed).  ``num_layers`` may be 0."""
-  c = lightgcn.check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed, method="train_directau",
-                            max_batch=MAX_BATCH, min_layers=0)
+  c = lightgcn.check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed, METHOD)
   return c[:5] + (_number("gamma", gamma, False), c[5])
 
 
@@ -63,34 +62,24 @@ def grad_workspace_bytes(T, h):
   return base if base < 0 else base + 256
 
 
+def extra_bytes(n_users, n_items, h, T):
+  """The workspace of rk_als_dau_grad, the three losses and the count, and the keys of the two sorts of T entries
+  this step makes itself (an int32 key in, a key and an int64 position out, as much again for its scratch)."""
+  return grad_workspace_bytes(T, h) + 16 + 2 * 2 * T * (4 + 4 + 8)
+
+
 def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True, allocate_state=True, allocate_csrs=True):
   """Device bytes of a fit: what LightGCN's fit holds (``lightgcn.required_bytes``: its BPR workspace is where
-  the draws, the validity vector and both [T, h] gradient images live), the workspace of rk_als_dau_grad, the
-  three losses and the count, and the keys of the two sorts of T entries this step makes itself (an int32 key in,
-  a key and an int64 position out, as much again for its scratch)."""
-  return lightgcn.required_bytes(n_users, n_items, h, nnz, T, allocate_model, allocate_state, allocate_csrs) + \
-      grad_workspace_bytes(T, h) + 16 + 2 * 2 * int(T) * (4 + 4 + 8)
+  the draws, the validity vector and both [T, h] gradient images live) and ``extra_bytes``."""
+  return lightgcn.method_required_bytes(METHOD, n_users, n_items, h, nnz, T, allocate_model, allocate_state,
+                                        allocate_csrs)
 
 
 def check_memory(n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True, allocate_state=True,
                  allocate_csrs=True):
-  """ValueError naming the sizes and the bytes needed when the fit cannot fit: against one device's whole HBM
-  without touching a device, then (``free_bytes`` None: asked from the current device) against what is free."""
-  n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
-  if grad_workspace_bytes(T, h) < 0:
-    raise ValueError("DirectAU needs 1 <= batch_size <= %d and 1 <= h <= %d (got %d, %d)" % (MAX_BATCH, MAX_H, T, h))
-  whole = required_bytes(n_users, n_items, h, nnz, T)
-  if whole > DEVICE_HBM_BYTES:
-    raise ValueError("DirectAU over %d users x %d items at h = %d with %d entries and batches of %d needs %d "
-                     "bytes: more than one device's memory (%d bytes); multi-device fits are not implemented"
-                     % (n_users, n_items, h, nnz, T, whole, DEVICE_HBM_BYTES))
-  need = required_bytes(n_users, n_items, h, nnz, T, allocate_model, allocate_state, allocate_csrs)
-  if free_bytes is None:
-    free_bytes = torch.cuda.mem_get_info()[0]
-  if need > free_bytes:
-    raise ValueError("DirectAU over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes "
-                     "of device memory, %d are free" % (n_users, n_items, h, nnz, T, need, free_bytes))
-  return need
+  """``lightgcn.method_check_memory`` of DirectAU."""
+  return lightgcn.method_check_memory(METHOD, n_users, n_items, h, nnz, T, free_bytes, allocate_model, allocate_state,
+                                      allocate_csrs)
 
 
 # ------------------------------------------------------------------ kernels
@@ -126,55 +115,41 @@ class Workspace(lightgcn.Workspace):
 def sorted_keys(ids, valid, n_rows):
   """(keys, order) of one side's T slots, stably sorted by row on the device; an invalid slot carries the key
   past the table."""
-  return torch.sort(torch.where(valid > 0, ids, torch.full_like(ids, n_rows)), stable=True)
+  return torch.sort(bpr.masked_keys(ids, valid > 0, n_rows), stable=True)
 
 
-def step(X, Y, graph, state, ws, seed, step_index, lr, reg, gamma):
-  """One DirectAU step: the state's base tables and moments move, X / Y receive the final tables of the base
-  tables as they were at the START of the step; the draws of the step stay in ``ws.bpr``, its three losses in
-  ``ws.loss`` and its valid slots in ``ws.valid_count``."""
-  K, b = state["num_layers"], ws.bpr
-  T = b.T
-  lightgcn.forward(graph, state["E0"], K, ws.layers, (X, Y))
-  bpr.sample(graph.ucsr, seed, step_index, b.users, b.pos, b.neg)
-  grad(b.users, b.pos, X, Y, gamma, ws.raw, b.D, b.P, b.g, ws.loss, ws.valid_count)
+def gradient(X, Y, graph, state, ws, seed, step_index, hyper):
+  """rk_als_dau_grad at the draws (the negative is ignored) and the sum of its rows per table row; the three losses
+  of the step stay in ``ws.loss`` and its valid slots in ``ws.valid_count``."""
+  b = ws.bpr
+  grad(b.users, b.pos, X, Y, hyper[0], ws.raw, b.D, b.P, b.g, ws.loss, ws.valid_count)
   for t in ws.G + ws.count:
     t.zero_()
   for side, (ids, V) in enumerate(((b.users, b.D), (b.pos, b.P))):
     keys, order = sorted_keys(ids, b.g, ws.G[side].shape[0])
     # (scatter's weight of a roles = 1 entry is -g_t: the scale -1 undoes it, exactly)
     scatter(keys, order, 1, b.g, V, -1.0, ws.G[side], ws.count[side])
-  lightgcn.forward(graph, ws.G, K, ws.layers, ws.H)
-  state["step"] += 1
-  for side in (0, 1):
-    adam(state["E0"][side], ws.H[side], ws.count[side], reg / T, state["M"][side], state["V"][side], lr,
-         state["step"])
+
+
+def _sums_add(sums, ws):
+  sums[0] += ws.loss
+
+
+METHOD = lightgcn.Method(
+    "DirectAU", "train_directau", MAX_BATCH, 0, skip_layer0=False, gradient=gradient, sums=(((3,), torch.float64),),
+    sums_add=_sums_add, entry=lambda v, steps: tuple(x / steps for x in v), workspace=Workspace, extra_bytes=extra_bytes)
+
+
+def step(X, Y, graph, state, ws, seed, step_index, lr, reg, gamma):
+  """One DirectAU step (``lightgcn.method_step``); the draws of the step stay in ``ws.bpr``, its three losses in
+  ``ws.loss`` and its valid slots in ``ws.valid_count``."""
+  lightgcn.method_step(METHOD, X, Y, graph, state, ws, seed, step_index, lr, reg, (gamma,))
 
 
 # ---------------------------------------------------------------------- fit
 def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, gamma, seed=0, state=None,
         first_step=None):
-  """num_epochs epochs of ceil(nnz / batch_size) steps, in the manner of ``lightgcn.fit`` (``state``,
-  ``first_step``, the tables, the bias and the one host synchronisation per epoch as there).  Returns (state, one
-  (alignment, uniformity of the users, uniformity of the items) triple of per-step means per epoch)."""
-  steps = check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size)
-  if state is not None:
-    check_resume(state, num_layers, (X.shape, Y.shape))
-  check_memory(X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False,
-               allocate_state=state is None, allocate_csrs=False)
-  if state is None:
-    state = new_state(X, Y, num_layers)
-  graph = lightgcn.Graph(ucsr, icsr)
-  ws = Workspace(X.shape[0], Y.shape[0], int(batch_size), X.shape[1], X.device)
-  bias.zero_()
-  hist = []
-  s = state["step"] if first_step is None else int(first_step)
-  for _ in range(num_epochs):
-    total = torch.zeros(3, dtype=torch.float64, device=X.device)
-    for _ in range(steps):
-      step(X, Y, graph, state, ws, seed, s, lr, reg, gamma)
-      total += ws.loss
-      s += 1
-    hist.append(tuple(v / steps for v in total.cpu().tolist()))                     # (the synchronisation)
-  lightgcn.forward(graph, state["E0"], state["num_layers"], ws.layers, (X, Y))
-  return state, hist
+  """``lightgcn.method_fit`` of DirectAU.  Returns (state, one (alignment, uniformity of the users, uniformity of the
+  items) triple of per-step means per epoch)."""
+  return lightgcn.method_fit(METHOD, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, (gamma,),
+                             seed, state, first_step)

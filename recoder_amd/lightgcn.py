@@ -17,7 +17,13 @@ and takes one Adam step on both base tables.
 
 ``Recoder.train_lightgcn`` is the public entry point; the functions below are the layer under it (and what
 the tests and tools/lightgcn_bench.py drive directly).
+
+SimGCL (recoder_amd/simgcl.py) and DirectAU (recoder_amd/directau.py) train the same base tables over the same
+graph with the same sampler, backward propagation and Adam: the one memory check, step and fit of all three are
+``method_check_memory``, ``method_step`` and ``method_fit`` below, and a ``Method`` says what differs.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -37,25 +43,25 @@ def check_not_distributed():
   als.check_not_distributed("train_lightgcn runs on one GPU: multi-GPU LightGCN is not implemented")
 
 
-def check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed, method="train_lightgcn",
-                 max_batch=bpr.MAX_BATCH, min_layers=1):
+def check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed, method=None):
   """The LightGCN contract, checked before any GPU work; returns (num_layers, num_epochs, batch_size, lr, reg,
-  seed).  ``method`` names the caller in the messages, ``max_batch`` bounds its batches and ``min_layers`` its
-  layers (recoder_amd/simgcl.py and recoder_amd/directau.py train the same model under the same contract; the
-  latter also without a layer)."""
+  seed).  ``method`` (a ``Method``; None: LightGCN) names the caller in the messages and bounds its batches and
+  layers: recoder_amd/simgcl.py and recoder_amd/directau.py train the same model under the same contract."""
+  method = method or METHOD
+  name = method.method
   if not isinstance(model, MatrixFactorization):
-    raise ValueError("%s trains a MatrixFactorization, not %s" % (method, type(model).__name__))
+    raise ValueError("%s trains a MatrixFactorization, not %s" % (name, type(model).__name__))
   if model.activation_type != "none":
-    raise ValueError("%s needs activation_type='none' (got %r)" % (method, model.activation_type))
+    raise ValueError("%s needs activation_type='none' (got %r)" % (name, model.activation_type))
   if model.dropout_prob and model.dropout_prob > 0:
-    raise ValueError("%s needs dropout_prob == 0 (got %r)" % (method, model.dropout_prob))
+    raise ValueError("%s needs dropout_prob == 0 (got %r)" % (name, model.dropout_prob))
   h = model.embedding_size
   if not isinstance(h, (int, np.integer)) or not 1 <= h <= MAX_H:
-    raise ValueError("%s supports embedding sizes 1..%d (got %r)" % (method, MAX_H, h))
+    raise ValueError("%s supports embedding sizes 1..%d (got %r)" % (name, MAX_H, h))
   if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not -2 ** 63 <= seed < 2 ** 63:
     raise ValueError("seed must be an integer that fits 64 bits (got %r)" % (seed,))
-  return (_count("num_layers", num_layers, min_layers, MAX_LAYERS), _count("num_epochs", num_epochs, 0),
-          _count("batch_size", batch_size, 1, max_batch), _number("lr", lr, True), _number("reg", reg, False),
+  return (_count("num_layers", num_layers, method.min_layers, MAX_LAYERS), _count("num_epochs", num_epochs, 0),
+          _count("batch_size", batch_size, 1, method.max_batch), _number("lr", lr, True), _number("reg", reg, False),
           int(seed))
 
 
@@ -74,7 +80,7 @@ def check_resume(state, num_layers, shapes=None, method="train_lightgcn"):
 
 def check_data(nnz, n_items, num_epochs, batch_size):
   """What the sampler needs of the matrix (bpr.check_data under this method's name); returns the steps of one epoch."""
-  return bpr.check_data(nnz, n_items, num_epochs, batch_size, method="train_lightgcn")
+  return bpr.check_data(nnz, n_items, num_epochs, batch_size, method=METHOD.method)
 
 
 def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True, allocate_state=True, allocate_csrs=True):
@@ -91,26 +97,41 @@ def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True, allocate_st
       2 * 3 * T * (4 + 4 + 8)
 
 
-def check_memory(n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True, allocate_state=True,
-                 allocate_csrs=True):
+def method_required_bytes(method, n_users, n_items, h, nnz, T, allocate_model=True, allocate_state=True,
+                          allocate_csrs=True, **opts):
+  """``required_bytes`` and what ``method`` holds on top of it under its options ``opts``."""
+  return required_bytes(n_users, n_items, h, nnz, T, allocate_model, allocate_state, allocate_csrs) + \
+      method.extra_bytes(int(n_users), int(n_items), int(h), int(T), **opts)
+
+
+def method_check_memory(method, n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True,
+                        allocate_state=True, allocate_csrs=True, **opts):
   """ValueError naming the sizes and the bytes needed when the fit cannot fit: against one device's whole HBM
   without touching a device, then (``free_bytes`` None: asked from the current device) against what is free."""
   n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
-  if bpr.workspace_bytes(T, h) < 0:
-    raise ValueError("LightGCN needs 1 <= batch_size <= %d and 1 <= h <= %d (got %d, %d)"
-                     % (bpr.MAX_BATCH, MAX_H, T, h))
-  whole = required_bytes(n_users, n_items, h, nnz, T)
+  if not (1 <= T <= method.max_batch and 1 <= h <= MAX_H):               # (where the workspaces' bytes are negative)
+    raise ValueError("%s needs 1 <= batch_size <= %d and 1 <= h <= %d (got %d, %d)"
+                     % (method.name, method.max_batch, MAX_H, T, h))
+  whole = method_required_bytes(method, n_users, n_items, h, nnz, T, **opts)
   if whole > DEVICE_HBM_BYTES:
-    raise ValueError("LightGCN over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes: "
+    raise ValueError("%s over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes: "
                      "more than one device's memory (%d bytes); multi-device fits are not implemented"
-                     % (n_users, n_items, h, nnz, T, whole, DEVICE_HBM_BYTES))
-  need = required_bytes(n_users, n_items, h, nnz, T, allocate_model, allocate_state, allocate_csrs)
+                     % (method.name, n_users, n_items, h, nnz, T, whole, DEVICE_HBM_BYTES))
+  need = method_required_bytes(method, n_users, n_items, h, nnz, T, allocate_model, allocate_state, allocate_csrs,
+                               **opts)
   if free_bytes is None:
     free_bytes = torch.cuda.mem_get_info()[0]
   if need > free_bytes:
-    raise ValueError("LightGCN over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes "
-                     "of device memory, %d are free" % (n_users, n_items, h, nnz, T, need, free_bytes))
+    raise ValueError("%s over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes "
+                     "of device memory, %d are free" % (method.name, n_users, n_items, h, nnz, T, need, free_bytes))
   return need
+
+
+def check_memory(n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True, allocate_state=True,
+                 allocate_csrs=True):
+  """``method_check_memory`` of LightGCN."""
+  return method_check_memory(METHOD, n_users, n_items, h, nnz, T, free_bytes, allocate_model, allocate_state,
+                             allocate_csrs)
 
 
 def degree_scales(degrees):
@@ -134,9 +155,11 @@ def _table(t, h=None):
       (t.dtype, t.shape, t.stride())
 
 
-def propagate(csr, row_scale, col_scale, F, out=None, acc=None, acc_scale=1.0, row_lo=0, row_hi=None):
+def propagate(csr, row_scale, col_scale, F, out=None, acc=None, acc_scale=1.0, row_lo=0, row_hi=None, noise=None):
   """out[r] = row_scale[r] sum_j col_scale[col_j] F[col_j] and acc[r] = (acc[r] + out[r]) acc_scale for the rows
-  [row_lo, row_hi) of ``csr`` (rk_als_lgcn_propagate); either of ``out`` / ``acc`` may be None."""
+  [row_lo, row_hi) of ``csr`` (rk_als_lgcn_propagate); either of ``out`` / ``acc`` may be None.  ``noise`` = (eps,
+  seed, step, view, layer, side): SimGCL's noise of that key and length eps is added to every row of ``out`` (and
+  so to what ``acc`` accumulates) in the epilogue (rk_als_gcl_propagate)."""
   rows, cols = csr.shape
   row_hi = rows if row_hi is None else row_hi
   _table(F)
@@ -148,10 +171,15 @@ def propagate(csr, row_scale, col_scale, F, out=None, acc=None, acc_scale=1.0, r
       _table(t, h)
       assert t.shape[0] == rows and t.data_ptr() != F.data_ptr()
   lib = _als_lib.load()
-  _als_lib.check(lib.rk_als_lgcn_propagate(
-      ptr(csr.indptr), ptr(csr.indices), ptr(row_scale), ptr(col_scale), row_lo, row_hi, ptr(F), F.stride(0), h,
-      ptr(out), out.stride(0) if out is not None else 0, ptr(acc), acc.stride(0) if acc is not None else 0,
-      float(acc_scale), current_stream()), "rk_als_lgcn_propagate")
+  args = (ptr(csr.indptr), ptr(csr.indices), ptr(row_scale), ptr(col_scale), row_lo, row_hi, ptr(F), F.stride(0), h,
+          ptr(out), out.stride(0) if out is not None else 0, ptr(acc), acc.stride(0) if acc is not None else 0,
+          float(acc_scale))
+  if noise is None:
+    _als_lib.check(lib.rk_als_lgcn_propagate(*args, current_stream()), "rk_als_lgcn_propagate")
+  else:
+    eps, seed, step, view, layer, side = noise
+    _als_lib.check(lib.rk_als_gcl_propagate(*args, float(eps), int(seed), int(step), int(view), int(layer), int(side),
+                                            current_stream()), "rk_als_gcl_propagate")
 
 
 def scatter(keys, order, roles, g, V, scale, G, count):
@@ -201,70 +229,122 @@ def new_state(X, Y, num_layers):
           "step": 0, "num_layers": int(num_layers)}
 
 
-def forward(graph, base, num_layers, layers, out):
-  """out = the mean over the layers 0..K of ``base`` = (users' table, items' table) propagated over ``graph``;
-  ``layers`` are two pairs of buffers.  2 K propagations; the mean is formed in their epilogues."""
-  out[0].copy_(base[0])
-  out[1].copy_(base[1])
+def forward(graph, base, num_layers, layers, out, skip_layer0=False, noise=None):
+  """out = the mean over the layers 0..K (``skip_layer0``: 1..K) of ``base`` = (users' table, items' table)
+  propagated over ``graph``; ``layers`` are two pairs of buffers.  ``noise`` = (eps, seed, step, view): SimGCL's
+  view ``view`` of step ``step``, noise of length ``eps`` after every layer.  2 K propagations; the mean is formed
+  in their epilogues."""
+  for o, b in zip(out, base):
+    if skip_layer0:
+      o.zero_()
+    else:
+      o.copy_(b)
   cur = base
   for k in range(num_layers):
     last = k == num_layers - 1
     nxt = (None, None) if last else layers[k % 2]
-    scale = 1.0 / (num_layers + 1) if last else 1.0
-    propagate(graph.ucsr, graph.su, graph.si, cur[1], nxt[0], out[0], scale)
-    propagate(graph.icsr, graph.si, graph.su, cur[0], nxt[1], out[1], scale)
+    scale = 1.0 / (num_layers + (0 if skip_layer0 else 1)) if last else 1.0
+    for side, (csr, rs, cs) in enumerate(((graph.ucsr, graph.su, graph.si), (graph.icsr, graph.si, graph.su))):
+      propagate(csr, rs, cs, cur[1 - side], nxt[side], out[side], scale,
+                noise=None if noise is None else noise + (k + 1, side))
     cur = nxt
 
 
-def step(X, Y, graph, state, ws, seed, step_index, lr, reg):
-  """One LightGCN step: the state's base tables and moments move, X / Y receive the final tables of the base
-  tables as they were at the START of the step; the triples, g and loss of the step stay in ``ws.bpr``."""
-  K, b = state["num_layers"], ws.bpr
-  T = b.T
-  forward(graph, state["E0"], K, ws.layers, (X, Y))
-  bpr.sample(graph.ucsr, seed, step_index, b.users, b.pos, b.neg)
+def bpr_gradient(X, Y, ws):
+  """``ws.G`` / ``ws.count`` = the gradient of the mean softplus(-x_t) over the triples in ``ws.bpr`` with respect
+  to the tables X / Y, and the rows' counts; g and the loss of the triples stay in ``ws.bpr``.  Returns the sorted
+  user keys."""
+  b = ws.bpr
   bpr.grad(b.users, b.pos, b.neg, X, Y, ws.zero_bias, b.g, b.loss, b.D, b.P)
   (uk, uo), (ik, io) = bpr.sorted_keys(b.users, b.pos, b.neg, X.shape[0], Y.shape[0])
   for t in ws.G + ws.count:
     t.zero_()
-  scatter(uk, uo, 1, b.g, b.D, 1.0 / T, ws.G[0], ws.count[0])
-  scatter(ik, io, 2, b.g, b.P, 1.0 / T, ws.G[1], ws.count[1])
-  forward(graph, ws.G, K, ws.layers, ws.H)
+  scatter(uk, uo, 1, b.g, b.D, 1.0 / b.T, ws.G[0], ws.count[0])
+  scatter(ik, io, 2, b.g, b.P, 1.0 / b.T, ws.G[1], ws.count[1])
+  return uk
+
+
+def bpr_sums_add(sums, ws):
+  sums[0] += ws.bpr.loss.sum(dtype=torch.float64)
+  sums[1] += (ws.bpr.neg >= 0).sum()
+
+
+# What a method of this family says of itself; the loop below is shared:
+#   name, method, max_batch, min_layers   "LightGCN", "train_lightgcn" (so the messages call it), the bounds of its
+#                   batches and layers
+#   skip_layer0     the layer mean leaves layer 0 out
+#   gradient(X, Y, graph, state, ws, seed, step_index, hyper)   from the final tables X / Y and the draws in ``ws.bpr``
+#                   to the summed gradient in ``ws.G`` and the row counts in ``ws.count``; ``hyper`` is what follows
+#                   lr and reg among the hyperparameters
+#   sums, sums_add(sums, ws), entry(values, steps)   the (shape, dtype) of an epoch's running sums on the device, what
+#                   a step adds to them, and the history entry from their values on the host
+#   workspace(n_users, n_items, T, h, device, **opts), extra_bytes(n_users, n_items, h, T, **opts)   its ``Workspace``
+#                   and that workspace's device bytes on top of ``required_bytes``, under ``opts(*hyper)``
+Method = collections.namedtuple(
+    "Method", "name method max_batch min_layers skip_layer0 gradient sums sums_add entry workspace extra_bytes opts",
+    defaults=(Workspace, lambda n_users, n_items, h, T: 0, lambda *hyper: {}))
+
+BPR_SUMS = (((), torch.float64), ((), torch.int64))     # the summed loss and the valid triples
+METHOD = Method("LightGCN", "train_lightgcn", bpr.MAX_BATCH, 1, skip_layer0=False,
+                gradient=lambda X, Y, graph, state, ws, seed, step_index, hyper: bpr_gradient(X, Y, ws),
+                sums=BPR_SUMS, sums_add=bpr_sums_add, entry=lambda v, steps: v[0] / v[1] if v[1] else float("nan"))
+
+
+def method_step(method, X, Y, graph, state, ws, seed, step_index, lr, reg, hyper=()):
+  """One step of ``method``: the state's base tables and moments move, X / Y receive the final tables of the base
+  tables as they were at the START of the step; the draws of the step stay in ``ws.bpr``."""
+  K, b = state["num_layers"], ws.bpr
+  forward(graph, state["E0"], K, ws.layers, (X, Y), method.skip_layer0)
+  bpr.sample(graph.ucsr, seed, step_index, b.users, b.pos, b.neg)
+  method.gradient(X, Y, graph, state, ws, seed, step_index, hyper)
+  forward(graph, ws.G, K, ws.layers, ws.H, method.skip_layer0)
   state["step"] += 1
   for side in (0, 1):
-    adam(state["E0"][side], ws.H[side], ws.count[side], reg / T, state["M"][side], state["V"][side], lr,
+    adam(state["E0"][side], ws.H[side], ws.count[side], reg / b.T, state["M"][side], state["V"][side], lr,
          state["step"])
 
 
+def step(X, Y, graph, state, ws, seed, step_index, lr, reg):
+  """One LightGCN step (``method_step``); the triples, g and loss of the step stay in ``ws.bpr``."""
+  method_step(METHOD, X, Y, graph, state, ws, seed, step_index, lr, reg)
+
+
 # ---------------------------------------------------------------------- fit
-def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, seed=0, state=None, first_step=None):
-  """num_epochs epochs of ceil(nnz / batch_size) steps.  ``state`` None: a fresh state (``new_state``: the base
-  tables are X, Y as they stand), made once every check has passed; else an earlier fit's, continued.  Step s
-  of the fit draws as step ``first_step + s`` (None: the state's step count, so that a continued fit draws what
-  one longer fit would have).  The model's tables X [users, h], Y [items, h] (f32, row-major, may be strided)
-  end as the final tables of the last base tables, ``bias`` as 0.  Returns (state, the mean loss per valid
-  triple of each epoch: floats, nan for an epoch without one).  One host synchronisation per epoch."""
-  steps = check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size)
+def method_fit(method, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, hyper=(), seed=0,
+               state=None, first_step=None):
+  """num_epochs epochs of ceil(nnz / batch_size) steps of ``method``.  ``state`` None: a fresh state (``new_state``:
+  the base tables are X, Y as they stand), made once every check has passed; else an earlier fit's, continued.
+  Step s of the fit draws as step ``first_step + s`` (None: the state's step count, so that a continued fit draws
+  what one longer fit would have).  The model's tables X [users, h], Y [items, h] (f32, row-major, may be strided)
+  end as the final tables of the last base tables, ``bias`` as 0.  Returns (state, the history: ``method.entry`` of
+  each epoch's sums).  One host synchronisation per epoch."""
+  steps = bpr.check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size, method=method.method)
   if state is not None:
-    check_resume(state, num_layers, (X.shape, Y.shape))
-  check_memory(X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False,
-               allocate_state=state is None, allocate_csrs=False)
+    check_resume(state, num_layers, (X.shape, Y.shape), method=method.method)
+  opts = method.opts(*hyper)
+  method_check_memory(method, X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False,
+                      allocate_state=state is None, allocate_csrs=False, **opts)
   if state is None:
     state = new_state(X, Y, num_layers)
   graph = Graph(ucsr, icsr)
-  ws = Workspace(X.shape[0], Y.shape[0], int(batch_size), X.shape[1], X.device)
+  ws = method.workspace(X.shape[0], Y.shape[0], int(batch_size), X.shape[1], X.device, **opts)
   bias.zero_()
   hist = []
   s = state["step"] if first_step is None else int(first_step)
   for _ in range(num_epochs):
-    total = torch.zeros((), dtype=torch.float64, device=X.device)
-    count = torch.zeros((), dtype=torch.int64, device=X.device)
+    sums = [torch.zeros(shape, dtype=dtype, device=X.device) for shape, dtype in method.sums]
     for _ in range(steps):
-      step(X, Y, graph, state, ws, seed, s, lr, reg)
-      total += ws.bpr.loss.sum(dtype=torch.float64)
-      count += (ws.bpr.neg >= 0).sum()
+      method_step(method, X, Y, graph, state, ws, seed, s, lr, reg, hyper)
+      method.sums_add(sums, ws)
       s += 1
-    total, count = torch.stack([total, count.double()]).cpu().tolist()      # (the synchronisation)
-    hist.append(total / count if count else float("nan"))
-  forward(graph, state["E0"], state["num_layers"], ws.layers, (X, Y))
+    values = torch.cat([t.double().reshape(-1) for t in sums]).cpu().tolist()      # (the synchronisation)
+    hist.append(method.entry(values, steps))
+  forward(graph, state["E0"], state["num_layers"], ws.layers, (X, Y), method.skip_layer0)
   return state, hist
+
+
+def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, seed=0, state=None, first_step=None):
+  """``method_fit`` of LightGCN.  Returns (state, the mean loss per valid triple of each epoch: floats, nan for an
+  epoch without one)."""
+  return method_fit(METHOD, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, (), seed, state,
+                    first_step)

@@ -546,6 +546,27 @@ class Recoder(object):
         size_check=lambda c, host: bpr.check_data(host().nnz, self.num_items, c[0], c[1]),
         fit=lambda m, ucsr, c: bpr.fit(*_mf_tables(m), m.bias.data, ucsr, *c))
 
+  def _graph_fit(self, mod, prefix, train_dataset, resume, log_format, *config):
+    """``_closed_form_fit`` for the three methods that train base tables over the user-item graph (the driver of
+    recoder_amd/lightgcn.py): ``mod.check_config(model, *config)``, then with ``resume`` the kept
+    ``self.<prefix>_state`` checked and handed to ``mod.fit``; the history goes to ``self.<prefix>_history``."""
+    def check(m):
+      c = mod.check_config(m, *config)
+      if resume:
+        mod.check_resume(getattr(self, prefix + "_state"), c[0])
+      return c
+
+    def fit(m, pair, c):
+      # (a fresh state replaces the kept one only once the fit's own checks have passed)
+      state, hist = mod.fit(*_mf_tables(m), m.bias.data, *pair, *c,
+                            state=getattr(self, prefix + "_state") if resume else None)
+      setattr(self, prefix + "_state", state)
+      return hist
+    return self._closed_form_fit(
+        mod, train_dataset, prefix + "_history", copy=list, check=check, fit=fit,
+        log_line=lambda c: (log_format,) + c,
+        size_check=lambda c, host: mod.check_data(host().nnz, self.num_items, c[1], c[2]))
+
   def train_lightgcn(self, train_dataset, num_layers=3, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3, seed=0,
                      resume=False):
     """LightGCN (He et al. 2020) for a MatrixFactorization with activation 'none' (recoder_amd/lightgcn.py): the
@@ -560,22 +581,9 @@ class Recoder(object):
     values and the configured ``loss`` play no part.  Returns (and keeps in ``lightgcn_history``) the mean
     loss per valid triple of each epoch."""
     from . import lightgcn
-
-    def check(m):
-      c = lightgcn.check_config(m, num_layers, num_epochs, batch_size, lr, reg, seed)
-      if resume:
-        lightgcn.check_resume(self.lightgcn_state, c[0])
-      return c
-
-    def fit(m, pair, c):
-      # (a fresh state replaces the kept one only once the fit's own checks have passed)
-      self.lightgcn_state, hist = lightgcn.fit(*_mf_tables(m), m.bias.data, *pair, *c,
-                                               state=self.lightgcn_state if resume else None)
-      return hist
-    return self._closed_form_fit(
-        lightgcn, train_dataset, "lightgcn_history", copy=list, check=check, fit=fit,
-        log_line=lambda c: ("LightGCN: %d layers, %d epochs of batches of %d, lr %g, reg %g, seed %d",) + c,
-        size_check=lambda c, host: lightgcn.check_data(host().nnz, self.num_items, c[1], c[2]))
+    return self._graph_fit(lightgcn, "lightgcn", train_dataset, resume,
+                           "LightGCN: %d layers, %d epochs of batches of %d, lr %g, reg %g, seed %d",
+                           num_layers, num_epochs, batch_size, lr, reg, seed)
 
   def train_simgcl(self, train_dataset, num_layers=2, num_epochs=10, batch_size=1024, lr=0.002, reg=1e-3,
                    cl_weight=0.1, cl_eps=0.2, cl_temperature=0.2, seed=0, resume=False):
@@ -594,24 +602,10 @@ class Recoder(object):
     ``loss`` play no part.  Returns (and keeps in ``simgcl_history``) one (mean BPR loss per valid triple, mean
     NCE_users + NCE_items per step) pair per epoch."""
     from . import simgcl
-
-    def check(m):
-      c = simgcl.check_config(m, num_layers, num_epochs, batch_size, lr, reg, cl_weight, cl_eps, cl_temperature,
-                              seed)
-      if resume:
-        simgcl.check_resume(self.simgcl_state, c[0])
-      return c
-
-    def fit(m, pair, c):
-      # (a fresh state replaces the kept one only once the fit's own checks have passed)
-      self.simgcl_state, hist = simgcl.fit(*_mf_tables(m), m.bias.data, *pair, *c,
-                                           state=self.simgcl_state if resume else None)
-      return hist
-    return self._closed_form_fit(
-        simgcl, train_dataset, "simgcl_history", copy=list, check=check, fit=fit,
-        log_line=lambda c: ("SimGCL: %d layers, %d epochs of batches of %d, lr %g, reg %g, cl_weight %g, eps %g, "
-                            "temperature %g, seed %d",) + c,
-        size_check=lambda c, host: simgcl.check_data(host().nnz, self.num_items, c[1], c[2]))
+    return self._graph_fit(simgcl, "simgcl", train_dataset, resume,
+                           "SimGCL: %d layers, %d epochs of batches of %d, lr %g, reg %g, cl_weight %g, eps %g, "
+                           "temperature %g, seed %d",
+                           num_layers, num_epochs, batch_size, lr, reg, cl_weight, cl_eps, cl_temperature, seed)
 
   def train_directau(self, train_dataset, num_layers=2, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3,
                      gamma=0.2, seed=0, resume=False):
@@ -632,22 +626,9 @@ class Recoder(object):
     (and keeps in ``directau_history``) one (alignment, uniformity of the users, uniformity of the items) triple
     of per-step means per epoch."""
     from . import directau
-
-    def check(m):
-      c = directau.check_config(m, num_layers, num_epochs, batch_size, lr, reg, gamma, seed)
-      if resume:
-        directau.check_resume(self.directau_state, c[0])
-      return c
-
-    def fit(m, pair, c):
-      # (a fresh state replaces the kept one only once the fit's own checks have passed)
-      self.directau_state, hist = directau.fit(*_mf_tables(m), m.bias.data, *pair, *c,
-                                               state=self.directau_state if resume else None)
-      return hist
-    return self._closed_form_fit(
-        directau, train_dataset, "directau_history", copy=list, check=check, fit=fit,
-        log_line=lambda c: ("DirectAU: %d layers, %d epochs of batches of %d, lr %g, reg %g, gamma %g, seed %d",) + c,
-        size_check=lambda c, host: directau.check_data(host().nnz, self.num_items, c[1], c[2]))
+    return self._graph_fit(directau, "directau", train_dataset, resume,
+                           "DirectAU: %d layers, %d epochs of batches of %d, lr %g, reg %g, gamma %g, seed %d",
+                           num_layers, num_epochs, batch_size, lr, reg, gamma, seed)
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'

@@ -24,9 +24,9 @@ import torch
 
 from . import _als_lib, als, bpr, lightgcn
 from ._lib import ptr
-from .bpr import _f32, _i32, _number
-from .device import DEVICE_HBM_BYTES, current_stream
-from .lightgcn import _table, adam, new_state, scatter
+from .bpr import _f32, _i32, _number, _round256
+from .device import current_stream
+from .lightgcn import _table, new_state  # noqa: F401  (new_state: this module's too)
 
 MAX_H = als.MAX_H                         # rk_als_max_h()
 MAX_LAYERS = lightgcn.MAX_LAYERS
@@ -40,8 +40,7 @@ def check_not_distributed():
 def check_config(model, num_layers, num_epochs, batch_size, lr, reg, cl_weight, cl_eps, cl_temperature, seed):
   """The SimGCL contract, checked before any GPU work; returns (num_layers, num_epochs, batch_size, lr, reg,
   cl_weight, cl_eps, cl_temperature, seed)."""
-  c = lightgcn.check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed, method="train_simgcl",
-                            max_batch=MAX_BATCH)
+  c = lightgcn.check_config(model, num_layers, num_epochs, batch_size, lr, reg, seed, METHOD)
   return c[:5] + (_number("cl_weight", cl_weight, False), _number("cl_eps", cl_eps, False),
                   _number("cl_temperature", cl_temperature, True), c[5])
 
@@ -56,10 +55,6 @@ def check_data(nnz, n_items, num_epochs, batch_size):
   return bpr.check_data(nnz, n_items, num_epochs, batch_size, method="train_simgcl")
 
 
-def _round256(x):
-  return -(-int(x) // 256) * 256
-
-
 def contrast_workspace_bytes(T, h):
   """rk_als_gcl_contrast_workspace_bytes(T, h), restated on the host: four [T, h] images, the T x T scores and
   five vectors of T, each rounded up to 64 floats."""
@@ -69,37 +64,25 @@ def contrast_workspace_bytes(T, h):
   return 4 * _round256(4 * T * h) + _round256(4 * T * T) + 5 * _round256(4 * T)
 
 
+def extra_bytes(n_users, n_items, h, T, contrast=True):
+  """With ``contrast`` (cl_weight > 0): both views (2 (users + items) h floats), the contrast's workspace and the
+  third sort (the positive items: T entries, an int32 key in, a key and an int64 position out, as much again for
+  its scratch)."""
+  return 2 * (n_users + n_items) * h * 4 + contrast_workspace_bytes(T, h) + 2 * T * (4 + 4 + 8) if contrast else 0
+
+
 def required_bytes(n_users, n_items, h, nnz, T, contrast=True, allocate_model=True, allocate_state=True,
                    allocate_csrs=True):
-  """Device bytes of a fit: what LightGCN's fit holds (``lightgcn.required_bytes``) and, with ``contrast``
-  (cl_weight > 0), both views (2 (users + items) h floats), the contrast's workspace and the third sort (the
-  positive items: T entries, an int32 key in, a key and an int64 position out, as much again for its scratch)."""
-  base = lightgcn.required_bytes(n_users, n_items, h, nnz, T, allocate_model, allocate_state, allocate_csrs)
-  if not contrast:
-    return base
-  return base + 2 * (int(n_users) + int(n_items)) * int(h) * 4 + contrast_workspace_bytes(T, h) + \
-      2 * int(T) * (4 + 4 + 8)
+  """Device bytes of a fit: what LightGCN's fit holds (``lightgcn.required_bytes``) and ``extra_bytes``."""
+  return lightgcn.method_required_bytes(METHOD, n_users, n_items, h, nnz, T, allocate_model, allocate_state,
+                                        allocate_csrs, contrast=contrast)
 
 
 def check_memory(n_users, n_items, h, nnz, T, contrast=True, free_bytes=None, allocate_model=True,
                  allocate_state=True, allocate_csrs=True):
-  """ValueError naming the sizes and the bytes needed when the fit cannot fit: against one device's whole HBM
-  without touching a device, then (``free_bytes`` None: asked from the current device) against what is free."""
-  n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
-  if contrast_workspace_bytes(T, h) < 0:
-    raise ValueError("SimGCL needs 1 <= batch_size <= %d and 1 <= h <= %d (got %d, %d)" % (MAX_BATCH, MAX_H, T, h))
-  whole = required_bytes(n_users, n_items, h, nnz, T, contrast)
-  if whole > DEVICE_HBM_BYTES:
-    raise ValueError("SimGCL over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes: "
-                     "more than one device's memory (%d bytes); multi-device fits are not implemented"
-                     % (n_users, n_items, h, nnz, T, whole, DEVICE_HBM_BYTES))
-  need = required_bytes(n_users, n_items, h, nnz, T, contrast, allocate_model, allocate_state, allocate_csrs)
-  if free_bytes is None:
-    free_bytes = torch.cuda.mem_get_info()[0]
-  if need > free_bytes:
-    raise ValueError("SimGCL over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes "
-                     "of device memory, %d are free" % (n_users, n_items, h, nnz, T, need, free_bytes))
-  return need
+  """``lightgcn.method_check_memory`` of SimGCL."""
+  return lightgcn.method_check_memory(METHOD, n_users, n_items, h, nnz, T, free_bytes, allocate_model, allocate_state,
+                                      allocate_csrs, contrast=contrast)
 
 
 # ------------------------------------------------------------------ kernels
@@ -107,22 +90,8 @@ def propagate(csr, row_scale, col_scale, F, out=None, acc=None, acc_scale=1.0, e
               layer=0, side=0, row_lo=0, row_hi=None):
   """``lightgcn.propagate`` with the noise of (seed, step, view, layer, side) and length ``eps`` added to every
   row of ``out`` (and so to what ``acc`` accumulates) in the epilogue (rk_als_gcl_propagate)."""
-  rows, cols = csr.shape
-  row_hi = rows if row_hi is None else row_hi
-  _table(F)
-  h = F.shape[1]
-  assert F.shape[0] == cols and 0 <= row_lo <= row_hi <= rows and (out is not None or acc is not None)
-  _f32(row_scale, (rows,)), _f32(col_scale, (cols,))
-  for t in (out, acc):
-    if t is not None:
-      _table(t, h)
-      assert t.shape[0] == rows and t.data_ptr() != F.data_ptr()
-  lib = _als_lib.load()
-  _als_lib.check(lib.rk_als_gcl_propagate(
-      ptr(csr.indptr), ptr(csr.indices), ptr(row_scale), ptr(col_scale), row_lo, row_hi, ptr(F), F.stride(0), h,
-      ptr(out), out.stride(0) if out is not None else 0, ptr(acc), acc.stride(0) if acc is not None else 0,
-      float(acc_scale), float(eps), int(seed), int(step), int(view), int(layer), int(side), current_stream()),
-      "rk_als_gcl_propagate")
+  lightgcn.propagate(csr, row_scale, col_scale, F, out, acc, acc_scale, row_lo, row_hi,
+                     (eps, seed, step, view, layer, side))
 
 
 def contrast(keys, V1, V2, tau, weight, G1, G2, raw, loss, count):
@@ -161,82 +130,49 @@ class Workspace(lightgcn.Workspace):
 
 
 def forward(graph, base, num_layers, layers, out, eps=None, seed=0, step=0, view=0):
-  """out = the mean over the layers 1..K of ``base`` propagated over ``graph``: the clean tables (``eps`` None,
-  rk_als_lgcn_propagate), or view ``view`` of step ``step`` with noise of length ``eps`` after every layer.  2 K
-  propagations; the mean is formed in their epilogues."""
-  out[0].zero_()
-  out[1].zero_()
-  cur = base
-  for k in range(num_layers):
-    last = k == num_layers - 1
-    nxt = (None, None) if last else layers[k % 2]
-    scale = 1.0 / num_layers if last else 1.0
-    for side, (csr, rs, cs) in enumerate(((graph.ucsr, graph.su, graph.si), (graph.icsr, graph.si, graph.su))):
-      if eps is None:
-        lightgcn.propagate(csr, rs, cs, cur[1 - side], nxt[side], out[side], scale)
-      else:
-        propagate(csr, rs, cs, cur[1 - side], nxt[side], out[side], scale, eps, seed, step, view, k + 1, side)
-    cur = nxt
+  """out = the mean over the layers 1..K of ``base`` propagated over ``graph`` (``lightgcn.forward``): the clean
+  tables (``eps`` None), or view ``view`` of step ``step`` with noise of length ``eps`` after every layer."""
+  lightgcn.forward(graph, base, num_layers, layers, out, True, None if eps is None else (eps, seed, step, view))
 
 
-def step(X, Y, graph, state, ws, seed, step_index, lr, reg, cl_weight, cl_eps, cl_temperature):
-  """One SimGCL step: the state's base tables and moments move, X / Y receive the clean tables of the base tables
-  as they were at the START of the step; the triples, g and loss of the step stay in ``ws.bpr``, the two NCE
-  terms (users, items) in ``ws.cl_loss``."""
-  K, b = state["num_layers"], ws.bpr
-  T = b.T
-  E0 = state["E0"]
-  forward(graph, E0, K, ws.layers, (X, Y))
-  bpr.sample(graph.ucsr, seed, step_index, b.users, b.pos, b.neg)
-  bpr.grad(b.users, b.pos, b.neg, X, Y, ws.zero_bias, b.g, b.loss, b.D, b.P)
-  (uk, uo), (ik, io) = bpr.sorted_keys(b.users, b.pos, b.neg, X.shape[0], Y.shape[0])
-  for t in ws.G + ws.count:
-    t.zero_()
-  scatter(uk, uo, 1, b.g, b.D, 1.0 / T, ws.G[0], ws.count[0])
-  scatter(ik, io, 2, b.g, b.P, 1.0 / T, ws.G[1], ws.count[1])
+def gradient(X, Y, graph, state, ws, seed, step_index, hyper):
+  """LightGCN's gradient of the triples and, with cl_weight > 0, that of both contrasts on top of it: 4 K noisy
+  propagations and two rk_als_gcl_contrast calls; the two NCE terms (users, items) stay in ``ws.cl_loss``."""
+  cl_weight, cl_eps, cl_temperature = hyper
+  uk = lightgcn.bpr_gradient(X, Y, ws)
   if cl_weight > 0:
+    b = ws.bpr
     for a in (0, 1):
-      forward(graph, E0, K, ws.layers, ws.views[a], cl_eps, seed, step_index, a + 1)
-    pk = torch.sort(torch.where(b.neg >= 0, b.pos, torch.full_like(b.pos, Y.shape[0])))[0]
+      forward(graph, state["E0"], state["num_layers"], ws.layers, ws.views[a], cl_eps, seed, step_index, a + 1)
+    pk = torch.sort(bpr.masked_keys(b.pos, b.neg >= 0, Y.shape[0]))[0]
     for side, keys in enumerate((uk, pk)):
       contrast(keys, ws.views[0][side], ws.views[1][side], cl_temperature, cl_weight, ws.G[side], ws.G[side],
                ws.raw, ws.cl_loss[side:side + 1], ws.cl_count[side:side + 1])
-  forward(graph, ws.G, K, ws.layers, ws.H)
-  state["step"] += 1
-  for side in (0, 1):
-    adam(E0[side], ws.H[side], ws.count[side], reg / T, state["M"][side], state["V"][side], lr, state["step"])
+
+
+def _sums_add(sums, ws):
+  lightgcn.bpr_sums_add(sums, ws)
+  sums[2] += ws.cl_loss.sum(dtype=torch.float64)
+
+
+METHOD = lightgcn.Method(
+    "SimGCL", "train_simgcl", MAX_BATCH, 1, skip_layer0=True, gradient=gradient,
+    sums=lightgcn.BPR_SUMS + (((), torch.float64),), sums_add=_sums_add,
+    entry=lambda v, steps: (v[0] / v[1] if v[1] else float("nan"), v[2] / steps),
+    workspace=Workspace, extra_bytes=extra_bytes,
+    opts=lambda cl_weight, cl_eps, cl_temperature: {"contrast": cl_weight > 0})
+
+
+def step(X, Y, graph, state, ws, seed, step_index, lr, reg, cl_weight, cl_eps, cl_temperature):
+  """One SimGCL step (``lightgcn.method_step``): X / Y receive the clean tables; the triples, g and loss of the
+  step stay in ``ws.bpr``, the two NCE terms (users, items) in ``ws.cl_loss``."""
+  lightgcn.method_step(METHOD, X, Y, graph, state, ws, seed, step_index, lr, reg, (cl_weight, cl_eps, cl_temperature))
 
 
 # ---------------------------------------------------------------------- fit
 def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, cl_weight, cl_eps, cl_temperature,
         seed=0, state=None, first_step=None):
-  """num_epochs epochs of ceil(nnz / batch_size) steps, in the manner of ``lightgcn.fit`` (``state``,
-  ``first_step``, the tables, the bias and the one host synchronisation per epoch as there).  Returns (state,
-  one (mean BPR loss per valid triple, mean NCE_users + NCE_items per step) pair per epoch)."""
-  steps = check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size)
-  if state is not None:
-    check_resume(state, num_layers, (X.shape, Y.shape))
-  on = cl_weight > 0
-  check_memory(X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, on, allocate_model=False,
-               allocate_state=state is None, allocate_csrs=False)
-  if state is None:
-    state = new_state(X, Y, num_layers)
-  graph = lightgcn.Graph(ucsr, icsr)
-  ws = Workspace(X.shape[0], Y.shape[0], int(batch_size), X.shape[1], X.device, on)
-  bias.zero_()
-  hist = []
-  s = state["step"] if first_step is None else int(first_step)
-  for _ in range(num_epochs):
-    total = torch.zeros((), dtype=torch.float64, device=X.device)
-    cl = torch.zeros((), dtype=torch.float64, device=X.device)
-    count = torch.zeros((), dtype=torch.int64, device=X.device)
-    for _ in range(steps):
-      step(X, Y, graph, state, ws, seed, s, lr, reg, cl_weight, cl_eps, cl_temperature)
-      total += ws.bpr.loss.sum(dtype=torch.float64)
-      cl += ws.cl_loss.sum(dtype=torch.float64)
-      count += (ws.bpr.neg >= 0).sum()
-      s += 1
-    total, cl, count = torch.stack([total, cl, count.double()]).cpu().tolist()      # (the synchronisation)
-    hist.append((total / count if count else float("nan"), cl / steps))
-  forward(graph, state["E0"], state["num_layers"], ws.layers, (X, Y))
-  return state, hist
+  """``lightgcn.method_fit`` of SimGCL.  Returns (state, one (mean BPR loss per valid triple, mean NCE_users +
+  NCE_items per step) pair per epoch)."""
+  return lightgcn.method_fit(METHOD, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg,
+                             (cl_weight, cl_eps, cl_temperature), seed, state, first_step)

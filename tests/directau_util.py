@@ -4,9 +4,8 @@ tests/lightgcn_util.py and the sampler of tests/bpr_util.py: the loss, its analy
 in float32 (the propagation chains and Adam in the kernels' operation order as lightgcn_util states them; the sums
 of the loss are numpy's), for the measurement of what f32 costs."""
 import numpy as np
-import scipy.sparse as sp
 
-from tests import bpr_util, lightgcn_util as lg
+from tests import lightgcn_util as lg
 from tests.lightgcn_util import F32, F64
 
 
@@ -105,34 +104,18 @@ def gradient(m, Eu, Ei, K, users, items, reg, gamma, dtype=F64):
 
 def step(m, state, K, users, items, lr, reg, gamma, dtype=F64):
   """One step on given slots, on ``state`` in place: ((align, unif_users, unif_items), valid slots)."""
-  T = len(users)
   _, _, Hu, Hi, cu, ci, losses, cnt = gradient(m, *state["E0"], K, users, items, reg, gamma, dtype)
-  state["step"] += 1
-  rs = F32(reg / T) if dtype == F32 else reg / T
-  out = [lg.adam(state["E0"][s], H, c, rs, state["M"][s], state["V"][s], lr, state["step"], dtype)
-         for s, (H, c) in enumerate(((Hu, cu), (Hi, ci)))]
-  state["E0"], state["M"], state["V"] = (tuple(o[k] for o in out) for k in range(3))
+  lg.adam_both(state, Hu, Hi, cu, ci, len(users), lr, reg, dtype)
   return losses, cnt
 
 
 def fit(m, Eu, Ei, K, num_epochs, batch_size, lr, reg, gamma, seed=0, dtype=F64, state=None, on_epoch=None):
   """(P, Q, state, history): recoder_amd.directau.fit restated, on the slots the kernel's sampler draws."""
-  m = sp.csr_matrix(m)
-  sampler = bpr_util.Sampler(m)
   state = lg.new_state(Eu, Ei, dtype) if state is None else state
-  steps = -(-m.nnz // batch_size)
-  hist = []
-  for ep in range(num_epochs):
-    total = np.zeros(3)
-    for _ in range(steps):
-      users, pos, _ = sampler.sample(seed, state["step"], batch_size)
-      losses, _ = step(m, state, K, users, pos, lr, reg, gamma, dtype)
-      total += losses
-    hist.append(tuple(total / steps))
-    if on_epoch is not None:
-      on_epoch(ep + 1, state)
-  P, Q = lg.forward(m, *state["E0"], K, dtype)
-  return P, Q, state, hist
+  hist = lg.epochs(m, state, num_epochs, batch_size, seed, on_epoch,
+                   lambda users, pos, neg, s: step(m, state, K, users, pos, lr, reg, gamma, dtype)[0], np.zeros(3),
+                   lambda sums, steps: tuple(sums / steps))
+  return lg.forward(m, *state["E0"], K, dtype) + (state, hist)
 
 
 quality = lg.quality

@@ -149,37 +149,52 @@ def gradient(m, Eu, Ei, K, users, pos, neg, reg, dtype=F64):
           float(ls.sum(dtype=F64)))
 
 
-def step(m, state, K, users, pos, neg, lr, reg, dtype=F64):
-  """One step on given triples, on ``state`` in place: (summed loss, valid triples)."""
-  T = len(users)
-  _, _, Hu, Hi, cu, ci, ls = gradient(m, *state["E0"], K, users, pos, neg, reg, dtype)
+def adam_both(state, Hu, Hi, cu, ci, T, lr, reg, dtype=F64):
+  """Adam on both sides of ``state`` in place, at reg / T in ``dtype``: the tail of every step of this family."""
   state["step"] += 1
   rs = F32(reg / T) if dtype == F32 else reg / T
   out = [adam(state["E0"][s], H, c, rs, state["M"][s], state["V"][s], lr, state["step"], dtype)
          for s, (H, c) in enumerate(((Hu, cu), (Hi, ci)))]
   state["E0"], state["M"], state["V"] = (tuple(o[k] for o in out) for k in range(3))
+
+
+def step(m, state, K, users, pos, neg, lr, reg, dtype=F64):
+  """One step on given triples, on ``state`` in place: (summed loss, valid triples)."""
+  _, _, Hu, Hi, cu, ci, ls = gradient(m, *state["E0"], K, users, pos, neg, reg, dtype)
+  adam_both(state, Hu, Hi, cu, ci, len(users), lr, reg, dtype)
   return ls, int((neg >= 0).sum())
+
+
+def epochs(m, state, num_epochs, batch_size, seed, on_epoch, step_fn, zero, entry):
+  """The history of ``num_epochs`` epochs on ``state`` in place, on the triples the kernel's sampler draws.
+  ``step_fn(users, pos, neg, step_index)`` takes one step and returns what it adds to the epoch's sums (an array
+  like ``zero``); ``entry(sums, steps)`` is an epoch's history entry; ``on_epoch(epoch, state)`` follows it."""
+  m = sp.csr_matrix(m)
+  sampler = bpr_util.Sampler(m)
+  steps = -(-m.nnz // batch_size)
+  hist = []
+  for ep in range(num_epochs):
+    sums = zero
+    for _ in range(steps):
+      s = state["step"]
+      sums = sums + np.asarray(step_fn(*sampler.sample(seed, s, batch_size), s))
+    hist.append(entry(sums, steps))
+    if on_epoch is not None:
+      on_epoch(ep + 1, state)
+  return hist
+
+
+def mean_loss(sums, steps=None):
+  return float(sums[0] / sums[1]) if sums[1] else float("nan")
 
 
 def fit(m, Eu, Ei, K, num_epochs, batch_size, lr, reg, seed=0, dtype=F64, state=None, on_epoch=None):
   """(P, Q, state, history): recoder_amd.lightgcn.fit restated, on the triples the kernel's sampler draws.
   ``state`` continues an earlier fit; ``on_epoch(epoch, state)`` is called after every epoch."""
-  m = sp.csr_matrix(m)
-  sampler = bpr_util.Sampler(m)
   state = new_state(Eu, Ei, dtype) if state is None else state
-  steps = -(-m.nnz // batch_size)
-  hist = []
-  for ep in range(num_epochs):
-    total, count = 0.0, 0
-    for _ in range(steps):
-      users, pos, neg = sampler.sample(seed, state["step"], batch_size)
-      l, c = step(m, state, K, users, pos, neg, lr, reg, dtype)
-      total, count = total + l, count + c
-    hist.append(total / count if count else float("nan"))
-    if on_epoch is not None:
-      on_epoch(ep + 1, state)
-  P, Q = forward(m, *state["E0"], K, dtype)
-  return P, Q, state, hist
+  hist = epochs(m, state, num_epochs, batch_size, seed, on_epoch,
+                lambda users, pos, neg, s: step(m, state, K, users, pos, neg, lr, reg, dtype), np.zeros(2), mean_loss)
+  return forward(m, *state["E0"], K, dtype) + (state, hist)
 
 
 def quality(P, Q, x, y):

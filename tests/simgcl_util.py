@@ -134,37 +134,21 @@ def gradient(m, Eu, Ei, K, users, pos, neg, reg, cl_weight, cl_eps, tau, seed=0,
 
 def step(m, state, K, users, pos, neg, lr, reg, cl_weight, cl_eps, tau, seed=0, step_index=0, dtype=F64):
   """One step on given triples, on ``state`` in place: (summed softplus, valid triples, NCE_users + NCE_items)."""
-  T = len(users)
   _, _, Hu, Hi, cu, ci, ls, cl = gradient(m, *state["E0"], K, users, pos, neg, reg, cl_weight, cl_eps, tau, seed,
                                           step_index, dtype)
-  state["step"] += 1
-  rs = F32(reg / T) if dtype == F32 else reg / T
-  out = [lg.adam(state["E0"][s], H, c, rs, state["M"][s], state["V"][s], lr, state["step"], dtype)
-         for s, (H, c) in enumerate(((Hu, cu), (Hi, ci)))]
-  state["E0"], state["M"], state["V"] = (tuple(o[k] for o in out) for k in range(3))
+  lg.adam_both(state, Hu, Hi, cu, ci, len(users), lr, reg, dtype)
   return ls, int((neg >= 0).sum()), cl
 
 
 def fit(m, Eu, Ei, K, num_epochs, batch_size, lr, reg, cl_weight, cl_eps, tau, seed=0, dtype=F64, state=None,
         on_epoch=None):
   """(P, Q, state, history): recoder_amd.simgcl.fit restated, on the triples the kernel's sampler draws."""
-  m = sp.csr_matrix(m)
-  sampler = bpr_util.Sampler(m)
   state = lg.new_state(Eu, Ei, dtype) if state is None else state
-  steps = -(-m.nnz // batch_size)
-  hist = []
-  for ep in range(num_epochs):
-    total, count, cl = 0.0, 0, 0.0
-    for _ in range(steps):
-      s = state["step"]
-      users, pos, neg = sampler.sample(seed, s, batch_size)
-      l, c, n = step(m, state, K, users, pos, neg, lr, reg, cl_weight, cl_eps, tau, seed, s, dtype)
-      total, count, cl = total + l, count + c, cl + n
-    hist.append((total / count if count else float("nan"), cl / steps))
-    if on_epoch is not None:
-      on_epoch(ep + 1, state)
-  P, Q = forward(m, *state["E0"], K, dtype)
-  return P, Q, state, hist
+  hist = lg.epochs(m, state, num_epochs, batch_size, seed, on_epoch,
+                   lambda users, pos, neg, s: step(m, state, K, users, pos, neg, lr, reg, cl_weight, cl_eps, tau, seed,
+                                                   s, dtype),
+                   np.zeros(3), lambda sums, steps: (lg.mean_loss(sums), float(sums[2] / steps)))
+  return forward(m, *state["E0"], K, dtype) + (state, hist)
 
 
 quality = lg.quality

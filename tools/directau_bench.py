@@ -28,7 +28,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bench_util import emit, guarded, load  # noqa: E402
+from bench_util import cpu_grid, emit, guarded, load, loop_ms, xavier_tables  # noqa: E402
 
 H, BATCH, REG = 64, 1024, 1e-3
 # (num_layers, gamma, lr): the paper's range of gamma, DirectAU-MF and a 2-layer encoder, three learning rates
@@ -78,45 +78,7 @@ def _job(job):
   return _auc_gap(job[1]) if job[0] == "gap" else _grid_point(job)
 
 
-def cpu_grid(jobs, out):
-  import multiprocessing as mp
-  for var in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
-    os.environ[var] = "1"                                # (the spawned workers read it when they import numpy)
-  work = [("gap", s) for s in (0, 1, 2)] + GRID
-  with mp.get_context("spawn").Pool(min(jobs, len(work))) as pool:
-    for recs in pool.imap(_job, work):
-      for rec in recs:
-        emit(rec, out)
-
-
 # ------------------------------------------------------------------ timing
-def _tables(n_users, n_items, h, dev):
-  import torch
-  torch.manual_seed(0)
-  X, Y = torch.empty(n_users, h), torch.empty(n_items, h)
-  torch.nn.init.xavier_uniform_(X)
-  torch.nn.init.xavier_uniform_(Y)
-  return X.to(dev), Y.to(dev)
-
-
-def _loop_ms(run, steps, reps):
-  """(the smallest ms per step of ``reps`` timed loops of ``steps`` steps after a warm-up, the largest)."""
-  import torch
-  for s in range(3):
-    run(s)
-  torch.cuda.synchronize()
-  got = []
-  for r in range(reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for s in range(3 + r * steps, 3 + (r + 1) * steps):
-      run(s)
-    e1.record()
-    torch.cuda.synchronize()
-    got.append(e0.elapsed_time(e1) / steps)
-  return round(min(got), 4), round(max(got), 4)
-
-
 def torch_step(m, graph, h, K, T, lr, reg, gamma):
   """The same step in torch ops on the same draws, as the paper's code writes the loss."""
   import torch
@@ -128,7 +90,7 @@ def torch_step(m, graph, h, K, T, lr, reg, gamma):
   idx = torch.as_tensor(np.stack([coo.row, coo.col]), device=dev, dtype=torch.int64)
   A = torch.sparse_coo_tensor(idx, torch.as_tensor(vals, dtype=torch.float32, device=dev), m.shape).coalesce()
   At = A.t().coalesce()
-  E = [torch.nn.Parameter(t) for t in _tables(m.shape[0], m.shape[1], h, dev)]
+  E = [torch.nn.Parameter(t) for t in xavier_tables(m.shape[0], m.shape[1], h, dev)]
   opt = torch.optim.Adam(E, lr=lr)
   users, pos, neg = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(3))
   unif = lambda z: torch.pdist(z, p=2).pow(2).mul(-2).exp().mean().log()
@@ -158,21 +120,21 @@ def step_lines(m, name, h, K, T, steps, reps, out):
   lr, reg, gamma = 0.01, REG, 1.0
   rec = {"bench": "directau_step", "data": name, "users": m.shape[0], "items": m.shape[1], "nnz": int(m.nnz), "h": h,
          "num_layers": K, "batch_size": T, "steps": steps, "repetitions": reps, "gamma": gamma}
-  X, Y = _tables(m.shape[0], m.shape[1], h, dev)
+  X, Y = xavier_tables(m.shape[0], m.shape[1], h, dev)
   state = directau.new_state(X, Y, K)
   ws = directau.Workspace(m.shape[0], m.shape[1], T, h, dev)
   run = lambda s: directau.step(X, Y, graph, state, ws, 0, s, lr, reg, gamma)
-  rec["hip_ms_per_step"], rec["hip_ms_per_step_max"] = _loop_ms(run, steps, reps)
+  rec["hip_ms_per_step"], rec["hip_ms_per_step_max"] = loop_ms(run, steps, reps)
   rec["slots_per_s"] = round(T / (rec["hip_ms_per_step"] * 1e-3))
   lstate, lws = lightgcn.new_state(X, Y, K), lightgcn.Workspace(m.shape[0], m.shape[1], T, h, dev)
   if K >= 1:
-    rec["lightgcn_ms_per_step"], rec["lightgcn_ms_per_step_max"] = _loop_ms(
+    rec["lightgcn_ms_per_step"], rec["lightgcn_ms_per_step_max"] = loop_ms(
         lambda s: lightgcn.step(X, Y, graph, lstate, lws, 0, s, lr, reg), steps, reps)
     rec["over_lightgcn_step"] = round(rec["hip_ms_per_step"] / rec["lightgcn_ms_per_step"], 3)
   # the loss-and-gradient call beside one pair of contrasts (users, items) at the same T and h
   b = ws.bpr
   bpr.sample(graph.ucsr, 0, 0, b.users, b.pos, b.neg)
-  rec["dau_grad_ms"], rec["dau_grad_ms_max"] = _loop_ms(
+  rec["dau_grad_ms"], rec["dau_grad_ms_max"] = loop_ms(
       lambda s: directau.grad(b.users, b.pos, X, Y, gamma, ws.raw, b.D, b.P, b.g, ws.loss, ws.valid_count), steps, reps)
   craw = torch.empty(simgcl.contrast_workspace_bytes(T, h), dtype=torch.uint8, device=dev)
   closs, ccount = torch.zeros(2, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)
@@ -183,7 +145,7 @@ def step_lines(m, name, h, K, T, steps, reps, out):
     for side, (V1, V2) in enumerate(((X, X2), (Y, Y2))):
       simgcl.contrast(keys[side], V1, V2, 0.2, 0.5, ws.G[side], ws.G[side], craw, closs[side:side + 1],
                       ccount[side:side + 1])
-  rec["contrast_pair_ms"], rec["contrast_pair_ms_max"] = _loop_ms(pair, steps, reps)
+  rec["contrast_pair_ms"], rec["contrast_pair_ms_max"] = loop_ms(pair, steps, reps)
   rec["distinct_users_items_of_the_pair"] = ccount.cpu().tolist()
   rec["dau_grad_faster_than_contrast_pair"] = rec["dau_grad_ms"] < rec["contrast_pair_ms"]
   # the split: the step's calls one by one between events
@@ -221,7 +183,7 @@ def step_lines(m, name, h, K, T, steps, reps, out):
   rec["losses_last_step"] = [round(v, 4) for v in ws.loss.cpu().tolist()]
 
   def torch_ms():
-    return _loop_ms(torch_step(m, graph, h, K, T, lr, reg, gamma), steps, reps)
+    return loop_ms(torch_step(m, graph, h, K, T, lr, reg, gamma), steps, reps)
   t = guarded(torch_ms)
   if isinstance(t, tuple):
     rec["torch_ops_step_ms"], rec["torch_ops_step_ms_max"] = t
@@ -271,7 +233,8 @@ def main():
   ap.add_argument("--out", default=None)
   args = ap.parse_args()
   if args.cpu_grid:
-    return cpu_grid(args.jobs, args.out or os.path.join(ROOT, "profiles", "directau_quality.jsonl"))
+    return cpu_grid(_job, [("gap", s) for s in (0, 1, 2)] + GRID, args.jobs,
+                    args.out or os.path.join(ROOT, "profiles", "directau_quality.jsonl"))
   import torch
   if not torch.cuda.is_available():
     sys.exit("directau_bench.py measures on the GPU (only --cpu-grid runs without one)")

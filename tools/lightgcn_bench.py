@@ -30,7 +30,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bench_util import emit, event_ms, guarded, load  # noqa: E402
+from bench_util import cpu_grid, emit, event_ms, guarded, load, loop_ms, xavier_tables  # noqa: E402
 
 H, BATCH = 64, 1024
 # (num_layers, lr, reg): num_layers x lr x reg, and one larger lr at two layers
@@ -59,26 +59,7 @@ def _grid_point(args):
            "source": "float64 restatement (tests/lightgcn_util.py), CPU"} for ep, r, n in rows]
 
 
-def cpu_grid(jobs, out):
-  import multiprocessing as mp
-  for var in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
-    os.environ[var] = "1"                                # (the spawned workers read it when they import numpy)
-  with mp.get_context("spawn").Pool(min(jobs, len(GRID))) as pool:
-    for recs in pool.imap(_grid_point, GRID):
-      for rec in recs:
-        emit(rec, out)
-
-
 # ------------------------------------------------------------------ timing
-def _tables(n_users, n_items, h, dev):
-  import torch
-  torch.manual_seed(0)
-  X, Y = torch.empty(n_users, h), torch.empty(n_items, h)
-  torch.nn.init.xavier_uniform_(X)
-  torch.nn.init.xavier_uniform_(Y)
-  return X.to(dev), Y.to(dev)
-
-
 def propagate_lines(name, graph, h, reps, out):
   """The fused propagate beside rk_svd_spmm + add + scale and torch.sparse.mm + add + scale, both orientations."""
   import torch
@@ -133,7 +114,7 @@ def torch_step_ms(m, graph, h, K, T, steps, lr, reg):
   idx = torch.as_tensor(np.stack([coo.row, coo.col]), device=dev, dtype=torch.int64)
   A = torch.sparse_coo_tensor(idx, torch.as_tensor(vals, dtype=torch.float32, device=dev), m.shape).coalesce()
   At = A.t().coalesce()
-  E = [torch.nn.Parameter(t) for t in _tables(m.shape[0], m.shape[1], h, dev)]
+  E = [torch.nn.Parameter(t) for t in xavier_tables(m.shape[0], m.shape[1], h, dev)]
   opt = torch.optim.Adam(E, lr=lr)
   users, pos, neg = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(3))
 
@@ -153,15 +134,7 @@ def torch_step_ms(m, graph, h, K, T, steps, lr, reg):
     opt.zero_grad(set_to_none=True)
     loss.backward()
     opt.step()
-  one(0)
-  torch.cuda.synchronize()
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for s in range(1, 1 + steps):
-    one(s)
-  e1.record()
-  torch.cuda.synchronize()
-  return round(e0.elapsed_time(e1) / steps, 4)
+  return loop_ms(one, steps)[0]
 
 
 def step_lines(m, name, h, K, T, steps, out):
@@ -169,23 +142,13 @@ def step_lines(m, name, h, K, T, steps, out):
   from recoder_amd import als, bpr, lightgcn
   dev = torch.device("cuda")
   graph = lightgcn.Graph(*als.csr_pair(m, m.shape[0], m.shape[1], dev))
-  X, Y = _tables(m.shape[0], m.shape[1], h, dev)
+  X, Y = xavier_tables(m.shape[0], m.shape[1], h, dev)
   state = lightgcn.new_state(X, Y, K)
   ws = lightgcn.Workspace(m.shape[0], m.shape[1], T, h, dev)
   rec = {"bench": "lightgcn_step", "data": name, "users": m.shape[0], "items": m.shape[1], "nnz": int(m.nnz), "h": h,
          "num_layers": K, "batch_size": T, "steps": steps}
   lr, reg = 0.01, 1e-3
-  run = lambda s: lightgcn.step(X, Y, graph, state, ws, 0, s, lr, reg)
-  for s in range(3):
-    run(s)
-  torch.cuda.synchronize()
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for s in range(3, 3 + steps):
-    run(s)
-  e1.record()
-  torch.cuda.synchronize()
-  rec["hip_ms_per_step"] = round(e0.elapsed_time(e1) / steps, 4)
+  rec["hip_ms_per_step"] = loop_ms(lambda s: lightgcn.step(X, Y, graph, state, ws, 0, s, lr, reg), steps)[0]
   rec["triples_per_s"] = round(T / (rec["hip_ms_per_step"] * 1e-3))
   # the split: the step's calls one by one between events
   b, parts = ws.bpr, {}
@@ -255,7 +218,8 @@ def main():
   ap.add_argument("--out", default=None)
   args = ap.parse_args()
   if args.cpu_grid:
-    return cpu_grid(args.jobs, args.out or os.path.join(ROOT, "profiles", "lightgcn_quality.jsonl"))
+    return cpu_grid(_grid_point, GRID, args.jobs,
+                    args.out or os.path.join(ROOT, "profiles", "lightgcn_quality.jsonl"))
   import torch
   if not torch.cuda.is_available():
     sys.exit("lightgcn_bench.py measures on the GPU (only --cpu-grid runs without one)")

@@ -30,7 +30,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bench_util import emit, event_ms, guarded, load  # noqa: E402
+from bench_util import cpu_grid, emit, event_ms, guarded, load, loop_ms, xavier_tables  # noqa: E402
 
 H, BATCH, TAU = 64, 1024, 0.2
 # (num_layers, cl_weight, cl_eps, lr, reg): layers x weight x eps x lr at LightGCN's reg, the paper's own lr and reg,
@@ -63,26 +63,7 @@ def _grid_point(args):
            "source": "float64 restatement (tests/simgcl_util.py), CPU"} for ep, r, n in rows]
 
 
-def cpu_grid(jobs, out):
-  import multiprocessing as mp
-  for var in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
-    os.environ[var] = "1"                                # (the spawned workers read it when they import numpy)
-  with mp.get_context("spawn").Pool(min(jobs, len(GRID))) as pool:
-    for recs in pool.imap(_grid_point, GRID):
-      for rec in recs:
-        emit(rec, out)
-
-
 # ------------------------------------------------------------------ timing
-def _tables(n_users, n_items, h, dev):
-  import torch
-  torch.manual_seed(0)
-  X, Y = torch.empty(n_users, h), torch.empty(n_items, h)
-  torch.nn.init.xavier_uniform_(X)
-  torch.nn.init.xavier_uniform_(Y)
-  return X.to(dev), Y.to(dev)
-
-
 def propagate_lines(name, graph, h, eps, reps, out):
   """The noise in the epilogue beside rk_als_lgcn_propagate and a separate torch pass over its output."""
   import torch
@@ -122,7 +103,7 @@ def torch_step_ms(m, graph, h, K, T, steps, lr, reg, w, eps, tau):
   idx = torch.as_tensor(np.stack([coo.row, coo.col]), device=dev, dtype=torch.int64)
   A = torch.sparse_coo_tensor(idx, torch.as_tensor(vals, dtype=torch.float32, device=dev), m.shape).coalesce()
   At = A.t().coalesce()
-  E = [torch.nn.Parameter(t) for t in _tables(m.shape[0], m.shape[1], h, dev)]
+  E = [torch.nn.Parameter(t) for t in xavier_tables(m.shape[0], m.shape[1], h, dev)]
   opt = torch.optim.Adam(E, lr=lr)
   users, pos, neg = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(3))
 
@@ -152,29 +133,7 @@ def torch_step_ms(m, graph, h, K, T, steps, lr, reg, w, eps, tau):
     opt.zero_grad(set_to_none=True)
     loss.backward()
     opt.step()
-  one(0)
-  torch.cuda.synchronize()
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for s in range(1, 1 + steps):
-    one(s)
-  e1.record()
-  torch.cuda.synchronize()
-  return round(e0.elapsed_time(e1) / steps, 4)
-
-
-def _loop_ms(run, steps):
-  import torch
-  for s in range(3):
-    run(s)
-  torch.cuda.synchronize()
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for s in range(3, 3 + steps):
-    run(s)
-  e1.record()
-  torch.cuda.synchronize()
-  return round(e0.elapsed_time(e1) / steps, 4)
+  return loop_ms(one, steps)[0]
 
 
 def step_lines(m, name, h, K, T, steps, out):
@@ -185,15 +144,15 @@ def step_lines(m, name, h, K, T, steps, out):
   lr, reg, w, eps, tau = 0.01, 1e-3, 0.5, 0.1, TAU
   rec = {"bench": "simgcl_step", "data": name, "users": m.shape[0], "items": m.shape[1], "nnz": int(m.nnz), "h": h,
          "num_layers": K, "batch_size": T, "steps": steps, "cl_weight": w, "cl_eps": eps, "cl_temperature": tau}
-  X, Y = _tables(m.shape[0], m.shape[1], h, dev)
+  X, Y = xavier_tables(m.shape[0], m.shape[1], h, dev)
   state = simgcl.new_state(X, Y, K)
   ws = simgcl.Workspace(m.shape[0], m.shape[1], T, h, dev)
-  rec["hip_ms_per_step"] = _loop_ms(lambda s: simgcl.step(X, Y, graph, state, ws, 0, s, lr, reg, w, eps, tau), steps)
+  rec["hip_ms_per_step"] = loop_ms(lambda s: simgcl.step(X, Y, graph, state, ws, 0, s, lr, reg, w, eps, tau), steps)[0]
   rec["triples_per_s"] = round(T / (rec["hip_ms_per_step"] * 1e-3))
-  rec["hip_ms_per_step_cl_weight_0"] = _loop_ms(
-      lambda s: simgcl.step(X, Y, graph, state, ws, 0, s, lr, reg, 0.0, eps, tau), steps)
+  rec["hip_ms_per_step_cl_weight_0"] = loop_ms(
+      lambda s: simgcl.step(X, Y, graph, state, ws, 0, s, lr, reg, 0.0, eps, tau), steps)[0]
   lstate, lws = lightgcn.new_state(X, Y, K), lightgcn.Workspace(m.shape[0], m.shape[1], T, h, dev)
-  rec["lightgcn_ms_per_step"] = _loop_ms(lambda s: lightgcn.step(X, Y, graph, lstate, lws, 0, s, lr, reg), steps)
+  rec["lightgcn_ms_per_step"] = loop_ms(lambda s: lightgcn.step(X, Y, graph, lstate, lws, 0, s, lr, reg), steps)[0]
   rec["over_lightgcn_step"] = round(rec["hip_ms_per_step"] / rec["lightgcn_ms_per_step"], 3)
   # the split: the step's calls one by one between events
   b, parts = ws.bpr, {}
@@ -279,7 +238,8 @@ def main():
   ap.add_argument("--out", default=None)
   args = ap.parse_args()
   if args.cpu_grid:
-    return cpu_grid(args.jobs, args.out or os.path.join(ROOT, "profiles", "simgcl_quality.jsonl"))
+    return cpu_grid(_grid_point, GRID, args.jobs,
+                    args.out or os.path.join(ROOT, "profiles", "simgcl_quality.jsonl"))
   import torch
   if not torch.cuda.is_available():
     sys.exit("simgcl_bench.py measures on the GPU (only --cpu-grid runs without one)")
