@@ -57,6 +57,30 @@
  *     the order given (ascending slot when the sort is stable), from +0; then
  *     new = fmaf(lr, fmaf(-(reg * c), old, sum), old).  One wave owns a row; nobody else writes it.
  *
+ * WARP (Weston, Bengio & Usunier 2011) and dynamic negative sampling (Zhang, Chen, Wang & Yu 2013) on the
+ * same step, rk_als_rank_sample and rk_als_warp_grad: the negative of a slot is chosen by the model's scores
+ * s(u, c) = p_u . q_c + b_c.  Per slot, sequentially (the kernel groups the work, its results are these):
+ *   - The key and draw 0 are rk_als_bpr_sample's: users and pos are its bits for the same (seed, step, slot).
+ *     Draws d = 1..max_draws map to c_d in [0, n_items) as there; a c_d the user holds is skipped, the others
+ *     are the slot's candidates, in draw order.
+ *   - A score is rk_als_bpr_grad's dot chain (lane l owns k = l + 64 m, fmaf over m ascending from +0, the xor
+ *     butterfly over lane distances 32..1), then + b_c with one rounding.  s_pos = s(u, pos).
+ *   - RK_ALS_RANK_WARP: candidate c violates when (s(u, c) - s_pos) + margin > 0, two f32 operations of one
+ *     rounding each.  The first violator is neg, trials = N = the candidates scored up to and including it,
+ *     s_neg its score.  No violator within max_draws draws: neg = -1, trials = 0, s_neg = +0, and the slot is
+ *     invalid in BPR's sense.
+ *   - RK_ALS_RANK_DNS: of the first num_candidates candidates neg is the one of the largest score (a tie stays
+ *     with the earlier draw), s_neg that score, trials how many were scored; no candidate: -1, 0, +0.  The
+ *     margin plays no part.  num_candidates = 1 with max_draws = 32 gives rk_als_bpr_sample's three arrays.
+ *   - scores[t, d - 1] is the score of draw d where the definition above scored it, +0 where the draw is held
+ *     or lies behind the stopping point.  Everything depends on (seed, step, slot, CSR, tables) alone: not on
+ *     T, the launch, or how the kernel groups the draws.
+ *   - rk_als_warp_grad: g = weight[trials], loss = g * ((s_neg - s_pos) + margin) with both scores recomputed
+ *     by the chain above, D = q_i - q_j (one rounding), P = p_u.  The hinge's gradient has BPR's form with g the
+ *     rank weight, so rk_als_bpr_apply makes the update.  weight is the caller's table, built in float64 on
+ *     the host and rounded once (recoder_amd/warp.py: log(max(1, (n_items - 1) / N)) or the harmonic number
+ *     of (n_items - 1) / N, the division an integer one): no logf and no harmonic loop runs on the device.
+ *
  * LightGCN (He, Deng, Wang, Li, Zhang & Wang 2020) for the same model, the rk_als_lgcn_* functions: the
  * final tables are the mean over K + 1 layers of the base tables propagated over the symmetrically
  * normalised user-item graph, trained with the BPR triples above and Adam (recoder_amd/lightgcn.py).
@@ -174,6 +198,38 @@ int rk_als_bpr_grad(const int32_t *users, const int32_t *pos, const int32_t *neg
 int rk_als_bpr_apply(const int32_t *keys, const int64_t *order, int32_t n, int32_t roles, const float *g,
                      const float *V, int32_t h, float lr, float reg, int32_t n_rows, float *table, int32_t ldt,
                      float *bias, void *stream);
+
+/* the most draws rk_als_rank_sample takes per slot, and its two modes */
+#define RK_ALS_RANK_MAX_DRAWS 256
+#define RK_ALS_RANK_WARP 0
+#define RK_ALS_RANK_DNS 1
+
+/*
+ * The model-aware sampler of a step (see WARP / DNS above): users, pos, neg, trials (int32 [T]) for the slots
+ * t < T of step `step` >= 0 under `seed`, from the CSR rk_als_bpr_sample takes and the tables X [n_users, ldx],
+ * Y [n_items, ldy], bias [n_items] at embedding size h <= rk_als_max_h().  1 <= max_draws <=
+ * RK_ALS_RANK_MAX_DRAWS; in DNS mode 1 <= num_candidates <= max_draws; in WARP mode margin is finite and >= 0.
+ * s_pos, s_neg (f32 [T]) and scores (f32 [T, max_draws], every entry written; for tests) may be NULL: not
+ * wanted.  s_pos is s(u, pos) of every slot, valid or not.  One wave per slot: 64 draws are hashed and searched
+ * at a time, and the rows of several candidates are gathered before any is reduced; a score computed behind
+ * the stopping point is dropped.
+ */
+int rk_als_rank_sample(const int64_t *indptr, const int32_t *indices, int32_t n_users, int32_t n_items,
+                       int64_t nnz, int64_t seed, int32_t step, int32_t T, const float *X, int32_t ldx,
+                       const float *Y, int32_t ldy, const float *bias, int32_t h, int32_t mode, int32_t max_draws,
+                       int32_t num_candidates, float margin, int32_t *users, int32_t *pos, int32_t *neg,
+                       int32_t *trials, float *s_pos, float *s_neg, float *scores, void *stream);
+
+/*
+ * rk_als_bpr_grad for WARP's hinge: for every slot t < T, g[t] = weight[trials[t]], loss[t] = g[t] * ((s_neg -
+ * s_pos) + margin) and the staging rows D[t, :] = q_i - q_j, P[t, :] = p_u (f32 [T, h]).  weight: f32
+ * [RK_ALS_RANK_MAX_DRAWS + 1], device memory.  A slot with neg[t] < 0, trials[t] outside 1..RK_ALS_RANK_MAX_DRAWS
+ * or an id outside the tables is invalid: g, loss and both rows are +0.  One wave per slot.
+ */
+int rk_als_warp_grad(const int32_t *users, const int32_t *pos, const int32_t *neg, const int32_t *trials, int32_t T,
+                     int32_t n_users, int32_t n_items, const float *X, int32_t ldx, const float *Y, int32_t ldy,
+                     const float *bias, int32_t h, float margin, const float *weight, float *g, float *loss,
+                     float *D, float *P, void *stream);
 
 /* rows of at least this many stored entries get a workgroup of 16 waves each in rk_als_lgcn_propagate */
 #define RK_ALS_LGCN_LONG_ROW 1024

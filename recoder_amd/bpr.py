@@ -69,6 +69,11 @@ def check_config(model, num_epochs, batch_size, lr, reg, seed):
           _number("lr", lr, True), _number("reg", reg, False), int(seed))
 
 
+def check_candidates(num_candidates):
+  """``num_candidates`` of ``train_bpr``: 1 (the uniform negative) or up to MAX_DRAWS candidates scored per slot."""
+  return _count("num_candidates", num_candidates, 1, MAX_DRAWS)
+
+
 def steps_per_epoch(nnz, batch_size):
   return -(-int(nnz) // int(batch_size))
 
@@ -234,9 +239,16 @@ def apply(keys, order, roles, g, V, lr, reg, table, bias=None):
                  "rk_als_bpr_apply")
 
 
-def step(X, Y, bias, ucsr, ws, seed, step_index, lr, reg):
-  """One BPR step on the tables in place; the triples, g and loss of the step stay in ``ws``."""
-  sample(ucsr, seed, step_index, ws.users, ws.pos, ws.neg)
+def step(X, Y, bias, ucsr, ws, seed, step_index, lr, reg, num_candidates=1):
+  """One BPR step on the tables in place; the triples, g and loss of the step stay in ``ws``.  With
+  ``num_candidates`` > 1 the negative is the highest-scored of that many candidates (dynamic negative sampling:
+  rk_als_rank_sample in its DNS mode, recoder_amd/warp.py; ``ws.trials`` must then exist)."""
+  if num_candidates == 1:
+    sample(ucsr, seed, step_index, ws.users, ws.pos, ws.neg)
+  else:
+    from . import warp
+    warp.sample(ucsr, seed, step_index, X, Y, bias, warp.DNS, MAX_DRAWS, num_candidates, 0.0, ws.users, ws.pos,
+                ws.neg, ws.trials)
   grad(ws.users, ws.pos, ws.neg, X, Y, bias, ws.g, ws.loss, ws.D, ws.P)
   (uk, uo), (ik, io) = sorted_keys(ws.users, ws.pos, ws.neg, X.shape[0], Y.shape[0])
   apply(uk, uo, 1, ws.g, ws.D, lr, reg, X)
@@ -244,21 +256,24 @@ def step(X, Y, bias, ucsr, ws, seed, step_index, lr, reg):
 
 
 # ---------------------------------------------------------------------- fit
-def fit(X, Y, bias, ucsr, num_epochs, batch_size, lr, reg, seed=0, first_step=0):
+def fit(X, Y, bias, ucsr, num_epochs, batch_size, lr, reg, seed=0, first_step=0, num_candidates=1):
   """num_epochs epochs of ceil(nnz / batch_size) steps on the tables X [users, h], Y [items, h] and bias
   [items] (in place, f32, row-major); step s of the fit draws as step ``first_step + s``.  Returns the mean
   loss per valid triple of each epoch (floats; nan for an epoch without one).  One host synchronisation
-  per epoch, to read that epoch's sums."""
+  per epoch, to read that epoch's sums.  ``num_candidates`` > 1 (up to MAX_DRAWS): see ``step``."""
+  num_candidates = check_candidates(num_candidates)
   steps = check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size)
   check_memory(X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False)
   ws = Workspace(int(batch_size), X.shape[1], X.device)
+  if num_candidates > 1:
+    ws.trials = torch.empty(int(batch_size), dtype=torch.int32, device=X.device)
   hist = []
   s = int(first_step)
   for _ in range(num_epochs):
     total = torch.zeros((), dtype=torch.float64, device=X.device)
     count = torch.zeros((), dtype=torch.int64, device=X.device)
     for _ in range(steps):
-      step(X, Y, bias, ucsr, ws, seed, s, lr, reg)
+      step(X, Y, bias, ucsr, ws, seed, s, lr, reg, num_candidates)
       total += ws.loss.sum(dtype=torch.float64)
       count += (ws.neg >= 0).sum()
       s += 1

@@ -9,7 +9,8 @@ librecoder_index.so  exact item similarity (include/recoder_index.h), a library 
                    own so that the training library's exported symbol set stays as it is
 librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recoder_als.h),
                    likewise a library of its own.  It also holds the BPR pairwise-ranking step of the
-                   same model (rk_als_bpr_*: sample, grad, apply) and the LightGCN kernels
+                   same model (rk_als_bpr_*: sample, grad, apply), the model-aware sampler of WARP and dynamic
+                   negative sampling with WARP's gradient (rk_als_rank_sample, rk_als_warp_grad) and the LightGCN kernels
                    (rk_als_lgcn_*: propagate, scatter, adam) that train it over the user-item graph
                    and SimGCL's on top of them (rk_als_gcl_*: the propagation with noise in its epilogue,
                    the contrast between two views) and DirectAU's (rk_als_dau_workspace_bytes,

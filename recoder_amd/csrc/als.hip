@@ -19,6 +19,11 @@
 //                      ascending slot order, one fmaf chain per element, then the row's own update.
 //                      No atomics: nobody else writes the row
 //
+// WARP and dynamic negative sampling on the same step (rk_als_rank_sample, rk_als_warp_grad):
+//   rk_als_rank_sample  one wave per slot: the sampler's draws 64 at a time, the candidates scored against p_u
+//                       several rows in flight, decided in draw order (first margin violator / hardest of M)
+//   rk_als_warp_grad    rk_als_bpr_grad's staging rows with g = the rank weight of the slot's trials
+//
 // LightGCN for the same model (rk_als_lgcn_*): the step of recoder_amd/lightgcn.py adds
 //   rk_als_lgcn_propagate  one group of lanes per CSR row: the scaled sum of the row's gathered table rows,
 //                          lanes own columns; long rows by a workgroup of 16 waves each, in fixed parts
@@ -36,6 +41,7 @@
 //                          per slot and side, on the contrast's tile code; the T x T weights are stored once and
 //                          staged as they are by one dZ product per side
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 
@@ -657,6 +663,165 @@ __global__ __launch_bounds__(256) void als_bpr_grad_kernel(const int32_t *__rest
     g[t] = x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);
     loss[t] = fmaxf(-x, 0.f) + log1pf(e);
     if (xout) xout[t] = x;
+  }
+}
+
+// ----------------------------------------------------------------- rank (WARP / DNS)
+// The model-aware sampler: one wave per slot.  Draw 0 is als_bpr_sample_kernel's; p_u stays in registers in
+// als_bpr_grad_kernel's lane layout.  The draws go 64 at a time: lane l hashes draw d0 + l and searches the
+// user's row for it, a ballot gives the candidates (the draws the user does not hold), and the candidates
+// are scored G at a time in draw order -- the G row gathers are issued before any of them is reduced --
+// and decided one after the other, as the sequential definition walks them.  A score computed behind the
+// stopping point is dropped: it reaches neither `scores` nor any decision.  Every decision is taken on a
+// butterfly's result, the same in all lanes, so every branch on it is wave-uniform.
+constexpr int RANK_MAX_DRAWS = 256;
+constexpr int RANK_WARP = 0;
+constexpr int RANK_DNS = 1;
+
+template <int NT, int G>
+__global__ __launch_bounds__(256) void als_rank_sample_kernel(
+    const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, int n_users, int n_items, uint32_t nnz,
+    uint64_t seed_key, uint32_t step, int T, const float *__restrict__ X, int ldx, const float *__restrict__ Y,
+    int ldy, const float *__restrict__ bias, int h, int mode, int max_draws, int num_candidates, float margin,
+    int32_t *__restrict__ users, int32_t *__restrict__ pos, int32_t *__restrict__ neg, int32_t *__restrict__ trials,
+    float *__restrict__ s_pos, float *__restrict__ s_neg, float *__restrict__ scores) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const uint64_t key = bpr_mix(seed_key ^ (((uint64_t)step << 32) | (uint32_t)t));
+  const int64_t e = (int64_t)bpr_draw(key, 0, nnz);
+  int lo = 0, hi = n_users;                 // (indptr[lo] <= e < indptr[hi] throughout)
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (indptr[mid] <= e) lo = mid; else hi = mid;
+  }
+  const int u = lo;
+  const int64_t r0 = indptr[u], r1 = indptr[u + 1];
+  const int i = indices[e];
+  const bool ok = i >= 0 && i < n_items;    // (a column outside the table: the slot is invalid, nothing is read)
+  float p[NT], q0[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int k = lane + 64 * q;
+    const bool in = ok && k < h;
+    p[q] = in ? X[(int64_t)u * ldx + k] : 0.f;
+    q0[q] = in ? Y[(int64_t)i * ldy + k] : 0.f;
+  }
+  const float sp = ok ? wave_dot<NT>(p, q0) + bias[i] : 0.f;
+  int j = -1, n_scored = 0;
+  float sn = 0.f;
+  bool done = !ok;
+  for (int d0 = 1; d0 <= max_draws; d0 += 64) {
+    const int d = d0 + lane;
+    int c = 0;
+    bool cand = false;
+    if (!done && d <= max_draws) {
+      c = (int)bpr_draw(key, (uint32_t)d, (uint32_t)n_items);
+      int64_t a = r0, b = r1;               // first position in [r0, r1) with indices[.] >= c
+      while (a < b) {
+        const int64_t mid = a + ((b - a) >> 1);
+        if (indices[mid] < c) a = mid + 1; else b = mid;
+      }
+      cand = !(a < r1 && indices[a] == c);
+    }
+    uint64_t m = __ballot(cand);
+    float mine = 0.f;                       // (the score of this lane's draw, once it has been decided on)
+    while (m && !done) {
+      // DNS knows how many it still wants; WARP scores G ahead and drops what lies behind the violator
+      const int want = mode == RANK_DNS ? min(G, num_candidates - n_scored) : G;
+      int L[G], cg[G];
+      float qg[G][NT], bg[G], s[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const bool on = m != 0 && g < want;
+        L[g] = on ? __ffsll((unsigned long long)m) - 1 : -1;
+        if (on) m &= m - 1;
+        cg[g] = __shfl(c, on ? L[g] : 0, 64);
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int q = 0; q < NT; ++q) {
+          const int k = lane + 64 * q;
+          qg[g][q] = (L[g] >= 0 && k < h) ? Y[(int64_t)cg[g] * ldy + k] : 0.f;
+        }
+        bg[g] = L[g] >= 0 ? bias[cg[g]] : 0.f;
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g) s[g] = wave_dot<NT>(p, qg[g]) + bg[g];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        if (L[g] >= 0 && !done) {
+          ++n_scored;
+          if (lane == L[g]) mine = s[g];
+          if (mode == RANK_DNS) {
+            if (n_scored == 1 || s[g] > sn) {     // (strictly: a tie stays with the earlier draw)
+              sn = s[g];
+              j = cg[g];
+            }
+            done = n_scored == num_candidates;
+          } else if ((s[g] - sp) + margin > 0.f) {
+            sn = s[g];
+            j = cg[g];
+            done = true;
+          }
+        }
+      }
+    }
+    if (scores && d <= max_draws) scores[(int64_t)t * max_draws + (d - 1)] = mine;
+  }
+  if (lane == 0) {
+    users[t] = u;
+    pos[t] = i;
+    neg[t] = j;
+    trials[t] = j >= 0 ? n_scored : 0;
+    if (s_pos) s_pos[t] = sp;
+    if (s_neg) s_neg[t] = j >= 0 ? sn : 0.f;
+  }
+}
+
+// One wave per slot, als_bpr_grad_kernel's layout: the two scores are the sampler's chain (dot, then + b),
+// g is the rank weight of the slot's trials, the loss is the hinge that the violator crossed.
+template <int NT>
+__global__ __launch_bounds__(256) void als_warp_grad_kernel(
+    const int32_t *__restrict__ users, const int32_t *__restrict__ pos, const int32_t *__restrict__ neg,
+    const int32_t *__restrict__ trials, int T, int n_users, int n_items, const float *__restrict__ X, int ldx,
+    const float *__restrict__ Y, int ldy, const float *__restrict__ bias, int h, float margin,
+    const float *__restrict__ weight, float *__restrict__ g, float *__restrict__ loss, float *__restrict__ D,
+    float *__restrict__ P) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const int u = users[t], i = pos[t], j = neg[t], n = trials[t];
+  const bool ok = u >= 0 && u < n_users && i >= 0 && i < n_items && j >= 0 && j < n_items && n >= 1 &&
+                  n <= RANK_MAX_DRAWS;                                                       // (wave-uniform)
+  float p[NT], qi[NT], qj[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int k = lane + 64 * q;
+    const bool in = ok && k < h;
+    p[q] = in ? X[(int64_t)u * ldx + k] : 0.f;
+    qi[q] = in ? Y[(int64_t)i * ldy + k] : 0.f;
+    qj[q] = in ? Y[(int64_t)j * ldy + k] : 0.f;
+  }
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int k = lane + 64 * q;
+    if (k < h) {
+      D[(int64_t)t * h + k] = qi[q] - qj[q];
+      P[(int64_t)t * h + k] = p[q];
+    }
+  }
+  if (!ok) {
+    if (lane == 0) g[t] = loss[t] = 0.f;
+    return;
+  }
+  const float sp = wave_dot<NT>(p, qi) + bias[i];
+  const float sn = wave_dot<NT>(p, qj) + bias[j];
+  if (lane == 0) {
+    const float w = weight[n];
+    g[t] = w;
+    loss[t] = w * ((sn - sp) + margin);
   }
 }
 
@@ -1626,7 +1791,65 @@ extern "C" int rk_als_bpr_apply(const int32_t *keys, const int64_t *order, int32
   return 0;
 }
 
-#define ALS_LGCN_PROP_LAUNCH(VEC, NT)                                                                          \
+// (G: the candidates whose rows are in flight together; 8 rows of h <= 128, 4 of the wider ones)
+#define ALS_RANK_SAMPLE_LAUNCH(NT, G)                                                                            \
+  hipLaunchKernelGGL((als_rank_sample_kernel<NT, G>), grid, dim3(256), 0, st, indptr, indices, n_users, n_items, \
+                     (uint32_t)nnz, bpr_mix((uint64_t)seed), (uint32_t)step, T, X, ldx, Y, ldy, bias, h, mode,   \
+                     max_draws, num_candidates, margin, users, pos, neg, trials, s_pos, s_neg, scores)
+
+extern "C" int rk_als_rank_sample(const int64_t *indptr, const int32_t *indices, int32_t n_users, int32_t n_items,
+                                  int64_t nnz, int64_t seed, int32_t step, int32_t T, const float *X, int32_t ldx,
+                                  const float *Y, int32_t ldy, const float *bias, int32_t h, int32_t mode,
+                                  int32_t max_draws, int32_t num_candidates, float margin, int32_t *users,
+                                  int32_t *pos, int32_t *neg, int32_t *trials, float *s_pos, float *s_neg,
+                                  float *scores, void *stream) {
+  RK_SIDE_REQUIRE(n_users >= 1 && n_items >= 1, "n_users >= 1, n_items >= 1");
+  RK_SIDE_REQUIRE(nnz >= 1 && nnz < ((int64_t)1 << 31), "1 <= nnz < 2^31");
+  RK_SIDE_REQUIRE(step >= 0 && T >= 1 && T <= BPR_MAX_T, "step >= 0, 1 <= T <= 2^24");
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldx >= h && ldy >= h, "1 <= h <= 512, ldx >= h, ldy >= h");
+  RK_SIDE_REQUIRE(mode == RANK_WARP || mode == RANK_DNS, "mode is RK_ALS_RANK_WARP or RK_ALS_RANK_DNS");
+  RK_SIDE_REQUIRE(max_draws >= 1 && max_draws <= RANK_MAX_DRAWS, "1 <= max_draws <= 256");
+  RK_SIDE_REQUIRE(mode != RANK_DNS || (num_candidates >= 1 && num_candidates <= max_draws),
+                  "1 <= num_candidates <= max_draws");
+  RK_SIDE_REQUIRE(mode != RANK_WARP || (margin >= 0.f && margin <= FLT_MAX), "margin must be finite and >= 0");
+  RK_SIDE_REQUIRE(indptr && indices && X && Y && bias && users && pos && neg && trials, "null pointer");
+  const dim3 grid((unsigned)((T + 3) / 4));
+  hipStream_t st = (hipStream_t)stream;
+  switch (nt_of(h)) {
+    case 1: ALS_RANK_SAMPLE_LAUNCH(1, 8); break;
+    case 2: ALS_RANK_SAMPLE_LAUNCH(2, 8); break;
+    case 4: ALS_RANK_SAMPLE_LAUNCH(4, 4); break;
+    default: ALS_RANK_SAMPLE_LAUNCH(8, 4); break;
+  }
+  RK_SIDE_CHECK_LAUNCH("als_rank_sample");
+  return 0;
+}
+
+#define ALS_WARP_GRAD_LAUNCH(NT)                                                                                  \
+  hipLaunchKernelGGL(als_warp_grad_kernel<NT>, grid, dim3(256), 0, st, users, pos, neg, trials, T, n_users, n_items, \
+                     X, ldx, Y, ldy, bias, h, margin, weight, g, loss, D, P)
+
+extern "C" int rk_als_warp_grad(const int32_t *users, const int32_t *pos, const int32_t *neg, const int32_t *trials,
+                                int32_t T, int32_t n_users, int32_t n_items, const float *X, int32_t ldx,
+                                const float *Y, int32_t ldy, const float *bias, int32_t h, float margin,
+                                const float *weight, float *g, float *loss, float *D, float *P, void *stream) {
+  RK_SIDE_REQUIRE(h >= 1 && h <= MAX_H && ldx >= h && ldy >= h, "1 <= h <= 512, ldx >= h, ldy >= h");
+  RK_SIDE_REQUIRE(T >= 1 && T <= BPR_MAX_T && n_users >= 1 && n_items >= 1, "1 <= T <= 2^24, n_users, n_items >= 1");
+  RK_SIDE_REQUIRE(margin >= 0.f && margin <= FLT_MAX, "margin must be finite and >= 0");
+  RK_SIDE_REQUIRE(users && pos && neg && trials && X && Y && bias && weight && g && loss && D && P, "null pointer");
+  const dim3 grid((unsigned)((T + 3) / 4));
+  hipStream_t st = (hipStream_t)stream;
+  switch (nt_of(h)) {
+    case 1: ALS_WARP_GRAD_LAUNCH(1); break;
+    case 2: ALS_WARP_GRAD_LAUNCH(2); break;
+    case 4: ALS_WARP_GRAD_LAUNCH(4); break;
+    default: ALS_WARP_GRAD_LAUNCH(8); break;
+  }
+  RK_SIDE_CHECK_LAUNCH("als_warp_grad");
+  return 0;
+}
+
+#define ALS_LGCN_PROP_LAUNCH(VEC, NT)                                                                         \
   do {                                                                                                         \
     hipLaunchKernelGGL((als_lgcn_propagate_kernel<VEC, NT, NOISE>), grid, dim3(256), 0, st, indptr, indices,   \
                        row_scale, col_scale, row_lo, row_hi, F, ldf, h, G, Out, ldo, Acc, lda, acc_scale, nz); \

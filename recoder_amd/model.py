@@ -97,6 +97,8 @@ class Recoder(object):
     self.loss_history = []      # per-epoch arrays of the per-step training losses
     self.als_history = []       # train_als: the ALS objective after each iteration
     self.bpr_history = []       # train_bpr: the mean loss per valid triple of each epoch
+    self.warp_history = []      # train_warp: the mean loss per valid slot of each epoch
+    self.warp_stats = []        # train_warp: (share of slots with a violator, their mean trials) of each epoch
     self.lightgcn_history = []  # train_lightgcn: the mean loss per valid triple of each epoch
     self.lightgcn_state = None  # train_lightgcn: base tables, Adam moments, step count, num_layers (device; not saved)
     self.simgcl_history = []    # train_simgcl: (mean BPR loss per valid triple, mean NCE per step) of each epoch
@@ -528,7 +530,7 @@ class Recoder(object):
         fit=lambda m, pair, alpha: als.fit(*_mf_tables(m), m.bias.data, *pair, alpha, float(reg), int(cg_steps),
                                            int(num_iterations)))
 
-  def train_bpr(self, train_dataset, num_epochs=40, batch_size=1024, lr=0.1, reg=0.01, seed=0):
+  def train_bpr(self, train_dataset, num_epochs=40, batch_size=1024, lr=0.1, reg=0.01, seed=0, num_candidates=1):
     """BPR-MF (Rendle et al. 2009) for a MatrixFactorization with activation 'none' (recoder_amd/bpr.py):
     pairwise ranking on sampled triples (user, a stored item, an item the user does not hold), loss
     softplus(-(x_ui - x_uj)), synchronous mini-batch SGD with learning rate ``lr`` and an L2 pull ``reg``
@@ -537,14 +539,42 @@ class Recoder(object):
     the step (counted from 0 in every call) and the slot, so a fixed seed gives the same bits.  The
     stored values and the configured ``loss`` play no part.  Builds a fresh optimizer of
     ``optimizer_type``, so that ``save_state``, ``train`` and ``train_als`` work on the tables it leaves.
+    With ``num_candidates`` > 1 (up to 32) the negative is not the first item the user does not hold but the
+    highest-scored of the first ``num_candidates`` such draws, at the tables as they stand at the start of the
+    step (dynamic negative sampling, Zhang et al. 2013); everything else is unchanged.
     Returns (and keeps in ``bpr_history``) the mean loss per valid triple of each epoch."""
     from . import bpr
     return self._closed_form_fit(
         bpr, train_dataset, "bpr_history", copy=list, csrs=bpr.user_csr,
-        check=lambda m: bpr.check_config(m, num_epochs, batch_size, lr, reg, seed),
-        log_line=lambda c: ("BPR: %d epochs of batches of %d, lr %g, reg %g, seed %d",) + c,
+        check=lambda m: bpr.check_config(m, num_epochs, batch_size, lr, reg, seed)
+        + (bpr.check_candidates(num_candidates),),
+        log_line=lambda c: ("BPR: %d epochs of batches of %d, lr %g, reg %g, seed %d, %d candidate(s) per slot",) + c,
         size_check=lambda c, host: bpr.check_data(host().nnz, self.num_items, c[0], c[1]),
-        fit=lambda m, ucsr, c: bpr.fit(*_mf_tables(m), m.bias.data, ucsr, *c))
+        fit=lambda m, ucsr, c: bpr.fit(*_mf_tables(m), m.bias.data, ucsr, *c[:5], num_candidates=c[5]))
+
+  def train_warp(self, train_dataset, num_epochs=10, batch_size=1024, lr=0.005, reg=0.05, margin=1.0,
+                 max_draws=32, rank_weight="log", seed=0):
+    """WARP (Weston et al. 2011; LightFM's loss) for a MatrixFactorization with activation 'none'
+    (recoder_amd/warp.py): a slot is one of ``train_bpr``'s stored entries (u, i); items the user does not hold
+    are drawn and scored until one violates the margin, (s_uj - s_ui) + ``margin`` > 0, and the update is BPR's
+    with the weight of the rank that the number N of scored candidates estimates: ``rank_weight`` 'log' is
+    log(max(1, (n_items - 1) // N)), 'harmonic' the harmonic number of (n_items - 1) // N.  A slot without a
+    violator in ``max_draws`` (1..256) draws adds nothing.  Epochs, ``lr``, ``reg``, the seed and what the fitted
+    tables plug into are as in ``train_bpr``; the users and stored items of a step are its draws for the same
+    seed.  Returns (and keeps in ``warp_history``) the mean loss per valid slot of each epoch; ``warp_stats``
+    keeps per epoch (the share of slots that found a violator, their mean N): as the model learns the share
+    falls and N rises."""
+    from . import warp
+
+    def fit(m, ucsr, c):
+      hist, self.warp_stats = warp.fit(*_mf_tables(m), m.bias.data, ucsr, *c)
+      return hist
+    return self._closed_form_fit(
+        warp, train_dataset, "warp_history", copy=list, csrs=warp.bpr.user_csr, fit=fit,
+        check=lambda m: warp.check_config(m, num_epochs, batch_size, lr, reg, margin, max_draws, rank_weight, seed),
+        log_line=lambda c: ("WARP: %d epochs of batches of %d, lr %g, reg %g, margin %g, at most %d draws, %s "
+                            "weights, seed %d",) + c,
+        size_check=lambda c, host: warp.check_data(host().nnz, self.num_items, c[0], c[1]))
 
   def _graph_fit(self, mod, prefix, train_dataset, resume, log_format, *config):
     """``_closed_form_fit`` for the three methods that train base tables over the user-item graph (the driver of
