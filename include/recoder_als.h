@@ -325,6 +325,41 @@ int rk_als_dau_grad(const int32_t *users, const int32_t *items, int32_t T, int32
                     const float *X, int32_t ldx, const float *Y, int32_t ldy, int32_t h, float gamma, void *ws,
                     int64_t ws_bytes, float *DU, float *DI, float *valid, float *loss, int32_t *count, void *stream);
 
+/* the largest T and S of rk_als_ssm_grad (its workspace holds the T x (T + S) scores) */
+#define RK_ALS_SSM_MAX_BATCH 4096
+#define RK_ALS_SSM_MAX_NEGATIVES 4096
+
+/* bytes of rk_als_ssm_grad's workspace; -2 unless 1 <= T <= RK_ALS_SSM_MAX_BATCH, 0 <= S <=
+ * RK_ALS_SSM_MAX_NEGATIVES and 1 <= h <= 512 */
+int64_t rk_als_ssm_workspace_bytes(int32_t T, int32_t S, int32_t h);
+
+/*
+ * The sampled softmax of the T slots (users[t], items[t]) of a step over C = T + S candidate columns, at the final
+ * tables X [n_users, ldx] and Y [n_items, ldy].  Column c < T holds items[c] (the in-batch negatives of every other
+ * row); column T + n holds the n-th shared negative, drawn uniformly from [0, n_items) by the sampler's counter hash
+ * of (seed, step, n) under a domain of its own, nothing rejected.  cand (int32 [C]) receives the columns' items.
+ * Slot t is valid when both ids lie in their tables, column c < T when slot c is, a shared column always.  With
+ *   s_tc = sim(X[users[t]], Y[cand[c]]) * inv_tau - corr[cand[c]]      (corr NULL: 0)
+ * sim the cosine (cosine = 1; a row of norm 0 has z = 0) or the dot product (cosine = 0), the LIVE columns of a
+ * valid row t are the valid ones except those c != t with cand[c] == items[t]; over them and the m valid slots
+ *   loss[0] = (1 / m) sum_t (lse_t - s_tt),   loss[1] = (1 / m) sum_t exp(s_tt - lse_t)          (0 when m == 0)
+ *   count[0] = m,  valid[t] and cvalid[c] = 1.0 or 0.0
+ *   DU[t, :h] = d loss[0] / d X[users[t]] taken through slot t alone, DC[c, :h] = d loss[0] / d Y[cand[c]] taken
+ *   through column c alone: rk_als_lgcn_scatter with roles = 1 sums them per row (g = valid over the T users,
+ *   g = cvalid over the C candidates).
+ * The rows of an invalid slot or column are +0, and so is the own row of a table row of norm 0 under the cosine.  A
+ * row whose only live column is its own has the loss term 0 and zero weights exactly.  DU (f32 [T, h]), DC (f32
+ * [C, h]), valid (f32 [T]), cvalid (f32 [C]), loss (f32 [2]) and count (int32 [1]) are device memory; the
+ * workspace holds the T x C scores, overwritten by the weights.  The scores and both gradient products run on
+ * v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32 with k ascending.  A fixed summation order: the same inputs give
+ * the same bits.
+ */
+int rk_als_ssm_grad(const int32_t *users, const int32_t *items, int32_t T, int32_t S, int64_t seed, int32_t step,
+                    int32_t n_users, int32_t n_items, const float *X, int32_t ldx, const float *Y, int32_t ldy,
+                    int32_t h, float inv_tau, int32_t cosine, const float *corr, void *ws, int64_t ws_bytes,
+                    int32_t *cand, float *DU, float *DC, float *valid, float *cvalid, float *loss, int32_t *count,
+                    void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

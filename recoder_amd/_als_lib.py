@@ -1,8 +1,8 @@
 """ctypes binding of librecoder_als.so (the C ABI in include/recoder_als.h): implicit-feedback ALS
 for recoder_amd.als, the BPR step (rk_als_bpr_*) for recoder_amd.bpr, the WARP / DNS sampler and WARP's
 gradient (rk_als_rank_sample, rk_als_warp_grad) for recoder_amd.warp, the LightGCN kernels
-(rk_als_lgcn_*) for recoder_amd.lightgcn, SimGCL's (rk_als_gcl_*) for recoder_amd.simgcl and DirectAU's
-(rk_als_dau_*) for recoder_amd.directau.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
+(rk_als_lgcn_*) for recoder_amd.lightgcn, SimGCL's (rk_als_gcl_*) for recoder_amd.simgcl, DirectAU's
+(rk_als_dau_*) for recoder_amd.directau and the sampled softmax's (rk_als_ssm_*) for recoder_amd.ssm.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
 import os
 
 # PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
@@ -21,6 +21,7 @@ FORCE_STREAM = 1      # RK_ALS_FORCE_STREAM
 G_GLOBAL = 2          # RK_ALS_G_GLOBAL
 LGCN_LONG_ROW = 1024  # RK_ALS_LGCN_LONG_ROW
 GCL_MAX_BATCH = 4096  # RK_ALS_GCL_MAX_BATCH
+SSM_MAX_BATCH, SSM_MAX_NEGATIVES = 4096, 4096  # RK_ALS_SSM_MAX_BATCH, RK_ALS_SSM_MAX_NEGATIVES
 RANK_MAX_DRAWS = 256  # RK_ALS_RANK_MAX_DRAWS
 RANK_WARP, RANK_DNS = 0, 1  # RK_ALS_RANK_WARP, RK_ALS_RANK_DNS
 
@@ -61,6 +62,9 @@ SIGNATURES = {
   "rk_als_dau_workspace_bytes": (c_int64, [c_int32, c_int32]),
   "rk_als_dau_grad": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32, c_float, _P,
                                 c_int64, _P, _P, _P, _P, _P, _P]),
+  "rk_als_ssm_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+  "rk_als_ssm_grad": (c_int32, [_P, _P, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, _P, c_int32, _P,
+                                c_int32, c_int32, c_float, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

@@ -15,7 +15,8 @@ librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recode
                    and SimGCL's on top of them (rk_als_gcl_*: the propagation with noise in its epilogue,
                    the contrast between two views) and DirectAU's (rk_als_dau_workspace_bytes,
                    rk_als_dau_grad: the alignment and uniformity loss with its gradient rows, on the contrast's
-                   tile code)
+                   tile code) and the sampled softmax's (rk_als_ssm_workspace_bytes, rk_als_ssm_grad: the
+                   softmax over in-batch and shared uniform negatives with its gradient rows, on the f32 MFMA)
 librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own
 librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencoder

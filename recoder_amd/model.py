@@ -105,6 +105,8 @@ class Recoder(object):
     self.simgcl_state = None    # train_simgcl: base tables, Adam moments, step count, num_layers (device; not saved)
     self.directau_history = []  # train_directau: (alignment, uniformity users, uniformity items) means of each epoch
     self.directau_state = None  # train_directau: base tables, Adam moments, step count, num_layers (device; not saved)
+    self.ssm_history = []       # train_ssm: (mean loss, mean probability of the positive) per step, of each epoch
+    self.ssm_state = None       # train_ssm: base tables, Adam moments, step count, num_layers (device; not saved)
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -659,6 +661,37 @@ class Recoder(object):
     return self._graph_fit(directau, "directau", train_dataset, resume,
                            "DirectAU: %d layers, %d epochs of batches of %d, lr %g, reg %g, gamma %g, seed %d",
                            num_layers, num_epochs, batch_size, lr, reg, gamma, seed)
+
+  def train_ssm(self, train_dataset, num_layers=2, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3,
+                temperature=0.2, num_negatives=1024, similarity="cosine", logq_weight=0.0, normalize=False, seed=0,
+                resume=False):
+    """Sampled-softmax training (Wu et al. 2022; the in-batch softmax of Yi et al. 2019 and the mixed negatives of
+    Yang et al. 2020) for a MatrixFactorization with activation 'none' (recoder_amd/ssm.py).  A step takes the
+    (user, stored item) pairs of BPR's draws (those of ``train_bpr`` and ``train_lightgcn`` for the same seed,
+    step and slot) and descends the mean of -log softmax of a pair's logit over ``batch_size`` +
+    ``num_negatives`` candidates: the batch's own positives and ``num_negatives`` items drawn uniformly from the
+    catalogue, shared by the batch (a function of seed, step and index; nothing is rejected, and of the items a
+    user holds only a repeat of the pair's own positive is left out of its row).  The logit is the cosine
+    (``similarity="dot"``: the dot product) of the rows of the final tables over ``temperature``, minus
+    ``logq_weight`` times the logarithm of the share of the candidates the item is expected to hold (Yi et
+    al.'s correction, on the positive as on the negatives; 0 switches it off).  The final tables are LightGCN's
+    mean over ``num_layers`` + 1 layers; ``num_layers = 0`` trains the tables themselves and propagates nothing.
+    Adam at learning rate ``lr``, the L2 term ``reg`` on the base rows a slot or a candidate touches;
+    ``batch_size`` is at most ``ssm.MAX_BATCH`` and ``num_negatives`` at most ``ssm.MAX_NEGATIVES``.  The base
+    tables of a first call are the tables as they stand; they, both Adam moments, the step count and
+    ``num_layers`` stay in ``ssm_state`` (device tensors, not part of a checkpoint), and ``resume=True`` continues
+    from them with the draws, moments and step count one longer call would have had.  The model's tables end as
+    the final tables -- un-normalised, or with ``normalize=True`` row-normalised, so that the dot product of
+    ``recommend`` ranks by the cosine the fit trained; the state's base tables are never normalised -- and the
+    bias as 0: ``save_state``, ``recommend``, ``evaluate``, ``train``, ``train_als`` and ``train_bpr`` take them
+    as they are.  The stored values and the configured ``loss`` play no part.  Returns (and keeps in
+    ``ssm_history``) one (loss, probability of the positive) pair of per-step means per epoch."""
+    from . import ssm
+    return self._graph_fit(ssm, "ssm", train_dataset, resume,
+                           "SSM: %d layers, %d epochs of batches of %d, lr %g, reg %g, temperature %g, %d shared "
+                           "negatives, %s similarity, logq_weight %g, normalize %s, seed %d",
+                           num_layers, num_epochs, batch_size, lr, reg, temperature, num_negatives, similarity,
+                           logq_weight, normalize, seed)
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
