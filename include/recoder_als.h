@@ -360,6 +360,61 @@ int rk_als_ssm_grad(const int32_t *users, const int32_t *items, int32_t T, int32
                     int32_t *cand, float *DU, float *DC, float *valid, float *cvalid, float *loss, int32_t *count,
                     void *stream);
 
+/* the limits of rk_als_ugcn_grad: T slots, R negatives and K neighbours a slot, T (1 + R + K) entries a step; a
+ * key of rk_als_ugcn_scatter with this many entries or more is summed by a whole workgroup */
+#define RK_ALS_UGCN_MAX_BATCH 4096
+#define RK_ALS_UGCN_MAX_NEGATIVES 1024
+#define RK_ALS_UGCN_MAX_NEIGHBOURS 64
+#define RK_ALS_UGCN_MAX_ENTRIES (1 << 22)
+#define RK_ALS_UGCN_LONG_KEY 1024
+
+/* bytes of the step's buffers cand (int32 [T, E]), coef (f32 [T, E]) and loss (f32 [T, 3]), E = 1 + R + K, each
+ * rounded up to 256 bytes and laid out in that order; -2 unless 1 <= T <= RK_ALS_UGCN_MAX_BATCH, 1 <= R <=
+ * RK_ALS_UGCN_MAX_NEGATIVES, 0 <= K <= RK_ALS_UGCN_MAX_NEIGHBOURS, T E <= RK_ALS_UGCN_MAX_ENTRIES and 1 <= h <= 512 */
+int64_t rk_als_ugcn_workspace_bytes(int32_t T, int32_t R, int32_t K, int32_t h);
+
+/*
+ * UltraGCN's constraint loss and its gradient over the T slots (users[t], items[t]) of a step, at the tables
+ * X [n_users, ldx] and Y [n_items, ldy].  Slot t is valid when both ids lie in their tables.  It scores E = 1 + R + K
+ * candidate items with s = X[users[t]] . Y[item] (no bias):
+ *   column 0            the positive items[t]:  a = w1 + w2 bu[u] bi[i],                  term a softplus(-s)
+ *   columns 1 .. R      negative r = column - 1, drawn uniformly from [0, n_items) by the sampler's counter hash of
+ *                       (seed, step, t R + r) under a domain of its own, nothing rejected:
+ *                       a = (negative_weight / R) (w3 + w4 bu[u] bi[j]),                  term a softplus(s)
+ *   columns R + 1 ..    neighbour n of the positive, nbr_ids[i, n] with the weight nbr_w[i, n] (an id outside
+ *                       [0, n_items) is an absent neighbour):  a = item_weight nbr_w[i, n],  term a softplus(-s)
+ * and leaves
+ *   cand [T, E]   the columns' items; n_items for an absent neighbour and for every column of an invalid slot
+ *   coef [T, E]   d term / d s; +0 for an absent or invalid entry
+ *   DU [T, :h]    sum_e coef[t, e] Y[cand[t, e]], over e ascending (+0 for an invalid slot)
+ *   valid [T]     1.0 or 0.0
+ *   loss [T, 3]   the positive's term, the sum of the negatives' terms, the sum of the neighbours' terms
+ * rk_als_lgcn_scatter with roles = 1 and g = valid sums DU per user row; rk_als_ugcn_scatter sums the item side.  One
+ * wave per slot; sigma and softplus through e = exp(-|x|) as in rk_als_bpr_grad.  bu (f32 [n_users]), bi (f32
+ * [n_items]), nbr_ids (int32 [n_items, K]) and nbr_w (f32 [n_items, K]) may be NULL when K == 0 (the two lists).
+ * A fixed summation order: the same inputs give the same bits, whatever the leading dimensions.
+ */
+int rk_als_ugcn_grad(const int32_t *users, const int32_t *items, int32_t T, int32_t R, int32_t K, int64_t seed,
+                     int32_t step, int32_t n_users, int32_t n_items, const float *X, int32_t ldx, const float *Y,
+                     int32_t ldy, int32_t h, const float *bu, const float *bi, const int32_t *nbr_ids,
+                     const float *nbr_w, float w1, float w2, float w3, float w4, float negative_weight,
+                     float item_weight, int32_t *cand, float *coef, float *DU, float *valid, float *loss,
+                     void *stream);
+
+/*
+ * The item side of rk_als_ugcn_grad: keys (int32 [n], n = T E) are the cand entries stably sorted ascending and
+ * order (int64 [n]) their positions e before the sort.  For every key in [0, n_rows) among them
+ *   G[key, :h] = scale * sum coef[e] X[users[e / E], :h]     over the key's entries in ascending position
+ *   count[key] = the key's entries with e % E == 0 (the slots whose positive it is)
+ * The user rows are gathered from X [n_users, ldx]; an entry whose position or user lies outside its range adds
+ * nothing.  Rows without a key are not touched: the caller zeroes G [n_rows, ldg] and count (int32 [n_rows]) first.
+ * A key with fewer than RK_ALS_UGCN_LONG_KEY entries is one f32 fmaf chain of one wave; a longer one is cut into 16
+ * equal parts, one chain each, summed in ascending part order.  No atomics.
+ */
+int rk_als_ugcn_scatter(const int32_t *keys, const int64_t *order, int32_t n, int32_t E, const int32_t *users,
+                        const float *coef, const float *X, int32_t ldx, int32_t n_users, int32_t h, float scale,
+                        int32_t n_rows, float *G, int32_t ldg, int32_t *count, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

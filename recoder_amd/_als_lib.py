@@ -2,7 +2,8 @@
 for recoder_amd.als, the BPR step (rk_als_bpr_*) for recoder_amd.bpr, the WARP / DNS sampler and WARP's
 gradient (rk_als_rank_sample, rk_als_warp_grad) for recoder_amd.warp, the LightGCN kernels
 (rk_als_lgcn_*) for recoder_amd.lightgcn, SimGCL's (rk_als_gcl_*) for recoder_amd.simgcl, DirectAU's
-(rk_als_dau_*) for recoder_amd.directau and the sampled softmax's (rk_als_ssm_*) for recoder_amd.ssm.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
+(rk_als_dau_*) for recoder_amd.directau, the sampled softmax's (rk_als_ssm_*) for recoder_amd.ssm and UltraGCN's (rk_als_ugcn_*) for
+recoder_amd.ultragcn.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
 import os
 
 # PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
@@ -22,6 +23,8 @@ G_GLOBAL = 2          # RK_ALS_G_GLOBAL
 LGCN_LONG_ROW = 1024  # RK_ALS_LGCN_LONG_ROW
 GCL_MAX_BATCH = 4096  # RK_ALS_GCL_MAX_BATCH
 SSM_MAX_BATCH, SSM_MAX_NEGATIVES = 4096, 4096  # RK_ALS_SSM_MAX_BATCH, RK_ALS_SSM_MAX_NEGATIVES
+UGCN_MAX_BATCH, UGCN_MAX_NEGATIVES, UGCN_MAX_NEIGHBOURS = 4096, 1024, 64  # RK_ALS_UGCN_MAX_BATCH, _NEGATIVES, _NEIGHBOURS
+UGCN_MAX_ENTRIES, UGCN_LONG_KEY = 1 << 22, 1024  # RK_ALS_UGCN_MAX_ENTRIES, RK_ALS_UGCN_LONG_KEY
 RANK_MAX_DRAWS = 256  # RK_ALS_RANK_MAX_DRAWS
 RANK_WARP, RANK_DNS = 0, 1  # RK_ALS_RANK_WARP, RK_ALS_RANK_DNS
 
@@ -65,6 +68,12 @@ SIGNATURES = {
   "rk_als_ssm_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
   "rk_als_ssm_grad": (c_int32, [_P, _P, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, _P, c_int32, _P,
                                 c_int32, c_int32, c_float, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+  "rk_als_ugcn_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+  "rk_als_ugcn_grad": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, _P, c_int32,
+                                 _P, c_int32, c_int32, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float,
+                                 c_float, _P, _P, _P, _P, _P, _P]),
+  "rk_als_ugcn_scatter": (c_int32, [_P, _P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, c_float, c_int32,
+                                    _P, c_int32, _P, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

@@ -17,6 +17,9 @@ librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recode
                    rk_als_dau_grad: the alignment and uniformity loss with its gradient rows, on the contrast's
                    tile code) and the sampled softmax's (rk_als_ssm_workspace_bytes, rk_als_ssm_grad: the
                    softmax over in-batch and shared uniform negatives with its gradient rows, on the f32 MFMA)
+                   and UltraGCN's (rk_als_ugcn_workspace_bytes, rk_als_ugcn_grad, rk_als_ugcn_scatter: the
+                   constraint loss over a slot's private negatives and the positive's neighbours, and the
+                   item-side sum that gathers its user rows)
 librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own
 librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencoder

@@ -107,6 +107,8 @@ class Recoder(object):
     self.directau_state = None  # train_directau: base tables, Adam moments, step count, num_layers (device; not saved)
     self.ssm_history = []       # train_ssm: (mean loss, mean probability of the positive) per step, of each epoch
     self.ssm_state = None       # train_ssm: base tables, Adam moments, step count, num_layers (device; not saved)
+    self.ultragcn_history = []  # train_ultragcn: (positive, negatives, neighbours) means per valid slot of each epoch
+    self.ultragcn_state = None  # train_ultragcn: the tables, Adam moments and step count (device; not saved)
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -692,6 +694,34 @@ class Recoder(object):
                            "negatives, %s similarity, logq_weight %g, normalize %s, seed %d",
                            num_layers, num_epochs, batch_size, lr, reg, temperature, num_negatives, similarity,
                            logq_weight, normalize, seed)
+
+  def train_ultragcn(self, train_dataset, num_epochs=20, batch_size=1024, lr=0.01, reg=1e-3, num_negatives=32,
+                     negative_weight=8.0, neighbours=10, item_weight=1e-3, w=(1e-7, 1.0, 1e-7, 1.0), seed=0,
+                     resume=False):
+    """UltraGCN (Mao et al. 2021) for a MatrixFactorization with activation 'none' (recoder_amd/ultragcn.py): no
+    message passing.  A step takes the (user, stored item) pairs of BPR's draws (those of ``train_bpr`` and
+    ``train_lightgcn`` for the same seed, step and slot), draws ``num_negatives`` items per pair uniformly from the
+    catalogue (a function of seed, step, slot and index, private to the slot; nothing is rejected) and descends the
+    mean over the pairs of a pointwise log-loss with degree-derived weights -- (w1 + w2 beta) on the positive,
+    ``negative_weight`` / ``num_negatives`` (w3 + w4 beta) on every negative, beta_ux = sqrt(r_u + 1) / r_u /
+    sqrt(d_x + 1) -- plus ``item_weight`` times the log-loss of the user against the ``neighbours`` items most
+    related to the positive in the item-item co-occurrence graph, weighted by the paper's omega.
+    ``item_weight = 0`` or ``neighbours = 0`` is UltraGCN-base: no item graph (an items x items buffer) is built.
+    Adam at learning rate ``lr``, the L2 term ``reg`` on the rows a pair touches as its user or its positive;
+    ``batch_size`` is at most ``ultragcn.MAX_BATCH``, ``num_negatives`` at most ``ultragcn.MAX_NEGATIVES``,
+    ``neighbours`` at most ``ultragcn.MAX_NEIGHBOURS`` and ``batch_size`` * (1 + ``num_negatives`` + ``neighbours``)
+    at most ``ultragcn.MAX_ENTRIES``.  The tables, both Adam moments and the step count stay in ``ultragcn_state``
+    (device tensors, not part of a checkpoint), and ``resume=True`` continues from them with the draws, moments and
+    step count one longer call would have had.  The model's tables end as the trained tables and the bias as 0:
+    ``save_state``, ``recommend``, ``evaluate``, ``train``, ``train_als`` and ``train_bpr`` take them as they are.  The
+    stored values and the configured ``loss`` play no part.  Returns (and keeps in ``ultragcn_history``) one
+    (positive, negatives, neighbours) triple of the three terms' means per valid pair per epoch."""
+    from . import ultragcn
+    return self._graph_fit(ultragcn, "ultragcn", train_dataset, resume,
+                           "UltraGCN: %d layers, %d epochs of batches of %d, lr %g, reg %g, %d negatives a slot at "
+                           "weight %g, %d neighbours at weight %g, w %s, seed %d",
+                           num_epochs, batch_size, lr, reg, num_negatives, negative_weight, neighbours, item_weight, w,
+                           seed)
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'

@@ -1,0 +1,344 @@
+"""UltraGCN (Mao, Zhu, Xiao, Lu, Wang & He, CIKM 2021, "UltraGCN: Ultra Simplification of Graph Convolutional
+Networks for Recommendation") for ``MatrixFactorization``, on rk_als_ugcn_grad and rk_als_ugcn_scatter of
+librecoder_als.so (include/recoder_als.h), the sampler of recoder_amd/bpr.py, the scatter, Adam and driver of
+recoder_amd/lightgcn.py and the sparse Gram of recoder_amd/ease.py.
+
+The model is a ``MatrixFactorization`` with ``activation_type="none"``; nothing is propagated: the tables X, Y are
+the trainable parameters (the driver runs at ``num_layers = 0``).  With r_u the stored items of user u, d_x the users
+of item x,
+
+    b^U_u = sqrt(r_u + 1) / r_u  (0 for r_u = 0),    b^I_x = 1 / sqrt(d_x + 1),    beta_ux = b^U_u b^I_x,
+
+the item-item graph G = A^T A over the binary matrix, g_i = sum_k G_ik and, for i != j with G_ij > 0,
+
+    omega_ij = G_ij / (g_i - G_ii) sqrt(g_i / g_j)                                               (the paper's eq. 11)
+
+with S(i) the ``neighbours`` largest omega_ij of row i (ties to the lower id), a step draws T slots (u_t, i_t) with
+BPR's sampler -- the negative of the draw is ignored -- and R items j_t1 .. j_tR per slot uniformly from the
+catalogue (a counter hash of (seed, step, t R + r); nothing rejected), and descends the mean over the valid slots of
+
+    L_t = (w1 + w2 beta_ui) softplus(-s_ui) + (negative_weight / R) sum_r (w3 + w4 beta_uj_r) softplus(s_uj_r)
+        + item_weight sum_{n in S(i)} omega_in softplus(-s_un),          s_ux = X[u] . Y[x],
+
+plus the driver's L2 term on the base rows a slot touches as user or as positive.  rk_als_ugcn_grad leaves the
+E = 1 + R + K candidates of every slot with d L_t / d s and the users' gradient rows; rk_als_lgcn_scatter sums those
+per user, rk_als_ugcn_scatter sums the T E weighted user rows per item, gathered from X; Adam steps both tables.
+
+``Recoder.train_ultragcn`` is the public entry point; the functions below are the layer under it (and what the tests
+and tools/ultragcn_bench.py drive directly).
+"""
+import types
+
+import numpy as np
+import torch
+
+from . import _als_lib, als, bpr, ease, lightgcn
+from ._lib import ptr
+from .bpr import _count, _f32, _i32, _number, _round256
+from .device import DEVICE_HBM_BYTES, current_stream
+from .lightgcn import _table, new_state  # noqa: F401  (new_state: this module's too)
+
+MAX_H = als.MAX_H                                   # rk_als_max_h()
+MAX_BATCH = _als_lib.UGCN_MAX_BATCH                 # RK_ALS_UGCN_MAX_BATCH
+MAX_NEGATIVES = _als_lib.UGCN_MAX_NEGATIVES         # RK_ALS_UGCN_MAX_NEGATIVES
+MAX_NEIGHBOURS = _als_lib.UGCN_MAX_NEIGHBOURS       # RK_ALS_UGCN_MAX_NEIGHBOURS
+MAX_ENTRIES = _als_lib.UGCN_MAX_ENTRIES             # RK_ALS_UGCN_MAX_ENTRIES: T (1 + R + K) at most
+LONG_KEY = _als_lib.UGCN_LONG_KEY                   # RK_ALS_UGCN_LONG_KEY
+GRAPH_BLOCK_BYTES = 1 << 28                         # about what one row block of ``item_graph`` holds at its peak
+GRAPH_BLOCK_IMAGES = 12                             # the [rows, n] 8-byte images that budget counts (see graph_block_rows)
+
+
+def check_not_distributed():
+  """ValueError under more than one rank."""
+  try:
+    als.check_not_distributed("train_ultragcn runs on one GPU: multi-GPU UltraGCN is not implemented")
+  except NotImplementedError as e:
+    raise ValueError(str(e)) from None
+
+
+def check_weights(w):
+  """``w`` = (w1, w2, w3, w4) as four floats >= 0."""
+  if isinstance(w, (str, bytes)) or not hasattr(w, "__len__") or len(w) != 4:
+    raise ValueError("w must be four numbers (w1, w2, w3, w4) (got %r)" % (w,))
+  return tuple(_number("w[%d]" % k, v, False) for k, v in enumerate(w))
+
+
+def check_config(model, num_epochs, batch_size, lr, reg, num_negatives, negative_weight, neighbours, item_weight, w,
+                 seed):
+  """The contract of ``train_ultragcn``, checked before any GPU work; returns (0, num_epochs, batch_size, lr, reg,
+  num_negatives, negative_weight, neighbours, item_weight, w, seed): the leading 0 is the driver's ``num_layers``."""
+  c = lightgcn.check_config(model, 0, num_epochs, batch_size, lr, reg, seed, METHOD)
+  R = _count("num_negatives", num_negatives, 1, MAX_NEGATIVES)
+  K = _count("neighbours", neighbours, 0, MAX_NEIGHBOURS)
+  if c[2] * (1 + R + K) > MAX_ENTRIES:
+    raise ValueError("batch_size * (1 + num_negatives + neighbours) must be at most %d (got %d * %d)"
+                     % (MAX_ENTRIES, c[2], 1 + R + K))
+  return c[:5] + (R, _number("negative_weight", negative_weight, False), K, _number("item_weight", item_weight, False),
+                  check_weights(w), c[5])
+
+
+def check_resume(state, num_layers=0, shapes=None):
+  """ValueError unless ``state`` (an ``ultragcn_state``) can continue a fit on tables of ``shapes``."""
+  lightgcn.check_resume(state, num_layers, shapes, method="train_ultragcn")
+
+
+def check_data(nnz, n_items, num_epochs, batch_size):
+  return bpr.check_data(nnz, n_items, num_epochs, batch_size, method="train_ultragcn")
+
+
+def active_neighbours(neighbours, item_weight):
+  """The K the kernels run at: 0 when the neighbour term is switched off (UltraGCN-base: no item graph is built)."""
+  return int(neighbours) if item_weight > 0 else 0
+
+
+def workspace_bytes(T, R, K, h):
+  """rk_als_ugcn_workspace_bytes(T, R, K, h), restated on the host: cand and coef [T, E] and loss [T, 3], each
+  rounded up to 256 bytes."""
+  T, R, K, h = int(T), int(R), int(K), int(h)
+  if not (1 <= T <= MAX_BATCH and 1 <= R <= MAX_NEGATIVES and 0 <= K <= MAX_NEIGHBOURS and 1 <= h <= MAX_H):
+    return -2
+  n = T * (1 + R + K)
+  if n > MAX_ENTRIES:
+    return -2
+  return 2 * _round256(4 * n) + _round256(12 * T)
+
+
+def graph_block_rows(n):
+  """The rows of one block of ``item_graph``, so that about GRAPH_BLOCK_BYTES are live at the block's peak: the
+  block of G in float64, the quotient, the ratio and its root, their product, the masked omega and its fill (seven
+  float64 images, the boolean mask beside them), the sorted values and int64 positions, and as much again for the
+  sort's own workspace -- counted as GRAPH_BLOCK_IMAGES = 12 images of 8 bytes.  What the allocator really holds
+  depends on torch's sort; the figure is a budget, not a measurement."""
+  return max(1, min(int(n), GRAPH_BLOCK_BYTES // (GRAPH_BLOCK_IMAGES * 8 * max(1, int(n)))))
+
+
+def graph_bytes(n, neighbours):
+  """Device bytes of ``item_graph`` over n items: the n x n f32 Gram (EASE's limit), the row sums and the diagonal in
+  float64, one row block's temporaries (about GRAPH_BLOCK_BYTES), and the two [n, K] lists it returns."""
+  n, K = int(n), int(neighbours)
+  return n * n * 4 + 2 * n * 8 + graph_block_rows(n) * n * GRAPH_BLOCK_IMAGES * 8 + n * K * 8
+
+
+def extra_bytes(n_users, n_items, h, T, num_negatives=1, neighbours=0):
+  """On top of ``lightgcn.required_bytes``: the step's buffers, b^U and b^I, the keys of the sort of the T E
+  candidates (an int32 key in, a key and an int64 position out, as much again for its scratch) and of the T users,
+  and, with neighbours, the lists and what ``item_graph`` holds while it builds them."""
+  E = 1 + int(num_negatives) + int(neighbours)
+  return workspace_bytes(T, num_negatives, neighbours, h) + 4 * (n_users + n_items) + \
+      2 * (T * E + T) * (4 + 4 + 8) + (graph_bytes(n_items, neighbours) if neighbours else 0)
+
+
+def required_bytes(n_users, n_items, h, nnz, T, num_negatives=1, neighbours=0, allocate_model=True,
+                   allocate_state=True, allocate_csrs=True):
+  """Device bytes of a fit: what the driver holds (``lightgcn.required_bytes``) and ``extra_bytes``."""
+  return lightgcn.method_required_bytes(METHOD, n_users, n_items, h, nnz, T, allocate_model, allocate_state,
+                                        allocate_csrs, num_negatives=num_negatives, neighbours=neighbours)
+
+
+def check_memory(n_users, n_items, h, nnz, T, num_negatives=1, neighbours=0, free_bytes=None, allocate_model=True,
+                 allocate_state=True, allocate_csrs=True):
+  """``lightgcn.method_check_memory`` of UltraGCN."""
+  return lightgcn.method_check_memory(METHOD, n_users, n_items, h, nnz, T, free_bytes, allocate_model, allocate_state,
+                                      allocate_csrs, num_negatives=num_negatives, neighbours=neighbours)
+
+
+# ------------------------------------------------------------- the constraints
+def degree_weights(user_degrees, item_degrees):
+  """(b^U [users], b^I [items]) in float64, rounded once to f32: sqrt(r + 1) / r (0 for r = 0) and 1 / sqrt(d + 1)."""
+  r, d = np.asarray(user_degrees, np.float64), np.asarray(item_degrees, np.float64)
+  bu = np.where(r > 0, np.sqrt(r + 1.0) / np.maximum(r, 1.0), 0.0)
+  return bu.astype(np.float32), (1.0 / np.sqrt(d + 1.0)).astype(np.float32)
+
+
+def _transpose(ucsr):
+  """The item-major pattern of ``ucsr`` on the device: (indptr int64 [n + 1], indices int32, users ascending)."""
+  n_users, n = ucsr.shape
+  nnz = ucsr.nnz
+  rows = torch.repeat_interleave(torch.arange(n_users, device=ucsr.indptr.device), ucsr.indptr.diff())
+  cols = ucsr.indices[:nnz].long()
+  order = torch.sort(cols, stable=True)[1]
+  indptr = torch.zeros(n + 1, dtype=torch.int64, device=cols.device)
+  indptr[1:] = torch.cumsum(torch.bincount(cols, minlength=n), 0)
+  indices = rows[order].int().contiguous() if nnz else torch.zeros(1, dtype=torch.int32, device=cols.device)
+  return indptr, indices
+
+
+def item_graph(ucsr, neighbours, icsr=None, free_bytes=None):
+  """(nbr_ids int32 [n, K], nbr_w f32 [n, K]) on the device: S(i) and its omega for every item, from the binary
+  Gram (rk_ease_gram over the pattern: the stored values play no part), its row sums, and a stable descending sort of
+  every row of omega in float64, in row blocks.  A row short of K candidates is padded with id -1 and weight 0.
+  ``icsr`` is the item-major CSR of ``als.csr_pair`` when the caller holds it.  ValueError when the n x n Gram
+  cannot fit one device (EASE's limit)."""
+  n_users, n = ucsr.shape
+  K = _count("neighbours", neighbours, 1, MAX_NEIGHBOURS)
+  need = graph_bytes(n, K)
+  if need > DEVICE_HBM_BYTES:
+    raise ValueError("UltraGCN's item graph over n = %d items needs %d bytes for its n x n fp32 Gram: more than one "
+                     "device's memory (%d bytes); item_weight = 0 or neighbours = 0 trains without it"
+                     % (n, need, DEVICE_HBM_BYTES))
+  if n >= 2 ** 31 // 256:
+    raise ValueError("UltraGCN's item graph over n = %d items is outside the Gram kernel's index range" % n)
+  if free_bytes is None:
+    free_bytes = torch.cuda.mem_get_info()[0]
+  if need > free_bytes:
+    raise ValueError("UltraGCN's item graph over n = %d items needs %d bytes of device memory, %d are free"
+                     % (n, need, free_bytes))
+  dev = ucsr.indptr.device
+  t_indptr, t_indices = (icsr.indptr, icsr.indices) if icsr is not None else _transpose(ucsr)
+  pattern = lambda indptr, indices, shape: types.SimpleNamespace(indptr=indptr, indices=indices, data=None, shape=shape)
+  G = ease.gram(pattern(ucsr.indptr, ucsr.indices, (n_users, n)), pattern(t_indptr, t_indices, (n, n_users)), 0.0)
+  g = G.sum(1, dtype=torch.float64)
+  diag = G.diagonal().double()
+  ids = torch.full((n, K), -1, dtype=torch.int32, device=dev)
+  wts = torch.zeros((n, K), dtype=torch.float32, device=dev)
+  k = min(K, n)
+  block = graph_block_rows(n)
+  safe = torch.where(g > 0, g, torch.ones_like(g))
+  for lo in range(0, n, block):
+    hi = min(n, lo + block)
+    Gb = G[lo:hi].double()
+    rest = (g[lo:hi] - diag[lo:hi])[:, None]
+    om = (Gb / torch.where(rest > 0, rest, torch.ones_like(rest))) * torch.sqrt(g[lo:hi, None] / safe[None, :])
+    dead = (Gb <= 0) | (rest <= 0)
+    dead[torch.arange(hi - lo, device=dev), torch.arange(lo, hi, device=dev)] = True
+    om = torch.where(dead, torch.full_like(om, -1.0), om)
+    val, idx = torch.sort(om, dim=1, descending=True, stable=True)
+    val, idx = val[:, :k], idx[:, :k]
+    ids[lo:hi, :k] = torch.where(val > 0, idx, torch.full_like(idx, -1)).int()
+    wts[lo:hi, :k] = torch.where(val > 0, val, torch.zeros_like(val)).float()
+    del Gb, om, dead, val, idx
+  return ids, wts
+
+
+# ------------------------------------------------------------------ kernels
+def grad(users, items, num_negatives, neighbours, seed, step_index, X, Y, bu, bi, nbr_ids, nbr_w, w, negative_weight,
+         item_weight, cand, coef, DU, valid, loss):
+  """``cand`` / ``coef`` [T, E] = the E = 1 + ``num_negatives`` + ``neighbours`` candidates of the slots (``users``,
+  ``items``) and d L_t / d s of each, ``DU`` [T, h] the users' gradient rows, ``valid`` [T] = 1.0 / 0.0 and ``loss``
+  [T, 3] the three terms of L_t (rk_als_ugcn_grad); ``nbr_ids`` / ``nbr_w`` are None at ``neighbours`` = 0."""
+  T, R, K = users.shape[0], int(num_negatives), int(neighbours)
+  if workspace_bytes(T, R, K, X.shape[1]) < 0:
+    raise ValueError("rk_als_ugcn_grad needs 1 <= T <= %d, 1 <= R <= %d, 0 <= K <= %d, T (1 + R + K) <= %d and "
+                     "1 <= h <= %d (got T = %d, R = %d, K = %d, h = %d)"
+                     % (MAX_BATCH, MAX_NEGATIVES, MAX_NEIGHBOURS, MAX_ENTRIES, MAX_H, T, R, K, X.shape[1]))
+  w = check_weights(w)
+  E = 1 + R + K
+  _i32(users, T), _i32(items, T), _table(X), _table(Y, X.shape[1])
+  h = X.shape[1]
+  _f32(bu, (X.shape[0],)), _f32(bi, (Y.shape[0],))
+  assert cand.dtype == torch.int32 and tuple(cand.shape) == (T, E) and cand.is_contiguous()
+  _f32(coef, (T, E)), _f32(DU, (T, h)), _f32(valid, (T,)), _f32(loss, (T, 3))
+  if K:
+    assert nbr_ids.dtype == torch.int32 and tuple(nbr_ids.shape) == (Y.shape[0], K) and nbr_ids.is_contiguous()
+    _f32(nbr_w, (Y.shape[0], K))
+  lib = _als_lib.load()
+  _als_lib.check(lib.rk_als_ugcn_grad(ptr(users), ptr(items), T, R, K, int(seed), int(step_index), X.shape[0],
+                                      Y.shape[0], ptr(X), X.stride(0), ptr(Y), Y.stride(0), h, ptr(bu), ptr(bi),
+                                      ptr(nbr_ids) if K else None, ptr(nbr_w) if K else None, w[0], w[1], w[2], w[3],
+                                      float(negative_weight), float(item_weight), ptr(cand), ptr(coef), ptr(DU),
+                                      ptr(valid), ptr(loss), current_stream()), "rk_als_ugcn_grad")
+
+
+def scatter(keys, order, E, users, coef, X, scale, G, count):
+  """G[key] = scale sum coef[e] X[users[e / E]] and count[key] = the key's positives, for the rows among the sorted
+  keys (rk_als_ugcn_scatter); the caller zeroes G and count."""
+  n, T = keys.shape[0], users.shape[0]
+  E = int(E)
+  if not (E >= 2 and n == T * E and 1 <= T <= MAX_BATCH and n <= MAX_ENTRIES):
+    raise ValueError("rk_als_ugcn_scatter needs n = T E keys, E >= 2, 1 <= T <= %d and n <= %d (got n = %d, T = %d, "
+                     "E = %d)" % (MAX_BATCH, MAX_ENTRIES, n, T, E))
+  _i32(keys, n), _i32(users, T), _table(X), _table(G, X.shape[1]), _i32(count, G.shape[0])
+  assert order.dtype == torch.int64 and order.shape == (n,) and order.is_contiguous()
+  assert coef.dtype == torch.float32 and coef.numel() == n and coef.is_contiguous()
+  lib = _als_lib.load()
+  _als_lib.check(lib.rk_als_ugcn_scatter(ptr(keys), ptr(order), n, E, ptr(users), ptr(coef), ptr(X), X.stride(0),
+                                         X.shape[0], X.shape[1], float(scale), G.shape[0], ptr(G), G.stride(0),
+                                         ptr(count), current_stream()), "rk_als_ugcn_scatter")
+
+
+# --------------------------------------------------------------------- step
+class Workspace(lightgcn.Workspace):
+  """The driver's workspace (the draws in ``bpr.users`` / ``bpr.pos``, the validity vector in ``bpr.g``, the users'
+  gradient image DU in ``bpr.D``), one allocation of rk_als_ugcn_workspace_bytes cut into ``cand``, ``coef`` and
+  ``loss``, and the constraints (b^U, b^I and the neighbour lists), made at the first step."""
+
+  def __init__(self, n_users, n_items, T, h, device, num_negatives=1, neighbours=0):
+    super().__init__(n_users, n_items, T, h, device)
+    R, K = int(num_negatives), int(neighbours)
+    need = _als_lib.load().rk_als_ugcn_workspace_bytes(T, R, K, h)
+    assert need == workspace_bytes(T, R, K, h) and need > 0, (need, T, R, K, h)
+    self.num_negatives, self.neighbours = R, K
+    E = 1 + R + K
+    self.raw = torch.empty(need, dtype=torch.uint8, device=device)
+    a, b = _round256(4 * T * E), 2 * _round256(4 * T * E)
+    self.cand = self.raw[:4 * T * E].view(torch.int32).view(T, E)
+    self.coef = self.raw[a:a + 4 * T * E].view(torch.float32).view(T, E)
+    self.loss = self.raw[b:b + 12 * T].view(torch.float32).view(T, 3)
+    self.bu = self.bi = self.nbr_ids = self.nbr_w = None
+
+
+def constraints(graph, ws):
+  """b^U, b^I and (with neighbours) the lists of ``item_graph`` in ``ws``, from the graph's CSRs."""
+  if ws.bu is None:
+    dev = graph.ucsr.indptr.device
+    bu, bi = degree_weights(np.diff(graph.ucsr.indptr.cpu().numpy()), np.diff(graph.icsr.indptr.cpu().numpy()))
+    ws.bu, ws.bi = torch.from_numpy(bu).to(dev), torch.from_numpy(bi).to(dev)
+    if ws.neighbours:
+      ws.nbr_ids, ws.nbr_w = item_graph(graph.ucsr, ws.neighbours, graph.icsr)
+
+
+def gradient(X, Y, graph, state, ws, seed, step_index, hyper):
+  """rk_als_ugcn_grad at the draws (the negative is ignored), then the users' rows summed per user by
+  rk_als_lgcn_scatter and the candidates' by rk_als_ugcn_scatter; the slots' three terms stay in ``ws.loss``."""
+  num_negatives, negative_weight, neighbours, item_weight, w = hyper
+  K = active_neighbours(neighbours, item_weight)
+  assert num_negatives == ws.num_negatives and K == ws.neighbours
+  constraints(graph, ws)
+  b = ws.bpr
+  grad(b.users, b.pos, num_negatives, K, seed, step_index, X, Y, ws.bu, ws.bi, ws.nbr_ids, ws.nbr_w, w,
+       negative_weight, item_weight, ws.cand, ws.coef, b.D, b.g, ws.loss)
+  for t in ws.G + ws.count:
+    t.zero_()
+  keys, order = torch.sort(bpr.masked_keys(b.users, b.g > 0, X.shape[0]), stable=True)
+  # (scatter's weight of a roles = 1 entry is -g: the negative scale undoes it, exactly)
+  lightgcn.scatter(keys, order, 1, b.g, b.D, -1.0 / b.T, ws.G[0], ws.count[0])
+  keys, order = torch.sort(ws.cand.view(-1), stable=True)
+  scatter(keys, order, ws.cand.shape[1], b.users, ws.coef, X, 1.0 / b.T, ws.G[1], ws.count[1])
+
+
+def _sums_add(sums, ws):
+  sums[0] += ws.loss.sum(0, dtype=torch.float64)
+  sums[1] += ws.bpr.g.sum(dtype=torch.float64)
+
+
+def _entry(v, steps):
+  return tuple(x / v[3] for x in v[:3]) if v[3] else (float("nan"),) * 3
+
+
+def _opts(num_negatives, negative_weight, neighbours, item_weight, w):
+  return {"num_negatives": num_negatives, "neighbours": active_neighbours(neighbours, item_weight)}
+
+
+METHOD = lightgcn.Method(
+    "UltraGCN", "train_ultragcn", MAX_BATCH, 0, skip_layer0=False, gradient=gradient,
+    sums=(((3,), torch.float64), ((), torch.float64)), sums_add=_sums_add, entry=_entry, workspace=Workspace,
+    extra_bytes=extra_bytes, opts=_opts)
+
+
+def step(X, Y, graph, state, ws, seed, step_index, lr, reg, num_negatives, negative_weight, neighbours, item_weight, w):
+  """One UltraGCN step (``lightgcn.method_step`` at no layers); the draws of the step stay in ``ws.bpr``, its
+  candidates in ``ws.cand`` / ``ws.coef`` and the slots' terms in ``ws.loss``."""
+  lightgcn.method_step(METHOD, X, Y, graph, state, ws, seed, step_index, lr, reg,
+                       (num_negatives, negative_weight, neighbours, item_weight, w))
+
+
+# ---------------------------------------------------------------------- fit
+def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, num_negatives, negative_weight, neighbours,
+        item_weight, w, seed=0, state=None, first_step=None):
+  """``lightgcn.method_fit`` of UltraGCN (``num_layers`` is 0).  Returns (state, one (positive, negatives,
+  neighbours) triple of means per valid slot per epoch)."""
+  if num_layers != 0:
+    raise ValueError("train_ultragcn propagates nothing: num_layers is 0 (got %r)" % (num_layers,))
+  return lightgcn.method_fit(METHOD, X, Y, bias, ucsr, icsr, 0, num_epochs, batch_size, lr, reg,
+                             (num_negatives, negative_weight, neighbours, item_weight, check_weights(w)), seed, state,
+                             first_step)
