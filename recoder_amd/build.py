@@ -38,7 +38,9 @@ librecoder_slim.so  the SLIM coordinate-descent fit and its scores for SparseLin
                    (include/recoder_slim.h), likewise a library of its own
 
 The seven side libraries share csrc/side_error.h (the last-error buffer and the argument / launch
-checks); each stays one translation unit, so each has its own buffer.
+checks); each stays one translation unit, so each has its own buffer.  A library's source may be laid out
+over private headers in csrc/<stem>/ (als.hip is: csrc/als/*.h, one file a family); they are that library's
+dependencies and nobody else's.
 
 hipcc cross-compiles without a GPU; the built libraries stay in-tree
 (recoder_amd/csrc/*.so, git-ignored) so that they travel with the repository
@@ -52,7 +54,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE = os.path.join(os.path.dirname(CSRC), "..", "include")
 # one row per library, in build order: (stem, sources, public headers, whether it depends on the training
 # path's headers (every csrc/*.h and include/recoder_hip*.h), the prefix of its exported names).  A side
-# library depends on its own header and csrc/side_error.h; vae.hip and svd.hip also include csrc/common.h
+# library depends on its own header, csrc/side_error.h and the headers in csrc/<stem>/; vae.hip and svd.hip also include csrc/common.h
 # (the counter RNG, the step cursor), so they follow the training headers too.
 LIBRARIES = (
     ("hip", ["capi.hip", "collate.hip", "encoder.hip", "gemm.hip", "decode16.hip", "linear.hip", "dw3.hip",
@@ -123,15 +125,24 @@ def _build_one(lib, sources, headers, force, verbose):
   return lib
 
 
-def build_library(force=False, verbose=True):
-  """Build the libraries (each only if one of its sources or headers is newer); returns the training library's path."""
+def headers_of(stem):
+  """The headers whose change rebuilds library `stem` (a row of LIBRARIES)."""
+  _, _, public, needs_training, _ = next(row for row in LIBRARIES if row[0] == stem)
   training = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + \
       [os.path.join(INCLUDE, h) for h in LIBRARIES[0][2]]
-  for stem, sources, public, needs_training, _ in LIBRARIES:
-    own = [os.path.join(INCLUDE, h) for h in public]
-    headers = training + [h for h in own if h not in training] if needs_training else \
-        own + [os.path.join(CSRC, "side_error.h")]
-    _build_one(lib_path(stem), sources, headers, force, verbose)
+  own = [os.path.join(INCLUDE, h) for h in public]
+  headers = training + [h for h in own if h not in training] if needs_training else \
+      own + [os.path.join(CSRC, "side_error.h")]
+  private = os.path.join(CSRC, stem)                 # csrc/<stem>/*.h: the library's own private headers
+  if os.path.isdir(private):
+    headers = headers + sorted(os.path.join(private, f) for f in os.listdir(private) if f.endswith(".h"))
+  return headers
+
+
+def build_library(force=False, verbose=True):
+  """Build the libraries (each only if one of its sources or headers is newer); returns the training library's path."""
+  for stem, sources, _, _, _ in LIBRARIES:
+    _build_one(lib_path(stem), sources, headers_of(stem), force, verbose)
   return LIB
 
 

@@ -40,7 +40,7 @@ def init_tables(n_users, n_items, h, dev):
 
 
 def stash_rows(h):
-  """rows of h floats rk_als_solve stashes per wave (csrc/als.hip: 64 KB per workgroup of 4 waves)."""
+  """rows of h floats rk_als_solve stashes per wave (csrc/als/solve.h: 64 KB per workgroup of 4 waves)."""
   g = h * h if h * h * 4 <= 32 * 1024 else 0
   return (64 * 1024 // 4 - g) // 4 // h
 
