@@ -80,6 +80,8 @@ int rk_act_grad_colsum(float *dY, const float *Y, int rows, int cols, int act, f
 // ---------------------------------------------------------------- activations
 // y = act(x);  derivative expressed through y (what autograd of torch.tanh /
 // sigmoid / relu / selu / elu evaluates to for the saved output).
+// (selu / elu through expm1f: expf(x) - 1 cancels for small negative x -- it returns 0 for x = -1e-30 and
+// loses most of the result's bits around x = -0.001; torch evaluates expm1 too)
 __device__ __forceinline__ float rk_act(float x, int act) {
   switch (act) {
     case RK_ACT_TANH: return tanhf(x);
@@ -88,9 +90,9 @@ __device__ __forceinline__ float rk_act(float x, int act) {
     case RK_ACT_SELU: {
       const float a = 1.6732632423543772848170429916717f;
       const float s = 1.0507009873554804934193349852946f;
-      return s * (x > 0.f ? x : a * (expf(x) - 1.0f));
+      return s * (x > 0.f ? x : a * expm1f(x));
     }
-    case RK_ACT_ELU: return x > 0.f ? x : (expf(x) - 1.0f);
+    case RK_ACT_ELU: return x > 0.f ? x : expm1f(x);
     default: return x;
   }
 }
