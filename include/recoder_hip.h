@@ -767,10 +767,30 @@ void *rk_event_create(int32_t timing); /* 0: ordering-only (no timing, device-sc
 void rk_event_destroy(void *event);
 float rk_event_elapsed_ms(void *ev0, void *ev1);   /* synchronises on ev1 */
 int rk_ae_train_step(const rk_ae_step_t *step);
-/* != 0: the step as described runs rk_pg_decode_loss / rk_pg_dz / rk_pg_dw (rk_ae_step_t.do_scales).  Bits 0-3: 1 = the
- * pipelined pair-plane kernels, 3 = the register-resident fused decode + rk_pg_dw; bit 4 (16):
- * the decoder bias gradient of the step is left as K slabs in gb_part -- gb_part[s * n_cap + c], s < counts[4] -- (the
- * dW tiles' output column h against a ones column of the Z image), not in gb_de */
+/* The ROUTE rk_ae_train_step takes for the step as described -- which kernels it launches and where it leaves the
+ * gradients -- as one word.  It follows from the configuration, the shape and which resources are offered (non-null),
+ * and reads host state only.  Of `phase` only the kind of step matters (0 / RK_STEP_ALL: a whole step; any other mask of
+ * RK_STEP_FWD_DW.. : a phased one; RK_STEP_IP_*: item parallel), so every call of one step sees the same route: ask once.
+ *   bits 0-3    != 0: the step runs its contractions on the pipelined pair-plane kernels (rk_ae_step_t.do_scales):
+ *               1 = rk_pg_decode_loss / rk_pg_dz / rk_pg_dw, 3 = the register-resident fused decode + the pgemm dW tiles
+ *   bit 4 (16)  the decoder bias gradient is left as K slabs in gb_part (= bits 10-11 == 2)
+ *   bits 5-7    decode family: 0 rk_decode_loss, 1 rk_decode_loss_planes, 2 rk_decode_loss_dz_planes, 3 rk_pg_decode_loss,
+ *               4 rk_fdec_loss_dz; dZ follows it: rk_decode_bwd_dz, rk_decode_bwd_dz_planes, rk_decode_dz_reduce, rk_pg_dz,
+ *               rk_fdec_dz_reduce
+ *   bits 8-9    decoder-side rows: 0 G_de; 1 K slabs at rk_dw3_slabs of dW's workspace (counts[4] of them); 2 K slabs at
+ *               the head of dW's workspace (counts[4] of them); 3 rk_plan_t.dw_splits K slabs of the fp32 tiles at the
+ *               head of ws (item parallel).  dW's workspace is ws_dw when dw_stream is given, else ws
+ *   bits 10-11  decoder bias gradient: 0 gb_de; 1 the decode's row-tile partials in gb_part (ceil(B / decode_row_tile)
+ *               rows, leading dimension counts[2]); 2 gb_part[s * n_cap + c], s < counts[4]: the dW tiles' output column h
+ *               against a ones column of the Z image
+ *   bits 12-15  n > 0: gb_en holds n row-segment partial vectors [n][h] -- the caller passes a buffer of 8 * h floats --
+ *               and G_en n partial arrays [n][n_cap * h] (the fused fp32 dW || encoder backward); 0: one of each
+ *   bits 16-18  dW kernel: 0 fp32 tiles, 1 fp16 pairs, 2 bf16 triples, 3 rk_pg_dw 64 x 32, 4 rk_pg_dw 32 x 64,
+ *               5 rk_pg_dw_dense
+ *   bits 19-20  dW placement: 0 on its own, dense, in front of the encoder backward (FWD_DW); 1 one launch with the
+ *               encoder backward; 2 on dw_stream next to dZ -> encoder backward; 3 in line behind dZ
+ *   bits 21-23  encoder forward: 0 rk_ae_encode_fwd, 1 rk_ae_encode_fwd_planes, 2 rk_ae_encode_fwd_at, 3 the same with
+ *               the operand split riding on it, 4 rk_ae_encode_fwd_partial */
 int32_t rk_ae_step_uses_pg(const rk_ae_step_t *step);
 
 /*

@@ -47,6 +47,7 @@ class Rows(enum.Enum):
   DENSE = 0        # G_de
   DW3 = 1          # K slabs in ws_dw at rk_dw3_slabs (csrc/dw3.hip)
   PG = 2           # K slabs at the head of ws_dw (rk_pg_dw)
+  SPLITK = 3       # rk_dw_splits(B) K slabs of the fp32 tiles at the head of ws (item-parallel steps of 1500+ rows)
 
 
 class Bias(enum.Enum):
@@ -54,6 +55,20 @@ class Bias(enum.Enum):
   DENSE = 0        # gb_de
   TILES = 1        # the decode's row-tile column sums of dO in gb_part
   SLABS = 2        # one partial per K slab of dW in gb_part
+
+
+class StepRoute(NamedTuple):
+  """What rk_ae_step_uses_pg reports of a one-call step's route (include/recoder_hip.h; Rows and Bias share the
+  library's numbering)."""
+  word: int
+  mode: int                    # bits 0-3: 0 decode16 / dw3 kernels, 1 csrc/pgemm.h, 3 csrc/fdecode.hip + pgemm's dW
+  rows: Rows
+  bias: Bias
+  en_segs: int
+
+  @classmethod
+  def of(cls, word):
+    return cls(word, word & 15, Rows((word >> 8) & 3), Bias((word >> 10) & 3), (word >> 12) & 15)
 
 
 class GradLayout(NamedTuple):
@@ -1116,8 +1131,8 @@ class FusedEngine:
     in the replayed group, table=Adam constants table) -- what changes per step is then derived on
     the device (rk_ae_step_t.cursor); `out` is the BASE of the epoch's loss buffer and the host
     counters (Adam steps, rng step) are advanced by the caller."""
-    from ._lib import (ENTRY, PAR_B_DE, PAR_B_EN, PAR_W_DE, PAR_W_EN, STEP_ALL, STEP_DZ_ENC,
-                       STEP_FWD_DW, STEP_UPDATE, RkAeStep)
+    from ._lib import (ENTRY, PAR_B_DE, PAR_B_EN, PAR_W_DE, PAR_W_EN, STEP_ALL, STEP_DZ_ENC, STEP_FWD_DW,
+                       STEP_IP_ENC, STEP_IP_MID, STEP_IP_TAIL, STEP_UPDATE, RkAeStep)
     raw = _lib.load()
     m, S = self.model, self.states
     st = self._cstep if replay is None else replay["st"]
@@ -1163,13 +1178,10 @@ class FusedEngine:
     st.do_scales, st.do_rows = ptr(self.do_scales), self.do_rows
     self._check_weight_range()
     st.ranges = ptr(self.ranges)
-    plain = dp is None and not m.is_constrained and self.loss_id != LOSS_MNLL
-    # the fused fp32 dW || encoder-backward launch writes row-segment partials; the bf16-pipe dW
-    # (whole single-GPU steps) leaves its K slabs in the workspace and runs the plain encoder backward
-    dw3 = plain and self.split16 and self.item_parallel is None
-    segmented = plain and not dw3
-    st.gb_en = ptr(self.gb_en_parts if segmented else self.gb_en)
-    en_segs = self.lib.rk_encode_bwd_segments(B) if segmented else 0
+    ip = self.item_parallel
+    # whole untied MSE / BCE steps on the 16-bit pipe get a side stream and a workspace of its own for dW
+    offer_dw = (dp is None and ip is None and self.split16 and not m.is_constrained and
+                self.loss_id != LOSS_MNLL)
     self.n_cap_last = blk.n_cap
     st.loss_part, st.loss_out = ptr(self.loss_part), ptr(loss_dst)
     st.stream = main_s.cuda_stream
@@ -1189,7 +1201,7 @@ class FusedEngine:
       st.lazy_need_list, st.lazy_need_count = lz.get("need") or (None, None)
     if dp is not None and self.ws_dw is not None and not m.is_constrained:
       st.ws_dw = ptr(self.ws_dw)        # (phased steps: dW's own workspace lets the decode launch keep its dZ slabs)
-    if dw3:
+    if offer_dw:
       if self._dw_objs is None:
         raw0 = _lib.load()
         self._dw_objs = (torch.cuda.Stream(device=self.device), raw0.rk_event_create(0), raw0.rk_event_create(0))
@@ -1202,6 +1214,12 @@ class FusedEngine:
       if replay.get("next") is not None:         # last step of a group: publish the next cursor
         st.cursor_next, st.cursor_advance = replay["next"]
       st.users = replay["users"]             # base of the epoch's user order (offset on the device)
+    # the library decides the route from what is on offer -- once per step: its phased calls see the same one --
+    # and reports where the gradients will be
+    st.phase = STEP_IP_ENC if ip is not None else STEP_ALL if dp is None else STEP_FWD_DW
+    route = StepRoute.of(int(raw.rk_ae_step_uses_pg(ctypes.byref(st))))
+    self._step_route = route.word
+    st.gb_en = ptr(self.gb_en_parts if route.en_segs else self.gb_en)
     self._c_calls += 1
     name = None
     if self.time_plan is not None and (replay is None or replay.get("timed")):
@@ -1225,13 +1243,10 @@ class FusedEngine:
       st.time_entry, st.time_ev0, st.time_ev1 = ENTRY[name], e0, e1
     else:
       st.time_entry = 0
-    ip = self.item_parallel
-    dw_rows, gb = (Rows.DW3 if dw3 else Rows.DENSE), Bias.DENSE
     if ip is not None:
       # item parallel (parallel.ItemParallel): the block holds every user of the global
       # batch restricted to this rank's items; two [B, h] all-reduces per step.  `out` gets
       # this rank's share of the loss (summed over the ranks once per epoch).
-      from ._lib import STEP_IP_ENC, STEP_IP_MID, STEP_IP_TAIL
       h0 = self.h[0]
       st.user_norm = ptr(ip.user_norm_dev)
       st.own_rank, st.own_world = ip.rank, ip.world
@@ -1243,21 +1258,11 @@ class FusedEngine:
       ip.allreduce_sum(self.denc[0][:B * h0])
       st.phase = STEP_IP_TAIL
       check(raw.rk_ae_train_step(ctypes.byref(st)), "rk_ae_train_step")
-      if self.loss_id != LOSS_MNLL:
-        gb = Bias.TILES
     elif dp is None:
-      st.phase = STEP_ALL
-      flags = int(raw.rk_ae_step_uses_pg(ctypes.byref(st)))
-      mode = flags & 15
-      self._step_flags = flags     # (bit 4: the bias gradient as output column h of the dW tiles -- recoder_hip.h)
-      if dw3 and mode:
-        dw_rows = Rows.PG
-      self._step_mode = mode       # (0: decode16 / dw3 kernels, 1: csrc/pgemm.h, 3: csrc/fdecode.hip + pgemm's dW; bench.py names the kernels by it)
+      # (bench.py names the kernels of the whole single-process step by these two; bit 4: the bias gradient as
+      # output column h of the dW tiles)
+      self._step_mode, self._step_flags = route.mode, route.word & 31
       check(raw.rk_ae_train_step(ctypes.byref(st)), "rk_ae_train_step")
-      if self.loss_id != LOSS_MNLL and mode != 3:
-        gb = Bias.TILES                  # (mode 3: gb_de itself, from the dO image)
-      elif flags & 16:
-        gb = Bias.SLABS                  # (... or one slab per K slab of dW in gb_part)
     else:
       # data parallel over users: forward + whole backward locally, then the live gradient rows
       # of both tables, the gathered-bias gradient, the encoder bias gradient and the loss go out
@@ -1349,7 +1354,7 @@ class FusedEngine:
       if zero is not None:
         names_ = ["en_embedding_layer.weight"] + ([] if tied else ["de_embedding_layer.weight"])
         dp.zero_publish([S[n_].p.data for n_ in names_], h0, extra_max=self.ranges[64:])
-    self.grads = GradLayout(blk, B, out, dw_rows, gb, en_segs)
+    self.grads = GradLayout(blk, B, out, route.rows, route.bias, route.en_segs)
     return out
 
   def _zero_grad_tails(self, blk, arrays, stream):
@@ -1425,10 +1430,10 @@ class FusedEngine:
     g, h0 = self.grads, self.h[0]
     if g.rows is Rows.DENSE:
       return self.G_de[:n_b * h0].view(n_b, h0).clone()
-    ws = self.ws_dw
-    ns = int(g.blk.counts[4].item())
-    # (rk_pg_dw: the slabs start at the workspace's head)
-    off = 0 if g.rows is Rows.PG else (self.lib.rk_dw3_slabs(ptr(ws), g.B, h0) - ws.data_ptr()) // 4
+    ws = self.ws if g.rows is Rows.SPLITK else self.ws_dw
+    ns = self.lib.rk_dw_splits(g.B) if g.rows is Rows.SPLITK else int(g.blk.counts[4].item())
+    # (rk_pg_dw, the fp32 tiles: the slabs start at the workspace's head)
+    off = (self.lib.rk_dw3_slabs(ptr(ws), g.B, h0) - ws.data_ptr()) // 4 if g.rows is Rows.DW3 else 0
     stride = g.blk.n_cap * h0
     return sum(ws[off + k * stride:off + k * stride + n_b * h0].view(n_b, h0) for k in range(ns))
 
