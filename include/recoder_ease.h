@@ -44,6 +44,23 @@
  *     A[i][j] = fma(p, col_scale[j], A[i][j]): three roundings after the chain's k.  An element depends on
  *     neither the tile it falls in nor the row range: a row range gives bitwise the rows of the full call.  A
  *     scale (or alpha) that is exactly 0 adds +-0: the element keeps its value.
+ *   - rk_ease_gemm: dot = ONE k-ascending f32 fmaf chain  fma(A[i][t], B[t][j], .)  over t = 0 .. k - 1, from +0, on
+ *     v_mfma_f32_32x32x2_f32 (k is never split over waves or workgroups, there are no atomics, no workspace); then
+ *     p = alpha * dot (one f32 multiply) and  D[i][j] = p  (E NULL: beta is not read)  or  D[i][j] = fma(beta, E[i][j], p):
+ *     one or two roundings after the chain's k.  An element depends on neither the tile it falls in nor the row
+ *     range: a row range gives bitwise the rows of the full call.
+ *   - rk_ease_admm_update, per element, every operation one f32 rounding in this order (fma: a fused multiply-add):
+ *       gamma_j = (T[j][j] + 1) / P[j][j]             an add, then a correctly rounded divide
+ *       B  = fma(-P[i][j], gamma_j, T[i][j])          fma (the negation is exact)
+ *       V  = B + U[i][j]                              add
+ *       w  = V - theta (nonneg)  or  |V| - theta      subtract
+ *       Cn = w > 0 ? w : +0 (nonneg)  or  w > 0 ? copysign(w, V) : +0       (exact; theta = 0 gives Cn = V, or max(V, 0))
+ *       Un = V - Cn,   Mn = Cn - Un                   two subtracts
+ *     and on the diagonal B = Cn = Un = Mn = +0 whatever is stored.  The row statistics: d1 = B - Cn and
+ *     d2 = Cn - C[i][j] (the value before the call) as f32 subtracts, their squares summed in float64 (fma chains:
+ *     thread t of 256 takes the columns t, t + 256, ... ascending, then a pairwise tree over the threads), rounded
+ *     once to f32; the count of Cn != 0 is exact.  No atomics: a fixed order, bitwise repeatable, and a row does
+ *     not depend on the row range.
  */
 #ifndef RECODER_EASE_H
 #define RECODER_EASE_H
@@ -110,6 +127,33 @@ int rk_ease_scores(const int64_t *indptr, const int32_t *indices, const float *d
  */
 int rk_ease_lowrank_add(float *A, int32_t n, int64_t lda, const float *V, int32_t k, int64_t ldv,
                         const float *row_scale, const float *col_scale, float alpha, int32_t row_lo, int32_t row_hi,
+                        void *stream);
+
+/*
+ * D[i][j] = alpha * (sum over t < k of A[i][t] * B[t][j]) + beta * E[i][j] for i in [row_lo, row_hi) and j in
+ * [0, n): a general dense product.  A [m, lda], lda >= k; B [k, ldb], ldb >= n; D [m, ldd], ldd >= n, columns at or
+ * past n and rows outside the range are not touched; m, n, k >= 1 and multiples of nothing.  E is NULL (beta is
+ * ignored), or D itself (lde == ldd: an in-place accumulate), or an [m, lde] buffer, lde >= n, that does not overlap
+ * D; it may be A or B.  D must not overlap A or B.  0 <= row_lo <= row_hi <= m (an empty range does nothing).  No
+ * workspace.
+ */
+int rk_ease_gemm(const float *A, int64_t lda, const float *B, int64_t ldb, const float *E, int64_t lde, float *D,
+                 int64_t ldd, int32_t m, int32_t n, int32_t k, float alpha, float beta, int32_t row_lo, int32_t row_hi,
+                 void *stream);
+
+/*
+ * The element-wise pass of one ADMM-SLIM iteration (Steck et al., WSDM 2020; recoder_amd/admm.py) over the rows
+ * [row_lo, row_hi) of five [n, n] matrices that do not overlap: with P = (G + (l2 + rho) I)^-1 and
+ * T = rho P M - (l2 + rho) P, it forms the ridge step's B = T - P diag(gamma) (zero diagonal), V = B + U, the
+ * soft-thresholded C_new (theta = l1 / rho >= 0, finite; nonneg 1: clipped at 0, 0: two-sided), the scaled dual
+ * U = V - C_new and the next product's operand M = C_new - U.  T and P are read (all n rows of their diagonals); C and
+ * U are read and written; M is written.  gamma [n] receives gamma_j for every j, whatever the range.  For the rows of
+ * the range, row_primal[i] = sum_j (B - C_new)^2, row_dual[i] = sum_j (C_new - C)^2 and row_nnz[i] = the count of
+ * C_new != 0; entries of rows outside the range are not touched (an empty range does nothing at all).
+ */
+int rk_ease_admm_update(const float *T, int64_t ldt, const float *P, int64_t ldp, float *C, int64_t ldc, float *U,
+                        int64_t ldu, float *M, int64_t ldm, int32_t n, float theta, int32_t nonneg, float *gamma,
+                        float *row_primal, float *row_dual, int32_t *row_nnz, int32_t row_lo, int32_t row_hi,
                         void *stream);
 
 #pragma GCC visibility pop

@@ -9,7 +9,7 @@ Drop-in for the reference's training path: ``Recoder`` / ``FactorizationModel``
 __version__ = "0.4.0"
 
 __all__ = ["ShallowAutoencoder", "RandomWalkItemModel", "SparseLinearModel", "UserNeighbourhoodModel",
-           "ItemNeighbourhoodModel", "GraphFilterModel"]
+           "ItemNeighbourhoodModel", "GraphFilterModel", "AdmmSlimModel"]
 
 
 def __getattr__(name):
@@ -32,4 +32,7 @@ def __getattr__(name):
   if name == "GraphFilterModel":
     from .nn import GraphFilterModel
     return GraphFilterModel
+  if name == "AdmmSlimModel":
+    from .nn import AdmmSlimModel
+    return AdmmSlimModel
   raise AttributeError("module %r has no attribute %r" % (__name__, name))

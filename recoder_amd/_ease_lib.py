@@ -25,6 +25,10 @@ SIGNATURES = {
   "rk_ease_finalize": (c_int32, [_P, c_int32, c_int64, _P, c_int64, _P, _P]),
   "rk_ease_scores": (c_int32, [_P, _P, _P, c_int32, _P, c_int64, c_int32, c_int32, _P, c_int64, _P]),
   "rk_ease_lowrank_add": (c_int32, [_P, c_int32, c_int64, _P, c_int32, c_int64, _P, _P, c_float, c_int32, c_int32, _P]),
+  "rk_ease_gemm": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, c_int32, c_float,
+                             c_float, c_int32, c_int32, _P]),
+  "rk_ease_admm_update": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_float,
+                                    c_int32, _P, _P, _P, _P, c_int32, c_int32, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

@@ -25,7 +25,8 @@ librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/
 librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencoder
                    (include/recoder_ease.h), likewise a library of its own.  It also holds the dense
                    rank-k update of GraphFilterModel's GF-CF fit (rk_ease_lowrank_add), which shares the
-                   inverse's MFMA tile
+                   inverse's MFMA tile, and the general dense f32 product and the element-wise pass of
+                   AdmmSlimModel's ADMM-SLIM fit (rk_ease_gemm, rk_ease_admm_update) on the same tile
 librecoder_svd.so  the randomized truncated SVD behind PureSVD for MatrixFactorization
                    (include/recoder_svd.h), likewise a library of its own
 librecoder_rp3.so  the RP3beta item-graph fit and its scores for RandomWalkItemModel

@@ -15,6 +15,10 @@
 //   rk_ease_lowrank_add  A += diag(alpha a) V V^T diag(b): the inverse's 128 x 128 MFMA tile walked over k in
 //                        slabs of 32, the whole k inside one wave (one chain per output, no atomics), the two
 //                        scalings and the add in the store
+//   rk_ease_gemm         D = alpha A B + beta E: the same tile over general row-major operands, the next k-slab
+//                        fetched into registers under this slab's MFMAs, edges padded with zeros in LDS
+//   rk_ease_admm_update  the element-wise pass of an ADMM-SLIM iteration (recoder_amd/admm.py): one workgroup per
+//                        row, the row's three statistics summed in a fixed order
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -386,6 +390,154 @@ __global__ __launch_bounds__(256) void ease_lowrank_add_kernel(float *__restrict
 #undef EASE_LR_STORE
 }
 
+// ----------------------------------------------------------------------- gemm
+constexpr int GM_KS = 32;               // k-slab held in LDS
+constexpr int GM_LDA = TILE + 1;        // odd row stride: the transposing store of the A slab is (nearly) conflict-free
+
+// D[i][j] = alpha (sum_t A[i][t] B[t][j]) + beta E[i][j] for i in [row_lo, row_hi), j < n.  One workgroup (4 waves) per
+// 128 x 128 tile; the A rows go through LDS transposed as [t][129], the B rows as they lie as [t][128], in slabs of 32
+// of k, zeros past the edges (so m, n and k need no alignment; a zero pair leaves the chain's value as it is).  The
+// next slab is fetched into registers while the MFMAs of this one run.  Wave w takes the 64 x 64 quadrant
+// (w >> 1, w & 1) as 2 x 2 accumulators, each ONE k-ascending chain over all the slabs.  E may be D: an element is
+// read and then written by the same thread.
+__global__ __launch_bounds__(256) void ease_gemm_kernel(const float *__restrict__ A, int64_t lda,
+                                                        const float *__restrict__ B, int64_t ldb, const float *E,
+                                                        int64_t lde, float *D, int64_t ldd, int n, int k, float alpha,
+                                                        float beta, int row_lo, int row_hi) {
+  __shared__ float As[GM_KS * GM_LDA];
+  __shared__ float Bs[GM_KS * TILE];
+  const int i0 = row_lo + blockIdx.y * TILE, j0 = blockIdx.x * TILE;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int m0 = (wv >> 1) * 64, n0 = (wv & 1) * 64, l31 = lane & 31, kh = lane >> 5;
+  // thread e of the A slab: row e / 32 of the tile, column t0 + e % 32 (a wave reads two rows' 128 contiguous bytes);
+  // of the B slab: row t0 + e / 128, column e % 128 (a wave reads 256 contiguous bytes)
+  const int ar = threadIdx.x >> 5, at = threadIdx.x & 31, bt = threadIdx.x >> 7, bc = threadIdx.x & 127;
+  const bool bok = j0 + bc < n;
+  float ra[16], rb[16];
+#define EASE_GM_FETCH(t0)                                                               \
+  _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                      \
+    const int gi = i0 + ar + 8 * q, tb = (t0) + bt + 2 * q;                             \
+    ra[q] = ((t0) + at < k && gi < row_hi) ? A[(int64_t)gi * lda + (t0) + at] : 0.f;    \
+    rb[q] = (tb < k && bok) ? B[(int64_t)tb * ldb + j0 + bc] : 0.f;                     \
+  }
+  f32x16 acc00, acc01, acc10, acc11;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc00[q] = acc01[q] = acc10[q] = acc11[q] = 0.f;
+  EASE_GM_FETCH(0)
+  for (int t0 = 0; t0 < k; t0 += GM_KS) {
+    if (t0) __syncthreads();            // (the previous slab has been read)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      As[at * GM_LDA + ar + 8 * q] = ra[q];
+      Bs[(bt + 2 * q) * TILE + bc] = rb[q];
+    }
+    __syncthreads();
+    if (t0 + GM_KS < k) EASE_GM_FETCH(t0 + GM_KS)
+    const int kend = min(GM_KS, (k - t0 + 1) & ~1);
+#pragma unroll 4
+    for (int kk = 0; kk < kend; kk += 2) {
+      const float *as = As + (kk + kh) * GM_LDA + m0 + l31, *bs = Bs + (kk + kh) * TILE + n0 + l31;
+      const float a0 = as[0], a1 = as[32], b0 = bs[0], b1 = bs[32];
+      acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc00, 0, 0, 0);
+      acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc01, 0, 0, 0);
+      acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc10, 0, 0, 0);
+      acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11, 0, 0, 0);
+    }
+  }
+#undef EASE_GM_FETCH
+  // C/D map of the 32x32 forms: column n = lane & 31, row m = (q & 3) + 8 (q >> 2) + 4 (lane >> 5).
+  // The order the header states: p = alpha * dot; D = p (E NULL) or fma(beta, E, p) -- one or two roundings.
+#define EASE_GM_STORE(acc, mi, ni)                                                      \
+  {                                                                                     \
+    const int gj = j0 + n0 + 32 * (ni) + l31;                                           \
+    if (gj < n) {                                                                       \
+      _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                  \
+        const int gi = i0 + m0 + 32 * (mi) + (q & 3) + 8 * (q >> 2) + 4 * kh;           \
+        if (gi < row_hi) {                                                              \
+          const float p = __fmul_rn(alpha, acc[q]);                                     \
+          D[(int64_t)gi * ldd + gj] = E ? fmaf(beta, E[(int64_t)gi * lde + gj], p) : p; \
+        }                                                                               \
+      }                                                                                 \
+    }                                                                                   \
+  }
+  EASE_GM_STORE(acc00, 0, 0)
+  EASE_GM_STORE(acc01, 0, 1)
+  EASE_GM_STORE(acc10, 1, 0)
+  EASE_GM_STORE(acc11, 1, 1)
+#undef EASE_GM_STORE
+}
+
+// true when [a, a + (rows - 1) lda + cols) and [b, ...) share an element
+bool gm_overlap(const float *a, int64_t rows, int64_t cols, int64_t lda, const float *b, int64_t rows_b, int64_t cols_b,
+                int64_t ldb) {
+  const float *ae = a + (rows - 1) * lda + cols, *be = b + (rows_b - 1) * ldb + cols_b;
+  return a < be && b < ae;
+}
+
+// ---------------------------------------------------------------- admm update
+// gamma[j] = (T[j][j] + 1) / P[j][j]: one add, one correctly rounded divide
+__global__ __launch_bounds__(256) void ease_admm_gamma_kernel(const float *__restrict__ T, int64_t ldt,
+                                                              const float *__restrict__ P, int64_t ldp, int n,
+                                                              float *__restrict__ gamma) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < n) gamma[j] = __fdiv_rn(__fadd_rn(T[j * ldt + j], 1.f), P[j * ldp + j]);
+}
+
+// One workgroup per row i: thread t takes the columns t, t + 256, ... in ascending order; the three row statistics are
+// per-thread float64 partials in that order, then a pairwise tree over the 256 threads (a fixed order: no atomics).
+__global__ __launch_bounds__(256) void ease_admm_update_kernel(const float *__restrict__ T, int64_t ldt,
+                                                               const float *__restrict__ P, int64_t ldp,
+                                                               float *__restrict__ C, int64_t ldc,
+                                                               float *__restrict__ U, int64_t ldu,
+                                                               float *__restrict__ M, int64_t ldm, int n, float theta,
+                                                               int nonneg, const float *__restrict__ gamma,
+                                                               float *__restrict__ row_primal,
+                                                               float *__restrict__ row_dual,
+                                                               int32_t *__restrict__ row_nnz, int row_lo) {
+  __shared__ double sp[256], sd[256];
+  __shared__ int sn[256];
+  const int64_t i = (int64_t)row_lo + blockIdx.x;
+  const float *t = T + i * ldt, *p = P + i * ldp;
+  float *c = C + i * ldc, *u = U + i * ldu, *m = M + i * ldm;
+  double ap = 0.0, ad = 0.0;
+  int an = 0;
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const float c_old = c[j];
+    float b = 0.f, cn = 0.f, un = 0.f, mn = 0.f;
+    if (j != i) {
+      b = fmaf(-p[j], gamma[j], t[j]);
+      const float v = __fadd_rn(b, u[j]);
+      const float w = __fsub_rn(nonneg ? v : fabsf(v), theta);
+      cn = w > 0.f ? (nonneg ? w : copysignf(w, v)) : 0.f;
+      un = __fsub_rn(v, cn);
+      mn = __fsub_rn(cn, un);
+    }
+    c[j] = cn;
+    u[j] = un;
+    m[j] = mn;
+    const double d1 = (double)__fsub_rn(b, cn), d2 = (double)__fsub_rn(cn, c_old);
+    ap = fma(d1, d1, ap);
+    ad = fma(d2, d2, ad);
+    an += cn != 0.f;
+  }
+  sp[threadIdx.x] = ap;
+  sd[threadIdx.x] = ad;
+  sn[threadIdx.x] = an;
+  for (int s = 128; s > 0; s >>= 1) {
+    __syncthreads();
+    if (threadIdx.x < s) {
+      sp[threadIdx.x] += sp[threadIdx.x + s];
+      sd[threadIdx.x] += sd[threadIdx.x + s];
+      sn[threadIdx.x] += sn[threadIdx.x + s];
+    }
+  }
+  if (threadIdx.x == 0) {
+    row_primal[i] = (float)sp[0];
+    row_dual[i] = (float)sd[0];
+    row_nnz[i] = sn[0];
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------ ABI
@@ -489,6 +641,44 @@ int rk_ease_lowrank_add(float *A, int32_t n, int64_t lda, const float *V, int32_
   hipLaunchKernelGGL(ease_lowrank_add_kernel, grid, dim3(256), 0, (hipStream_t)stream, A, n, lda, V, k, ldv,
                      row_scale, col_scale, alpha, row_lo, row_hi);
   RK_SIDE_CHECK_LAUNCH("ease_lowrank_add_kernel");
+  return 0;
+}
+
+int rk_ease_gemm(const float *A, int64_t lda, const float *B, int64_t ldb, const float *E, int64_t lde, float *D,
+                 int64_t ldd, int32_t m, int32_t n, int32_t k, float alpha, float beta, int32_t row_lo, int32_t row_hi,
+                 void *stream) {
+  RK_SIDE_REQUIRE(A && B && D, "null pointer");
+  RK_SIDE_REQUIRE(m >= 1 && n >= 1 && k >= 1 && lda >= k && ldb >= n && ldd >= n && (!E || lde >= n), "bad sizes");
+  RK_SIDE_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= m, "bad row range");
+  RK_SIDE_REQUIRE(!gm_overlap(D, m, n, ldd, A, m, k, lda) && !gm_overlap(D, m, n, ldd, B, k, n, ldb),
+                  "D must not overlap A or B");
+  RK_SIDE_REQUIRE(!E || E == D || !gm_overlap(D, m, n, ldd, E, m, n, lde), "E must be NULL, D or not overlap D");
+  RK_SIDE_REQUIRE(E != D || lde == ldd, "E == D needs lde == ldd");
+  if (row_lo == row_hi) return 0;
+  const int row_tiles = (row_hi - row_lo + TILE - 1) / TILE;
+  RK_SIDE_REQUIRE(row_tiles <= 65535, "m too large for one launch");
+  const dim3 grid((n + TILE - 1) / TILE, row_tiles);
+  hipLaunchKernelGGL(ease_gemm_kernel, grid, dim3(256), 0, (hipStream_t)stream, A, lda, B, ldb, E, lde, D, ldd, n, k,
+                     alpha, beta, row_lo, row_hi);
+  RK_SIDE_CHECK_LAUNCH("ease_gemm_kernel");
+  return 0;
+}
+
+int rk_ease_admm_update(const float *T, int64_t ldt, const float *P, int64_t ldp, float *C, int64_t ldc, float *U,
+                        int64_t ldu, float *M, int64_t ldm, int32_t n, float theta, int32_t nonneg, float *gamma,
+                        float *row_primal, float *row_dual, int32_t *row_nnz, int32_t row_lo, int32_t row_hi,
+                        void *stream) {
+  RK_SIDE_REQUIRE(T && P && C && U && M && gamma && row_primal && row_dual && row_nnz, "null pointer");
+  RK_SIDE_REQUIRE(n >= 1 && ldt >= n && ldp >= n && ldc >= n && ldu >= n && ldm >= n, "bad sizes");
+  RK_SIDE_REQUIRE(theta >= 0.f && theta <= 3.4028234663852886e38f, "theta must be finite and >= 0");
+  RK_SIDE_REQUIRE(nonneg == 0 || nonneg == 1, "nonneg must be 0 or 1");
+  RK_SIDE_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= n, "bad row range");
+  if (row_lo == row_hi) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ease_admm_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, s, T, ldt, P, ldp, n, gamma);
+  hipLaunchKernelGGL(ease_admm_update_kernel, dim3(row_hi - row_lo), dim3(256), 0, s, T, ldt, P, ldp, C, ldc, U, ldu, M,
+                     ldm, n, theta, nonneg, gamma, row_primal, row_dual, row_nnz, row_lo);
+  RK_SIDE_CHECK_LAUNCH("rk_ease_admm_update");
   return 0;
 }
 

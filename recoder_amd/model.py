@@ -466,7 +466,7 @@ class Recoder(object):
 
   def _closed_form_fit(self, mod, train_dataset, keep, check, log_line, fit, hint_check=None, check_values=False,
                        store=None, place=None, size_check=None, csrs=None, copy=dict):
-    """The one sequence behind the twelve ``train_*`` methods below: ``mod`` is the fit module, the callables say
+    """The one sequence behind the thirteen ``train_*`` methods below: ``mod`` is the fit module, the callables say
     what differs, ``cfg`` is what ``check`` returned and ``host()`` the dataset's host matrix, built at the step
     that first asks for it.  The order decides which exception wins, and a call that raises in A-D leaves the
     Recoder and the model as they were:
@@ -805,6 +805,33 @@ class Recoder(object):
         size_check=lambda c, host: sizes(c, self.num_users, self.num_items, host().nnz, allocate_matrix=False),
         fit=lambda m, pair, c: gfcf.fit(pair, c[0], c[1], int(oversample), int(num_power_iterations), int(seed),
                                         out=m.item_weights.data)[-1])
+
+  def train_admm_slim(self, train_dataset, l1_reg=None, l2_reg=None, rho=None, num_iterations=None, nonneg=None):
+    """The ADMM-SLIM fit of an AdmmSlimModel (recoder_amd/admm.py): ``item_weights`` becomes the sparse iterate C
+    after ``num_iterations`` iterations of ADMM with penalty ``rho`` on SLIM's objective ``1/2 |X - X B|^2 +
+    l2_reg/2 |B|^2 + l1_reg |B|_1`` with a zero diagonal, over the dataset's interaction matrix X (values as stored;
+    with ``nonneg``, B >= 0 and the values must be >= 0: ValueError otherwise).  Each iteration is a ridge step on
+    ``(X^T X + (l2_reg + rho) I)^-1`` (EASE's Gram and inverse, one dense n^3 product) and a soft-threshold at
+    ``l1_reg / rho``.  ``None`` takes the model's value; explicit values are stored back into the model, so that a
+    checkpoint's ``model_params`` describe the weights it holds.  Five n x n matrices have to fit the device
+    (ValueError otherwise).  The configured ``loss`` plays no part.  Builds a fresh optimizer of ``optimizer_type``
+    so that ``save_state`` works.  Returns (and keeps in ``admm_info``) n, nnz, the hyperparameters, iterations,
+    primal_residual and dual_residual (per iteration: |B - C|_F and rho |C - C_previous|_F), density (the share of
+    non-zeros of C) and gram_ms, inverse_ms and admm_ms (HIP events)."""
+    from . import admm
+    m = self.model
+    names = ("l1_reg", "l2_reg", "rho", "num_iterations", "nonneg")
+    given = (l1_reg, l2_reg, rho, num_iterations, nonneg)
+    return self._closed_form_fit(
+        admm, train_dataset, "admm_info", check_values=_default(nonneg, m, "nonneg") is True,
+        check=lambda m: admm.check_config(m, *(_default(v, m, k) for v, k in zip(given, names))),
+        hint_check=lambda c, u, n, host: n and admm.check_memory(n, c[3], free_bytes=float("inf")),
+        log_line=lambda c: ("ADMM-SLIM: l1_reg %g, l2_reg %g, rho %g, %d iterations, nonneg %s",) + c,
+        store=lambda c: dict(zip(names, c)),
+        # (first use: the parameter itself is one of the n x n matrices, and all have to fit what is free)
+        place=lambda c, first, host: first and admm.check_memory(self._size_hints(train_dataset)[1] or 1, c[3]),
+        size_check=lambda c, host: admm.check_memory(self.num_items, c[3], allocate_matrix=False),
+        fit=lambda m, pair, c: admm.fit(pair, *c, out=m.item_weights.data)[-1])
 
   def train_rp3beta(self, train_dataset, alpha=None, beta=None, neighbours=None):
     """The closed-form RP3beta fit of a RandomWalkItemModel (recoder_amd/rp3.py): every item keeps its
