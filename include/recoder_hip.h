@@ -580,8 +580,8 @@ typedef struct rk_adam_param {
  * (par.sparse: rows / n_dev / n_cap).  The gradient of a dense job may be the
  * sum of g_parts arrays g + t * stride (t ascending; stride = *gstride_dev when
  * given, else g_stride) -- the decoder-bias gradient is consumed straight from
- * rk_decode_loss's per-row-tile partials this way.  loss_part != NULL: the last
- * workgroup does what rk_loss_reduce does.
+ * rk_decode_loss's per-row-tile partials this way.  loss_part != NULL: workgroup 0
+ * does what rk_loss_reduce does (every job then starts one workgroup later).
  */
 #define RK_ADAM_MULTI_MAX 10
 typedef struct rk_adam_job {

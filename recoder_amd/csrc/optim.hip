@@ -746,6 +746,9 @@ extern "C" int rk_adam_lazy_flush(const rk_adam_job_t *jobs, int32_t n_jobs, con
   RK_REQUIRE(n_jobs >= 0 && n_jobs <= RK_ADAM_MULTI_MAX, "too many jobs for one launch");
   RK_REQUIRE(n_jobs == 0 || (jobs != nullptr && table != nullptr && tab_slots != nullptr), "null jobs / table / slots");
   RK_REQUIRE(next_step >= epoch_base, "next_step >= epoch_base");
+  // the epoch's first step: stamps are >= epoch_base, no row can be behind -- and the sweep loads the constants of
+  // step next_step - 1 whatever the rows need, which here would be the entry in FRONT of the table
+  if (next_step == epoch_base) return 0;
   for (int j0 = 0; j0 < n_jobs; j0 += 2) {              // two tables per launch
     UArgs a = {};
     int blocks = 0;

@@ -13,6 +13,7 @@ from recoder_amd import _lib
 from recoder_amd._lib import check, ptr
 from recoder_amd.device import Block, DeviceCSR, current_stream
 from tests import encoder_util as eu
+from tests.adam_util import E, sadam64  # noqa: F401  (the error-carrying float64 and sadam1's restatement)
 from tests.encoder_util import ACT_ELU, ACT_NONE, ACT_RELU, ACT_SELU, ACT_SIGMOID, ACT_TANH, ACTS, U, gamma
 
 pytestmark = pytest.mark.gpu
@@ -69,49 +70,6 @@ def test_bias_act_against_float64(rows, cols, act):
 
 
 # ------------------------------------------------------------------ rk_adam_rows
-class E:
-  """A float64 value with a running bound of the distance of the kernel's fp32 value from it: every fp32
-  operation adds u times the magnitude of its result to what its operands carry."""
-
-  def __init__(self, v, e=None):
-    self.v = np.asarray(v, dtype=np.float64)
-    self.e = np.zeros_like(self.v) if e is None else e
-
-  def _rnd(self, v, e):
-    return E(v, e + U * (np.abs(v) + e))
-
-  def __add__(self, o):
-    return self._rnd(self.v + o.v, self.e + o.e)
-
-  def __sub__(self, o):
-    return self._rnd(self.v - o.v, self.e + o.e)
-
-  def __mul__(self, o):
-    return self._rnd(self.v * o.v, np.abs(self.v) * o.e + np.abs(o.v) * self.e + self.e * o.e)
-
-  def __truediv__(self, o):
-    q = self.v / o.v
-    return self._rnd(q, (self.e + np.abs(q) * o.e) / (np.abs(o.v) - o.e))
-
-  def sqrt(self):
-    return self._rnd(np.sqrt(self.v), np.sqrt(self.v + self.e) - np.sqrt(np.maximum(self.v - self.e, 0.0)))
-
-
-def sadam64(p, m, v, g, lr, b1, b2, eps, step):
-  """sadam1 of csrc/optim.hip in float64 with the bound beside it.  The constants as the host forms them:
-  doubles, then one conversion to fp32.  A contracted g * g - v (or any other product folded into the add
-  behind it) rounds once where this count rounds twice: inside the bound either way."""
-  bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
-  c1, c2 = E(np.float32(1.0 - b1)), E(np.float32(1.0 - b2))
-  ceps, cstep = E(np.float32(eps)), E(np.float32(-(lr * math.sqrt(bc2) / bc1)))
-  p, m, v, g = E(p), E(m), E(v), E(g)
-  um = (g - m) * c1
-  uv = (g * g - v) * c2
-  numer = um + m
-  dsq = uv + v
-  return p + (numer / (dsq.sqrt() + ceps)) * cstep, m + um, v + uv
-
-
 @pytest.mark.parametrize("h", [1, 3, 64, 200])
 @pytest.mark.parametrize("step", [1, 2, 1000])
 @pytest.mark.parametrize("wide", [False, True])
