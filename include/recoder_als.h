@@ -415,6 +415,37 @@ int rk_als_ugcn_scatter(const int32_t *keys, const int64_t *order, int32_t n, in
                         const float *coef, const float *X, int32_t ldx, int32_t n_users, int32_t h, float scale,
                         int32_t n_rows, float *G, int32_t ldg, int32_t *count, void *stream);
 
+/* the metric kinds of rk_als_rank_metrics and how many records one call takes */
+#define RK_ALS_METRIC_RECALL 0
+#define RK_ALS_METRIC_NDCG 1
+#define RK_ALS_METRIC_AP 2
+#define RK_ALS_RANK_METRICS_MAX 8
+
+/*
+ * Ranking metrics of B users' top-K lists, everything on the device: recs (int64 [B, K], row stride ld >= K, the ids
+ * of a row distinct: what rk_topk_masked leaves) against the target CSR tgt_indptr (int64 [B + 1]) / tgt_indices
+ * (int32 [tgt_nnz], ascending within a row, stored zeros dropped; may be NULL when tgt_nnz == 0).  Metric m < n_metrics
+ * is (kinds[m], ks[m], normalize[m]), three host arrays; with hit_r = (recs[u, r] is a target of u), c_r = the hits
+ * up to and including rank r, ny = the user's targets and k' = min(ks[m], K) ranks read:
+ *   RECALL  (sum_{r < k'} hit_r) / norm                       norm = normalize ? min(ks[m], ny) : ny
+ *   AP      (sum_{r < k'} hit_r c_r / (r + 1)) / norm
+ *   NDCG    (sum_{r < k'} hit_r inv_w[r]) / ideal[min(ks[m], ny)]
+ * inv_w (float64 [>= min(K, max k)], 1 / log2(2 + r)) and ideal (float64 [max k + 1], ideal[c] = the sequential sum
+ * of inv_w[:c]) are device tables the host builds, so that a term is the very double the host arithmetic divides
+ * out.  Leaves
+ *   values [B, n_metrics]   float64; nan in every column for a user without targets (0 / 0)
+ *   sums [n_metrics]        float64: the non-nan values of each column, user t + 256 j added to partial t in ascending
+ *                           j, then the 256 partials by a halving tree (partial t += partial t + off, off = 128 .. 1)
+ *   count [1]               int64: the non-nan rows (of column 0)
+ * One wave per user, lanes on ranks lane + 64 j; a binary search per rank, a ballot per 64 ranks; all sums float64 in
+ * ascending rank order.  Two launches on `stream`, no atomics: the same inputs give the same bits.  -2 unless B, K >= 1,
+ * ld >= K, 1 <= n_metrics <= RK_ALS_RANK_METRICS_MAX, every ks[m] >= 1, every kind one of the three, no NULL pointer.
+ */
+int rk_als_rank_metrics(const int64_t *recs, int32_t B, int32_t K, int64_t ld, const int64_t *tgt_indptr,
+                        const int32_t *tgt_indices, int64_t tgt_nnz, int32_t n_metrics, const int32_t *kinds,
+                        const int32_t *ks, const int32_t *normalize, const double *inv_w, const double *ideal,
+                        double *values, double *sums, int64_t *count, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

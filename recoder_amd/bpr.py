@@ -104,30 +104,31 @@ def workspace_bytes(T, h):
   return 5 * _round256(4 * T) + 2 * _round256(4 * T * h)
 
 
-def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True):
+def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True, snapshot=False):
   """Device bytes of a fit: the tables and the bias (unless the caller already holds them), the user-major
   CSR (int64 indptr, int32 indices), the step's workspace, and the keys of both sorts with what
   torch.sort returns and holds meanwhile (3 T entries: an int32 key in, an int32 key and an int64
-  position out, as much again for its scratch)."""
+  position out, as much again for its scratch).  ``snapshot``: and the copy of the tables and the bias that
+  validation with ``restore_best`` keeps (recoder_amd/validation.py)."""
   n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
-  model = (n_users + n_items) * h * 4 + n_items * 4 if allocate_model else 0
+  model = ((n_users + n_items) * h * 4 + n_items * 4) * (int(bool(allocate_model)) + int(bool(snapshot)))
   csr = (n_users + 1) * 8 + max(1, nnz) * 4
   return model + csr + workspace_bytes(T, h) + 2 * 3 * T * (4 + 4 + 8)
 
 
-def check_memory(n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True):
+def check_memory(n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True, snapshot=False):
   """ValueError naming the sizes and the bytes needed when the fit cannot fit: against one device's whole
   HBM without touching a device, then (``free_bytes`` None: asked from the current device) against
   what is free."""
   n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
   if workspace_bytes(T, h) < 0:
     raise ValueError("BPR needs 1 <= batch_size <= %d and 1 <= h <= %d (got %d, %d)" % (MAX_BATCH, MAX_H, T, h))
-  whole = required_bytes(n_users, n_items, h, nnz, T, True)
+  whole = required_bytes(n_users, n_items, h, nnz, T, True, snapshot)
   if whole > DEVICE_HBM_BYTES:
     raise ValueError("BPR over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes: "
                      "more than one device's memory (%d bytes); multi-device fits are not implemented"
                      % (n_users, n_items, h, nnz, T, whole, DEVICE_HBM_BYTES))
-  need = required_bytes(n_users, n_items, h, nnz, T, allocate_model)
+  need = required_bytes(n_users, n_items, h, nnz, T, allocate_model, snapshot)
   if free_bytes is None:
     free_bytes = torch.cuda.mem_get_info()[0]
   if need > free_bytes:
@@ -256,20 +257,23 @@ def step(X, Y, bias, ucsr, ws, seed, step_index, lr, reg, num_candidates=1):
 
 
 # ---------------------------------------------------------------------- fit
-def fit(X, Y, bias, ucsr, num_epochs, batch_size, lr, reg, seed=0, first_step=0, num_candidates=1):
+def fit(X, Y, bias, ucsr, num_epochs, batch_size, lr, reg, seed=0, first_step=0, num_candidates=1, monitor=None):
   """num_epochs epochs of ceil(nnz / batch_size) steps on the tables X [users, h], Y [items, h] and bias
   [items] (in place, f32, row-major); step s of the fit draws as step ``first_step + s``.  Returns the mean
   loss per valid triple of each epoch (floats; nan for an epoch without one).  One host synchronisation
-  per epoch, to read that epoch's sums.  ``num_candidates`` > 1 (up to MAX_DRAWS): see ``step``."""
+  per epoch, to read that epoch's sums.  ``num_candidates`` > 1 (up to MAX_DRAWS): see ``step``.
+  ``monitor`` (a ``validation.Monitor``) scores the tables after every epoch that is due, may stop the fit and at
+  the end puts the best epoch's tables and bias back; the history keeps every epoch that ran."""
   num_candidates = check_candidates(num_candidates)
   steps = check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size)
-  check_memory(X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False)
+  check_memory(X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False,
+               snapshot=monitor is not None and monitor.restore_best)
   ws = Workspace(int(batch_size), X.shape[1], X.device)
   if num_candidates > 1:
     ws.trials = torch.empty(int(batch_size), dtype=torch.int32, device=X.device)
   hist = []
   s = int(first_step)
-  for _ in range(num_epochs):
+  for e in range(num_epochs):
     total = torch.zeros((), dtype=torch.float64, device=X.device)
     count = torch.zeros((), dtype=torch.int64, device=X.device)
     for _ in range(steps):
@@ -279,4 +283,8 @@ def fit(X, Y, bias, ucsr, num_epochs, batch_size, lr, reg, seed=0, first_step=0,
       s += 1
     total, count = torch.stack([total, count.double()]).cpu().tolist()      # (the synchronisation)
     hist.append(total / count if count else float("nan"))
+    if monitor is not None and monitor.due(e) and monitor.epoch_end(e, (X, Y, bias)):
+      break
+  if monitor is not None:
+    monitor.finish((X, Y, bias), len(hist))
   return hist

@@ -53,6 +53,11 @@
 //   rk_als_ugcn_scatter    the item side: the scatter's segment walk with the user rows gathered through the slot,
 //                          a key of RK_ALS_UGCN_LONG_KEY entries or more by a workgroup of 16 waves in fixed parts
 //
+// Ranking metrics on device-resident top-k lists (rk_als_rank_metrics): what recoder_amd/validation.py reads per epoch
+//   rk_als_rank_metrics    one wave per user: a binary search of each rank's id in the user's target row, a ballot per
+//                          64 ranks, Recall / NDCG / AP summed in float64 in ascending rank order; a second launch of
+//                          one workgroup adds the users in a fixed order.  No atomics
+//
 // One translation unit (one last-error buffer, one anonymous namespace), laid out by family under als/: every file
 // holds its kernels, then its extern "C" entry points.
 #include "als/common.h"     // the lane layout, the counter hash, the segment walk, the NT dispatch
@@ -62,6 +67,7 @@
 #include "als/contrast.h"   // rk_als_gcl_contrast, rk_als_dau_*
 #include "als/ssm.h"        // rk_als_ssm_*
 #include "als/ugcn.h"       // rk_als_ugcn_*
+#include "als/metrics.h"    // rk_als_rank_metrics
 
 extern "C" int rk_als_version(void) { return 100; }
 extern "C" const char *rk_als_last_error(void) { return g_rk_side_err; }

@@ -148,8 +148,8 @@ def step(X, Y, graph, state, ws, seed, step_index, lr, reg, gamma):
 
 # ---------------------------------------------------------------------- fit
 def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, gamma, seed=0, state=None,
-        first_step=None):
+        first_step=None, monitor=None):
   """``lightgcn.method_fit`` of DirectAU.  Returns (state, one (alignment, uniformity of the users, uniformity of the
   items) triple of per-step means per epoch)."""
   return lightgcn.method_fit(METHOD, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, (gamma,),
-                             seed, state, first_step)
+                             seed, state, first_step, monitor)

@@ -83,42 +83,44 @@ def check_data(nnz, n_items, num_epochs, batch_size):
   return bpr.check_data(nnz, n_items, num_epochs, batch_size, method=METHOD.method)
 
 
-def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True, allocate_state=True, allocate_csrs=True):
+def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True, allocate_state=True, allocate_csrs=True,
+                   snapshot=False):
   """Device bytes of a fit: the model's tables and bias, the state (the base tables E0 and both Adam moments)
   and both CSRs (int64 indptr, int32 indices), each unless the caller already holds it; the gradient G and
   its propagated form H; two layer buffers; the counts and the two scale vectors; BPR's workspace and the
-  buffers of its two sorts."""
+  buffers of its two sorts.  ``snapshot``: and the copy of the state that validation with ``restore_best`` keeps
+  (recoder_amd/validation.py)."""
   n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
   rows = n_users + n_items
   model = rows * h * 4 + n_items * 4 if allocate_model else 0
-  state = 3 * rows * h * 4 if allocate_state else 0
+  state = (3 * rows * h * 4 if allocate_state else 0) + (3 * rows * h * 4 if snapshot else 0)
   csrs = (n_users + 1) * 8 + (n_items + 1) * 8 + 2 * max(1, nnz) * 4 if allocate_csrs else 0
   return model + state + csrs + (2 + 2) * rows * h * 4 + 2 * rows * 4 + bpr.workspace_bytes(T, h) + \
       2 * 3 * T * (4 + 4 + 8)
 
 
 def method_required_bytes(method, n_users, n_items, h, nnz, T, allocate_model=True, allocate_state=True,
-                          allocate_csrs=True, **opts):
+                          allocate_csrs=True, snapshot=False, **opts):
   """``required_bytes`` and what ``method`` holds on top of it under its options ``opts``."""
-  return required_bytes(n_users, n_items, h, nnz, T, allocate_model, allocate_state, allocate_csrs) + \
+  return required_bytes(n_users, n_items, h, nnz, T, allocate_model, allocate_state, allocate_csrs, snapshot) + \
       method.extra_bytes(int(n_users), int(n_items), int(h), int(T), **opts)
 
 
 def method_check_memory(method, n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True,
-                        allocate_state=True, allocate_csrs=True, **opts):
+                        allocate_state=True, allocate_csrs=True, snapshot=False, **opts):
   """ValueError naming the sizes and the bytes needed when the fit cannot fit: against one device's whole HBM
   without touching a device, then (``free_bytes`` None: asked from the current device) against what is free."""
   n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
   if not (1 <= T <= method.max_batch and 1 <= h <= MAX_H):               # (where the workspaces' bytes are negative)
     raise ValueError("%s needs 1 <= batch_size <= %d and 1 <= h <= %d (got %d, %d)"
                      % (method.name, method.max_batch, MAX_H, T, h))
-  whole = method_required_bytes(method, n_users, n_items, h, nnz, T, **opts)
+  whole = method_required_bytes(method, n_users, n_items, h, nnz, T, snapshot=snapshot, **opts)
   if whole > DEVICE_HBM_BYTES:
     raise ValueError("%s over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes: "
                      "more than one device's memory (%d bytes); multi-device fits are not implemented"
                      % (method.name, n_users, n_items, h, nnz, T, whole, DEVICE_HBM_BYTES))
   need = method_required_bytes(method, n_users, n_items, h, nnz, T, allocate_model, allocate_state, allocate_csrs,
-                               **opts)
+                               snapshot, **opts)
   if free_bytes is None:
     free_bytes = torch.cuda.mem_get_info()[0]
   if need > free_bytes:
@@ -310,20 +312,32 @@ def step(X, Y, graph, state, ws, seed, step_index, lr, reg):
 
 
 # ---------------------------------------------------------------------- fit
+def state_tensors(state):
+  """The device tensors of a state (``new_state``), in a fixed order: what a snapshot copies."""
+  return list(state["E0"]) + list(state["M"]) + list(state["V"])
+
+
 def method_fit(method, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, hyper=(), seed=0,
-               state=None, first_step=None):
+               state=None, first_step=None, monitor=None, monitor_prepare=None):
   """num_epochs epochs of ceil(nnz / batch_size) steps of ``method``.  ``state`` None: a fresh state (``new_state``:
   the base tables are X, Y as they stand), made once every check has passed; else an earlier fit's, continued.
   Step s of the fit draws as step ``first_step + s`` (None: the state's step count, so that a continued fit draws
   what one longer fit would have).  The model's tables X [users, h], Y [items, h] (f32, row-major, may be strided)
   end as the final tables of the last base tables, ``bias`` as 0.  Returns (state, the history: ``method.entry`` of
-  each epoch's sums).  One host synchronisation per epoch."""
+  each epoch's sums).  One host synchronisation per epoch.
+  ``monitor`` (a ``validation.Monitor``): after every epoch that is due the final tables of the base tables as they
+  stand are written into X, Y -- what a fit ending there leaves; the next step's own forward pass overwrites them
+  with the same bits -- and the monitor scores them (``monitor_prepare``: a function applied in place to X and Y for
+  the scoring alone, the sampled softmax's normalisation); it may stop the fit, and at the end puts the best
+  epoch's state back, so that the tables, the state and its step count are those of a fit of that many epochs.  The
+  history keeps every epoch that ran."""
   steps = bpr.check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size, method=method.method)
   if state is not None:
     check_resume(state, num_layers, (X.shape, Y.shape), method=method.method)
   opts = method.opts(*hyper)
   method_check_memory(method, X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False,
-                      allocate_state=state is None, allocate_csrs=False, **opts)
+                      allocate_state=state is None, allocate_csrs=False,
+                      snapshot=monitor is not None and monitor.restore_best, **opts)
   if state is None:
     state = new_state(X, Y, num_layers)
   graph = Graph(ucsr, icsr)
@@ -331,7 +345,7 @@ def method_fit(method, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_siz
   bias.zero_()
   hist = []
   s = state["step"] if first_step is None else int(first_step)
-  for _ in range(num_epochs):
+  for e in range(num_epochs):
     sums = [torch.zeros(shape, dtype=dtype, device=X.device) for shape, dtype in method.sums]
     for _ in range(steps):
       method_step(method, X, Y, graph, state, ws, seed, s, lr, reg, hyper)
@@ -339,12 +353,20 @@ def method_fit(method, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_siz
       s += 1
     values = torch.cat([t.double().reshape(-1) for t in sums]).cpu().tolist()      # (the synchronisation)
     hist.append(method.entry(values, steps))
+    if monitor is not None and monitor.due(e):
+      forward(graph, state["E0"], state["num_layers"], ws.layers, (X, Y), method.skip_layer0)
+      if monitor.epoch_end(e, state_tensors(state), state["step"],
+                           prepare=None if monitor_prepare is None else ((X, Y), monitor_prepare)):
+        break
+  if monitor is not None and monitor.finish(state_tensors(state), len(hist)):
+    state["step"] = monitor.best_step
   forward(graph, state["E0"], state["num_layers"], ws.layers, (X, Y), method.skip_layer0)
   return state, hist
 
 
-def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, seed=0, state=None, first_step=None):
+def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, seed=0, state=None, first_step=None,
+        monitor=None):
   """``method_fit`` of LightGCN.  Returns (state, the mean loss per valid triple of each epoch: floats, nan for an
   epoch without one)."""
   return method_fit(METHOD, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, (), seed, state,
-                    first_step)
+                    first_step, monitor)

@@ -132,21 +132,129 @@ def batch_metrics(recommendations, target_csr, metrics):
   return out
 
 
+# ---------------------------------------------------------------- on the device
+MAX_DEVICE_METRICS = 8        # RK_ALS_RANK_METRICS_MAX: the records of one rk_als_rank_metrics call
+_KINDS = {Recall: 0, NDCG: 1, AveragePrecision: 2}      # RK_ALS_METRIC_RECALL, _NDCG, _AP
+
+
+def device_metrics_ok(metrics):
+  """True when ``metrics`` are what rk_als_rank_metrics computes: built-in ones only, 1..8 of them, every k an
+  integer >= 1 that fits 32 bits."""
+  metrics = list(metrics)
+  return 1 <= len(metrics) <= MAX_DEVICE_METRICS and all(
+      type(m) in _KINDS and isinstance(m.k, (int, np.integer)) and not isinstance(m.k, bool) and 1 <= m.k < 2 ** 31
+      for m in metrics)
+
+
+class DeviceTarget(object):
+  """A batch's target CSR on the device, uploaded once: int64 indptr [B + 1] and int32 indices, ascending within a
+  row, stored zeros dropped (as ``batch_metrics`` does with ``tm.data != 0``)."""
+
+  def __init__(self, target_csr, device):
+    import torch
+    tm = target_csr.tocsr().copy()
+    tm.eliminate_zeros()
+    tm.sort_indices()
+    self.rows, self.nnz = int(tm.shape[0]), int(tm.nnz)
+    self.indptr = torch.from_numpy(tm.indptr.astype(np.int64)).to(device)
+    self.indices = torch.from_numpy(tm.indices.astype(np.int32)).to(device)
+
+
+class DeviceMetricTables(object):
+  """The metric records of a call and the two float64 tables the kernel divides by, built on the host with numpy --
+  1 / log2(2 + r) and its cumulative sum from 0, the doubles ``batch_metrics`` uses -- and uploaded once."""
+
+  def __init__(self, metrics, device):
+    import torch
+    from ctypes import c_int32
+    metrics = list(metrics)
+    if not device_metrics_ok(metrics):
+      raise ValueError("the device path computes 1..%d of Recall, NDCG and AveragePrecision with integer k >= 1 "
+                       "(got %s)" % (MAX_DEVICE_METRICS, ", ".join(str(m) for m in metrics) or "none"))
+    n = len(metrics)
+    self.n, self.max_k = n, max(int(m.k) for m in metrics)
+    self.kinds = (c_int32 * n)(*[_KINDS[type(m)] for m in metrics])
+    self.ks = (c_int32 * n)(*[int(m.k) for m in metrics])
+    self.normalize = (c_int32 * n)(*[int(bool(getattr(m, "normalize", True))) for m in metrics])
+    inv_w = 1.0 / np.log2(2 + np.arange(self.max_k))
+    self.inv_w = torch.from_numpy(inv_w).to(device)
+    self.ideal = torch.from_numpy(np.concatenate([[0.0], np.cumsum(inv_w)])).to(device)
+
+
+def device_batch_metrics(recs_dev, ld, target, metrics, tables=None, out=None):
+  """``batch_metrics`` without the host: ``recs_dev`` an int64 device tensor whose first B rows of K ids lie ``ld``
+  elements apart (a contiguous [B, K] tensor, or a strided view such as ``cand_idx[:, :k]``), ``target`` a
+  ``DeviceTarget`` of at least B rows, ``metrics`` 1..8 of Recall / NDCG / AveragePrecision.  Returns (values
+  [B, len(metrics)] float64, (sums [len(metrics)] float64, count [1] int64)), all device tensors and nothing
+  synchronised: nan for a user without targets, ``sums`` over the other rows, ``count`` of them
+  (rk_als_rank_metrics; fixed summation orders, the same inputs give the same bits).  ``tables`` (a
+  ``DeviceMetricTables`` of ``metrics``) and ``out`` (an earlier call's three tensors) are reused when given."""
+  import torch
+  from . import _als_lib
+  from ._lib import ptr
+  from .device import current_stream
+  B, K = int(recs_dev.shape[0]), int(recs_dev.shape[1])
+  assert recs_dev.dtype == torch.int64 and recs_dev.dim() == 2 and recs_dev.stride(1) == 1 and int(ld) >= K and \
+      (B == 1 or recs_dev.stride(0) == int(ld)), (recs_dev.dtype, recs_dev.shape, recs_dev.stride(), ld)
+  if target.rows < B:
+    raise ValueError("the target holds %d users, the recommendations %d" % (target.rows, B))
+  if tables is None:
+    tables = DeviceMetricTables(metrics, recs_dev.device)
+  if out is None:
+    out = (torch.empty((B, tables.n), dtype=torch.float64, device=recs_dev.device),
+           torch.empty(tables.n, dtype=torch.float64, device=recs_dev.device),
+           torch.empty(1, dtype=torch.int64, device=recs_dev.device))
+  values, sums, count = out
+  values = values[:B]
+  assert values.is_contiguous() and values.shape[1] == tables.n
+  lib = _als_lib.load()
+  _als_lib.check(lib.rk_als_rank_metrics(ptr(recs_dev), B, K, int(ld), ptr(target.indptr), ptr(target.indices),
+                                         target.nnz, tables.n, tables.kinds, tables.ks, tables.normalize,
+                                         ptr(tables.inv_w), ptr(tables.ideal), ptr(values), ptr(sums), ptr(count),
+                                         current_stream()), "rk_als_rank_metrics")
+  return values, (sums, count)
+
+
 class RecommenderEvaluator(object):
   """Evaluates a recommender on a dataset with input/target interactions
   (metrics.py:135-232).  ``num_workers`` is accepted for compatibility; scoring
-  and top-k run on the GPU, the per-user metric arithmetic on the host."""
+  and top-k run on the GPU, the per-user metric arithmetic on the host -- or, with
+  ``evaluate(on_device=True)``, on the GPU as well."""
 
   def __init__(self, recommender, metrics):
     self.recommender = recommender
     self.metrics = metrics
 
-  def evaluate(self, eval_dataset, batch_size=1, num_users=None, num_workers=0):
+  def _device_lists(self):
+    """``recommender``'s device top-k (``recommend_device(inp) -> (ids, ld)``) when it has one and the metrics are
+    the kernel's, else None."""
+    fn = getattr(self.recommender, "recommend_device", None)
+    return fn if fn is not None and device_metrics_ok(self.metrics) else None
+
+  def evaluate(self, eval_dataset, batch_size=1, num_users=None, num_workers=0, on_device=False):
+    """``on_device=True``: with a ``Recoder``-backed recommender and only built-in metrics the top-k lists stay on
+    the device and rk_als_rank_metrics computes the per-user values, read back as one array per batch; anything
+    else takes the host path below."""
     dataloader = RecommendationDataLoader(eval_dataset, batch_size=batch_size,
                                           collate_fn=lambda _: _)
     results = {metric: [] for metric in self.metrics}
     processed = 0
+    device_lists = self._device_lists() if on_device else None
+    tables = None
     for inp, target in dataloader:
+      if device_lists is not None:
+        recs_dev, ld = device_lists(inp)
+        if tables is None:
+          tables = DeviceMetricTables(self.metrics, recs_dev.device)
+        values, _ = device_batch_metrics(recs_dev, ld, DeviceTarget(target.interactions_matrix, recs_dev.device),
+                                         self.metrics, tables)
+        host = values.cpu().numpy()
+        for j, metric in enumerate(self.metrics):
+          results[metric].extend(host[:, j].tolist())
+        processed += len(target.users)
+        if num_users is not None and processed >= num_users:
+          break
+        continue
       as_array = getattr(self.recommender, "recommend_array", None)
       recommendations = as_array(inp) if as_array is not None else self.recommender.recommend(inp)
       tm = target.interactions_matrix.tocsr()

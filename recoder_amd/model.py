@@ -109,6 +109,11 @@ class Recoder(object):
     self.ssm_state = None       # train_ssm: base tables, Adam moments, step count, num_layers (device; not saved)
     self.ultragcn_history = []  # train_ultragcn: (positive, negatives, neighbours) means per valid slot of each epoch
     self.ultragcn_state = None  # train_ultragcn: the tables, Adam moments and step count (device; not saved)
+    # the seven iterative trainers' validation curve of the last fit (None: it had no val_dataset): {"metric", "k",
+    # "values", "epochs", "best_epoch", "stopped_epoch"}; not saved
+    self.fit_validation = None  # validation settings for the iterative fits called without a val_dataset (_validated)
+    self.bpr_validation = self.warp_validation = self.lightgcn_validation = self.simgcl_validation = None
+    self.directau_validation = self.ssm_validation = self.ultragcn_validation = None
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -534,7 +539,47 @@ class Recoder(object):
         fit=lambda m, pair, alpha: als.fit(*_mf_tables(m), m.bias.data, *pair, alpha, float(reg), int(cg_steps),
                                            int(num_iterations)))
 
-  def train_bpr(self, train_dataset, num_epochs=40, batch_size=1024, lr=0.1, reg=0.01, seed=0, num_candidates=1):
+  def _validated(self, method, prefix, train_dataset, args):
+    """The validation keywords the seven iterative trainers share (recoder_amd/validation.py), ``args`` =
+    (val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience, restore_best).  With a
+    ``val_dataset`` (a dataset with an ``interactions_matrix`` to score from and a ``target_interactions_matrix``
+    to hit) the fit evaluates ``eval_metric`` (None: Recall(20); one of Recall, NDCG, AveragePrecision) after every
+    ``eval_freq`` epochs on the first ``eval_num_users`` users (None: all) in batches of ``eval_batch_size``, at
+    the model a fit ending at that epoch would leave, scoring, top-k and metric on the device.  ``patience = p``
+    stops the fit after p evaluations in a row without a new best (strictly greater; nan never is one);
+    ``restore_best`` keeps a device copy of the best epoch and puts it back at the end, so that the model (and a
+    graph method's ``<prefix>_state``) is what a fit of ``best_epoch`` epochs leaves.  The loss history keeps every
+    epoch that ran; ``self.<prefix>_validation`` = {"metric", "k", "values", "epochs", "best_epoch",
+    "stopped_epoch"} (None without a ``val_dataset``).  Nothing of this touches the fit's draws or arithmetic.
+    ``train_ssm`` and ``train_ultragcn`` keep the parameter lists their contracts pin, so they take the same settings
+    from ``self.fit_validation``: a dict of these keywords (``val_dataset`` at least), set like the Recoder's other
+    hooks and read by every one of the seven fits that is called without a ``val_dataset`` keyword, until it is set
+    back to None.
+    Returns (check, monitor, keep): ``check()`` raises the ValueErrors before any GPU work, ``monitor()`` builds the
+    fit's ``validation.Monitor`` (None without validation) once the model is placed, ``keep()`` stores the result."""
+    from . import validation
+    box = {}
+
+    def check():
+      n_items = self._size_hints(train_dataset)[1]
+      box["cfg"] = validation.check_config(method, *args, num_items=n_items)
+      if box["cfg"] is None and self.fit_validation is not None:
+        box["cfg"] = validation.check_config(method, **validation.check_settings(self.fit_validation), num_items=n_items)
+
+    def monitor():
+      cfg = box["cfg"]
+      if cfg is not None:
+        box["monitor"] = validation.Monitor(
+            validation.Validator(self, cfg.dataset, cfg.metric, None, cfg.batch_size, cfg.num_users), cfg)
+      return box.get("monitor")
+
+    def keep():
+      setattr(self, prefix + "_validation", box["monitor"].result() if "monitor" in box else None)
+    return check, monitor, keep
+
+  def train_bpr(self, train_dataset, num_epochs=40, batch_size=1024, lr=0.1, reg=0.01, seed=0, num_candidates=1,
+                val_dataset=None, eval_metric=None, eval_freq=1, eval_batch_size=500,
+                eval_num_users=None, patience=None, restore_best=True):
     """BPR-MF (Rendle et al. 2009) for a MatrixFactorization with activation 'none' (recoder_amd/bpr.py):
     pairwise ranking on sampled triples (user, a stored item, an item the user does not hold), loss
     softplus(-(x_ui - x_uj)), synchronous mini-batch SGD with learning rate ``lr`` and an L2 pull ``reg``
@@ -546,18 +591,28 @@ class Recoder(object):
     With ``num_candidates`` > 1 (up to 32) the negative is not the first item the user does not hold but the
     highest-scored of the first ``num_candidates`` such draws, at the tables as they stand at the start of the
     step (dynamic negative sampling, Zhang et al. 2013); everything else is unchanged.
-    Returns (and keeps in ``bpr_history``) the mean loss per valid triple of each epoch."""
+    Returns (and keeps in ``bpr_history``) the mean loss per valid triple of each epoch.
+    ``val_dataset`` and the keywords after it: validation during the fit and early stopping (``_validated``)."""
     from . import bpr
+    vcheck, monitor, vkeep = self._validated("train_bpr", "bpr", train_dataset, (val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience, restore_best))
+
+    def check(m):
+      c = bpr.check_config(m, num_epochs, batch_size, lr, reg, seed) + (bpr.check_candidates(num_candidates),)
+      vcheck()
+      return c
+
+    def fit(m, ucsr, c):
+      hist = bpr.fit(*_mf_tables(m), m.bias.data, ucsr, *c[:5], num_candidates=c[5], monitor=monitor())
+      vkeep()
+      return hist
     return self._closed_form_fit(
-        bpr, train_dataset, "bpr_history", copy=list, csrs=bpr.user_csr,
-        check=lambda m: bpr.check_config(m, num_epochs, batch_size, lr, reg, seed)
-        + (bpr.check_candidates(num_candidates),),
+        bpr, train_dataset, "bpr_history", copy=list, csrs=bpr.user_csr, check=check, fit=fit,
         log_line=lambda c: ("BPR: %d epochs of batches of %d, lr %g, reg %g, seed %d, %d candidate(s) per slot",) + c,
-        size_check=lambda c, host: bpr.check_data(host().nnz, self.num_items, c[0], c[1]),
-        fit=lambda m, ucsr, c: bpr.fit(*_mf_tables(m), m.bias.data, ucsr, *c[:5], num_candidates=c[5]))
+        size_check=lambda c, host: bpr.check_data(host().nnz, self.num_items, c[0], c[1]))
 
   def train_warp(self, train_dataset, num_epochs=10, batch_size=1024, lr=0.005, reg=0.05, margin=1.0,
-                 max_draws=32, rank_weight="log", seed=0):
+                 max_draws=32, rank_weight="log", seed=0, val_dataset=None, eval_metric=None, eval_freq=1, eval_batch_size=500,
+                 eval_num_users=None, patience=None, restore_best=True):
     """WARP (Weston et al. 2011; LightFM's loss) for a MatrixFactorization with activation 'none'
     (recoder_amd/warp.py): a slot is one of ``train_bpr``'s stored entries (u, i); items the user does not hold
     are drawn and scored until one violates the margin, (s_uj - s_ui) + ``margin`` > 0, and the update is BPR's
@@ -567,34 +622,47 @@ class Recoder(object):
     tables plug into are as in ``train_bpr``; the users and stored items of a step are its draws for the same
     seed.  Returns (and keeps in ``warp_history``) the mean loss per valid slot of each epoch; ``warp_stats``
     keeps per epoch (the share of slots that found a violator, their mean N): as the model learns the share
-    falls and N rises."""
+    falls and N rises.
+    ``val_dataset`` and the keywords after it: validation during the fit and early stopping (``_validated``)."""
     from . import warp
+    vcheck, monitor, vkeep = self._validated("train_warp", "warp", train_dataset, (val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience, restore_best))
+
+    def check(m):
+      c = warp.check_config(m, num_epochs, batch_size, lr, reg, margin, max_draws, rank_weight, seed)
+      vcheck()
+      return c
 
     def fit(m, ucsr, c):
-      hist, self.warp_stats = warp.fit(*_mf_tables(m), m.bias.data, ucsr, *c)
+      hist, self.warp_stats = warp.fit(*_mf_tables(m), m.bias.data, ucsr, *c, monitor=monitor())
+      vkeep()
       return hist
     return self._closed_form_fit(
-        warp, train_dataset, "warp_history", copy=list, csrs=warp.bpr.user_csr, fit=fit,
-        check=lambda m: warp.check_config(m, num_epochs, batch_size, lr, reg, margin, max_draws, rank_weight, seed),
+        warp, train_dataset, "warp_history", copy=list, csrs=warp.bpr.user_csr, fit=fit, check=check,
         log_line=lambda c: ("WARP: %d epochs of batches of %d, lr %g, reg %g, margin %g, at most %d draws, %s "
                             "weights, seed %d",) + c,
         size_check=lambda c, host: warp.check_data(host().nnz, self.num_items, c[0], c[1]))
 
-  def _graph_fit(self, mod, prefix, train_dataset, resume, log_format, *config):
+  def _graph_fit(self, mod, prefix, train_dataset, resume, log_format, *config,
+                 validation=(None, None, 1, 500, None, None, True)):
     """``_closed_form_fit`` for the three methods that train base tables over the user-item graph (the driver of
     recoder_amd/lightgcn.py): ``mod.check_config(model, *config)``, then with ``resume`` the kept
-    ``self.<prefix>_state`` checked and handed to ``mod.fit``; the history goes to ``self.<prefix>_history``."""
+    ``self.<prefix>_state`` checked and handed to ``mod.fit``; the history goes to ``self.<prefix>_history``.
+    ``validation``: the arguments of ``_validated``, the fit's one hook at the epoch's end."""
+    vcheck, monitor, vkeep = self._validated("train_" + prefix, prefix, train_dataset, validation)
+
     def check(m):
       c = mod.check_config(m, *config)
       if resume:
         mod.check_resume(getattr(self, prefix + "_state"), c[0])
+      vcheck()
       return c
 
     def fit(m, pair, c):
       # (a fresh state replaces the kept one only once the fit's own checks have passed)
       state, hist = mod.fit(*_mf_tables(m), m.bias.data, *pair, *c,
-                            state=getattr(self, prefix + "_state") if resume else None)
+                            state=getattr(self, prefix + "_state") if resume else None, monitor=monitor())
       setattr(self, prefix + "_state", state)
+      vkeep()
       return hist
     return self._closed_form_fit(
         mod, train_dataset, prefix + "_history", copy=list, check=check, fit=fit,
@@ -602,7 +670,8 @@ class Recoder(object):
         size_check=lambda c, host: mod.check_data(host().nnz, self.num_items, c[1], c[2]))
 
   def train_lightgcn(self, train_dataset, num_layers=3, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3, seed=0,
-                     resume=False):
+                     resume=False, val_dataset=None, eval_metric=None, eval_freq=1, eval_batch_size=500,
+                     eval_num_users=None, patience=None, restore_best=True):
     """LightGCN (He et al. 2020) for a MatrixFactorization with activation 'none' (recoder_amd/lightgcn.py): the
     final tables are the mean over ``num_layers`` + 1 layers of trainable base tables propagated over the
     symmetrically normalised user-item graph of the stored entries, trained on BPR's triples (the draws of
@@ -613,14 +682,18 @@ class Recoder(object):
     call would have had.  The model's tables end as the final tables and the bias as 0: ``save_state``,
     ``recommend``, ``evaluate``, ``train``, ``train_als`` and ``train_bpr`` take them as they are.  The stored
     values and the configured ``loss`` play no part.  Returns (and keeps in ``lightgcn_history``) the mean
-    loss per valid triple of each epoch."""
+    loss per valid triple of each epoch.
+    ``val_dataset`` and the keywords after it: validation during the fit and early stopping (``_validated``)."""
     from . import lightgcn
     return self._graph_fit(lightgcn, "lightgcn", train_dataset, resume,
                            "LightGCN: %d layers, %d epochs of batches of %d, lr %g, reg %g, seed %d",
-                           num_layers, num_epochs, batch_size, lr, reg, seed)
+                           num_layers, num_epochs, batch_size, lr, reg, seed,
+                           validation=(val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience,
+                                       restore_best))
 
   def train_simgcl(self, train_dataset, num_layers=2, num_epochs=10, batch_size=1024, lr=0.002, reg=1e-3,
-                   cl_weight=0.1, cl_eps=0.2, cl_temperature=0.2, seed=0, resume=False):
+                   cl_weight=0.1, cl_eps=0.2, cl_temperature=0.2, seed=0, resume=False, val_dataset=None, eval_metric=None, eval_freq=1, eval_batch_size=500,
+                   eval_num_users=None, patience=None, restore_best=True):
     """SimGCL (Yu et al. 2022) for a MatrixFactorization with activation 'none' (recoder_amd/simgcl.py):
     LightGCN's propagation with the mean over the layers 1..``num_layers`` (layer 0 is left out), trained on
     BPR's triples (the draws of ``train_bpr`` and ``train_lightgcn`` for the same seed, step and slot) plus
@@ -634,15 +707,19 @@ class Recoder(object):
     model's tables end as the clean tables and the bias as 0: ``save_state``, ``recommend``, ``evaluate``,
     ``train``, ``train_als`` and ``train_bpr`` take them as they are.  The stored values and the configured
     ``loss`` play no part.  Returns (and keeps in ``simgcl_history``) one (mean BPR loss per valid triple, mean
-    NCE_users + NCE_items per step) pair per epoch."""
+    NCE_users + NCE_items per step) pair per epoch.
+    ``val_dataset`` and the keywords after it: validation during the fit and early stopping (``_validated``)."""
     from . import simgcl
     return self._graph_fit(simgcl, "simgcl", train_dataset, resume,
                            "SimGCL: %d layers, %d epochs of batches of %d, lr %g, reg %g, cl_weight %g, eps %g, "
                            "temperature %g, seed %d",
-                           num_layers, num_epochs, batch_size, lr, reg, cl_weight, cl_eps, cl_temperature, seed)
+                           num_layers, num_epochs, batch_size, lr, reg, cl_weight, cl_eps, cl_temperature, seed,
+                           validation=(val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience,
+                                       restore_best))
 
   def train_directau(self, train_dataset, num_layers=2, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3,
-                     gamma=0.2, seed=0, resume=False):
+                     gamma=0.2, seed=0, resume=False, val_dataset=None, eval_metric=None, eval_freq=1, eval_batch_size=500,
+                     eval_num_users=None, patience=None, restore_best=True):
     """DirectAU (Wang et al. 2022) for a MatrixFactorization with activation 'none' (recoder_amd/directau.py):
     no negatives are drawn.  A step takes the (user, stored item) pairs of BPR's draws (those of ``train_bpr``,
     ``train_lightgcn`` and ``train_simgcl`` for the same seed, step and slot), normalises their rows of the final
@@ -658,11 +735,14 @@ class Recoder(object):
     code), and the bias as 0: ``save_state``, ``recommend``, ``evaluate``, ``train``, ``train_als`` and
     ``train_bpr`` take them as they are.  The stored values and the configured ``loss`` play no part.  Returns
     (and keeps in ``directau_history``) one (alignment, uniformity of the users, uniformity of the items) triple
-    of per-step means per epoch."""
+    of per-step means per epoch.
+    ``val_dataset`` and the keywords after it: validation during the fit and early stopping (``_validated``)."""
     from . import directau
     return self._graph_fit(directau, "directau", train_dataset, resume,
                            "DirectAU: %d layers, %d epochs of batches of %d, lr %g, reg %g, gamma %g, seed %d",
-                           num_layers, num_epochs, batch_size, lr, reg, gamma, seed)
+                           num_layers, num_epochs, batch_size, lr, reg, gamma, seed,
+                           validation=(val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience,
+                                       restore_best))
 
   def train_ssm(self, train_dataset, num_layers=2, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3,
                 temperature=0.2, num_negatives=1024, similarity="cosine", logq_weight=0.0, normalize=False, seed=0,
@@ -687,7 +767,9 @@ class Recoder(object):
     ``recommend`` ranks by the cosine the fit trained; the state's base tables are never normalised -- and the
     bias as 0: ``save_state``, ``recommend``, ``evaluate``, ``train``, ``train_als`` and ``train_bpr`` take them
     as they are.  The stored values and the configured ``loss`` play no part.  Returns (and keeps in
-    ``ssm_history``) one (loss, probability of the positive) pair of per-step means per epoch."""
+    ``ssm_history``) one (loss, probability of the positive) pair of per-step means per epoch.
+    Validation during the fit and early stopping: ``self.fit_validation`` (``_validated``).  With
+    ``normalize=True`` an evaluation scores the row-normalised tables, as the finished fit would."""
     from . import ssm
     return self._graph_fit(ssm, "ssm", train_dataset, resume,
                            "SSM: %d layers, %d epochs of batches of %d, lr %g, reg %g, temperature %g, %d shared "
@@ -715,7 +797,8 @@ class Recoder(object):
     step count one longer call would have had.  The model's tables end as the trained tables and the bias as 0:
     ``save_state``, ``recommend``, ``evaluate``, ``train``, ``train_als`` and ``train_bpr`` take them as they are.  The
     stored values and the configured ``loss`` play no part.  Returns (and keeps in ``ultragcn_history``) one
-    (positive, negatives, neighbours) triple of the three terms' means per valid pair per epoch."""
+    (positive, negatives, neighbours) triple of the three terms' means per valid pair per epoch.
+    Validation during the fit and early stopping: ``self.fit_validation`` (``_validated``)."""
     from . import ultragcn
     return self._graph_fit(ultragcn, "ultragcn", train_dataset, resume,
                            "UltraGCN: %d layers, %d epochs of batches of %d, lr %g, reg %g, %d negatives a slot at "
@@ -1583,9 +1666,10 @@ class Recoder(object):
       return out, dense
     return out, out
 
-  def _input_block(self, users_interactions):
+  def _input_block(self, users_interactions, ws=None):
     """The users' interactions as an unsampled device block (bitmap over the whole catalogue),
-    in buffers that are kept and reused across predict / recommend calls."""
+    in buffers that are kept and reused across predict / recommend calls (``ws``: in that
+    workspace instead, ``recoder_amd.validation`` keeps one per batch)."""
     m = users_interactions.interactions_matrix
     B = m.shape[0]
     n_items = self.num_items if self.num_items is not None else m.shape[1]
@@ -1593,9 +1677,10 @@ class Recoder(object):
     assert dcsr.n_items <= n_items
     if dcsr.n_items != n_items:
       dcsr.shape = (B, n_items)
-    ws = getattr(self, "_eval_ws", None)
-    if ws is None or ws["n_items"] != n_items:
-      ws = self._eval_ws = dict(n_items=n_items, blk=None, strips={}, scores=None, cand=None)
+    if ws is None:
+      ws = getattr(self, "_eval_ws", None)
+      if ws is None or ws["n_items"] != n_items:
+        ws = self._eval_ws = self._new_eval_ws(n_items)
     ws["dcsr"] = dcsr
     blk = ws["blk"]
     if blk is None or blk.S_cap < B or blk.nnz_cap < max(1, dcsr.nnz):
@@ -1609,6 +1694,10 @@ class Recoder(object):
         .to(self.device)
     return blk, B, n_items
 
+  @staticmethod
+  def _new_eval_ws(n_items):
+    return dict(n_items=n_items, blk=None, strips={}, scores=None, cand=None)
+
   def _predict_scores(self, users_interactions):
     engine = self._engine()
     blk, B, n_items = self._input_block(users_interactions)
@@ -1620,13 +1709,15 @@ class Recoder(object):
     engine.predict_scores(blk, 0, B, out, ld, blk)
     return out[:, :n_items], blk, B
 
-  def _evaluate(self, eval_dataset, num_recommendations, metrics, batch_size=1, num_users=None):
+  def _evaluate(self, eval_dataset, num_recommendations, metrics, batch_size=1, num_users=None, on_device=False):
     """model.py:513-523."""
     if self.model is None:
       raise Exception("Model not initialized")
     self.model.eval()
     recommender = InferenceRecommender(self, num_recommendations)
     evaluator = RecommenderEvaluator(recommender, metrics)
+    if on_device:
+      return evaluator.evaluate(eval_dataset, batch_size=batch_size, num_users=num_users, on_device=True)
     return evaluator.evaluate(eval_dataset, batch_size=batch_size, num_users=num_users)
 
   # items decoded at a time by recommend(): [B, strip] fp32 scores stay cache-resident
@@ -1646,6 +1737,18 @@ class Recoder(object):
     in strips of ``eval_strip_items`` items, each strip's masked top k is kept
     (``rk_topk_masked`` with a column offset) and the per-strip winners are merged with one more top-k pass --
     ties resolve to the lower item id at both levels, as torch.topk on the full row would."""
+    ids, _ = self._recommend_device(users_interactions, num_recommendations, host_ok=True)
+    if isinstance(ids, np.ndarray):                                 # (the fused form: already on the host)
+      return ids
+    return ids.cpu().numpy().copy()
+
+  def _recommend_device(self, users_interactions, num_recommendations, host_ok=False, ws=None, inputs=None):
+    """``recommend_array`` before its copy to the host: (ids, ld), an int64 device tensor [users, k] (possibly a
+    strided view of the candidate buffer, valid until the next call on the same workspace) and its row stride.
+    The fused form of ``engine.recommend_fused`` reads its ids back with its status word, so it is taken only
+    with ``host_ok`` and then returns (the numpy array, k); without it the catalogue is decoded strip by strip.
+    ``ws`` is the workspace of the scores and candidates (None: the Recoder's own ``_eval_ws``), ``inputs`` an
+    earlier ``(blk, B, n_items, dcsr)`` of ``_input_block`` for these users (None: collated now)."""
     self.model.eval()
     self._check_ranges()
     k = int(num_recommendations)
@@ -1655,9 +1758,15 @@ class Recoder(object):
     engine = self._engine()
     csr_model = self._scores_from_csr_rows()
     if (getattr(engine, "generic", False) and not csr_model) or k > lib.rk_topk_max_k():
-      return self._recommend_dense(users_interactions, k)
-    blk, B, n_items = self._input_block(users_interactions)
-    ws = self._eval_ws
+      return self._recommend_dense_device(users_interactions, k), k
+    if inputs is None:
+      blk, B, n_items = self._input_block(users_interactions, ws)
+      if ws is None:
+        ws = self._eval_ws
+      dcsr = ws["dcsr"]
+    else:
+      blk, B, n_items, dcsr = inputs
+      assert ws is not None and ws["n_items"] == n_items
     z = None if csr_model else engine.encode_eval(blk, 0, B)
     strip = max(k, min(n_items, int(self.eval_strip_items)))
     bounds = [(lo, min(n_items, lo + strip)) for lo in range(0, n_items, strip)]
@@ -1665,7 +1774,7 @@ class Recoder(object):
       lo0 = bounds[-2][0]                                         # merge it into the one before
       bounds = bounds[:-2] + [(lo0, n_items)]
     ns = len(bounds)
-    if ns > 1 and not csr_model and os.environ.get("RK_EVAL_FUSED", "1") != "0" and \
+    if host_ok and ns > 1 and not csr_model and os.environ.get("RK_EVAL_FUSED", "1") != "0" and \
         hasattr(engine, "recommend_fused"):
       # catalogues of more than one strip: the top-k filter rides in the decode's epilogue (no score
       # matrix, no passes over it): a strided sample of the catalogue bounds every row's k-th best
@@ -1677,7 +1786,7 @@ class Recoder(object):
         host = torch.cat([out.reshape(-1), status.to(torch.int64)]).cpu().numpy()
         if host[-1] == 0:
           self.eval_fused_batches = getattr(self, "eval_fused_batches", 0) + 1
-          return host[:-1].reshape(B, k).copy()
+          return host[:-1].reshape(B, k).copy(), k
         # (a candidate list overflowed, or a row has fewer than k unseen items: strip by strip)
     width = max(hi - lo for lo, hi in bounds)
     ld = -(-width // 32) * 32
@@ -1691,7 +1800,7 @@ class Recoder(object):
     for s, (lo, hi) in enumerate(bounds):
       if csr_model:
         # an item-item model's strip of scores: the users' CSR rows times W[:, lo:hi]
-        self.model.csr_scores(ws["dcsr"], lo, hi, scores, ld, B)
+        self.model.csr_scores(dcsr, lo, hi, scores, ld, B)
         _lib.check(lib.rk_topk_masked(scores.data_ptr(), B, hi - lo, ld, blk.ref, 0, k, lo, 1,
                                       cand_idx[:, s * k:].data_ptr(), cand_val[:, s * k:].data_ptr(),
                                       ns * k, current_stream()), "rk_topk_masked")
@@ -1710,26 +1819,30 @@ class Recoder(object):
                                           cand_idx[:, s * k:].data_ptr(), cand_val[:, s * k:].data_ptr(),
                                           ns * k, current_stream()), "rk_topk_masked")
     if ns == 1:
-      return cand_idx[:, :k].cpu().numpy().copy()
+      return cand_idx[:, :k], ns * k
     # merge: top k of the ns * k candidates (positions), then their item ids.  Candidates are laid
     # out strip by strip, each sorted by (score desc, id asc): equal scores keep ascending ids
     pos = torch.empty(B, k, dtype=torch.int64, device=self.device)
     _lib.check(lib.rk_topk_masked(cand_val.data_ptr(), B, ns * k, ns * k, None, 0, k, 0, 1, pos.data_ptr(),
                                   None, k, current_stream()), "rk_topk_masked")
-    return torch.gather(cand_idx, 1, pos).cpu().numpy()
+    return torch.gather(cand_idx, 1, pos), k
 
   def _recommend_dense(self, users_interactions, k):
     """Full score matrix + torch.topk: the generic (torch-autograd) engine and k above the
     top-k kernel's limit."""
+    return self._recommend_dense_device(users_interactions, k).cpu().numpy()
+
+  def _recommend_dense_device(self, users_interactions, k):
     out, dense = self.predict(users_interactions, return_input=True)
     out = out.clone()
     out[dense > 0] = -float("inf")
-    return torch.topk(out, k, dim=1, sorted=True)[1].cpu().numpy()
+    return torch.topk(out, k, dim=1, sorted=True)[1]
 
-  def evaluate(self, eval_dataset, num_recommendations, metrics, batch_size=1, num_users=None):
-    """model.py:546-559."""
+  def evaluate(self, eval_dataset, num_recommendations, metrics, batch_size=1, num_users=None, on_device=False):
+    """model.py:546-559.  ``on_device=True``: the top-k lists stay on the device and the three built-in metrics are
+    computed there (``metrics.RecommenderEvaluator.evaluate``); the same values, user-defined metrics fall back."""
     results = self._evaluate(eval_dataset, num_recommendations, metrics, batch_size=batch_size,
-                             num_users=num_users)
+                             num_users=num_users, on_device=on_device)
     for metric in results:
       log.info("{}: {}".format(metric, np.mean(results[metric])))
     return results

@@ -168,3 +168,8 @@ class InferenceRecommender(Recommender):
   def recommend_array(self, users_hist):
     """The same lists as one [users, k] integer array (metrics.RecommenderEvaluator's fast path)."""
     return self.model.recommend_array(users_hist, self.num_recommendations)
+
+  def recommend_device(self, users_hist):
+    """The same lists left on the device: (int64 tensor [users, k], its row stride), what
+    ``RecommenderEvaluator.evaluate(on_device=True)`` hands to rk_als_rank_metrics."""
+    return self.model._recommend_device(users_hist, self.num_recommendations)

@@ -171,8 +171,8 @@ def step(X, Y, graph, state, ws, seed, step_index, lr, reg, cl_weight, cl_eps, c
 
 # ---------------------------------------------------------------------- fit
 def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, cl_weight, cl_eps, cl_temperature,
-        seed=0, state=None, first_step=None):
+        seed=0, state=None, first_step=None, monitor=None):
   """``lightgcn.method_fit`` of SimGCL.  Returns (state, one (mean BPR loss per valid triple, mean NCE_users +
   NCE_items per step) pair per epoch)."""
   return lightgcn.method_fit(METHOD, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg,
-                             (cl_weight, cl_eps, cl_temperature), seed, state, first_step)
+                             (cl_weight, cl_eps, cl_temperature), seed, state, first_step, monitor)

@@ -222,12 +222,14 @@ def normalize_rows(table):
 
 
 def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, temperature, num_negatives,
-        similarity="cosine", logq_weight=0.0, normalize=False, seed=0, state=None, first_step=None):
+        similarity="cosine", logq_weight=0.0, normalize=False, seed=0, state=None, first_step=None, monitor=None):
   """``lightgcn.method_fit`` of the sampled softmax; with ``normalize`` the model's tables X, Y are left
-  row-normalised (the state's base tables are not touched).  Returns (state, one (loss, probability of the
+  row-normalised (the state's base tables are not touched), and a ``monitor`` scores them row-normalised too: what
+  a fit ending at that epoch would leave.  Returns (state, one (loss, probability of the
   positive) pair of per-step means per epoch)."""
   state, hist = lightgcn.method_fit(METHOD, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg,
-                                    (temperature, num_negatives, similarity, logq_weight), seed, state, first_step)
+                                    (temperature, num_negatives, similarity, logq_weight), seed, state, first_step,
+                                    monitor, normalize_rows if normalize else None)
   if normalize:
     normalize_rows(X), normalize_rows(Y)
   return state, hist

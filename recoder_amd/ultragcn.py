@@ -334,11 +334,11 @@ def step(X, Y, graph, state, ws, seed, step_index, lr, reg, num_negatives, negat
 
 # ---------------------------------------------------------------------- fit
 def fit(X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_size, lr, reg, num_negatives, negative_weight, neighbours,
-        item_weight, w, seed=0, state=None, first_step=None):
+        item_weight, w, seed=0, state=None, first_step=None, monitor=None):
   """``lightgcn.method_fit`` of UltraGCN (``num_layers`` is 0).  Returns (state, one (positive, negatives,
   neighbours) triple of means per valid slot per epoch)."""
   if num_layers != 0:
     raise ValueError("train_ultragcn propagates nothing: num_layers is 0 (got %r)" % (num_layers,))
   return lightgcn.method_fit(METHOD, X, Y, bias, ucsr, icsr, 0, num_epochs, batch_size, lr, reg,
                              (num_negatives, negative_weight, neighbours, item_weight, check_weights(w)), seed, state,
-                             first_step)
+                             first_step, monitor)

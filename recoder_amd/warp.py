@@ -76,23 +76,23 @@ def workspace_bytes(T, h):
   return base if base < 0 else base + 3 * _round256(4 * int(T))
 
 
-def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True):
+def required_bytes(n_users, n_items, h, nnz, T, allocate_model=True, snapshot=False):
   """``bpr.required_bytes`` with this workspace, the weight table and the epoch's three device counters."""
-  return (bpr.required_bytes(n_users, n_items, h, nnz, T, allocate_model) - bpr.workspace_bytes(T, h)
+  return (bpr.required_bytes(n_users, n_items, h, nnz, T, allocate_model, snapshot) - bpr.workspace_bytes(T, h)
           + workspace_bytes(T, h) + 4 * (MAX_DRAWS + 1) + 3 * 8)
 
 
-def check_memory(n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True):
+def check_memory(n_users, n_items, h, nnz, T, free_bytes=None, allocate_model=True, snapshot=False):
   """``bpr.check_memory`` for the bytes of a WARP fit."""
   n_users, n_items, h, nnz, T = int(n_users), int(n_items), int(h), int(nnz), int(T)
   if workspace_bytes(T, h) < 0:
     raise ValueError("WARP needs 1 <= batch_size <= %d and 1 <= h <= %d (got %d, %d)" % (MAX_BATCH, MAX_H, T, h))
-  whole = required_bytes(n_users, n_items, h, nnz, T, True)
+  whole = required_bytes(n_users, n_items, h, nnz, T, True, snapshot)
   if whole > DEVICE_HBM_BYTES:
     raise ValueError("WARP over %d users x %d items at h = %d with %d entries and batches of %d needs %d bytes: "
                      "more than one device's memory (%d bytes); multi-device fits are not implemented"
                      % (n_users, n_items, h, nnz, T, whole, DEVICE_HBM_BYTES))
-  need = required_bytes(n_users, n_items, h, nnz, T, allocate_model)
+  need = required_bytes(n_users, n_items, h, nnz, T, allocate_model, snapshot)
   if free_bytes is None:
     free_bytes = torch.cuda.mem_get_info()[0]
   if need > free_bytes:
@@ -168,19 +168,20 @@ def step(X, Y, bias, ucsr, ws, weight, seed, step_index, lr, reg, margin, max_dr
 
 # ---------------------------------------------------------------------- fit
 def fit(X, Y, bias, ucsr, num_epochs, batch_size, lr, reg, margin=1.0, max_draws=32, rank_weight="log", seed=0,
-        first_step=0):
+        first_step=0, monitor=None):
   """num_epochs epochs of ceil(nnz / batch_size) WARP steps on the tables X [users, h], Y [items, h] and bias
   [items] (in place, f32, row-major); step s of the fit draws as step ``first_step + s``.  Returns (history,
   stats): the mean loss per valid slot of each epoch (nan for an epoch without one), and per epoch (the share
   of slots that found a violator, the mean trials of those that did).  One host synchronisation per epoch, to
-  read that epoch's sums."""
+  read that epoch's sums.  ``monitor``: as in ``bpr.fit``; the history and the stats keep every epoch that ran."""
   steps = check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size)
-  check_memory(X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False)
+  check_memory(X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False,
+               snapshot=monitor is not None and monitor.restore_best)
   ws = Workspace(int(batch_size), X.shape[1], X.device)
   weight = torch.as_tensor(weight_table(Y.shape[0], rank_weight), device=X.device)
   hist, stats = [], []
   s = int(first_step)
-  for _ in range(num_epochs):
+  for e in range(num_epochs):
     total = torch.zeros((), dtype=torch.float64, device=X.device)
     count = torch.zeros((), dtype=torch.int64, device=X.device)
     drawn = torch.zeros((), dtype=torch.int64, device=X.device)
@@ -193,4 +194,8 @@ def fit(X, Y, bias, ucsr, num_epochs, batch_size, lr, reg, margin=1.0, max_draws
     total, count, drawn = torch.stack([total, count.double(), drawn.double()]).cpu().tolist()   # (the synchronisation)
     hist.append(total / count if count else float("nan"))
     stats.append((count / (steps * int(batch_size)), drawn / count if count else float("nan")))
+    if monitor is not None and monitor.due(e) and monitor.epoch_end(e, (X, Y, bias)):
+      break
+  if monitor is not None:
+    monitor.finish((X, Y, bias), len(hist))
   return hist, stats

@@ -6,7 +6,16 @@ path (RK_EVAL_FUSED=0: decode a 65 536-item strip -> scores -> radix-select top-
     python tools/eval_bench.py [n_items] [h] [k]
 
 Synthetic: 20 000 users x n_items uniform, 100 interactions per user; random-init weights (scores of
-an untrained model: a harder case for the sample bound than a trained one, whose scores are peaked)."""
+an untrained model: a harder case for the sample bound than a trained one, whose scores are peaked).
+
+    python tools/eval_bench.py --metrics [--data slice|c2] [--out profiles/eval_bench.jsonl]
+
+The metric arithmetic on the host (recommend_array + metrics.batch_metrics) against the device path
+(_recommend_device + rk_als_rank_metrics, recoder_amd/validation.py) for a MatrixFactorization (h = 64) after one
+train_bpr epoch, on the ML-20M slice and the C2-shaped synthetic matrix (a fifth of every row held out as targets):
+the metric step alone at B = 500 and over the whole user set for K in {20, 100}, the whole evaluation both ways, and
+a train_bpr epoch with and without validation.  Every figure is the minimum of 5 timed loops after a warm-up, the
+largest beside it; one JSON line per measurement."""
 import os
 import sys
 import time
@@ -69,5 +78,88 @@ def main():
           (mode, dt, 4000 / dt, {str(m): float(np.mean(v)) for m, v in r.items()}))
 
 
+def _min_max_ms(fn, reps=5):
+  """(min, max) wall-clock ms of ``reps`` calls of ``fn`` after a warm one, the device drained before each stop."""
+  fn()
+  torch.cuda.synchronize()
+  got = []
+  for _ in range(reps):
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    got.append((time.perf_counter() - t0) * 1e3)
+  return round(min(got), 3), round(max(got), 3)
+
+
+def _split(x, seed=0, hold=0.2):
+  """(input, target): a share ``hold`` of the stored entries held out, drawn per entry."""
+  import scipy.sparse as sp
+  x = sp.csr_matrix(x)
+  keep = np.random.RandomState(seed).rand(x.nnz) >= hold
+  coo = x.tocoo()
+  mk = lambda m: sp.csr_matrix((np.ones(int(m.sum()), np.float32), (coo.row[m], coo.col[m])), shape=x.shape)
+  return mk(keep), mk(~keep)
+
+
+def metrics_main(argv):
+  import argparse
+  from recoder_amd import metrics as M, validation
+  from recoder_amd.nn import MatrixFactorization
+  import bench_util
+  ap = argparse.ArgumentParser()
+  ap.add_argument("--metrics", action="store_true")
+  ap.add_argument("--data", default="slice,c2")
+  ap.add_argument("--out", default=None)
+  args = ap.parse_args(argv)
+  for name in args.data.split(","):
+    x, y = bench_util.load(name)
+    if y is None:
+      x, y = _split(x)
+    n_users, n_items = x.shape
+    train_ds, val_ds = RecommendationDataset(x), RecommendationDataset(x, y)
+    rec = Recoder(model=MatrixFactorization(64), use_cuda=True, optimizer_type="adam", loss="mse")
+    rec.train_bpr(train_ds, num_epochs=1, batch_size=4096, seed=0)
+    base = dict(tool="eval_bench", data=name, users=n_users, items=n_items, nnz=int(x.nnz), targets=int(y.nnz), h=64)
+    for K in (20, 100):
+      ms = [M.Recall(K), M.NDCG(K), M.AveragePrecision(K)]
+      for B in (500, n_users):
+        # the metric step alone: lists of B users already where each path wants them
+        ids = np.concatenate([rec.recommend_array(UsersInteractions(np.arange(lo, min(B, lo + 500)),
+                                                                      x[lo:min(B, lo + 500)]), K)
+                              for lo in range(0, B, 500)])
+        tm = y[:B]
+        dev, tgt, tab = torch.as_tensor(ids, device="cuda"), M.DeviceTarget(tm, "cuda"), M.DeviceMetricTables(ms, "cuda")
+        out = M.device_batch_metrics(dev, K, tgt, ms, tab)
+        out = (out[0],) + out[1]
+        kernel = bench_util.loop_ms(lambda s: M.device_batch_metrics(dev, K, tgt, ms, tab, out), 20, reps=5)
+        host = _min_max_ms(lambda: M.batch_metrics(ids, tm, ms))
+        bench_util.emit(dict(base, what="metrics_only", B=B, K=K, metrics=3, kernel_ms_min_max=kernel,
+                             host_numpy_ms_min_max=host), args.out)
+      # the whole evaluation of one metric over every user, batches of 500: scoring + top-k + metric
+      metric = M.Recall(K)
+
+      def host_path():
+        total, count = 0.0, 0
+        for lo in range(0, n_users, 500):
+          rows = np.arange(lo, min(n_users, lo + 500))
+          r = M.batch_metrics(rec.recommend_array(UsersInteractions(rows, x[rows]), K), y[rows], [metric])[metric]
+          total, count = total + np.nansum(r), count + int(np.sum(~np.isnan(r)))
+        return total / count
+      val = validation.Validator(rec, val_ds, metric, batch_size=500)
+      agree = abs(host_path() - val.score())
+      bench_util.emit(dict(base, what="evaluation", K=K, batch=500, host_path_ms_min_max=_min_max_ms(host_path),
+                           device_path_ms_min_max=_min_max_ms(val.score), mean_abs_difference=agree), args.out)
+      del val
+    # a train_bpr epoch with and without validation (Recall@20 after the epoch; the validator's uploads included)
+    plain = _min_max_ms(lambda: rec.train_bpr(train_ds, num_epochs=1, batch_size=4096, seed=0))
+    watched = _min_max_ms(lambda: rec.train_bpr(train_ds, num_epochs=1, batch_size=4096, seed=0, val_dataset=val_ds,
+                                                restore_best=False))
+    bench_util.emit(dict(base, what="train_bpr_epoch", batch=4096, plain_ms_min_max=plain,
+                         with_validation_ms_min_max=watched), args.out)
+
+
 if __name__ == "__main__":
-  main()
+  if "--metrics" in sys.argv:
+    metrics_main(sys.argv[1:])
+  else:
+    main()
