@@ -96,6 +96,48 @@ int rk_slim_fit(const float *G, int64_t ldg, int32_t n_items, const float *inv_d
                 void *stream);
 
 /*
+ * fsSLIM (Ning & Karypis 2011, section 4.3): rk_slim_fit with column j's regression restricted to a candidate list,
+ * without the n x n Gram.  The matrix comes as both CSRs with the conventions of rk_rp3_item_fit: item-major
+ * t_* [n_items + 1] / [nnz] (the users of an item, ascending), user-major u_* [n_users + 1] / [nnz] (the items of a
+ * user, ascending), t_data / u_data the values in either entry order, both NULL: every value is 1.0.
+ *   cand_ids   int32 [n_items, M]  the candidates of column j, ascending, -1 past cand_count[j]
+ *   cand_count int32 [n_items]     how many (taken as 0 below 0 and as M above M)
+ * 1 <= M <= rk_rp3_max_neighbours() (1024).  inv_denom, l1, K, max_sweeps, tol, col_lo, col_hi and the five outputs
+ * are rk_slim_fit's; columns outside [col_lo, col_hi) are not touched.
+ *
+ * The local Gram of column j, with a_vi the value of user v for item i (f32; no atomics, no reductions):
+ *   L[c][c'] = sum over the users v of a_{v, cand c} * a_{v, cand c'}     q[c] = sum over v of a_{v, cand c} * a_{v, j}
+ * each entry one chain acc = fmaf(a_{v, cand c}, a_{v, other}, acc) from +0 over the users v of candidate c that hold
+ * the other item, in ascending v.  L is bitwise symmetric (the product commutes), L[c][c] is the G_kk of the sweep.
+ * A candidate whose q[c] is not > l1 (negative and NaN included), that is j itself or lies outside [0, n_items) is
+ * screened: its weight is +0 and it is never visited.  On the others runs rk_slim_fit's sweep, stop rule and cut,
+ * operation for operation (one device function serves both kernels), reading L[c][c'] where rk_slim_fit reads
+ * G[cand c][cand c'].  With every item that shares a user with j among the candidates, and a Gram whose entries are
+ * these chains, the result is rk_slim_fit's bit for bit.
+ *
+ * A workgroup of four waves solves a column; columns are handed to the resident workgroups through one counter in
+ * the workspace.  A column costs about  sum over its candidates c, over the users v of c, of r_v  (r_v the entries
+ * of user v) for L, then sweeps x candidates^2.  The candidate rows are handed to the four waves through a counter,
+ * so the long user list of a popular candidate holds one wave while the others take the remaining rows; one
+ * entry's chain is never split.  L lives in LDS for a column of up to rk_slim_sparse_lds_candidates()
+ * candidates, beyond that in the workgroup's slice of the workspace; a column's result depends neither on where L
+ * lives, nor on the column range, nor on the workgroup that took it.  ws must be 256-byte aligned and hold
+ * rk_slim_fit_sparse_workspace_bytes(M) bytes.  col_screened int32 [n_items], or NULL: how many candidates of the
+ * column passed the screen (what the sweep ran over), beside rk_slim_fit's five outputs.
+ */
+int rk_slim_sparse_lds_candidates(void);
+
+/* bytes of workspace rk_slim_fit_sparse needs for lists of M candidates (host arithmetic; > 0; < 0 on a bad M) */
+int64_t rk_slim_fit_sparse_workspace_bytes(int32_t M);
+
+int rk_slim_fit_sparse(const int64_t *t_indptr, const int32_t *t_indices, const float *t_data, const int64_t *u_indptr,
+                       const int32_t *u_indices, const float *u_data, int32_t n_users, int32_t n_items,
+                       const int32_t *cand_ids, const int32_t *cand_count, int32_t M, const float *inv_denom, float l1,
+                       int32_t K, int32_t max_sweeps, float tol, int32_t col_lo, int32_t col_hi, int32_t *nbr_ids,
+                       float *nbr_w, int32_t *nbr_count, int32_t *col_sweeps, int32_t *col_support,
+                       int32_t *col_screened, void *ws, int64_t ws_bytes, void *stream);
+
+/*
  * out[u][c] = sum over the kept entries (k, w) of column lo + c, ascending, of x_uk * w for those k that CSR
  * row u stores (looked up by binary search in the row's ascending indices), for u in [0, n_rows) and c in
  * [0, hi - lo); a column nobody reaches is +0.  data NULL: every value is 1.0.  0 <= lo < hi <= n_items.

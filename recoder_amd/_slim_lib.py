@@ -24,6 +24,10 @@ SIGNATURES = {
   "rk_slim_fit_workspace_bytes": (c_int64, [c_int32]),
   "rk_slim_fit": (c_int32, [_P, c_int64, c_int32, _P, c_float, c_int32, c_int32, c_float, c_int32, c_int32, _P, _P, _P,
                             _P, _P, _P, c_int64, _P]),
+  "rk_slim_sparse_lds_candidates": (c_int32, []),
+  "rk_slim_fit_sparse_workspace_bytes": (c_int64, [c_int32]),
+  "rk_slim_fit_sparse": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, c_int32, _P, c_float, c_int32,
+                                   c_int32, c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
   "rk_slim_scores": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P]),
 }
 

@@ -508,9 +508,11 @@ class Recoder(object):
     self._weights_written()
     return copy(getattr(self, keep))
 
-  def _neighbour_list_fit(self, mod, train_dataset, keep, check, k_at, log_line, store, check_values=False):
+  def _neighbour_list_fit(self, mod, train_dataset, keep, check, k_at, log_line, store, check_values=False,
+                          memory=lambda cfg: {}):
     """``_closed_form_fit`` for the three models stored as [n, K] neighbour lists, K = ``cfg[k_at]``: the same
-    memory checks, the same tensors to (re-)allocate and to hand to ``mod.fit(csrs, *cfg, out=...)``."""
+    memory checks (``memory(cfg)``: what else ``mod.check_memory`` is told), the same tensors to (re-)allocate and
+    to hand to ``mod.fit(csrs, *cfg, out=...)``."""
     def place(cfg, first, host):
       if first:
         self.model.neighbours = cfg[k_at]
@@ -518,9 +520,10 @@ class Recoder(object):
         self.model.allocate(cfg[k_at], self.device)
     return self._closed_form_fit(
         mod, train_dataset, keep, check, log_line, store=store, place=place, check_values=check_values,
-        hint_check=lambda c, u, n, host: n and mod.check_memory(u or 0, n, c[k_at], 0, free_bytes=float("inf")),
+        hint_check=lambda c, u, n, host: n and mod.check_memory(u or 0, n, c[k_at], 0, free_bytes=float("inf"),
+                                                                **memory(c)),
         size_check=lambda c, host: mod.check_memory(self.num_users, self.num_items, c[k_at], host().nnz,
-                                                    allocate_model=False),
+                                                    allocate_model=False, **memory(c)),
         fit=lambda m, pair, c: mod.fit(pair, *c, out=(m.item_neighbours, m.item_weights.data, m.neighbour_counts))[-1])
 
   def train_als(self, train_dataset, num_iterations=10, reg=100.0, cg_steps=3):
@@ -954,7 +957,8 @@ class Recoder(object):
                             c[1]),
         store=lambda c: {"shrink": c[1], "similarity": c[2], "feature_weighting": c[3]})
 
-  def train_slim(self, train_dataset, l1_reg=None, l2_reg=None, neighbours=None, max_sweeps=50, tol=1e-5):
+  def train_slim(self, train_dataset, l1_reg=None, l2_reg=None, neighbours=None, max_sweeps=50, tol=1e-5,
+                 candidates=None, candidate_similarity="cosine", candidate_shrink=0.0):
     """The SLIM fit of a SparseLinearModel (recoder_amd/slim.py): column j of W becomes the non-negative
     elastic-net regression of item j on the other items over the dataset's interaction matrix X (values as
     stored, all >= 0: ValueError otherwise), ``min over w >= 0, w_j = 0 of 1/2 |x_j - X w|^2 + l2_reg/2 |w|^2 +
@@ -962,19 +966,30 @@ class Recoder(object):
     weight by more than ``tol`` or after ``max_sweeps`` sweeps, and cut to its ``neighbours`` largest
     weights.  ``None`` takes the model's value; explicit values are stored back into the model, so that a
     checkpoint's ``model_params`` describe the weights it holds, and another ``neighbours`` re-allocates the
-    model's tensors.  The configured ``loss`` plays no part.  The n x n Gram has to fit the device
-    (EASE's limit; ValueError otherwise).  Builds a fresh optimizer of ``optimizer_type`` so that
+    model's tensors.  The configured ``loss`` plays no part.  With ``candidates`` None the n x n Gram has to fit
+    the device (EASE's limit; ValueError otherwise).  ``candidates`` = M (fsSLIM, section 4.3 of the paper)
+    regresses column j on the M items most similar to j only, by an ItemKNN fit with ``candidate_similarity`` and
+    ``candidate_shrink`` over the stored values: no n x n buffer exists, and the catalogue is limited by the
+    [n, M] lists.  The three are stored in the model (``candidates`` travels in ``model_params`` unless None).
+    Builds a fresh optimizer of ``optimizer_type`` so that
     ``save_state`` works.  Returns (and keeps in ``slim_info``) n, nnz, l1_reg, l2_reg, neighbours, kept
     (entries kept over all columns), cut_columns (columns whose support was larger than ``neighbours``),
     unconverged_columns (columns that ran all ``max_sweeps`` sweeps), max_sweeps_run, gram_ms and fit_ms
-    (HIP events)."""
+    (HIP events); with ``candidates`` also candidates, candidate_ms (the ItemKNN fit) and mean_candidates (the
+    mean number of a column's candidates that passed the l1 screen)."""
     from . import slim
     return self._neighbour_list_fit(
-        slim, train_dataset, "slim_info", k_at=2, check_values=True,         # c = (l1, l2, K, max_sweeps, tol)
+        slim, train_dataset, "slim_info", k_at=2, check_values=True,
+        # c = (l1, l2, K, max_sweeps, tol, candidates, candidate_similarity, candidate_shrink)
         check=lambda m: slim.check_config(m, _default(l1_reg, m, "l1_reg"), _default(l2_reg, m, "l2_reg"),
-                                          _default(neighbours, m, "neighbours"), max_sweeps, tol),
-        log_line=lambda c: ("SLIM: l1_reg %g, l2_reg %g, %d neighbours, at most %d sweeps, tol %g",) + c,
-        store=lambda c: {"l1_reg": c[0], "l2_reg": c[1]})
+                                          _default(neighbours, m, "neighbours"), max_sweeps, tol) +
+        slim.check_candidates(candidates, candidate_similarity, candidate_shrink),
+        log_line=lambda c: ("SLIM: l1_reg %g, l2_reg %g, %d neighbours, at most %d sweeps, tol %g",) + c[:5]
+        if c[5] is None else
+        ("SLIM: l1_reg %g, l2_reg %g, %d neighbours, at most %d sweeps, tol %g, %d candidates by %s, shrink %g",) + c,
+        store=lambda c: {"l1_reg": c[0], "l2_reg": c[1], "candidates": c[5], "candidate_similarity": c[6],
+                         "candidate_shrink": c[7]},
+        memory=lambda c: {"candidates": c[5]})
 
   def train_userknn(self, train_dataset, neighbours=None, shrink=None):
     """The "fit" of a UserNeighbourhoodModel (recoder_amd/userknn.py): the model takes the dataset's

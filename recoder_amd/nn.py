@@ -700,7 +700,9 @@ class SparseLinearModel(_ColumnListModel):
   Three tensors, all in ``state_dict()``, laid out as ``RandomWalkItemModel``'s but per COLUMN of W:
   ``item_neighbours`` int32 [num_items, neighbours] (the kept k of column j, ascending, -1 where a column
   has fewer), ``item_weights`` f32 of the same shape (``W[k, j]``) and ``neighbour_counts`` int32
-  [num_items]; empty until fitted.  ``l1_reg``, ``l2_reg`` and ``neighbours`` travel in ``model_params()``.
+  [num_items]; empty until fitted.  ``l1_reg``, ``l2_reg`` and ``neighbours`` travel in ``model_params()``, and
+  so do ``candidates``, ``candidate_similarity`` and ``candidate_shrink`` after an fsSLIM fit
+  (``train_slim(candidates=M)``; ``candidates`` is None otherwise and then none of the three is listed).
   ``Recoder.train`` refuses this model and points at ``train_slim``.
   """
   fit_module = "slim"
@@ -712,21 +714,32 @@ class SparseLinearModel(_ColumnListModel):
     self.l1_reg = l1_reg
     self.l2_reg = l2_reg
     self.neighbours = neighbours
+    # (what the last ``train_slim`` restricted the columns to: None, or fsSLIM's candidate lists)
+    self.candidates, self.candidate_similarity, self.candidate_shrink = None, "cosine", 0.0
     self.num_items = None
     self.item_weights = None
     self._validate()
 
   def _validate(self):
-    from .slim import check_params
+    from .slim import check_candidates, check_params
     self.l1_reg, self.l2_reg, self.neighbours = check_params(self.l1_reg, self.l2_reg, self.neighbours)[:3]
+    self.candidates, self.candidate_similarity, self.candidate_shrink = check_candidates(
+        self.candidates, self.candidate_similarity, self.candidate_shrink)
 
   def model_params(self):
-    return {"l1_reg": float(self.l1_reg), "l2_reg": float(self.l2_reg), "neighbours": int(self.neighbours)}
+    params = {"l1_reg": float(self.l1_reg), "l2_reg": float(self.l2_reg), "neighbours": int(self.neighbours)}
+    if self.candidates is not None:
+      params.update(candidates=int(self.candidates), candidate_similarity=self.candidate_similarity,
+                    candidate_shrink=float(self.candidate_shrink))
+    return params
 
   def load_model_params(self, model_params):
     self.l1_reg = float(model_params["l1_reg"])
     self.l2_reg = float(model_params["l2_reg"])
     self.neighbours = int(model_params["neighbours"])
+    self.candidates = model_params.get("candidates")
+    self.candidate_similarity = model_params.get("candidate_similarity", "cosine")
+    self.candidate_shrink = model_params.get("candidate_shrink", 0.0)
     self._validate()
 
 

@@ -2,6 +2,11 @@
 """SLIM fit and serving times (recoder_amd/slim.py, include/recoder_slim.h), one JSON line per run:
 
     python tools/slim_bench.py [--data slice|c2] [--quality] [--no-torch] [--no-rp3] [--out FILE]
+    python tools/slim_bench.py --cpu-grid [--jobs N]        (no GPU) fsSLIM's quality grid on the slice by the float64
+          restatement of tests/fsslim_util.py, into profiles/fsslim_quality.jsonl and tests/golden/fsslim_slice.json
+    python tools/slim_bench.py --candidates [--data slice|c2|large]   fsSLIM's fit times at M = 100 and 200 beside the
+          dense-Gram fit, into profiles/fsslim_bench.jsonl; large = synthetic.uniform(100 000, 1 000 000, 100), which
+          the dense path refuses
 
   hip     ms of the Gram (rk_ease_gram) and of rk_slim_fit (HIP events, second of two fits), the coordinate
           updates of the fit (sum over the columns of sweeps x candidates) and updates per second; users/s
@@ -164,14 +169,124 @@ def quality(x, y, out):
   out["popularity_recall@20"] = float(np.mean(vals))
 
 
+# ------------------------------------------------------------ fsSLIM: the CPU cells
+FS_GOLDEN = os.path.join(ROOT, "tests", "golden", "fsslim_slice.json")
+FS_DENSE = dict(recall20=0.1301, ndcg100=0.1142)       # unrestricted SLIM at the same (l1, l2, K) on the slice
+# (M, shrink, precision): cosine candidates; the f32 cell is the one the GPU test is held against
+FS_CELLS = [(50, 0.0, "f64"), (100, 0.0, "f64"), (200, 0.0, "f64"), (400, 0.0, "f64"), (100, 300.0, "f64"),
+            (100, 0.0, "f32")]
+
+
+def fs_cell(cell):
+  """One cell of the fsSLIM grid on the slice by the restatement of tests/fsslim_util.py at SLIM's defaults: the
+  model cut to K, Recall@20 / NDCG@100 and the density.  float64: weights and scores in float64; f32: the kernels'
+  chains (``cd_f32`` and the ascending f32 chain of rk_slim_scores)."""
+  from tests import fsslim_util as fu, gfcf_util as gu, itemknn_util
+  M, shrink, prec = cell
+  x, y = load("slice")
+  x64 = sp.csr_matrix(x).astype(np.float64)
+  G = (x64.T @ x64).tocsr()
+  n = x.shape[1]
+  t0 = time.perf_counter()
+  cand, cnt = fu.select(x, M, "cosine", shrink)
+  passed = fu.screened(G, cand, cnt, L1)
+  if prec == "f64":
+    W, run = fu.cd_f64(G, cand, cnt, L1, L2, MAX_SWEEPS, TOL, K=NEIGHBOURS)
+    kept = int(W.nnz)
+    S = np.asarray((x64 @ W).todense())
+  else:
+    d = G.diagonal() + L2
+    inv = np.where(d > 0, 1.0 / np.where(d > 0, d, 1.0), 0.0).astype(np.float32)
+    ids, w, count, run, _ = fu.cd_f32(G, inv, cand, cnt, L1, NEIGHBOURS, MAX_SWEEPS, TOL)
+    kept = int(count.sum())
+    S = itemknn_util.scores_binary_f32(x, ids, w, count)
+  r20, n100 = gu.quality(x, y, S=S)
+  return [dict(bench="fsslim_quality", data="slice", precision=prec, candidates=M, candidate_similarity="cosine",
+               candidate_shrink=shrink, l1_reg=L1, l2_reg=L2, neighbours=NEIGHBOURS, max_sweeps=MAX_SWEEPS, tol=TOL,
+               recall20=r20, ndcg100=n100, density=kept / (n * n), kept=kept,
+               mean_candidates=float(passed.mean()), max_sweeps_run=int(run.max()),
+               dense_recall20=FS_DENSE["recall20"], dense_ndcg100=FS_DENSE["ndcg100"],
+               seconds=round(time.perf_counter() - t0, 1))]
+
+
+def fs_cpu_grid(out, jobs):
+  import json
+  import multiprocessing as mp
+  with mp.get_context("spawn").Pool(min(jobs, len(FS_CELLS))) as pool:
+    recs = [r for rs in pool.map(fs_cell, FS_CELLS) for r in rs]
+  for r in recs:
+    emit(r, out)
+  at = {(r["candidates"], r["candidate_shrink"], r["precision"]): r for r in recs}
+  f32, f64 = at[100, 0.0, "f32"], at[100, 0.0, "f64"]
+  keys = ("candidates", "candidate_similarity", "candidate_shrink", "l1_reg", "l2_reg", "neighbours", "max_sweeps",
+          "tol")
+  golden = dict(params={k: f32[k] for k in keys},
+                f32=dict(recall20=f32["recall20"], ndcg100=f32["ndcg100"], density=f32["density"],
+                         mean_candidates=f32["mean_candidates"]),
+                f64=dict(recall20=f64["recall20"], ndcg100=f64["ndcg100"], density=f64["density"]),
+                recall20_f32_minus_f64=f32["recall20"] - f64["recall20"])
+  with open(FS_GOLDEN, "w") as f:
+    json.dump(golden, f, indent=1, sort_keys=True)
+    f.write("\n")
+
+
+# -------------------------------------------------------------- fsSLIM: the times
+FS_LARGE = (100_000, 1_000_000, 100)     # synthetic.uniform(users, items, degree): a catalogue the dense path refuses
+
+
+def fs_times(names, out, loops=5):
+  """Per data set and M in (100, 200): the smallest of ``loops`` timed ``train_slim`` calls after a warm one (wall
+  ms of the whole call, the ItemKNN candidate ms and the Gram-build + sweep ms of that call) with the largest
+  beside it, and the dense-Gram ``train_slim`` on the slice."""
+  from recoder_amd import slim, synthetic
+  from recoder_amd.data import RecommendationDataset
+  from recoder_amd.model import Recoder
+  from recoder_amd.nn import SparseLinearModel
+
+  def timed(ds, **kw):
+    rec = Recoder(model=SparseLinearModel(L1, L2, NEIGHBOURS))
+    rec.train_slim(ds, max_sweeps=MAX_SWEEPS, tol=TOL, **kw)
+    rows = []
+    for _ in range(loops):
+      torch.cuda.synchronize()
+      t0 = time.perf_counter()
+      info = rec.train_slim(ds, max_sweeps=MAX_SWEEPS, tol=TOL, **kw)
+      rows.append((time.perf_counter() - t0) * 1e3)
+    best = int(np.argmin(rows))
+    return dict(call_ms=rows[best], call_ms_max=max(rows), fit_ms=info["fit_ms"], gram_ms=info["gram_ms"],
+                candidate_ms=info.get("candidate_ms"), mean_candidates=info.get("mean_candidates"), kept=info["kept"])
+
+  for name in names:
+    x = sp.csr_matrix(synthetic.uniform(*FS_LARGE)) if name == "large" else load(name)[0]
+    ds = RecommendationDataset(x)
+    base = dict(bench="fsslim", data=name, users=int(x.shape[0]), n=int(x.shape[1]), nnz=int(x.nnz), loops=loops,
+                device=torch.cuda.get_device_name(0))
+    # (the dense fit beside it where it ends in reasonable time: on c2 nearly every pair of the 20 108 items is a
+    # candidate at l1 = 1, sweeps x candidates^2 per column; the large catalogue's Gram is refused outright)
+    if name == "slice":
+      emit(dict(base, candidates=None, **timed(ds)), out)
+    for M in ((100,) if name == "large" else (100, 200)):
+      emit(dict(base, candidates=M, **timed(ds, candidates=M)), out)
+    torch.cuda.empty_cache()
+
+
 def main():
   ap = argparse.ArgumentParser()
-  ap.add_argument("--data", choices=["c2", "slice"], action="append")
+  ap.add_argument("--data", choices=["c2", "slice", "large"], action="append")
   ap.add_argument("--quality", action="store_true")
   ap.add_argument("--no-torch", action="store_true")
   ap.add_argument("--no-rp3", action="store_true")
-  ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "slim_bench.jsonl"))
+  ap.add_argument("--cpu-grid", action="store_true", help="fsSLIM's float64 grid on the slice (no GPU)")
+  ap.add_argument("--candidates", action="store_true", help="fsSLIM's fit times beside the dense-Gram fit")
+  ap.add_argument("--jobs", type=int, default=6)
+  ap.add_argument("--out", default=None)
   args = ap.parse_args()
+  if args.cpu_grid:
+    return fs_cpu_grid(args.out or os.path.join(ROOT, "profiles", "fsslim_quality.jsonl"), args.jobs)
+  if args.candidates:
+    return fs_times(args.data or ["slice", "c2", "large"],
+                    args.out or os.path.join(ROOT, "profiles", "fsslim_bench.jsonl"))
+  args.out = args.out or os.path.join(ROOT, "profiles", "slim_bench.jsonl")
   for name in (args.data or ["slice"]):
     x, y = load(name)
     out = dict(bench="slim", data=name, users=int(x.shape[0]), device=torch.cuda.get_device_name(0))
