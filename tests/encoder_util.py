@@ -1,6 +1,7 @@
-"""Plain restatements for tests/test_encoder_fwd.py and tests/test_row_kernels.py: the counter-RNG keep
-draw of csrc/common.h in numpy uint64, the encoder forward of csrc/encoder.hip in float64, and the
-exact-length CSR the encoder tests collate.  Nothing here touches the GPU."""
+"""Plain restatements for tests/test_encoder_fwd.py, tests/test_encoder_bwd.py and tests/test_row_kernels.py: the
+counter-RNG keep draw of csrc/common.h in numpy uint64, the encoder forward and backward of csrc/encoder.hip in
+float64, the backward's host dispatch, and the hand-made CSRs the encoder tests collate.  Nothing here touches the
+GPU."""
 import numpy as np
 import scipy.sparse as sp
 
@@ -114,6 +115,73 @@ def csr_with_row_lengths(lengths, users, n_users, n_items, seed, ratings=False):
   m = sp.csr_matrix((vals, (rows, cols)), shape=(n_users, n_items))
   m.sort_indices()
   return m
+
+
+def csr_with_column_rows(n_rows, n_items, col_rows, seed=0, ratings=False):
+  """A [n_rows, n_items] CSR whose column `item` holds exactly the rows col_rows[item] (every other column is
+  empty); values 1.0, or random ratings in (0.5, 5]."""
+  rows = np.concatenate([np.asarray(r, dtype=np.int64) for r in col_rows.values()])
+  cols = np.concatenate([np.full(len(r), int(c), dtype=np.int64) for c, r in col_rows.items()])
+  rng = np.random.RandomState(seed)
+  vals = (0.5 + 4.5 * rng.rand(len(cols))).astype(np.float32) if ratings else np.ones(len(cols), np.float32)
+  m = sp.csr_matrix((vals, (rows, cols)), shape=(n_rows, n_items))
+  m.sort_indices()
+  assert m.nnz == len(cols), "a (row, column) pair was listed twice"
+  return m
+
+
+# ------------------------------------------------------------- float64 encoder backward
+def act_dy64(y, act):
+  """act'(x) written in the OUTPUT y = act(x), in float64: the formulas of rk_act_dy (csrc/common.h), which
+  rk_act_grad and the slab reduces apply."""
+  y = np.asarray(y, dtype=np.float64)
+  if act == ACT_TANH:
+    return 1.0 - y * y
+  if act == ACT_SIGMOID:
+    return (1.0 - y) * y
+  if act == ACT_RELU:
+    return np.where(y > 0, 1.0, 0.0)
+  if act == ACT_SELU:
+    return np.where(y > 0, SELU_S, y + SELU_S * SELU_A)
+  if act == ACT_ELU:
+    return np.where(y > 0, 1.0, y + 1.0)
+  return np.ones_like(y)
+
+
+def encode_bwd64(indptr, cols, s, dZ, row_off, B, n_b):
+  """(G, A, n, gb, gA) of rows [row_off, row_off + B) of a block in float64: G[c] = sum_r s[r, c] dZ[r - row_off],
+  A[c] = sum_r |s[r, c]| |dZ[r - row_off]| (the magnitude the rounding bound multiplies), n[c] = the column's stored
+  entries in the window (dropped ones included), gb = the column sums of dZ and gA those of |dZ|."""
+  indptr = np.asarray(indptr, dtype=np.int64)
+  lo, hi = int(indptr[row_off]), int(indptr[row_off + B])
+  ip = indptr[row_off:row_off + B + 1] - lo
+  c = np.asarray(cols[lo:hi], dtype=np.int64)
+  sv = np.asarray(s[lo:hi], dtype=np.float64)
+  dz = np.asarray(dZ, dtype=np.float64)
+  S = sp.csr_matrix((sv, c, ip), shape=(B, n_b))
+  G = np.asarray(S.T.dot(dz))
+  A = np.asarray(abs(S).T.dot(np.abs(dz)))
+  n = np.bincount(c, minlength=n_b).astype(np.int64)
+  return G, A, n, dz.sum(0), np.abs(dz).sum(0)
+
+
+BWD_WINDOW = 4064         # rows per window of the window recursion (127 bitmap words)
+
+
+def bwd_route(blk, row_off, B, h):
+  """(route, HV, light): the kernel rk_ae_encode_bwd (csrc/encoder.hip) launches for rows [row_off, row_off + B)
+  of a block (anything with n_cap and nnz_cap), restated from the host entry's conditions.  route is "cols1" /
+  "cols2" (a wave per column, one / two bitmap words per lane), "windows" (the recursion over windows of
+  BWD_WINDOW rows) or "wg" (a workgroup per column); light only selects a kernel on the cols routes."""
+  hv = -(-h // 256)
+  HV = 1 if hv == 1 else 2 if hv == 2 else 4
+  words = ((row_off + B + 31) >> 5) - (row_off >> 5)
+  light = blk.n_cap >= 4096 and blk.nnz_cap <= 2 * blk.n_cap
+  if words <= 64:
+    return "cols1", HV, light
+  if blk.n_cap >= 4096:
+    return ("cols2" if words <= 128 else "windows"), HV, light
+  return "wg", HV, False
 
 
 def ulp_distance(got, ref64):

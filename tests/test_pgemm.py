@@ -306,6 +306,63 @@ def _fdec_case(B, h, n_items, loss, ratings):
         assert torch.equal(out.view(ns, blk.n_cap, h)[:live, :n_b], slabs.view(ns, blk.n_cap, h)[:live, :n_b])
 
 
+@pytest.mark.parametrize("B,h,n_items,row_off", [(130, 64, 900, 0), (37, 20, 400, 0), (300, 260, 2000, 0),
+                                                 (200, 128, 1500, 56), (130, 600, 900, 0)])
+def test_pg_dw_and_encoder_backward_in_one_launch_equal_the_two_launches(B, h, n_items, row_off):
+  """rk_pg_dw_encode_bwd (pgemm.hip dw_encbwd_kernel: dW tiles || image column sums || encoder-backward columns)
+  against rk_pg_dw + rk_ae_encode_bwd: the same workgroup bodies, so the K slabs of dW, their count, the decoder bias
+  gradient, G_en and the encoder-bias gradient agree bit for bit (tests/test_encoder_bwd.py pins rk_ae_encode_bwd to
+  float64: this equality carries the pin over to the fused launch, h = 600 on its HV = 4 instantiation)."""
+  S = B + row_off
+  lib, blk, W, bias, Z, ranges, pl, buf = _setup(S, h, max(S, 600), n_items, 14, seed=B + h + 2)
+  if lib.rk_dw_encode_bwd_fused_ok(row_off, B) != 1:
+    pytest.skip("the fused dW || encoder-backward launch is switched off")
+  st = current_stream()
+  dev = Z.device
+  f = dict(dtype=torch.float32, device=dev)
+  n_b, nnz, ld, _ = blk.counts_host()
+  Zb = Z[:B].contiguous()
+  check(lib.rk_split_wz(ptr(W), ptr(Zb), B, h, blk.ref, ptr(ranges), ctypes.byref(pl), None, st))
+  rows_img = -(-B // 32) * 32
+  img = torch.full(((rows_img + 256) * blk.ld_cap * 2,), 0x7e00, dtype=torch.int16, device=dev)
+  sc = torch.full((lib.rk_pg_scale_floats(B, blk.n_cap),), float("nan"), **f)
+  dO = torch.zeros(B * blk.ld_cap, **f)
+  part = torch.zeros(lib.rk_loss_partials(B, blk.n_cap), **f)
+  check(lib.rk_pg_decode_loss(ctypes.byref(pl), B, blk.ref, row_off, ptr(bias), LOSS_MSE, 0.5, 1.0 / B, ptr(img),
+                              rows_img, ptr(sc), ptr(dO), ptr(part), None, st))
+  gr, gc = ctypes.c_int32(), ctypes.c_int32()
+  lib.rk_pg_decode_granule(B, blk.n_cap, ctypes.byref(gr), ctypes.byref(gc))
+  gr, gc = gr.value, gc.value
+  g = torch.Generator(device=dev)
+  g.manual_seed(B)
+  dZ0 = torch.randn(B, h, generator=g, **f) * 1e-2
+  blk.svals[:nnz].copy_(torch.rand(nnz, generator=g, **f))       # (what the encoder forward leaves: any values do)
+  ns = lib.rk_pg_dw_splits(B, h, blk.n_cap)
+
+  def run(fused):
+    slabs = torch.full((lib.rk_pg_dw_workspace_bytes(B, h, blk.n_cap) // 4,), float("nan"), **f)
+    G_en = torch.full((blk.n_cap * h,), 3.0, **f)
+    gb = torch.full((h * 8,), 3.0, **f)
+    gb_de = torch.full((blk.n_cap,), 7.0, **f)
+    blk.counts[4:5].zero_()
+    if fused:
+      check(lib.rk_pg_dw_encode_bwd(ptr(img), ptr(sc), gr, gc, B, ctypes.byref(pl), blk.ref, ptr(slabs), row_off,
+                                    ptr(dZ0), ptr(G_en), ptr(gb), ptr(gb_de), st))
+    else:
+      check(lib.rk_pg_dw(ptr(img), ptr(sc), gr, gc, B, ctypes.byref(pl), blk.ref, ptr(slabs), ptr(gb_de), st))
+      check(lib.rk_ae_encode_bwd(blk.ref, row_off, B, ptr(dZ0), h, ptr(G_en), 0, ptr(gb), st))
+    torch.cuda.synchronize()
+    live = int(blk.counts[4].item())
+    return (live, slabs.view(ns, blk.n_cap, h)[:live, :n_b].clone(), G_en[:n_b * h].clone(), gb[:h].clone(),
+            gb_de[:n_b].clone(), G_en[n_b * h:].clone(), gb[h:].clone())
+  a, b = run(False), run(True)
+  assert a[0] == b[0] and 1 <= a[0] <= ns
+  for x, y in zip(a[1:], b[1:]):
+    assert torch.equal(x, y)
+  assert float(a[1].abs().max()) > 0 and float(a[2].abs().max()) > 0 and bool(torch.isfinite(a[1]).all())
+  assert bool((b[5] == 3.0).all()) and bool((b[6] == 3.0).all())        # nothing past the live columns / past h
+
+
 def test_fdec_scale_table_has_no_write_past_the_capacity():
   """A granule half past the item capacity has no slot in the scale table: its write used to land in the next
   row's first column and won or lost a race against that granule's own scale (intermittent: 34 of 40 runs)."""

@@ -238,7 +238,7 @@ def test_device_csr_from_arrays_rejects_inconsistent_indptr():
 
 
 @pytest.mark.parametrize("B,h,n_items,row_off", [(500, 200, 3000, 0), (130, 64, 900, 0), (33, 20, 400, 0),
-                                                 (300, 260, 2000, 0), (200, 128, 1500, 56)])
+                                                 (300, 260, 2000, 0), (200, 128, 1500, 56), (130, 600, 900, 0)])
 def test_dw_and_encoder_backward_in_one_launch_equal_the_two_launches(B, h, n_items, row_off):
   """rk_decode_bwd_dw2_encode_bwd (dw3.hip dw_encbwd_kernel: dW tiles || encoder-backward columns)
   against rk_decode_bwd_dw2 + rk_ae_encode_bwd: the same workgroup bodies, so the K slabs of dW, their
@@ -445,9 +445,10 @@ def test_dw_and_dz_reduce_in_one_launch_equal_the_two_launches(B, h, n_items, ac
 
 @pytest.mark.parametrize("B,h,n_items,row_off", [(2500, 64, 9000, 0), (2100, 32, 6000, 37), (700, 64, 5000, 0)])
 def test_encoder_backward_over_row_windows(B, h, n_items, row_off):
-  """rk_ae_encode_bwd on a row window of more than 2048 rows over a long item set: the wave-per-column
-  kernel once per window of <= 2016 rows, accumulating (csrc/encoder.hip) -- G_en[c] = sum_r svals[r, c] dZ[r]
-  and gb_en = column sums of dZ against float64."""
+  """rk_ae_encode_bwd on a row window of more than 2048 rows over a long item set: the wave-per-column kernel
+  with two bitmap words per lane (up to 4096 rows; past that it runs once per window of <= 4064 rows, accumulating:
+  tests/test_encoder_bwd.py), and with one word per lane (700 rows) -- G_en[c] = sum_r svals[r, c] dZ[r] and
+  gb_en = column sums of dZ against float64."""
   S = B + row_off
   lib, blk, W, bias, Z, ranges, pl, buf = _setup(S, h, S, n_items, 6, seed=B + h)
   st = current_stream()
