@@ -32,6 +32,17 @@
  *   - rk_als_solve: a row's result depends only on its CSR row, G, v, the fixed table, the biases
  *     and its own current value: any [row_lo, row_hi) gives bitwise the rows of the full solve,
  *     whatever path (stashed or streamed factor rows, G from LDS or from memory) a row takes.
+ *     The order (tests/als_util.py restates it, tests/test_als.py compares bit for bit): lane l of the
+ *     row's wave owns dimensions k = l + 64 t; a dot product is each lane's fmaf chain over t ascending
+ *     from +0, then an xor butterfly over lane distances 32, 16, 8, 4, 2, 1.  G p is one fmaf chain per
+ *     output k over j ascending from +0, q_k = fmaf(G[j][k], p_j, q_k).  r starts as -(s_u v) and takes
+ *     the row's entries in CSR order, r = fmaf(coef_j, f_j, r), while q = G x takes q = fmaf(a_j (f_j . x),
+ *     f_j, q) for the entries with a_j != 0; then r -= q.  A CG step: q = G p plus the entries as before,
+ *     al = rs / (p . q), x = fmaf(al, p, x), r = fmaf(-al, q, r), p = fmaf((r . r) / rs, p, r), both
+ *     divisions correctly rounded; it stops at rs == 0 and at !(p . q > 0).  A row of >= 512 entries is
+ *     cut into 16 contiguous pieces of ceil(n / 16) entries: each piece's sums are chains of their own
+ *     from +0, added onto r and onto G x (G p) in ascending piece order.
+ *     rk_als_objective: s is that dot chain + b_i in f32; everything after it is float64.
  *
  * BPR pairwise ranking (Rendle, Freudenthaler, Gantner & Schmidt-Thieme 2009) for the same model, the
  * rk_als_bpr_* functions: a triple t = (u, i, j) scores x_t = p_u . (q_i - q_j) + b_i - b_j, its loss is

@@ -1,7 +1,10 @@
 """GPU: implicit-feedback ALS (recoder_amd/als.py, librecoder_als.so) against the float64 restatement
 of tests/als_util.py -- the Gram, one half-step on every path (stashed / streamed factor rows, G from
 LDS / from memory), row ranges, the objective, a fit on the ML-20M slice and what the trained tables
-plug into (checkpoints, Adam fine-tuning, the similarity index)."""
+plug into (checkpoints, Adam fine-tuning, the similarity index) -- and, without a measured tolerance, the solve
+byte for byte against the f32 restatement in the kernels' order at both ends of every NT, the Gram on integer
+tables, the objective within a counted rounding bound."""
+import functools
 import os
 
 import numpy as np
@@ -189,6 +192,197 @@ def test_objective_matches_the_dense_mse_loss():
   hist = als.fit(Xt, Yt, bt, uc, ic, alpha, reg, 3, 3)
   _, _, want_hist = als_util.fit(csr, X, Y, b, alpha, reg, 3, 3)
   np.testing.assert_allclose(hist, want_hist, rtol=1e-4)
+
+
+# ------------------------------------------------------------ bit for bit / exact
+# The comparisons below carry no measured tolerance: the solve equals tests/als_util.solve_row32 (the kernels' own
+# order of f32 operations) byte for byte, the Gram equals an integer product, the objective lies within a counted
+# float64 rounding bound.  tests/test_als_host.py ties those restatements to the float64 model.
+BITS_HS = [1, 64, 65, 90, 91, 128, 129, 256, 257, 512]     # both ends of every NT of dispatch_nt; G in LDS up to 90
+BITS_COLS = 900
+BITS_REG = 3.0
+X_PAD = np.array([0xDEADBEEF], np.uint32).view(np.float32)[0]      # what the padding of X holds before and after
+VARIANTS = ((10.0, True), (10.0, False), (0.0, True))            # (alpha, CSR values given; False: data = NULL)
+
+
+def _bits_lengths(h):
+  """Row lengths around SOLVE_UNROLL (4), the LDS stash and LONG_ROW_MIN (512).  Rows 0 and 1 and the last two are
+  long ones; the first and the last lie outside [row_lo, row_hi) = [1, rows - 1)."""
+  s = als_util.stash_rows(h)
+  return [777, 512, 0, 1, 3, 4, 5] + ([s, s + 1] if s <= 511 else []) + [511, 777, 513, 512]
+
+
+@functools.lru_cache(maxsize=None)
+def _bits_problem(h):
+  """alpha, the CSR values and the biases carry few bits, so coef = (1 + a) val - a b is exact however the compiler
+  contracts it; F, X, G and v are generic f32.  G comes from the host: the solve does not depend on the Gram."""
+  rng = np.random.RandomState(1000 + h)
+  lens = _bits_lengths(h)
+  indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+  indices = np.concatenate([np.sort(rng.choice(BITS_COLS, n, replace=False)) for n in lens]).astype(np.int32)
+  nnz = len(indices)
+  vals = np.where(rng.rand(nnz) < 0.75, rng.randint(1, 17, nnz), rng.randint(-16, 1, nnz)) / 2.0
+  csr = sp.csr_matrix((vals.astype(np.float32), indices, indptr), shape=(len(lens), BITS_COLS))
+  ones = sp.csr_matrix((np.ones(nnz, np.float32), indices, indptr), shape=csr.shape)
+  F = (0.1 * rng.randn(BITS_COLS, h)).astype(np.float32)
+  X = (0.1 * rng.randn(len(lens), h)).astype(np.float32)
+  F64 = F.astype(np.float64)
+  G = F64.T @ F64 + BITS_REG * np.eye(h)
+  G = (0.5 * (G + G.T)).astype(np.float32)
+  v = rng.randn(h).astype(np.float32)
+  col_bias = (rng.randint(-255, 256, BITS_COLS) / 256.0).astype(np.float32)
+  row_bias = (rng.randint(-255, 256, len(lens)) / 256.0).astype(np.float32)
+  return dict(lens=lens, csr=csr, ones=ones, F=F, X=X, G=G, v=v, col_bias=col_bias, row_bias=row_bias)
+
+
+def _side_biases(p, side):
+  return (p["col_bias"] if side == "user" else None), (p["row_bias"] if side == "item" else None)
+
+
+@functools.lru_cache(maxsize=None)
+def _bits_want(h, side, alpha, use_data):
+  """{row: [x after 1, 2, 3 CG steps]} of the rows in range (computed once, shared by the cg_steps cases)."""
+  p = _bits_problem(h)
+  cb, rb = _side_biases(p, side)
+  return als_util.solve32(p["csr"], p["F"], p["G"], p["v"], p["X"], alpha, 3, col_bias=cb, row_bias=rb,
+                          rows=range(1, len(p["lens"]) - 1), use_data=use_data)
+
+
+def _padded(a, pad, fill):
+  out = np.full((a.shape[0], a.shape[1] + pad), fill, np.float32)
+  out[:, :a.shape[1]] = a
+  return out
+
+
+def _solve_padded(csr, F, G, v, X, alpha, cg_steps, cb, rb, row_lo, row_hi, flags):
+  """rk_als_solve on tables with ldf = h + 3 (NaN in the padding: a read of it poisons the row) and ldx = h + 5
+  (X_PAD in the padding); returns the whole padded X."""
+  from recoder_amd import als
+  h = F.shape[1]
+  Ft, Xt = _t(_padded(F, 3, np.nan)), _t(_padded(X, 5, X_PAD))
+  als.solve(als.AlsCSR(csr, DEV), Ft[:, :h], _t(G), _t(v), Xt[:, :h], alpha, cg_steps,
+            col_bias=None if cb is None else _t(cb), row_bias=None if rb is None else _t(rb),
+            row_lo=row_lo, row_hi=row_hi, flags=flags)
+  return Xt.cpu().numpy()
+
+
+@pytest.mark.parametrize("cg_steps", [1, 3])
+@pytest.mark.parametrize("side", ["user", "item", "no bias"])
+@pytest.mark.parametrize("h", BITS_HS)
+def test_solve_equals_the_f32_restatement_bit_for_bit(h, side, cg_steps):
+  p = _bits_problem(h)
+  lens, X = p["lens"], p["X"]
+  rows = len(lens)
+  cb, rb = _side_biases(p, side)
+  before = _padded(X, 5, X_PAD)
+  for alpha, use_data in VARIANTS:
+    want = _bits_want(h, side, alpha, use_data)
+    csr = p["csr"] if use_data else p["ones"]
+    outs = [_solve_padded(csr, p["F"], p["G"], p["v"], X, alpha, cg_steps, cb, rb, 1, rows - 1, f) for f in (0, 1, 2, 3)]
+    got = outs[0]
+    wrong = [(r, lens[r]) for r in range(1, rows - 1) if got[r, :h].tobytes() != want[r][cg_steps - 1].tobytes()]
+    assert wrong == [], ("(row, entries) that differ from solve_row32", alpha, use_data, wrong)
+    assert got[0].tobytes() == before[0].tobytes() and got[-1].tobytes() == before[-1].tobytes(), "row out of range"
+    assert got[:, h:].tobytes() == before[:, h:].tobytes(), "padding of X written"
+    for f in (1, 2, 3):
+      assert outs[f].tobytes() == got.tobytes(), ("flags change the bits", alpha, use_data, f)
+
+
+def test_solve_stop_rules():
+  """rs == 0 (an empty row at x = +0 with b = 0: no 0 / 0), a NaN in x (rs > 0 is false: the row is left as it is
+  and no other row sees it) and p . q == 0 at rs > 0 (G = 0, the singular case of reg = 0: !(pq > 0) ends the loop)."""
+  h = 65
+  p = _bits_problem(h)
+  lens, rows = p["lens"], len(p["lens"])
+  empty, nan_row = lens.index(0), lens.index(5)
+  zero_v = np.zeros(h, np.float32)
+  X = p["X"].copy()
+  X[empty] = 0.0
+  run = lambda X, G, v: _solve_padded(p["csr"], p["F"], G, v, X, 10.0, 3, None, None, 0, rows, 0)[:, :h]
+  clean = run(X, p["G"], zero_v)
+  assert clean[empty].tobytes() == np.zeros(h, np.float32).tobytes()                     # bitwise +0
+  Xn = X.copy()
+  Xn[nan_row, 7] = np.nan
+  got = run(Xn, p["G"], zero_v)
+  lo, hi = p["csr"].indptr[nan_row], p["csr"].indptr[nan_row + 1]
+  want = als_util.solve_row32(p["csr"].indices[lo:hi], p["csr"].data[lo:hi], p["F"], p["G"], zero_v, Xn[nan_row], 10.0, 3)
+  assert got[nan_row].tobytes() == want.tobytes() == Xn[nan_row].tobytes()
+  others = [r for r in range(rows) if r != nan_row]
+  assert got[others].tobytes() == clean[others].tobytes()
+  assert np.isfinite(got[others]).all()
+  # G = 0: on the empty row q = G p = 0 and p . q = 0 while rs = |v|^2 > 0; x stays where it was
+  zero_G = np.zeros((h, h), np.float32)
+  got = run(p["X"], zero_G, p["v"])
+  assert got[empty].tobytes() == p["X"][empty].tobytes()
+  for r in (empty, lens.index(3), lens.index(513)):
+    lo, hi = p["csr"].indptr[r], p["csr"].indptr[r + 1]
+    want = als_util.solve_row32(p["csr"].indices[lo:hi], p["csr"].data[lo:hi], p["F"], zero_G, p["v"], p["X"][r], 10.0, 3)
+    assert got[r].tobytes() == want.tobytes()
+
+
+@pytest.mark.parametrize("h", [1, 31, 32, 33, 65, 512])
+@pytest.mark.parametrize("rows", [1, 2, 511, 512, 513, 1025, 20108, 32770])
+def test_gram_exact_on_integer_tables(rows, h):
+  """F in {-3 .. 3}, w in {-2 .. 2}, an integer reg: every partial sum of any order is an integer below 2^24, so G
+  and v must EQUAL the integer product.  A row dropped or doubled at a chunk boundary cannot pass (rows = 513 is two
+  chunks of 258, 32770 is 64 of 514), nor can a read of the NaN padding (ldf = h + 3)."""
+  from recoder_amd import als
+  rng = np.random.RandomState(rows + 31 * h)
+  F = rng.randint(-3, 4, (rows, h)).astype(np.float32)
+  w = rng.randint(-2, 3, rows).astype(np.float32)
+  reg = 3
+  Ft, wt = _t(_padded(F, 3, np.nan))[:, :h], _t(w)
+  assert Ft.stride(0) == h + 3
+  G, v = (x.cpu().numpy() for x in als.gram(Ft, reg, wt))
+  Gs, s = (x.cpu().numpy() for x in als.gram(Ft, reg, None))
+  Gi, vi = als_util.gram_exact(F, w, reg)
+  assert np.array_equal(G, Gi) and np.array_equal(G, G.T)
+  assert np.array_equal(v, vi)
+  assert np.array_equal(Gs, Gi) and np.array_equal(s, F.astype(np.int64).sum(0))
+
+
+def _objective_case(rows, h, alpha, with_bias, use_data, seed):
+  """(kernel's L, objective_parts' L, its bound) on padded tables, the Grams built on the host."""
+  from recoder_amd import als
+  cols, reg = 70, 2.0
+  rng = np.random.RandomState(seed)
+  csr = als_util.random_csr(rows, cols, 0.05, seed, values="counts", empty_rows=(1,)) if rows else \
+      sp.csr_matrix((0, cols), dtype=np.float32)
+  if not use_data:
+    csr.data[:] = 1.0
+  X, Y = (0.3 * rng.randn(rows, h)).astype(np.float32), (0.3 * rng.randn(cols, h)).astype(np.float32)
+  b = (0.3 * rng.randn(cols)).astype(np.float32) if with_bias else None
+  X64, Y64 = X.astype(np.float64), Y.astype(np.float64)
+  Gx, Gy = (X64.T @ X64 + reg * np.eye(h)).astype(np.float32), (Y64.T @ Y64 + reg * np.eye(h)).astype(np.float32)
+  sx = X64.sum(0).astype(np.float32)
+  cy = (Y64.T @ b.astype(np.float64)).astype(np.float32) if with_bias else Y64.sum(0).astype(np.float32)
+  Xt = _t(_padded(X, 5, np.nan))[:, :h] if rows else torch.empty(0, h, dtype=torch.float32, device=DEV)
+  Yt = _t(_padded(Y, 3, np.nan))[:, :h]
+  out = torch.full((1,), np.nan, dtype=torch.float64, device=DEV)
+  als.objective(als.AlsCSR(csr, DEV), Xt, Yt, None if b is None else _t(b), alpha, reg, _t(Gx), _t(sx), _t(Gy),
+                _t(cy), out)
+  want, bound = als_util.objective_parts(csr, X, Y, b, alpha, reg, Gx, sx, Gy, cy)
+  return out.item(), want, bound
+
+
+@pytest.mark.parametrize("use_data", [True, False])
+@pytest.mark.parametrize("with_bias", [False, True])
+@pytest.mark.parametrize("alpha", [0.0, 10.0])
+@pytest.mark.parametrize("h", [1, 65, 200, 300, 512])
+def test_objective_against_float64_at_every_nt(h, alpha, with_bias, use_data):
+  """300 rows (thread t of the final kernel adds part[t] and part[t + 256]), ldx = h + 5 and ldy = h + 3 with NaN in
+  the padding.  The bound is counted (als_util.objective_parts), not measured; the largest |error| / bound seen on
+  the MI355X was 0.054 at h = 1, 0.022 at 65, 0.0045 at 200, 0.0015 at 300 and 0.00033 at 512."""
+  got, want, bound = _objective_case(300, h, alpha, with_bias, use_data, seed=11 + h)
+  print("objective h = %d alpha = %g bias = %s data = %s: |error| / bound = %.3g" %
+        (h, alpha, with_bias, use_data, abs(got - want) / bound))
+  assert abs(got - want) <= bound
+
+
+def test_objective_with_no_rows():
+  """rows = 0: no row kernel runs; L = reg tr(Y^T Y) from the Grams alone."""
+  got, want, bound = _objective_case(0, 65, 10.0, True, True, seed=5)
+  assert abs(got - want) <= bound and want > 0
 
 
 def _quality_run():
