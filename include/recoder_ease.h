@@ -61,6 +61,33 @@
  *     thread t of 256 takes the columns t, t + 256, ... ascending, then a pairwise tree over the threads), rounded
  *     once to f32; the count of Cn != 0 is exact.  No atomics: a fixed order, bitwise repeatable, and a row does
  *     not depend on the row range.
+ *   - the ELSA calls (recoder_amd/elsa.py).  A "wave sum" of 64 float64 values is the butterfly s += s[lane ^ d] for
+ *     d = 32, 16, 8, 4, 2, 1; a "row dot" <x, y> of two rows of h columns is: lane l of 64 takes the float64 fma chain of
+ *     x[k] y[k] (exact products) over k = l, l + 64, .. ascending, from 0, then the wave sum of the 64 chains.
+ *       rk_ease_elsa_normalize: ss = (float)(row dot <W_j, W_j>) (the float64 sum rounded once), norm_j = sqrt(ss)
+ *         (correctly rounded f32), d = max(norm_j, 1e-12f), A[j][k] = W[j][k] / d (a correctly rounded f32 divide).  Against
+ *         the exact value that is (1/2 + 1 + 1) 2^-24 relative: ss within 2^-24 (halved by the root), the root, the divide.
+ *         A zero row gives norm 0 and a row of +-0.  At is a copy: bitwise the transpose of A.
+ *       rk_ease_elsa_rows, all in float64: z2 = row dot <Z_u, Z_u>, q = row dot <Z_u, Q_u>, t = t2[u],
+ *         p2 = (q - 2 z2) + t, live = t > 0 and 0 < p2 < inf; for a live row c = (z2 - t) / (sqrt(p2) sqrt(t)),
+ *         a = -2 / (B n sqrt(p2) sqrt(t)), b = 2 c / (B n p2), E[u][k] = (float)fma(2 (a - b), Z[u][k], b Q[u][k]),
+ *         F[u][k] = (float)(b Z[u][k]) (one rounding to f32 each) and row_loss[u] = 2 - 2 c; a dead row writes E = F = +0
+ *         and row_loss[u] = (t > 0 ? 1 : 0), whatever Z and Q hold; a row whose float64 E or F holds a NaN or a value
+ *         beyond the f32 range (a p2 next to nothing) is dead in the same way: nothing written is ever not finite.  Then loss_acc[0] += (sum of row_loss) / (B n), the sum
+ *         in float64 in a fixed order: thread v of 256 adds the rows v, v + 256, .. ascending from 0, then the pairwise
+ *         tree s[v] += s[v + d] for d = 128, 64, .. 1.
+ *       rk_ease_elsa_scatter: G[j][k] is ONE f32 fmaf chain fma(x_uj, E[u - lo][k], .) from +0 over the positions u of row
+ *         j inside [lo, hi), ascending.  An item with RK_EASE_ELSA_LONG or more such positions is summed by a workgroup
+ *         that splits the COLUMNS, not the positions: the chain of an output is the same on either path, and a row
+ *         depends on nothing outside the range.  No atomics.
+ *       rk_ease_elsa_project: dot = (float)(row dot <dA_j, A_j>), d = max(norm_j, 1e-12f),
+ *         dW[j][k] = fma(-dot, A[j][k], dA[j][k]) / d: an fmaf and a correctly rounded divide.
+ *       rk_ease_elsa_adam, per element, every operation one f32 rounding: g = rk_ease_elsa_project's dW[j][k];
+ *         m = fma(beta1, m, (1 - beta1) * g); v = fma(beta2, v, ((1 - beta2) * g) * g);
+ *         W = fma(-step, m / fma(sqrt(v), isb2, eps), W) (sqrt and / correctly rounded; 1 - beta one f32 subtract on the
+ *         host; step = lr / (1 - beta1^t) and isb2 = 1 / sqrt(1 - beta2^t) come from the caller, who forms them in
+ *         float64 and rounds once); then norm_j and A[j] from the new W[j] exactly as rk_ease_elsa_normalize does.
+ *       rk_ease_csr_sub: one f32 subtract per stored entry of the strip.
  */
 #ifndef RECODER_EASE_H
 #define RECODER_EASE_H
@@ -155,6 +182,61 @@ int rk_ease_admm_update(const float *T, int64_t ldt, const float *P, int64_t ldp
                         int64_t ldu, float *M, int64_t ldm, int32_t n, float theta, int32_t nonneg, float *gamma,
                         float *row_primal, float *row_dual, int32_t *row_nnz, int32_t row_lo, int32_t row_hi,
                         void *stream);
+
+/* ---- ELSA: the low-rank shallow autoencoder scores = x (A A^T - I) (recoder_amd/elsa.py; Vancura et al., RecSys 2022) ---- */
+
+/* items with at least this many positions inside the batch's range get a workgroup each in rk_ease_elsa_scatter */
+#define RK_EASE_ELSA_LONG 128
+
+/*
+ * A[j] = W[j] / max(|W[j]|, 1e-12) and norms[j] = |W[j]| for j in [0, n): W [n, ldw], A [n, lda], 1 <= h <= 512 columns,
+ * ldw, lda >= h.  At NULL, or [h, ldt], ldt >= n: At[k][j] = A[j][k].  A must not overlap W.
+ */
+int rk_ease_elsa_normalize(const float *W, int64_t ldw, int32_t n, int32_t h, float *A, int64_t lda, float *norms,
+                           float *At, int64_t ldt, void *stream);
+
+/*
+ * The per-row pass of one ELSA step over B batch rows (B >= 0: none does nothing) of a catalogue of n items: from
+ * Z = X_b A [B, ldz], Q = Z (A^T A) [B, ldq] and t2[u] = |X_u|^2 it writes the gradient's two row factors E [B, lde] and
+ * F [B, ldf] (dA = X_b^T E + A (Z^T F)) and row_loss [B] (float64), and adds the batch's loss
+ * mse_loss(normalize(Z A^T - X_b), normalize(X_b)) to loss_acc[0] (float64; NULL: not wanted).  E and F may not overlap
+ * Z or Q.
+ */
+int rk_ease_elsa_rows(const float *Z, int64_t ldz, const float *Q, int64_t ldq, const float *t2, int32_t B, int32_t h,
+                      int32_t n, float *E, int64_t lde, float *F, int64_t ldf, double *row_loss, double *loss_acc,
+                      void *stream);
+
+/*
+ * G[j] = sum over the entries (u, x_uj) of row j of the item-major CSR with lo <= u < hi, ascending, of x_uj * E[u - lo],
+ * for every j in [0, n): all n rows of G [n, ldg] are written, zeros where the range holds no entry.  (t_*): n rows,
+ * the column indices (positions of users) STRICTLY ascending inside a row (a position held twice is not supported: the
+ * count of a row's entries inside the range is then bounded by hi - lo, which the launch relies on); E [hi - lo, lde]; 0 <= lo <= hi (lo == hi: zeros, E
+ * is not read).  The cost follows the entries inside the range: each row is searched for lo and hi.
+ */
+int rk_ease_elsa_scatter(const int64_t *t_indptr, const int32_t *t_indices, const float *t_data, int32_t n, int32_t lo,
+                         int32_t hi, const float *E, int64_t lde, int32_t h, float *G, int64_t ldg, void *stream);
+
+/* dW[j] = (dA[j] - <dA[j], A[j]> A[j]) / max(norms[j], 1e-12): the gradient through the normalisation, j in [0, n) */
+int rk_ease_elsa_project(const float *dA, int64_t ldd, const float *A, int64_t lda, const float *norms, int32_t n,
+                         int32_t h, float *dW, int64_t ldw, void *stream);
+
+/*
+ * One Adam step on every row of W [n, ldw] from dA [n, ldd] (the gradient with respect to A; projected as
+ * rk_ease_elsa_project does), with the moments M, V packed [n, h]; then A [n, lda] and norms [n] are taken again from
+ * the new W.  0 <= beta1, beta2 < 1, eps > 0; step = lr / (1 - beta1^t) and isb2 = 1 / sqrt(1 - beta2^t) for the step
+ * count t >= 1.  No weight decay.
+ */
+int rk_ease_elsa_adam(float *W, int64_t ldw, const float *dA, int64_t ldd, float *A, int64_t lda, float *norms,
+                      float *M, float *V, int32_t n, int32_t h, float beta1, float beta2, float eps, float step,
+                      float isb2, void *stream);
+
+/*
+ * out[u][j - lo] -= x_uj for the stored entries (j, x_uj) of CSR row u with lo <= j < hi, u in [0, n_rows): the
+ * "- x" of a strip of ELSA's scores.  out [n_rows, ldo], ldo >= hi - lo.  The column indices of a row are distinct (an
+ * entry is a lane's own read-modify-write).
+ */
+int rk_ease_csr_sub(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows, int32_t lo,
+                    int32_t hi, float *out, int64_t ldo, void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

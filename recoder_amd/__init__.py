@@ -9,7 +9,7 @@ Drop-in for the reference's training path: ``Recoder`` / ``FactorizationModel``
 __version__ = "0.4.0"
 
 __all__ = ["ShallowAutoencoder", "RandomWalkItemModel", "SparseLinearModel", "UserNeighbourhoodModel",
-           "ItemNeighbourhoodModel", "GraphFilterModel", "AdmmSlimModel"]
+           "ItemNeighbourhoodModel", "GraphFilterModel", "AdmmSlimModel", "LowRankShallowAutoencoder"]
 
 
 def __getattr__(name):
@@ -35,4 +35,7 @@ def __getattr__(name):
   if name == "AdmmSlimModel":
     from .nn import AdmmSlimModel
     return AdmmSlimModel
+  if name == "LowRankShallowAutoencoder":
+    from .nn import LowRankShallowAutoencoder
+    return LowRankShallowAutoencoder
   raise AttributeError("module %r has no attribute %r" % (__name__, name))

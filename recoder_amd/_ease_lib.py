@@ -29,6 +29,14 @@ SIGNATURES = {
                              c_float, c_int32, c_int32, _P]),
   "rk_ease_admm_update": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_float,
                                     c_int32, _P, _P, _P, _P, c_int32, c_int32, _P]),
+  "rk_ease_elsa_normalize": (c_int32, [_P, c_int64, c_int32, c_int32, _P, c_int64, _P, _P, c_int64, _P]),
+  "rk_ease_elsa_rows": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int32, c_int32, c_int32, _P, c_int64, _P, c_int64, _P,
+                                  _P, _P]),
+  "rk_ease_elsa_scatter": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, c_int64, c_int32, _P, c_int64, _P]),
+  "rk_ease_elsa_project": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int32, c_int32, _P, c_int64, _P]),
+  "rk_ease_elsa_adam": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, c_int32, c_int32, c_float, c_float,
+                                  c_float, c_float, c_float, _P]),
+  "rk_ease_csr_sub": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

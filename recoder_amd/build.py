@@ -27,7 +27,9 @@ librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencod
                    (include/recoder_ease.h), likewise a library of its own.  It also holds the dense
                    rank-k update of GraphFilterModel's GF-CF fit (rk_ease_lowrank_add), which shares the
                    inverse's MFMA tile, and the general dense f32 product and the element-wise pass of
-                   AdmmSlimModel's ADMM-SLIM fit (rk_ease_gemm, rk_ease_admm_update) on the same tile
+                   AdmmSlimModel's ADMM-SLIM fit (rk_ease_gemm, rk_ease_admm_update) on the same tile, and the row
+                   passes of LowRankShallowAutoencoder's ELSA fit and serving (rk_ease_elsa_*, rk_ease_csr_sub), which
+                   live in the private header csrc/ease/elsa.h that ease.hip includes
 librecoder_svd.so  the randomized truncated SVD behind PureSVD for MatrixFactorization
                    (include/recoder_svd.h), likewise a library of its own
 librecoder_rp3.so  the RP3beta item-graph fit and its scores for RandomWalkItemModel
@@ -41,7 +43,7 @@ librecoder_slim.so  the SLIM coordinate-descent fit and its scores for SparseLin
 
 The seven side libraries share csrc/side_error.h (the last-error buffer and the argument / launch
 checks); each stays one translation unit, so each has its own buffer.  A library's source may be laid out
-over private headers in csrc/<stem>/ (als.hip is: csrc/als/*.h, one file a family); they are that library's
+over private headers in csrc/<stem>/ (als.hip is: csrc/als/*.h, one file a family; ease.hip has csrc/ease/elsa.h); they are that library's
 dependencies and nobody else's.
 
 hipcc cross-compiles without a GPU; the built libraries stay in-tree

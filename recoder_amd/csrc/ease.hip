@@ -19,6 +19,7 @@
 //                        fetched into registers under this slab's MFMAs, edges padded with zeros in LDS
 //   rk_ease_admm_update  the element-wise pass of an ADMM-SLIM iteration (recoder_amd/admm.py): one workgroup per
 //                        row, the row's three statistics summed in a fixed order
+//   rk_ease_elsa_*, rk_ease_csr_sub   the row passes of the low-rank autoencoder ELSA (recoder_amd/elsa.py): ease/elsa.h
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -683,3 +684,5 @@ int rk_ease_admm_update(const float *T, int64_t ldt, const float *P, int64_t ldp
 }
 
 }  // extern "C"
+
+#include "ease/elsa.h"    // rk_ease_elsa_normalize, _rows, _scatter, _project, _adam, rk_ease_csr_sub

@@ -471,7 +471,7 @@ class Recoder(object):
 
   def _closed_form_fit(self, mod, train_dataset, keep, check, log_line, fit, hint_check=None, check_values=False,
                        store=None, place=None, size_check=None, csrs=None, copy=dict):
-    """The one sequence behind the thirteen ``train_*`` methods below: ``mod`` is the fit module, the callables say
+    """The one sequence behind the ``train_*`` methods below: ``mod`` is the fit module, the callables say
     what differs, ``cfg`` is what ``check`` returned and ``host()`` the dataset's host matrix, built at the step
     that first asks for it.  The order decides which exception wins, and a call that raises in A-D leaves the
     Recoder and the model as they were:
@@ -919,6 +919,30 @@ class Recoder(object):
         size_check=lambda c, host: admm.check_memory(self.num_items, c[3], allocate_matrix=False),
         fit=lambda m, pair, c: admm.fit(pair, *c, out=m.item_weights.data)[-1])
 
+  def train_elsa(self, train_dataset, num_epochs=None, batch_size=1024, lr=0.03, seed=0):
+    """The ELSA fit of a LowRankShallowAutoencoder (recoder_amd/elsa.py): ``item_factors`` becomes W after
+    ``num_epochs`` (None: ``elsa.DEFAULT_EPOCHS``) epochs of mini-batch Adam steps (betas 0.9 / 0.999, eps 1e-8, no weight
+    decay) with learning rate ``lr`` on the cosine loss ``mse_loss(normalize(X_b A A^T - X_b), normalize(X_b))`` over
+    batches of ``batch_size`` users of the dataset's interaction matrix X (values as stored), A the rows of W at unit
+    length.  Loss and gradient come from the h x h Gram ``A^T A``, sparse products over the batch's stored entries and one
+    n x h x h product; the batch x items block is never formed.  The start and every epoch's user order are drawn from
+    ``seed`` on the host: a fixed seed gives the same bits.  The configured ``loss`` plays no part.  Builds a fresh
+    optimizer of ``optimizer_type`` so that ``save_state`` works; the fit's own Adam moments are not kept.  Returns (and
+    keeps in ``elsa_history``) the mean batch loss of each epoch."""
+    from . import elsa
+    return self._closed_form_fit(
+        elsa, train_dataset, "elsa_history", copy=list,
+        check=lambda m: elsa.check_config(m, elsa.DEFAULT_EPOCHS if num_epochs is None else num_epochs, batch_size, lr,
+                                          seed),                       # c = (h, epochs, batch, lr, seed)
+        hint_check=lambda c, u, n, host: n and elsa.check_memory(u or 0, n, c[0], c[2], 0, free_bytes=float("inf")),
+        log_line=lambda c: ("ELSA: embedding size %d, %d epochs of batches of %d, lr %g, seed %d",) + c,
+        # (first use: the parameter itself is one of the five [n, h] tables, and all have to fit what is free)
+        place=lambda c, first, host: first and elsa.check_memory(
+            self._size_hints(train_dataset)[0] or 0, self._size_hints(train_dataset)[1] or 1, c[0], c[2], host().nnz),
+        size_check=lambda c, host: elsa.check_memory(self.num_users, self.num_items, c[0], c[2], host().nnz,
+                                                     allocate_model=False),
+        fit=lambda m, pair, c: elsa.fit(pair, *c, out=m.item_factors.data)[-1])
+
   def train_rp3beta(self, train_dataset, alpha=None, beta=None, neighbours=None):
     """The closed-form RP3beta fit of a RandomWalkItemModel (recoder_amd/rp3.py): every item keeps its
     ``neighbours`` largest ``W[i, j] = d_i^-alpha * (sum over the users v of i and j of r_v^-alpha) * d_j^-beta``
@@ -1086,6 +1110,8 @@ class Recoder(object):
     if hasattr(eng, "_w_range_stale"):
       eng._w_range_stale = True
       eng._eval_img = None
+    if hasattr(self.model, "_weights_written"):       # (a model with derived state of its own: nn.LowRankShallowAutoencoder)
+      self.model._weights_written()
 
   def _setup_data_parallel(self, train_dataset, negative_sampling=True, batch_size=None):
     """Under an initialised torch.distributed group (one process per GPU, backend

@@ -596,6 +596,109 @@ class AdmmSlimModel(ItemItemModel):
     return self.item_weights
 
 
+class LowRankShallowAutoencoder(CsrScoresModel):
+  """ELSA (Vancura, Alves, Kasalicky & Kordik 2022, "Scalable Linear Shallow Autoencoder for Collaborative
+  Filtering"): the EASE-like autoencoder ``scores = input @ (A A^T - I)`` whose item-item matrix is never formed: A
+  [num_items, embedding_size] holds the rows of ``item_factors`` at unit length, ``A_j = W_j / max(|W_j|, 1e-12)``, so
+  the diagonal of ``A A^T`` is 1 and the model is 4 n h bytes where EASE, GF-CF and ADMM-SLIM are 4 n^2.  Trained by
+  ``Recoder.train_elsa`` (recoder_amd/elsa.py): mini-batch Adam steps on the cosine loss of the published code, computed
+  from the h x h Gram ``A^T A`` without the batch x items prediction block.
+
+  One parameter, ``item_factors`` [num_items, embedding_size], which is W, zero until fitted; ``embedding_size`` (1..512)
+  travels in ``model_params()``.  A and its transpose are derived state: taken again after a fit and after a checkpoint
+  is loaded, and not part of ``state_dict()``.  The defaults (embedding_size 256 here; 5 epochs, lr 0.03 and batches of
+  1024 in ``train_elsa``) are the best Recall@20 of the float64 grid on the ML-20M slice, embedding_size {64, 256} x lr
+  {0.03, 0.1, 0.3} read after 5, 10 and 20 epochs, at the fewest epochs that reach it: 0.1365, against 0.1357 after 10
+  epochs and 0.1285 after 20 at the same cell, which overfits from there, and 0.1350 at lr 0.1 after 10
+  (profiles/elsa_quality.jsonl; tools/elsa_bench.py --cpu-grid).  ``Recoder.train`` refuses this model and
+  points at ``train_elsa``: its loss is not one of the fused epilogues, and its step is not the encoder-decoder one.
+  """
+  fit_method = "train_elsa"
+  fit_sentence = ("a LowRankShallowAutoencoder is trained by its own mini-batch steps on the cosine loss, from the "
+                  "Gram matrix of its factors: call %s(train_dataset)")
+
+  def __init__(self, embedding_size=256):
+    super().__init__()
+    self.embedding_size = embedding_size
+    self.num_items = None
+    self.item_factors = None
+    self._images = None            # (A, A^T) of item_factors, and what they were taken from
+    self._batch = None             # (the csr of the last batch, its rows, Z = X_b A)
+    self._validate()
+
+  def _validate(self):
+    from .elsa import check_embedding_size
+    self.embedding_size = check_embedding_size(self.embedding_size)
+
+  def init_model(self, num_items=None, num_users=None):
+    self._validate()
+    self.num_items = num_items
+    self.item_factors = nn.Parameter(torch.zeros(num_items, self.embedding_size), requires_grad=False)
+    self._weights_written()
+
+  def model_params(self):
+    return {"embedding_size": int(self.embedding_size)}
+
+  def load_model_params(self, model_params):
+    self.embedding_size = model_params["embedding_size"]
+    self._validate()
+
+  def _weights_written(self):
+    """``item_factors`` was written: the normalised images and the last batch's Z are taken again on next use."""
+    self._images = self._batch = None
+
+  def _load_from_state_dict(self, *args, **kwargs):
+    self._weights_written()
+    return super()._load_from_state_dict(*args, **kwargs)
+
+  def images(self):
+    """(A [n, h], A^T [h, n]) of ``item_factors`` on its device (rk_ease_elsa_normalize), kept until the factors are
+    written again."""
+    from . import elsa
+    W = self.item_factors.data
+    key = (W.data_ptr(), W.device)               # (a move or a re-allocation; a write in place is _weights_written's to tell)
+    if self._images is None or self._images[0] != key:
+      At = torch.empty(W.shape[1], W.shape[0], dtype=torch.float32, device=W.device)
+      A, _ = elsa.normalize(W.contiguous(), At=At)
+      self._images, self._batch = (key, A, At), None
+    return self._images[1:]
+
+  def csr_scores(self, csr, lo, hi, out, ld, n_rows):
+    """Z = (the rows of ``csr``) @ A once per ``csr`` object (rk_ease_scores), then the strip Z @ A^T[:, lo:hi]
+    (rk_ease_gemm) minus the strip's stored entries (rk_ease_csr_sub)."""
+    from . import _ease_lib, ease, elsa
+    from ._lib import ptr
+    from .device import current_stream
+    A, At = self.images()
+    n, h = A.shape
+    if out is None:
+      ld = hi - lo if ld is None else ld
+      out = torch.empty(n_rows, ld, dtype=torch.float32, device=A.device)
+    ld = out.stride(0) if ld is None else ld
+    if n_rows == 0:
+      return out
+    b = self._batch
+    if b is None or b[0] is not csr or b[1] != n_rows:
+      b = self._batch = (csr, n_rows, ease.scores(csr, A, 0, h, n_rows=n_rows))
+    Z = b[2]
+    _ease_lib.check(_ease_lib.load().rk_ease_gemm(ptr(Z), h, At.data_ptr() + 4 * lo, n, None, 0, ptr(out), ld, n_rows,
+                                                  hi - lo, h, 1.0, 0.0, 0, n_rows, current_stream()), "rk_ease_gemm")
+    return elsa.csr_sub(csr, lo, hi, out, ld, n_rows)
+
+  def torch_forward(self, input, input_users=None, input_items=None, target_users=None,
+                    target_items=None):
+    """The same forward in torch ops (the generic engine's validation loss; host tensors)."""
+    W = self.item_factors
+    A = W / W.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    x = input.to(A.dtype)
+    if input_items is not None:
+      full = torch.zeros(x.shape[0], A.shape[0], dtype=A.dtype, device=x.device)
+      full[:, input_items.to(torch.int64)] = x
+      x = full
+    out = (x @ A) @ A.t() - x
+    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
+
+
 class _NeighbourListModel(ItemItemModel):
   """An item-item model stored as neighbour lists: ``item_neighbours`` int32 [num_items, neighbours],
   ``item_weights`` f32 of the same shape and ``neighbour_counts`` int32 [num_items].  A subclass names
