@@ -872,7 +872,8 @@ int rk_stream_wait_event(void *stream, void *event);
 /*
  * rk_topk_masked -- Recoder.recommend (model.py:525-544): scores[B, ld] with the seen items (bits_rc of
  * the non-sampled block; only positive stored interactions, model.py:537 `output[input > 0]`) set to -inf,
- * top-k sorted descending (ties: lower index first, as torch.topk on CPU).  Score column c is item
+ * top-k sorted descending (ties: lower index first, as torch.topk on CPU; -0.0 and +0.0 tie and are returned as
+ * +0.0; the canonical NaN 0x7fc00000 ranks above +inf; rk_topk_pairs orders alike).  Score column c is item
  * col_off + c * col_stride (mask lookup and returned indices are global); row r's k results go to
  * out_idx / out_val [r * out_ld ...].
  *   whole rows          : col_off 0, col_stride 1, out_ld k

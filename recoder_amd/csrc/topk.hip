@@ -10,8 +10,11 @@ namespace {
 
 constexpr int KMAX = 1024;
 
+// (-0.0 and +0.0 are ONE value, as for torch.topk: their tie resolves to the lower item id; key2f
+// returns +0.0 for either)
 __device__ __forceinline__ uint32_t f2key(float f) {
   uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float key2f(uint32_t k) {
