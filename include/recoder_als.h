@@ -426,6 +426,67 @@ int rk_als_ugcn_scatter(const int32_t *keys, const int64_t *order, int32_t n, in
                         const float *coef, const float *X, int32_t ldx, int32_t n_users, int32_t h, float scale,
                         int32_t n_rows, float *G, int32_t ldg, int32_t *count, void *stream);
 
+/* the limits of rk_als_ccl_grad: T slots, R negatives a slot, T (1 + R) entries a step (UltraGCN's at K = 0) */
+#define RK_ALS_CCL_MAX_BATCH 4096
+#define RK_ALS_CCL_MAX_NEGATIVES 1024
+#define RK_ALS_CCL_MAX_ENTRIES (1 << 22)
+
+/* bytes of the step's buffers cand, key (int32 [T, E]), coef, self (f32 [T, E]), loss (f32 [T, 2]) and live (int32
+ * [T]), E = 1 + R, each rounded up to 256 bytes and laid out in that order; -2 unless 1 <= T <= RK_ALS_CCL_MAX_BATCH,
+ * 1 <= R <= RK_ALS_CCL_MAX_NEGATIVES, T E <= RK_ALS_CCL_MAX_ENTRIES and 1 <= h <= 512 */
+int64_t rk_als_ccl_workspace_bytes(int32_t T, int32_t R, int32_t h);
+
+/*
+ * SimpleX's cosine contrastive loss (Mao et al. 2021) and its gradient over the T slots (users[t], items[t]) of a
+ * step, at the tables X [n_users, ldx] and Y [n_items, ldy].  Slot t is valid when both ids lie in their tables.  Its
+ * E = 1 + R candidates are the positive items[t] (column 0) and the R draws of rk_als_ugcn_grad for the same (seed,
+ * step, t R + r) (columns 1 .. R: the same domain, uniform over [0, n_items), nothing rejected).  With p = X[users[t]],
+ * a = p / |p|, y = Y[item] and c = (a . y) / |y| the cosine (a row of norm 0 normalises to the zero vector: c = 0),
+ *   L_t = (1 - c_0) + (negative_weight / R) sum_r max(0, c_r - margin),
+ * a negative is live when the one f32 subtraction c - margin is > 0, w = d L_t / d c is -1 for the positive,
+ * negative_weight / R for a live negative and 0 for a dead one, and the call leaves
+ *   cand [T, E]   the columns' items (rk_als_ugcn_grad's columns 0 .. R at K = 0); n_items in an invalid slot
+ *   key [T, E]    the item where the entry carries a gradient (w != 0, |p| > 0, |y| > 0), else the sentinel n_items
+ *   coef [T, E]   w / (|p| |y|); +0 under a sentinel
+ *   self [T, E]   w c / |y|^2;   +0 under a sentinel      (d L_t / d Y[item] = coef p - self y)
+ *   DU [T, :h]    d L_t / d p = (sum_e (w_e / |y_e|) y_e - (sum_e w_e c_e) a) / |p|   (+0 for an invalid slot)
+ *   valid [T]     1.0 or 0.0
+ *   loss [T, 2]   1 - c_0 and (negative_weight / R) sum_r max(0, c_r - margin)
+ *   live [T]      the live negatives of the slot
+ * rk_als_lgcn_scatter with roles = 1 and g = valid sums DU per user row; rk_als_ccl_scatter sums the item side.
+ * Numerics, all f32.  A row is held dimension k = l + 64 q on lane l of a group of W lanes (W = 16 for h <= 16, 32 for
+ * h <= 32, else 64).  |p|^2 and |y|^2 are fmaf chains over q ascending from +0, then an xor butterfly over the group
+ * (offsets W / 2 .. 1); 1 / |.| = 1.f / sqrtf(.), a_k = p_k (1 / |p|); a . y is the same chain and butterfly and
+ * c = (a . y) (1 / |y|).  Over the live candidates in ascending e: acc_k = fmaf(w (1 / |y|), y_k, acc_k) and
+ * sc = fmaf(w, c, sc); below the wave, group g of the 64 / W takes the candidates e with e mod (64 / W) == g and the
+ * groups' acc and sc are added in ascending g from +0; DU_k = fmaf(-sc, a_k, acc_k) (1 / |p|).  coef = (w (1 / |p|))
+ * (1 / |y|), self = ((w c) (1 / |y|)) (1 / |y|).  The negatives' term: lane l adds c - margin of its live candidates
+ * e = l + 64 j in ascending j, wave_sum's butterfly (offsets 32 .. 1), times negative_weight / R (one f32 division on
+ * the host).  No atomics: the same inputs give the same bits, whatever T, the launch and the leading dimensions.
+ */
+int rk_als_ccl_grad(const int32_t *users, const int32_t *items, int32_t T, int32_t R, int64_t seed, int32_t step,
+                    int32_t n_users, int32_t n_items, const float *X, int32_t ldx, const float *Y, int32_t ldy,
+                    int32_t h, float margin, float negative_weight, int32_t *cand, int32_t *key, float *coef,
+                    float *self, float *DU, float *valid, float *loss, int32_t *live, void *stream);
+
+/*
+ * The item side of rk_als_ccl_grad: keys (int32 [n], n = T E) are the key entries stably sorted ascending and order
+ * (int64 [n]) their positions e before the sort.  For every key in [0, n_rows) among them
+ *   G[key, :h] = scale * (sum coef[e] X[users[e / E], :h] - (sum self[e]) Y[key, :h])
+ *   count[key] = the key's entries with e % E == 0 (the slots whose positive it is)
+ * over the key's entries, walked as rk_als_ugcn_scatter walks them (the same device function): the coefficients' sum
+ * is one f32 fmaf chain of one wave in ascending position below RK_ALS_UGCN_LONG_KEY entries, and 16 equal parts, one
+ * chain each, added in ascending part order from there on.  The self sum of a chain's positions: lane l adds the
+ * positions l + 64 j in ascending j, then the xor butterfly; the parts' sums in ascending part order; the row is
+ * scale * fmaf(-(sum self), Y[key, k], sum_k).  The sentinels sort last and are never read: no user row is gathered
+ * for a dead entry.  Y [>= n_rows, ldy] is the item table rk_als_ccl_grad read.  Rows without a key are not touched:
+ * the caller zeroes G [n_rows, ldg] and count (int32 [n_rows]) first.  No atomics.
+ */
+int rk_als_ccl_scatter(const int32_t *keys, const int64_t *order, int32_t n, int32_t E, const int32_t *users,
+                       const float *coef, const float *self, const float *X, int32_t ldx, int32_t n_users,
+                       const float *Y, int32_t ldy, int32_t h, float scale, int32_t n_rows, float *G, int32_t ldg,
+                       int32_t *count, void *stream);
+
 /* the metric kinds of rk_als_rank_metrics and how many records one call takes */
 #define RK_ALS_METRIC_RECALL 0
 #define RK_ALS_METRIC_NDCG 1

@@ -19,7 +19,9 @@ librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recode
                    softmax over in-batch and shared uniform negatives with its gradient rows, on the f32 MFMA)
                    and UltraGCN's (rk_als_ugcn_workspace_bytes, rk_als_ugcn_grad, rk_als_ugcn_scatter: the
                    constraint loss over a slot's private negatives and the positive's neighbours, and the
-                   item-side sum that gathers its user rows) and the ranking metrics of device-resident top-k lists
+                   item-side sum that gathers its user rows) and the cosine contrastive loss' (rk_als_ccl_workspace_bytes,
+                   rk_als_ccl_grad, rk_als_ccl_scatter: the hinge on the cosine over a slot's private negatives, and
+                   the item-side sum over the live entries only) and the ranking metrics of device-resident top-k lists
                    (rk_als_rank_metrics: Recall / NDCG / AveragePrecision for validation during a fit)
 librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own

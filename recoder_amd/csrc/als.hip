@@ -53,6 +53,13 @@
 //   rk_als_ugcn_scatter    the item side: the scatter's segment walk with the user rows gathered through the slot,
 //                          a key of RK_ALS_UGCN_LONG_KEY entries or more by a workgroup of 16 waves in fixed parts
 //
+// SimpleX's cosine contrastive loss for the same model (rk_als_ccl_*): the step of recoder_amd/ccl.py adds
+//   rk_als_ccl_grad        the hinge on the cosine of every slot over its positive and R private uniform negatives
+//                          (rk_als_ugcn_grad's draws): norm and dot product from one gathered copy of a row, a dead
+//                          negative dropped at once, a live row used for DU while it is in registers
+//   rk_als_ccl_scatter     rk_als_ugcn_scatter's walk over the keys of the live entries only (the dead carry a
+//                          sentinel that sorts last), with the row's own -sum self Y[key] term
+//
 // Ranking metrics on device-resident top-k lists (rk_als_rank_metrics): what recoder_amd/validation.py reads per epoch
 //   rk_als_rank_metrics    one wave per user: a binary search of each rank's id in the user's target row, a ballot per
 //                          64 ranks, Recall / NDCG / AP summed in float64 in ascending rank order; a second launch of
@@ -67,6 +74,7 @@
 #include "als/contrast.h"   // rk_als_gcl_contrast, rk_als_dau_*
 #include "als/ssm.h"        // rk_als_ssm_*
 #include "als/ugcn.h"       // rk_als_ugcn_*
+#include "als/ccl.h"        // rk_als_ccl_*
 #include "als/metrics.h"    // rk_als_rank_metrics
 
 extern "C" int rk_als_version(void) { return 100; }

@@ -109,11 +109,14 @@ class Recoder(object):
     self.ssm_state = None       # train_ssm: base tables, Adam moments, step count, num_layers (device; not saved)
     self.ultragcn_history = []  # train_ultragcn: (positive, negatives, neighbours) means per valid slot of each epoch
     self.ultragcn_state = None  # train_ultragcn: the tables, Adam moments and step count (device; not saved)
-    # the seven iterative trainers' validation curve of the last fit (None: it had no val_dataset): {"metric", "k",
+    self.ccl_history = []       # train_ccl: (positive term, negative term) means per valid slot of each epoch
+    self.ccl_stats = []         # train_ccl: the mean share of live negatives of each epoch
+    self.ccl_state = None       # train_ccl: base tables, Adam moments, step count, num_layers (device; not saved)
+    # the iterative trainers' validation curve of the last fit (None: it had no val_dataset): {"metric", "k",
     # "values", "epochs", "best_epoch", "stopped_epoch"}; not saved
     self.fit_validation = None  # validation settings for the iterative fits called without a val_dataset (_validated)
     self.bpr_validation = self.warp_validation = self.lightgcn_validation = self.simgcl_validation = None
-    self.directau_validation = self.ssm_validation = self.ultragcn_validation = None
+    self.directau_validation = self.ssm_validation = self.ultragcn_validation = self.ccl_validation = None
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -543,7 +546,7 @@ class Recoder(object):
                                            int(num_iterations)))
 
   def _validated(self, method, prefix, train_dataset, args):
-    """The validation keywords the seven iterative trainers share (recoder_amd/validation.py), ``args`` =
+    """The validation keywords the iterative trainers share (recoder_amd/validation.py), ``args`` =
     (val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience, restore_best).  With a
     ``val_dataset`` (a dataset with an ``interactions_matrix`` to score from and a ``target_interactions_matrix``
     to hit) the fit evaluates ``eval_metric`` (None: Recall(20); one of Recall, NDCG, AveragePrecision) after every
@@ -554,9 +557,9 @@ class Recoder(object):
     graph method's ``<prefix>_state``) is what a fit of ``best_epoch`` epochs leaves.  The loss history keeps every
     epoch that ran; ``self.<prefix>_validation`` = {"metric", "k", "values", "epochs", "best_epoch",
     "stopped_epoch"} (None without a ``val_dataset``).  Nothing of this touches the fit's draws or arithmetic.
-    ``train_ssm`` and ``train_ultragcn`` keep the parameter lists their contracts pin, so they take the same settings
+    ``train_ssm``, ``train_ultragcn`` and ``train_ccl`` keep the parameter lists their contracts pin, so they take the same settings
     from ``self.fit_validation``: a dict of these keywords (``val_dataset`` at least), set like the Recoder's other
-    hooks and read by every one of the seven fits that is called without a ``val_dataset`` keyword, until it is set
+    hooks and read by every one of these fits that is called without a ``val_dataset`` keyword, until it is set
     back to None.
     Returns (check, monitor, keep): ``check()`` raises the ValueErrors before any GPU work, ``monitor()`` builds the
     fit's ``validation.Monitor`` (None without validation) once the model is placed, ``keep()`` stores the result."""
@@ -808,6 +811,39 @@ class Recoder(object):
                            "weight %g, %d neighbours at weight %g, w %s, seed %d",
                            num_epochs, batch_size, lr, reg, num_negatives, negative_weight, neighbours, item_weight, w,
                            seed)
+
+  def train_ccl(self, train_dataset, num_layers=0, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3,
+                num_negatives=64, negative_weight=16.0, margin=0.0, normalize=False, seed=0, resume=False):
+    """SimpleX's cosine contrastive loss (Mao et al. 2021) for a MatrixFactorization with activation 'none'
+    (recoder_amd/ccl.py).  A step takes the (user, stored item) pairs of BPR's draws (those of ``train_bpr`` and
+    ``train_lightgcn`` for the same seed, step and slot), draws ``num_negatives`` items per pair uniformly from the
+    catalogue (``train_ultragcn``'s draws for the same seed, step, slot and index; nothing is rejected) and descends
+    the mean over the pairs of (1 - cos(u, i)) + ``negative_weight`` / ``num_negatives`` times the sum over the
+    negatives of max(0, cos(u, j) - ``margin``), the cosines taken between rows of the final tables.  A negative
+    below the margin is dead: it gets no gradient, and the item-side sum never reads it.  The final tables are
+    LightGCN's mean over ``num_layers`` + 1 layers; ``num_layers = 0`` trains the tables themselves and propagates
+    nothing.  Of SimpleX only the loss is built: the pooling of the user's history, the dropout and the attention
+    pooling are not.  Adam at learning rate ``lr``, the L2 term ``reg`` on the base rows a pair touches as its user
+    or its positive; ``batch_size`` is at most ``ccl.MAX_BATCH``, ``num_negatives`` at most ``ccl.MAX_NEGATIVES``
+    and ``batch_size`` * (1 + ``num_negatives``) at most ``ccl.MAX_ENTRIES``; ``margin`` lies in [-1, 1).  The base
+    tables of a first call are the tables as they stand; they, both Adam moments, the step count and ``num_layers``
+    stay in ``ccl_state`` (device tensors, not part of a checkpoint), and ``resume=True`` continues from them with
+    the draws, moments and step count one longer call would have had.  The model's tables end as the final tables
+    -- un-normalised, or with ``normalize=True`` row-normalised, so that the dot product of ``recommend`` ranks by
+    the cosine the fit trained; the state's base tables are never normalised -- and the bias as 0: ``save_state``,
+    ``recommend``, ``evaluate``, ``train``, ``train_als`` and ``train_bpr`` take them as they are.  The stored values
+    and the configured ``loss`` play no part.  Returns (and keeps in ``ccl_history``) one (positive term, negative
+    term) pair of means per valid pair per epoch; ``ccl_stats`` keeps the mean share of live negatives of each epoch.
+    Validation during the fit and early stopping: ``self.fit_validation`` (``_validated``).  With
+    ``normalize=True`` an evaluation scores the row-normalised tables, as the finished fit would."""
+    from . import ccl
+    hist = self._graph_fit(ccl, "ccl", train_dataset, resume,
+                           "CCL: %d layers, %d epochs of batches of %d, lr %g, reg %g, %d negatives a slot at weight "
+                           "%g, margin %g, normalize %s, seed %d",
+                           num_layers, num_epochs, batch_size, lr, reg, num_negatives, negative_weight, margin,
+                           normalize, seed)
+    self.ccl_stats = list(self.ccl_state["live_share"])
+    return hist
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
