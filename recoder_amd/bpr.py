@@ -96,6 +96,17 @@ def _round256(x):
   return -(-int(x) // 256) * 256
 
 
+def _carve(raw, *fields):
+  """One view of the uint8 allocation ``raw`` per (dtype, shape) of ``fields``, in order, each starting at the next
+  multiple of 256 bytes: how the rk_als_*_workspace_bytes functions lay their buffers out."""
+  views, off = [], 0
+  for dtype, shape in fields:
+    nbytes = torch.empty((), dtype=dtype).element_size() * int(np.prod(shape))
+    views.append(raw[off:off + nbytes].view(dtype).view(shape))
+    off += _round256(nbytes)
+  return views
+
+
 def workspace_bytes(T, h):
   """rk_als_bpr_workspace_bytes(T, h), restated on the host (the memory check needs no library)."""
   T, h = int(T), int(h)
@@ -160,16 +171,8 @@ class Workspace:
     assert need == workspace_bytes(T, h) and need > 0, (need, T, h)
     self.T, self.h = T, h
     self.raw = torch.empty(need, dtype=torch.uint8, device=device)
-    off = 0
-
-    def cut(nbytes, dtype, shape):
-      nonlocal off
-      v = self.raw[off:off + nbytes].view(dtype).view(shape)
-      off += _round256(nbytes)
-      return v
-    self.users, self.pos, self.neg = (cut(4 * T, torch.int32, (T,)) for _ in range(3))
-    self.g, self.loss = (cut(4 * T, torch.float32, (T,)) for _ in range(2))
-    self.D, self.P = (cut(4 * T * h, torch.float32, (T, h)) for _ in range(2))
+    self.users, self.pos, self.neg, self.g, self.loss, self.D, self.P = _carve(
+        self.raw, *[(torch.int32, (T,))] * 3, *[(torch.float32, (T,))] * 2, *[(torch.float32, (T, h))] * 2)
 
 
 def _i32(t, n):

@@ -29,10 +29,11 @@ import torch
 
 from . import _als_lib, als, bpr, lightgcn
 from ._lib import ptr
-from .bpr import _count, _f32, _i32, _number, _round256
+from .bpr import _carve, _count, _f32, _i32, _number, _round256
 from .device import current_stream
 from .lightgcn import _table, new_state  # noqa: F401  (new_state: this module's too)
 from .ssm import normalize_rows
+from .ultragcn import check_entries
 
 MAX_H = als.MAX_H                                   # rk_als_max_h()
 MAX_LAYERS = lightgcn.MAX_LAYERS
@@ -136,16 +137,10 @@ def grad(users, items, num_negatives, seed, step_index, X, Y, margin, negative_w
 def scatter(keys, order, E, users, coef, self_, X, Y, scale, G, count):
   """G[key] = scale (sum coef[e] X[users[e / E]] - (sum self_[e]) Y[key]) and count[key] = the key's positives, for
   the rows among the sorted keys (rk_als_ccl_scatter); the caller zeroes G and count."""
-  n, T = keys.shape[0], users.shape[0]
-  E = int(E)
-  if not (2 <= E <= 1 + MAX_NEGATIVES and n == T * E and 1 <= T <= MAX_BATCH and n <= MAX_ENTRIES):
-    raise ValueError("rk_als_ccl_scatter needs n = T E keys, 2 <= E <= %d, 1 <= T <= %d and n <= %d (got n = %d, "
-                     "T = %d, E = %d)" % (1 + MAX_NEGATIVES, MAX_BATCH, MAX_ENTRIES, n, T, E))
-  _i32(keys, n), _i32(users, T), _table(X), _table(Y, X.shape[1]), _table(G, X.shape[1]), _i32(count, G.shape[0])
+  n, E = check_entries("rk_als_ccl_scatter", keys, order, E, users, (coef, self_), X, G, count, MAX_BATCH, MAX_ENTRIES,
+                       1 + MAX_NEGATIVES)
+  _table(Y, X.shape[1])
   assert Y.shape[0] >= G.shape[0], (Y.shape, G.shape)
-  assert order.dtype == torch.int64 and order.shape == (n,) and order.is_contiguous()
-  for t in (coef, self_):
-    assert t.dtype == torch.float32 and t.numel() == n and t.is_contiguous()
   lib = _als_lib.load()
   _als_lib.check(lib.rk_als_ccl_scatter(ptr(keys), ptr(order), n, E, ptr(users), ptr(coef), ptr(self_), ptr(X),
                                         X.stride(0), X.shape[0], ptr(Y), Y.stride(0), X.shape[1], float(scale),
@@ -167,13 +162,9 @@ class Workspace(lightgcn.Workspace):
     self.num_negatives = R
     E = 1 + R
     self.raw = torch.empty(need, dtype=torch.uint8, device=device)
-    a = _round256(4 * T * E)
-    cut = lambda k, dtype: self.raw[k * a:k * a + 4 * T * E].view(dtype).view(T, E)
-    self.cand, self.key = cut(0, torch.int32), cut(1, torch.int32)
-    self.coef, self.self_ = cut(2, torch.float32), cut(3, torch.float32)
-    b = 4 * a + _round256(8 * T)
-    self.loss = self.raw[4 * a:4 * a + 8 * T].view(torch.float32).view(T, 2)
-    self.live = self.raw[b:b + 4 * T].view(torch.int32)
+    self.cand, self.key, self.coef, self.self_, self.loss, self.live = _carve(
+        self.raw, *[(torch.int32, (T, E))] * 2, *[(torch.float32, (T, E))] * 2, (torch.float32, (T, 2)),
+        (torch.int32, (T,)))
 
 
 def gradient(X, Y, graph, state, ws, seed, step_index, hyper):

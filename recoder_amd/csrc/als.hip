@@ -50,15 +50,19 @@
 //   rk_als_ugcn_grad       the constraint loss of every slot over its positive, R private uniform negatives and the
 //                          positive's K neighbours: one wave per slot, the candidates' rows gathered several at a
 //                          time by lane groups of 16, 32 or 64, the loss terms and DU in ascending candidate order
-//   rk_als_ugcn_scatter    the item side: the scatter's segment walk with the user rows gathered through the slot,
-//                          a key of RK_ALS_UGCN_LONG_KEY entries or more by a workgroup of 16 waves in fixed parts
+//   rk_als_ugcn_scatter    the item side, the entry scatter: the scatter's segment walk with the user rows gathered
+//                          through the slot, a key of RK_ALS_UGCN_LONG_KEY entries or more by a workgroup of 16 waves
+//                          in fixed parts
+// als/ugcn.h also holds what the losses with private per-slot negatives share: the candidate round of the grad kernels
+// (the draw, the round's gather, the way back to the owning lane; dispatch_group picks the lane groups) and the
+// entry scatter's one pair of kernels and one launcher.
 //
 // SimpleX's cosine contrastive loss for the same model (rk_als_ccl_*): the step of recoder_amd/ccl.py adds
 //   rk_als_ccl_grad        the hinge on the cosine of every slot over its positive and R private uniform negatives
-//                          (rk_als_ugcn_grad's draws): norm and dot product from one gathered copy of a row, a dead
+//                          (ugcn.h's candidate round): norm and dot product from one gathered copy of a row, a dead
 //                          negative dropped at once, a live row used for DU while it is in registers
-//   rk_als_ccl_scatter     rk_als_ugcn_scatter's walk over the keys of the live entries only (the dead carry a
-//                          sentinel that sorts last), with the row's own -sum self Y[key] term
+//   rk_als_ccl_scatter     the entry scatter (the same kernels, SELF) over the keys of the live entries only (the dead
+//                          carry a sentinel that sorts last), with the row's own -sum self Y[key] term
 //
 // Ranking metrics on device-resident top-k lists (rk_als_rank_metrics): what recoder_amd/validation.py reads per epoch
 //   rk_als_rank_metrics    one wave per user: a binary search of each rank's id in the user's target row, a ballot per
@@ -67,14 +71,14 @@
 //
 // One translation unit (one last-error buffer, one anonymous namespace), laid out by family under als/: every file
 // holds its kernels, then its extern "C" entry points.
-#include "als/common.h"     // the lane layout, the counter hash, the segment walk, the NT dispatch
+#include "als/common.h"     // the lane layout, the counter hash, the segment walk, the NT and lane-group dispatch
 #include "als/solve.h"      // rk_als_gram, rk_als_solve, rk_als_objective
 #include "als/pairwise.h"   // rk_als_bpr_*, rk_als_rank_sample, rk_als_warp_grad
 #include "als/lgcn.h"       // rk_als_lgcn_*, rk_als_gcl_propagate
 #include "als/contrast.h"   // rk_als_gcl_contrast, rk_als_dau_*
 #include "als/ssm.h"        // rk_als_ssm_*
-#include "als/ugcn.h"       // rk_als_ugcn_*
-#include "als/ccl.h"        // rk_als_ccl_*
+#include "als/ugcn.h"       // rk_als_ugcn_*, the candidate round, the entry scatter
+#include "als/ccl.h"        // rk_als_ccl_* (on ugcn.h)
 #include "als/metrics.h"    // rk_als_rank_metrics
 
 extern "C" int rk_als_version(void) { return 100; }

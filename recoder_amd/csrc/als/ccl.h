@@ -5,9 +5,9 @@ namespace {
 
 // ------------------------------------------------------------------------ ccl
 // SimpleX's cosine contrastive loss (rk_als_ccl_grad): one wave per slot, the user's row normalised once in
-// registers (a = p / |p|).  The E = 1 + R candidates go 64 at a time, as in als_ugcn_grad_kernel: lane l prepares
-// candidate e0 + l (the positive, or UltraGCN's draw of (seed, step, t R + r) under UGCN_TAG), and the candidates are
-// scored UG_G rows of a lane group at a time, the row gathers issued before any is reduced.  Norm and dot product
+// registers (a = p / |p|).  The E = 1 + R candidates go 64 at a time through ugcn.h's candidate round: lane l prepares
+// candidate e0 + l (the positive, or UltraGCN's draw: entry_draw), and the candidates are scored UG_G rows of a lane
+// group at a time (entry_gather), the row gathers issued before any is reduced.  Norm and dot product
 // come from the one gathered copy of a row: two fmaf chains over the lane's registers, then the xor butterfly of the
 // group's W lanes each, so that every lane of the group holds c = (a . y) (1 / sqrt(y . y)) and decides by itself
 // whether the candidate is live.  A dead negative is never touched again; a live row (and the positive's) goes
@@ -16,6 +16,7 @@ namespace {
 // the groups' acc and sc are added in ascending g at the end), DU_k = (acc_k - sc a_k) / |p|.  c and 1 / |y| go back
 // to the lane that owns the candidate, which forms key, coef and self and the loss terms: a lane's live negatives
 // summed over the chunks in ascending e, then by wave_sum.
+// The item side (rk_als_ccl_scatter) has no kernel here: it is ugcn.h's entry scatter with SELF.
 template <int NT, int W>
 __global__ __launch_bounds__(256) void als_ccl_grad_kernel(
     const int32_t *__restrict__ users, const int32_t *__restrict__ items, int T, int R, uint64_t seed_key,
@@ -77,24 +78,13 @@ __global__ __launch_bounds__(256) void als_ccl_grad_kernel(
     if (e == 0) {
       id = i;
     } else if (e <= R) {
-      const uint64_t dk = mix64(seed_key ^ (((uint64_t)step << 32) | UGCN_TAG | (draw0 + (uint32_t)(e - 1))));
-      id = (int)draw32(dk, 0, (uint32_t)n_items);
+      id = entry_draw(seed_key, step, draw0, e, n_items);
     }
     float mc = 0.f, mi = 0.f;                     // this lane's candidate: its cosine and 1 / its norm
     const int here = min(64, E - e0);
     for (int r0 = 0; r0 < here; r0 += ROUND) {
-      int cg[UG_G];
       float y[UG_G][NT], cs[UG_G], iv[UG_G];
-#pragma unroll
-      for (int g = 0; g < UG_G; ++g) cg[g] = __shfl(id, r0 + g * C + sub, 64);
-#pragma unroll
-      for (int g = 0; g < UG_G; ++g) {
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-          const int k = kk + 64 * q;
-          y[g][q] = (cg[g] < n_items && k < h) ? Y[(int64_t)cg[g] * ldy + k] : 0.f;
-        }
-      }
+      entry_gather<NT, W>(id, r0, lane, Y, ldy, n_items, h, y);
 #pragma unroll
       for (int g = 0; g < UG_G; ++g) {
         float d = 0.f, n2 = 0.f;
@@ -122,16 +112,8 @@ __global__ __launch_bounds__(256) void als_ccl_grad_kernel(
           sc = fmaf(w, cs[g], sc);
         }
       }
-#pragma unroll
-      for (int g = 0; g < UG_G; ++g) {            // the cosine and the norm to the lane that owns the candidate
-        const int first = r0 + g * C;
-        const int from = ((lane - first) & (C - 1)) * W;
-        const float vc = __shfl(cs[g], from, 64), vi = __shfl(iv[g], from, 64);
-        if ((unsigned)(lane - first) < (unsigned)C) {
-          mc = vc;
-          mi = vi;
-        }
-      }
+      entry_to_owner<W>(cs, r0, lane, mc);        // the cosine and the norm to the lane that owns the candidate
+      entry_to_owner<W>(iv, r0, lane, mi);
     }
     if (e < E) {
       const bool lv = e >= 1 && mc - margin > 0.f;
@@ -174,125 +156,6 @@ __global__ __launch_bounds__(256) void als_ccl_grad_kernel(
   }
 }
 
-// The sum of self over the sorted positions [s_lo, s_hi), under ugcn_walk's validity of an entry: lane l adds the
-// positions s_lo + l + 64 j in ascending j, then wave_sum.
-__device__ __forceinline__ float ccl_self_sum(const int64_t *__restrict__ order, int s_lo, int s_hi, int n, int E,
-                                              const int32_t *__restrict__ users, int n_users,
-                                              const float *__restrict__ self, int lane) {
-  float ss = 0.f;
-  for (int s = s_lo + lane; s < s_hi; s += 64) {
-    const int64_t e = order[s];
-    const bool in = e >= 0 && e < n;
-    const uint32_t ee = in ? (uint32_t)e : 0u;
-    const int u = in ? users[ee / (uint32_t)E] : -1;
-    ss += (u >= 0 && u < n_users) ? self[ee] : 0.f;
-  }
-  return wave_sum(ss);
-}
-
-// The item side (rk_als_ccl_scatter): als_ugcn_scatter_kernel's hand-out and walk (ugcn_walk) over the sorted keys,
-// which end at the first sentinel: a dead entry's key is not below n_rows, so nothing of it is gathered.
-template <int NT>
-__global__ __launch_bounds__(256) void als_ccl_scatter_kernel(
-    const int32_t *__restrict__ keys, const int64_t *__restrict__ order, int n, int E,
-    const int32_t *__restrict__ users, const float *__restrict__ coef, const float *__restrict__ self,
-    const float *__restrict__ X, int ldx, int n_users, const float *__restrict__ Y, int ldy, int h, float scale,
-    int n_rows, float *__restrict__ Gt, int ldg, int32_t *__restrict__ count) {
-  const int lane = threadIdx.x & 63;
-  const int s0 = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (s0 >= n) return;
-  const int key = keys[s0];
-  if (key < 0 || key >= n_rows) return;                  // (the sentinels and invalid entries, sorted last)
-  if (s0 > 0 && keys[s0 - 1] == key) return;             // (not a head)
-  int c = 0;
-  for (;;) {
-    const int s = s0 + c + lane;
-    const bool same = s < n && keys[s] == key;
-    const uint64_t m = __ballot(!same);
-    if (m) {
-      c += __ffsll((unsigned long long)m) - 1;
-      break;
-    }
-    c += 64;
-    if (c >= UG_LONG) return;                            // (a long key)
-  }
-  if (c >= UG_LONG) return;
-  float acc[NT];
-#pragma unroll
-  for (int q = 0; q < NT; ++q) acc[q] = 0.f;
-  int cnt = 0;
-  ugcn_walk<NT>(order, s0, s0 + c, n, E, users, n_users, coef, X, ldx, h, lane, acc, cnt);
-  const float ss = ccl_self_sum(order, s0, s0 + c, n, E, users, n_users, self, lane);
-  float *row = Gt + (int64_t)key * ldg;
-#pragma unroll
-  for (int q = 0; q < NT; ++q) {
-    const int k = lane + 64 * q;
-    if (k < h) row[k] = scale * fmaf(-ss, Y[(int64_t)key * ldy + k], acc[q]);
-  }
-  if (lane == 0) count[key] = cnt;
-}
-
-// The long keys, as als_ugcn_scatter_long_kernel hands them out: wave w sums part w of UG_LONG_WAVES equal parts,
-// the coefficients' chain and the part's self sum; thread k adds the parts' sums in ascending w.
-template <int NT>
-__global__ __launch_bounds__(64 * UG_LONG_WAVES) void als_ccl_scatter_long_kernel(
-    const int32_t *__restrict__ keys, const int64_t *__restrict__ order, int n, int E,
-    const int32_t *__restrict__ users, const float *__restrict__ coef, const float *__restrict__ self,
-    const float *__restrict__ X, int ldx, int n_users, const float *__restrict__ Y, int ldy, int h, float scale,
-    int n_rows, float *__restrict__ Gt, int ldg, int32_t *__restrict__ count) {
-  __shared__ float red[UG_LONG_WAVES][64 * NT];
-  __shared__ float selfs[UG_LONG_WAVES];
-  __shared__ int cnts[UG_LONG_WAVES];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int at = blockIdx.x * UG_LONG;
-  if (at >= n) return;                                   // (workgroup-uniform, as every return below)
-  const int key = keys[at];
-  if (key < 0 || key >= n_rows) return;
-  int lo = 0, hi = at;                                   // the first position with keys[.] >= key, in [0, at]
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  const int s_lo = lo;
-  if (at - s_lo >= UG_LONG) return;                      // (an earlier workgroup's)
-  lo = at + 1, hi = n;                                   // the first position with keys[.] > key, in (at, n]
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] <= key) lo = mid + 1; else hi = mid;
-  }
-  const int s_hi = lo, c = s_hi - s_lo;
-  if (c < UG_LONG) return;
-  const int part = (c + UG_LONG_WAVES - 1) / UG_LONG_WAVES;
-  const int p_lo = min(s_lo + wv * part, s_hi), p_hi = min(s_lo + (wv + 1) * part, s_hi);
-  float acc[NT];
-#pragma unroll
-  for (int q = 0; q < NT; ++q) acc[q] = 0.f;
-  int cnt = 0;
-  ugcn_walk<NT>(order, p_lo, p_hi, n, E, users, n_users, coef, X, ldx, h, lane, acc, cnt);
-  const float ss = ccl_self_sum(order, p_lo, p_hi, n, E, users, n_users, self, lane);
-#pragma unroll
-  for (int q = 0; q < NT; ++q) red[wv][lane + 64 * q] = acc[q];
-  if (lane == 0) {
-    cnts[wv] = cnt;
-    selfs[wv] = ss;
-  }
-  __syncthreads();
-  const int k = threadIdx.x;
-  if (k < h) {
-    float s = red[0][k], st = selfs[0];
-    for (int w = 1; w < UG_LONG_WAVES; ++w) {
-      s += red[w][k];
-      st += selfs[w];
-    }
-    Gt[(int64_t)key * ldg + k] = scale * fmaf(-st, Y[(int64_t)key * ldy + k], s);
-  }
-  if (k == 0) {
-    int total = 0;
-    for (int w = 0; w < UG_LONG_WAVES; ++w) total += cnts[w];
-    count[key] = total;
-  }
-}
-
 }  // namespace
 
 extern "C" int64_t rk_als_ccl_workspace_bytes(int32_t T, int32_t R, int32_t h) {
@@ -312,15 +175,13 @@ extern "C" int rk_als_ccl_grad(const int32_t *users, const int32_t *items, int32
   RK_SIDE_REQUIRE(n_users >= 1 && n_items >= 1 && step >= 0, "n_users, n_items >= 1, step >= 0");
   RK_SIDE_REQUIRE(users && items && X && Y && cand && key && coef && self && DU && valid && loss && live,
                   "null pointer");
-  auto launch = [&](auto nt, auto w) {                   // (w: the lanes of a group, the wave itself above h = 32)
+  auto launch = [&](auto nt, auto w) {
     hipLaunchKernelGGL((als_ccl_grad_kernel<decltype(nt)::value, decltype(w)::value>), dim3((unsigned)((T + 3) / 4)),
                        dim3(256), 0, (hipStream_t)stream, users, items, T, R, mix64((uint64_t)seed), (uint32_t)step,
                        n_users, n_items, X, ldx, Y, ldy, h, margin, negative_weight / (float)R, cand, key, coef, self,
                        DU, valid, loss, live);
   };
-  if (h <= 16) launch(Int<1>{}, Int<16>{});
-  else if (h <= 32) launch(Int<1>{}, Int<32>{});
-  else dispatch_nt(h, [&](auto nt) { launch(nt, Int<64>{}); });
+  dispatch_group(h, launch);
   RK_SIDE_CHECK_LAUNCH("als_ccl_grad");
   return 0;
 }
@@ -335,15 +196,9 @@ extern "C" int rk_als_ccl_scatter(const int32_t *keys, const int64_t *order, int
                   "n = T E, 2 <= E <= 1025, 1 <= T <= 4096, n <= 2^22");
   RK_SIDE_REQUIRE(n_users >= 1 && n_rows >= 1, "n_users, n_rows >= 1");
   RK_SIDE_REQUIRE(keys && order && users && coef && self && X && Y && G && count, "null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  dispatch_nt(h, [&](auto nt) {
-    constexpr int NT = decltype(nt)::value;
-    hipLaunchKernelGGL(als_ccl_scatter_kernel<NT>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, keys, order, n, E,
-                       users, coef, self, X, ldx, n_users, Y, ldy, h, scale, n_rows, G, ldg, count);
-    hipLaunchKernelGGL(als_ccl_scatter_long_kernel<NT>, dim3((unsigned)((n + UG_LONG - 1) / UG_LONG)),
-                       dim3(64 * UG_LONG_WAVES), 0, st, keys, order, n, E, users, coef, self, X, ldx, n_users, Y, ldy,
-                       h, scale, n_rows, G, ldg, count);
-  });
+  // (the keys end at the first sentinel: a dead entry's key is not below n_rows, so nothing of it is gathered)
+  entry_scatter<true>(keys, order, n, E, users, coef, self, X, ldx, n_users, Y, ldy, h, scale, n_rows, G, ldg, count,
+                      stream);
   RK_SIDE_CHECK_LAUNCH("als_ccl_scatter");
   return 0;
 }

@@ -35,6 +35,15 @@ void dispatch_nt(int h, F &&f) {
   else f(Int<8>{});
 }
 
+// f(Int<NT>{}, Int<W>{}) for the kernels whose wave is 64 / W lane groups of W lanes (the candidate round of
+// als/ugcn.h): W = 16 or 32 with a dimension a lane while h fits a group, else the wave itself with dispatch_nt's NT.
+template <class F>
+void dispatch_group(int h, F &&f) {
+  if (h <= 16) f(Int<1>{}, Int<16>{});
+  else if (h <= 32) f(Int<1>{}, Int<32>{});
+  else dispatch_nt(h, [&](auto nt) { f(nt, Int<64>{}); });
+}
+
 // ---------------------------------------------------------------------- rows
 // Lane l of a wave owns dimensions k = l + 64 q (q < NT) of a row; every dot product is a per-lane fmaf chain over
 // q ascending from +0, then an xor butterfly (a + b == b + a bitwise: every lane ends with the same value, so
@@ -93,8 +102,10 @@ __host__ __device__ __forceinline__ uint32_t draw32(uint64_t slot_key, uint32_t 
 // The hand-out of rk_als_bpr_apply and rk_als_lgcn_scatter: one wave per sorted position s0; the wave at the head
 // of a run of equal keys owns that row, the others leave (false).  So does a key outside [0, n_rows): the invalid
 // slots' sentinel, sorted last.  c = the run's length: 64 keys at a time, the first lane whose key differs.
-// (als_ugcn_scatter_kernel keeps this scan written out, with its hand-over of long keys: through this function it
-// compiled to other, slower code.)
+// (als_entry_scatter_kernel of ugcn.h keeps this scan written out, with its hand-over of long keys: through this
+// function it once compiled to other, slower code.  When UltraGCN's and CCL's scatters became that one kernel the scan
+// was left where it was, now the only copy beside this one, and was not routed through here again: every
+// instantiation kept the registers it had.)
 __device__ __forceinline__ bool segment_head(const int32_t *__restrict__ keys, int n, int n_rows, int s0, int lane,
                                              int &key, int &c) {
   if (s0 >= n) return false;

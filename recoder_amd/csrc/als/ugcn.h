@@ -5,15 +5,17 @@ namespace {
 
 // ----------------------------------------------------------------------- ugcn
 // UltraGCN's constraint loss (rk_als_ugcn_grad): one wave per slot, p_u in registers.  The E = 1 + R + K candidates
-// go 64 at a time: lane l prepares candidate e0 + l -- the positive, a draw (item = draw32(key, 0, n_items), key a
-// hash of (seed, step, t R + r) whose low word carries the tag 0xA0000000: a sampler slot is below 2^24, SimGCL's
-// noise has the top byte 0x80, the sampled softmax's shared draws 0xC0) or a neighbour of the positive -- with its
-// weight a and the sign of its logit.  The candidates are then scored UG_G rows of a lane group at a time, the row
-// gathers issued before any is reduced.  At h <= 32 a group is W = 32 or 16 lanes and the wave's 64 / W groups
-// score as many candidates side by side; at larger h the group is the wave.  A score goes back to the lane that
-// owns the candidate, which forms coef = sign a sigma(sign s); the owners' coefs come back to the groups, and DU
-// takes coef y in ascending e (fmaf at W = 64; the groups' products one after the other below that).  The loss
-// terms are formed once per 64 candidates, a lane each, and summed per lane over the chunks, then by wave_sum.
+// go 64 at a time: lane l prepares candidate e0 + l -- the positive, a draw (entry_draw) or a neighbour of the
+// positive -- with its weight a and the sign of its logit.  The candidates are then scored a round at a time
+// (entry_gather, entry_to_owner: the candidate round below, which als_ccl_grad_kernel of ccl.h runs too).  A score
+// goes back to the lane that owns the candidate, which forms coef = sign a sigma(sign s); the owners' coefs come back
+// to the groups, and DU takes coef y in ascending e (fmaf at W = 64; the groups' products one after the other below
+// that).  The loss terms are formed once per 64 candidates, a lane each, and summed per lane over the chunks, then by
+// wave_sum.
+//
+// This file also holds what every loss with private per-slot negatives shares: the candidate round of its grad kernel
+// and the item side's entry scatter (als_entry_scatter_kernel and its long-key partner, launched by entry_scatter),
+// which rk_als_ugcn_scatter and rk_als_ccl_scatter both are.
 constexpr int UG_MAX_T = RK_ALS_UGCN_MAX_BATCH, UG_MAX_R = RK_ALS_UGCN_MAX_NEGATIVES;
 constexpr int UG_MAX_K = RK_ALS_UGCN_MAX_NEIGHBOURS, UG_MAX_ENTRIES = RK_ALS_UGCN_MAX_ENTRIES;
 constexpr uint32_t UGCN_TAG = 0xA0000000u;
@@ -26,6 +28,53 @@ __device__ __forceinline__ float ug_sigmoid(float x) {
   return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
 }
 __device__ __forceinline__ float ug_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+// ------------------------------------------------------------ candidate round
+// A slot's wave is 64 / W lane groups of W lanes (W = 16 or 32 at h <= 16 or 32, a dimension a lane; else the wave,
+// NT dimensions a lane: dispatch_group).  Lane l owns candidate e0 + l of a chunk of 64; a round scores
+// ROUND = UG_G 64 / W of them, group sub taking the candidates r0 + g 64 / W + sub (g < UG_G), their UG_G rows
+// gathered before any is reduced.
+//
+// Negative r (candidate e = 1 + r) of slot t: draw32 of a key that hashes (seed, step, t R + r), whose low word
+// carries the tag 0xA0000000 (a sampler slot is below 2^24, SimGCL's noise has the top byte 0x80, the sampled
+// softmax's shared draws 0xC0); draw0 = t R.
+__device__ __forceinline__ int entry_draw(uint64_t seed_key, uint32_t step, uint32_t draw0, int e, int n_items) {
+  const uint64_t key = mix64(seed_key ^ (((uint64_t)step << 32) | UGCN_TAG | (draw0 + (uint32_t)(e - 1))));
+  return (int)draw32(key, 0, (uint32_t)n_items);
+}
+
+// y[g] = this lane's dimensions of the row of the g-th candidate of its group in the round at r0: the ids come from
+// the owners by __shfl; +0 for an id that is no item (n_items: no candidate there) and past h.
+template <int NT, int W>
+__device__ __forceinline__ void entry_gather(int id, int r0, int lane, const float *__restrict__ Y, int ldy,
+                                             int n_items, int h, float (&y)[UG_G][NT]) {
+  constexpr int C = 64 / W;
+  const int sub = lane / W, kk = lane % W;
+  int cg[UG_G];
+#pragma unroll
+  for (int g = 0; g < UG_G; ++g) cg[g] = __shfl(id, r0 + g * C + sub, 64);
+#pragma unroll
+  for (int g = 0; g < UG_G; ++g) {
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int k = kk + 64 * q;
+      y[g][q] = (cg[g] < n_items && k < h) ? Y[(int64_t)cg[g] * ldy + k] : 0.f;
+    }
+  }
+}
+
+// mine = s[g] of the group that scored this lane's candidate, for the owners of the round at r0 (every lane of a
+// group holds the same s[g]); the other lanes keep theirs.
+template <int W>
+__device__ __forceinline__ void entry_to_owner(const float (&s)[UG_G], int r0, int lane, float &mine) {
+  constexpr int C = 64 / W;
+#pragma unroll
+  for (int g = 0; g < UG_G; ++g) {
+    const int first = r0 + g * C;
+    const float v = __shfl(s[g], ((lane - first) & (C - 1)) * W, 64);
+    if ((unsigned)(lane - first) < (unsigned)C) mine = v;
+  }
+}
 
 template <int NT, int W>
 __global__ __launch_bounds__(256) void als_ugcn_grad_kernel(
@@ -79,8 +128,7 @@ __global__ __launch_bounds__(256) void als_ugcn_grad_kernel(
       id = i;
       a = fmaf(w2, bu_u * bi[i], w1);
     } else if (e <= R) {
-      const uint64_t key = mix64(seed_key ^ (((uint64_t)step << 32) | UGCN_TAG | (draw0 + (uint32_t)(e - 1))));
-      id = (int)draw32(key, 0, (uint32_t)n_items);
+      id = entry_draw(seed_key, step, draw0, e, n_items);
       a = neg_scale * fmaf(w4, bu_u * bi[id], w3);
       sg = 1.f;
     } else if (e < E) {
@@ -94,18 +142,8 @@ __global__ __launch_bounds__(256) void als_ugcn_grad_kernel(
     float ms = 0.f, mc = 0.f;                     // this lane's candidate: its score and its coef
     const int live = min(64, E - e0);
     for (int r0 = 0; r0 < live; r0 += ROUND) {
-      int cg[UG_G];
       float y[UG_G][NT], s[UG_G];
-#pragma unroll
-      for (int g = 0; g < UG_G; ++g) cg[g] = __shfl(id, r0 + g * C + sub, 64);
-#pragma unroll
-      for (int g = 0; g < UG_G; ++g) {
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-          const int k = kk + 64 * q;
-          y[g][q] = (cg[g] < n_items && k < h) ? Y[(int64_t)cg[g] * ldy + k] : 0.f;
-        }
-      }
+      entry_gather<NT, W>(id, r0, lane, Y, ldy, n_items, h, y);
 #pragma unroll
       for (int g = 0; g < UG_G; ++g) {
         float d = 0.f;
@@ -115,12 +153,7 @@ __global__ __launch_bounds__(256) void als_ugcn_grad_kernel(
         for (int off = W / 2; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
         s[g] = d;
       }
-#pragma unroll
-      for (int g = 0; g < UG_G; ++g) {            // the score to the lane that owns the candidate
-        const int first = r0 + g * C;
-        const float v = __shfl(s[g], ((lane - first) & (C - 1)) * W, 64);
-        if ((unsigned)(lane - first) < (unsigned)C) ms = v;
-      }
+      entry_to_owner<W>(s, r0, lane, ms);         // the score to the lane that owns the candidate
       const float cf = id < n_items ? (sg * a) * ug_sigmoid(sg * ms) : 0.f;
       if ((unsigned)(lane - r0) < (unsigned)ROUND) mc = cf;
 #pragma unroll
@@ -159,8 +192,10 @@ __global__ __launch_bounds__(256) void als_ugcn_grad_kernel(
   }
 }
 
-// The item side (rk_als_ugcn_scatter).  acc_k = fmaf(coef[e], X[users[e / E], k], acc_k) over the sorted positions
-// [s_lo, s_hi) from what acc holds, SEG_UNROLL user rows gathered before any is added; cnt counts the positives.
+// -------------------------------------------------------------- entry scatter
+// The item side (rk_als_ugcn_scatter; with SELF, rk_als_ccl_scatter) over the n = T E entries sorted by key.
+// acc_k = fmaf(coef[e], X[users[e / E], k], acc_k) over the sorted positions [s_lo, s_hi) from what acc holds,
+// SEG_UNROLL user rows gathered before any is added; cnt counts the positives.
 template <int NT>
 __device__ __forceinline__ void ugcn_walk(const int64_t *__restrict__ order, int s_lo, int s_hi, int n, int E,
                                           const int32_t *__restrict__ users, int n_users,
@@ -194,18 +229,38 @@ __device__ __forceinline__ void ugcn_walk(const int64_t *__restrict__ order, int
   }
 }
 
+// The sum of self over the sorted positions [s_lo, s_hi), under ugcn_walk's validity of an entry: lane l adds the
+// positions s_lo + l + 64 j in ascending j, then wave_sum.
+__device__ __forceinline__ float entry_self_sum(const int64_t *__restrict__ order, int s_lo, int s_hi, int n, int E,
+                                                const int32_t *__restrict__ users, int n_users,
+                                                const float *__restrict__ self, int lane) {
+  float ss = 0.f;
+  for (int s = s_lo + lane; s < s_hi; s += 64) {
+    const int64_t e = order[s];
+    const bool in = e >= 0 && e < n;
+    const uint32_t ee = in ? (uint32_t)e : 0u;
+    const int u = in ? users[ee / (uint32_t)E] : -1;
+    ss += (u >= 0 && u < n_users) ? self[ee] : 0.f;
+  }
+  return wave_sum(ss);
+}
+
 // als_lgcn_scatter_kernel's hand-out: one wave per sorted position, the wave at the head of a segment of equal keys
-// owns that row.  A segment of UG_LONG entries or more is left to als_ugcn_scatter_long_kernel.
-template <int NT>
-__global__ __launch_bounds__(256) void als_ugcn_scatter_kernel(
+// owns that row.  A segment of UG_LONG entries or more is left to als_entry_scatter_long_kernel.  The keys end at the
+// first one outside [0, n_rows): absent and invalid entries and, with SELF, the dead ones, of which nothing is
+// gathered.  The row is scale acc; with SELF (self, Y and ldy are read only then) it is
+// scale fmaf(-ss, Y[key], acc), ss the run's entry_self_sum, taken after the walk.
+template <int NT, bool SELF>
+__global__ __launch_bounds__(256) void als_entry_scatter_kernel(
     const int32_t *__restrict__ keys, const int64_t *__restrict__ order, int n, int E,
-    const int32_t *__restrict__ users, const float *__restrict__ coef, const float *__restrict__ X, int ldx,
-    int n_users, int h, float scale, int n_rows, float *__restrict__ Gt, int ldg, int32_t *__restrict__ count) {
+    const int32_t *__restrict__ users, const float *__restrict__ coef, const float *__restrict__ self,
+    const float *__restrict__ X, int ldx, int n_users, const float *__restrict__ Y, int ldy, int h, float scale,
+    int n_rows, float *__restrict__ Gt, int ldg, int32_t *__restrict__ count) {
   const int lane = threadIdx.x & 63;
   const int s0 = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (s0 >= n) return;
   const int key = keys[s0];
-  if (key < 0 || key >= n_rows) return;                  // (absent and invalid entries, sorted last)
+  if (key < 0 || key >= n_rows) return;                  // (sorted last)
   if (s0 > 0 && keys[s0 - 1] == key) return;             // (not a head)
   int c = 0;
   for (;;) {                                             // segment_head's scan, leaving once the key is a long one
@@ -225,11 +280,16 @@ __global__ __launch_bounds__(256) void als_ugcn_scatter_kernel(
   for (int q = 0; q < NT; ++q) acc[q] = 0.f;
   int cnt = 0;
   ugcn_walk<NT>(order, s0, s0 + c, n, E, users, n_users, coef, X, ldx, h, lane, acc, cnt);
+  float ss = 0.f;
+  if constexpr (SELF) ss = entry_self_sum(order, s0, s0 + c, n, E, users, n_users, self, lane);
   float *row = Gt + (int64_t)key * ldg;
 #pragma unroll
   for (int q = 0; q < NT; ++q) {
     const int k = lane + 64 * q;
-    if (k < h) row[k] = scale * acc[q];
+    if (k < h) {
+      if constexpr (SELF) row[k] = scale * fmaf(-ss, Y[(int64_t)key * ldy + k], acc[q]);
+      else row[k] = scale * acc[q];
+    }
   }
   if (lane == 0) count[key] = cnt;
 }
@@ -237,13 +297,16 @@ __global__ __launch_bounds__(256) void als_ugcn_scatter_kernel(
 // The long keys: a segment of c >= UG_LONG equal keys holds a position that is a multiple of UG_LONG; workgroup b
 // looks at position b UG_LONG, finds the ends of its segment in the sorted keys and takes the segment when that
 // position is the first such multiple in it.  Wave w sums part w of UG_LONG_WAVES equal parts (the last may be
-// shorter or empty) as one chain; thread k adds the parts' sums in ascending w.
-template <int NT>
-__global__ __launch_bounds__(64 * UG_LONG_WAVES) void als_ugcn_scatter_long_kernel(
+// shorter or empty): the coefficients' chain and, with SELF, the part's entry_self_sum after it; thread k adds the
+// parts' sums in ascending w.
+template <int NT, bool SELF>
+__global__ __launch_bounds__(64 * UG_LONG_WAVES) void als_entry_scatter_long_kernel(
     const int32_t *__restrict__ keys, const int64_t *__restrict__ order, int n, int E,
-    const int32_t *__restrict__ users, const float *__restrict__ coef, const float *__restrict__ X, int ldx,
-    int n_users, int h, float scale, int n_rows, float *__restrict__ Gt, int ldg, int32_t *__restrict__ count) {
+    const int32_t *__restrict__ users, const float *__restrict__ coef, const float *__restrict__ self,
+    const float *__restrict__ X, int ldx, int n_users, const float *__restrict__ Y, int ldy, int h, float scale,
+    int n_rows, float *__restrict__ Gt, int ldg, int32_t *__restrict__ count) {
   __shared__ float red[UG_LONG_WAVES][64 * NT];
+  __shared__ float selfs[UG_LONG_WAVES];                 // (SELF only)
   __shared__ int cnts[UG_LONG_WAVES];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int at = blockIdx.x * UG_LONG;
@@ -265,20 +328,29 @@ __global__ __launch_bounds__(64 * UG_LONG_WAVES) void als_ugcn_scatter_long_kern
   const int s_hi = lo, c = s_hi - s_lo;
   if (c < UG_LONG) return;
   const int part = (c + UG_LONG_WAVES - 1) / UG_LONG_WAVES;
+  const int p_lo = min(s_lo + wv * part, s_hi), p_hi = min(s_lo + (wv + 1) * part, s_hi);
   float acc[NT];
 #pragma unroll
   for (int q = 0; q < NT; ++q) acc[q] = 0.f;
   int cnt = 0;
-  ugcn_walk<NT>(order, min(s_lo + wv * part, s_hi), min(s_lo + (wv + 1) * part, s_hi), n, E, users, n_users, coef, X,
-                ldx, h, lane, acc, cnt);
+  ugcn_walk<NT>(order, p_lo, p_hi, n, E, users, n_users, coef, X, ldx, h, lane, acc, cnt);
 #pragma unroll
   for (int q = 0; q < NT; ++q) red[wv][lane + 64 * q] = acc[q];
   if (lane == 0) cnts[wv] = cnt;
+  if constexpr (SELF) {
+    const float ss = entry_self_sum(order, p_lo, p_hi, n, E, users, n_users, self, lane);
+    if (lane == 0) selfs[wv] = ss;
+  }
   __syncthreads();
   const int k = threadIdx.x;
   if (k < h) {
     float s = red[0][k];
     for (int w = 1; w < UG_LONG_WAVES; ++w) s += red[w][k];
+    if constexpr (SELF) {
+      float st = selfs[0];
+      for (int w = 1; w < UG_LONG_WAVES; ++w) st += selfs[w];
+      s = fmaf(-st, Y[(int64_t)key * ldy + k], s);
+    }
     Gt[(int64_t)key * ldg + k] = scale * s;
   }
   if (k == 0) {
@@ -286,6 +358,22 @@ __global__ __launch_bounds__(64 * UG_LONG_WAVES) void als_ugcn_scatter_long_kern
     for (int w = 0; w < UG_LONG_WAVES; ++w) total += cnts[w];
     count[key] = total;
   }
+}
+
+// The two launches of an entry scatter; the entry point has checked its arguments (self and Y null without SELF).
+template <bool SELF>
+void entry_scatter(const int32_t *keys, const int64_t *order, int n, int E, const int32_t *users, const float *coef,
+                   const float *self, const float *X, int ldx, int n_users, const float *Y, int ldy, int h,
+                   float scale, int n_rows, float *G, int ldg, int32_t *count, void *stream) {
+  dispatch_nt(h, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    hipLaunchKernelGGL((als_entry_scatter_kernel<NT, SELF>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, keys, order, n, E, users, coef, self, X, ldx, n_users, Y, ldy, h, scale,
+                       n_rows, G, ldg, count);
+    hipLaunchKernelGGL((als_entry_scatter_long_kernel<NT, SELF>), dim3((unsigned)((n + UG_LONG - 1) / UG_LONG)),
+                       dim3(64 * UG_LONG_WAVES), 0, (hipStream_t)stream, keys, order, n, E, users, coef, self, X, ldx,
+                       n_users, Y, ldy, h, scale, n_rows, G, ldg, count);
+  });
 }
 
 }  // namespace
@@ -309,15 +397,13 @@ extern "C" int rk_als_ugcn_grad(const int32_t *users, const int32_t *items, int3
   RK_SIDE_REQUIRE(n_users >= 1 && n_items >= 1 && step >= 0, "n_users, n_items >= 1, step >= 0");
   RK_SIDE_REQUIRE(users && items && X && Y && bu && bi && cand && coef && DU && valid && loss, "null pointer");
   RK_SIDE_REQUIRE(K == 0 || (nbr_ids && nbr_w), "K > 0 needs the neighbour lists");
-  auto launch = [&](auto nt, auto w) {                   // (w: the lanes of a group, the wave itself above h = 32)
+  auto launch = [&](auto nt, auto w) {
     hipLaunchKernelGGL((als_ugcn_grad_kernel<decltype(nt)::value, decltype(w)::value>), dim3((unsigned)((T + 3) / 4)),
                        dim3(256), 0, (hipStream_t)stream, users, items, T, R, K, mix64((uint64_t)seed), (uint32_t)step,
                        n_users, n_items, X, ldx, Y, ldy, h, bu, bi, nbr_ids, nbr_w, w1, w2, w3, w4,
                        negative_weight / (float)R, item_weight, cand, coef, DU, valid, loss);
   };
-  if (h <= 16) launch(Int<1>{}, Int<16>{});
-  else if (h <= 32) launch(Int<1>{}, Int<32>{});
-  else dispatch_nt(h, [&](auto nt) { launch(nt, Int<64>{}); });
+  dispatch_group(h, launch);
   RK_SIDE_CHECK_LAUNCH("als_ugcn_grad");
   return 0;
 }
@@ -332,15 +418,8 @@ extern "C" int rk_als_ugcn_scatter(const int32_t *keys, const int64_t *order, in
                   "n = T E, 2 <= E <= 1089, 1 <= T <= 4096, n <= 2^22");
   RK_SIDE_REQUIRE(n_users >= 1 && n_rows >= 1, "n_users, n_rows >= 1");
   RK_SIDE_REQUIRE(keys && order && users && coef && X && G && count, "null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  dispatch_nt(h, [&](auto nt) {
-    constexpr int NT = decltype(nt)::value;
-    hipLaunchKernelGGL(als_ugcn_scatter_kernel<NT>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, keys, order, n, E,
-                       users, coef, X, ldx, n_users, h, scale, n_rows, G, ldg, count);
-    hipLaunchKernelGGL(als_ugcn_scatter_long_kernel<NT>, dim3((unsigned)((n + UG_LONG - 1) / UG_LONG)),
-                       dim3(64 * UG_LONG_WAVES), 0, st, keys, order, n, E, users, coef, X, ldx, n_users, h, scale,
-                       n_rows, G, ldg, count);
-  });
+  entry_scatter<false>(keys, order, n, E, users, coef, nullptr, X, ldx, n_users, nullptr, 0, h, scale, n_rows, G, ldg,
+                       count, stream);
   RK_SIDE_CHECK_LAUNCH("als_ugcn_scatter");
   return 0;
 }

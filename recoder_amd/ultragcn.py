@@ -34,7 +34,7 @@ import torch
 
 from . import _als_lib, als, bpr, ease, lightgcn
 from ._lib import ptr
-from .bpr import _count, _f32, _i32, _number, _round256
+from .bpr import _carve, _count, _f32, _i32, _number, _round256
 from .device import DEVICE_HBM_BYTES, current_stream
 from .lightgcn import _table, new_state  # noqa: F401  (new_state: this module's too)
 
@@ -239,17 +239,26 @@ def grad(users, items, num_negatives, neighbours, seed, step_index, X, Y, bu, bi
                                       ptr(valid), ptr(loss), current_stream()), "rk_als_ugcn_grad")
 
 
+def check_entries(name, keys, order, E, users, coefs, X, G, count, max_batch, max_entries, max_E=None):
+  """What the entry scatters (``scatter`` here and ``ccl.scatter``) ask of their arguments: n = T E sorted ``keys``
+  with their ``order``, the slots' ``users``, one f32 of ``coefs`` per entry, the tables.  Returns (n, E); ValueError
+  in ``name``'s words when the sizes are outside the kernels' limits."""
+  n, T = keys.shape[0], users.shape[0]
+  E = int(E)
+  if not (E >= 2 and (max_E is None or E <= max_E) and n == T * E and 1 <= T <= max_batch and n <= max_entries):
+    raise ValueError("%s needs n = T E keys, %s, 1 <= T <= %d and n <= %d (got n = %d, T = %d, E = %d)"
+                     % (name, "E >= 2" if max_E is None else "2 <= E <= %d" % max_E, max_batch, max_entries, n, T, E))
+  _i32(keys, n), _i32(users, T), _table(X), _table(G, X.shape[1]), _i32(count, G.shape[0])
+  assert order.dtype == torch.int64 and order.shape == (n,) and order.is_contiguous()
+  for t in coefs:
+    assert t.dtype == torch.float32 and t.numel() == n and t.is_contiguous()
+  return n, E
+
+
 def scatter(keys, order, E, users, coef, X, scale, G, count):
   """G[key] = scale sum coef[e] X[users[e / E]] and count[key] = the key's positives, for the rows among the sorted
   keys (rk_als_ugcn_scatter); the caller zeroes G and count."""
-  n, T = keys.shape[0], users.shape[0]
-  E = int(E)
-  if not (E >= 2 and n == T * E and 1 <= T <= MAX_BATCH and n <= MAX_ENTRIES):
-    raise ValueError("rk_als_ugcn_scatter needs n = T E keys, E >= 2, 1 <= T <= %d and n <= %d (got n = %d, T = %d, "
-                     "E = %d)" % (MAX_BATCH, MAX_ENTRIES, n, T, E))
-  _i32(keys, n), _i32(users, T), _table(X), _table(G, X.shape[1]), _i32(count, G.shape[0])
-  assert order.dtype == torch.int64 and order.shape == (n,) and order.is_contiguous()
-  assert coef.dtype == torch.float32 and coef.numel() == n and coef.is_contiguous()
+  n, E = check_entries("rk_als_ugcn_scatter", keys, order, E, users, (coef,), X, G, count, MAX_BATCH, MAX_ENTRIES)
   lib = _als_lib.load()
   _als_lib.check(lib.rk_als_ugcn_scatter(ptr(keys), ptr(order), n, E, ptr(users), ptr(coef), ptr(X), X.stride(0),
                                          X.shape[0], X.shape[1], float(scale), G.shape[0], ptr(G), G.stride(0),
@@ -270,10 +279,8 @@ class Workspace(lightgcn.Workspace):
     self.num_negatives, self.neighbours = R, K
     E = 1 + R + K
     self.raw = torch.empty(need, dtype=torch.uint8, device=device)
-    a, b = _round256(4 * T * E), 2 * _round256(4 * T * E)
-    self.cand = self.raw[:4 * T * E].view(torch.int32).view(T, E)
-    self.coef = self.raw[a:a + 4 * T * E].view(torch.float32).view(T, E)
-    self.loss = self.raw[b:b + 12 * T].view(torch.float32).view(T, 3)
+    self.cand, self.coef, self.loss = _carve(self.raw, (torch.int32, (T, E)), (torch.float32, (T, E)),
+                                             (torch.float32, (T, 3)))
     self.bu = self.bi = self.nbr_ids = self.nbr_w = None
 
 
