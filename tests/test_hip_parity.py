@@ -86,7 +86,8 @@ def test_collate_bit_exact(n_users, n_items, S, ns):
     assert np.array_equal(got_t, dense.T)
 
 
-@pytest.mark.parametrize("n_items", [300, 40000])        # one-workgroup scan / chunked scan
+# (300 and 40 000 items: the one-workgroup scan, which takes every catalogue up to 65 536; 70 000: the count + assign pair)
+@pytest.mark.parametrize("n_items", [300, 40000, 70000])
 def test_collate_overflow_is_clamped_in_bounds_and_raises(n_items):
   """A block sized below its item set (never by construction): rk_collate truncates
   in bounds, leaves the true count in counts[5], and the host raises when it looks."""
