@@ -255,6 +255,10 @@ __device__ __forceinline__ void gemm_body(const GemmP &p, const int L, const int
   const float *a_ptr[A_PT], *b_ptr[B_PT];
   int a_k[A_PT], b_k[B_PT];           // k index of the element inside the tile
   int b_n[B_PT];                      // BMODE 1: column offset (row pointer varies with the gather)
+  // k-major operands, scalar loads: how many more elements the row holds behind the group's first one.  Where the
+  // leading dimension is no multiple of 4 the row's last group is ragged, and its loads stop at the row's last
+  // element (the repeats land in columns past ld, which no epilogue stores).  VEC: the caller guarantees ld % 4 == 0.
+  int a_rem[A_PT], b_rem[B_PT];
 #pragma unroll
   for (int i = 0; i < A_PT; ++i) {
     const int idx = min(tid + i * 256, A_F4 - 1);
@@ -269,7 +273,9 @@ __device__ __forceinline__ void gemm_body(const GemmP &p, const int L, const int
       const int m4 = A_UNIT ? u / QK : idx % (BM / 4);
       const int m = m0 + m4 * 4;
       a_k[i] = k;
-      a_ptr[i] = p.A + (int64_t)(kbeg + k) * lda + ((m + 3 < lda) ? m : 0);
+      const int mc = VEC ? ((m + 3 < lda) ? m : 0) : ((m < lda) ? m : 0);
+      a_rem[i] = lda - 1 - mc;
+      a_ptr[i] = p.A + (int64_t)(kbeg + k) * lda + mc;
     }
   }
 #pragma unroll
@@ -288,7 +294,8 @@ __device__ __forceinline__ void gemm_body(const GemmP &p, const int L, const int
       const int n4 = B_UNIT ? u / QK : idx % (BN / 4);
       const int n = n0 + n4 * 4;
       b_k[i] = k;
-      b_n[i] = (n + 3 < ldb) ? n : 0;
+      b_n[i] = VEC ? ((n + 3 < ldb) ? n : 0) : ((n < ldb) ? n : 0);
+      b_rem[i] = ldb - 1 - b_n[i];
       b_ptr[i] = p.Bm + b_n[i];          // + row * ldb per tile
     }
   }
@@ -310,9 +317,9 @@ __device__ __forceinline__ void gemm_body(const GemmP &p, const int L, const int
     const int last = klen - 1 - kk;          // >= 0
     return make_float4(q[0], q[last > 0 ? 1 : 0], q[last > 1 ? 2 : 0], q[last > 2 ? 3 : 0]);
   };
-  auto load4 = [&](const float *q) -> float4 {
+  auto load4 = [&](const float *q, int rem) -> float4 {
     if (VEC) return *reinterpret_cast<const float4 *>(q);
-    return make_float4(q[0], q[1], q[2], q[3]);
+    return make_float4(q[0], q[rem > 0 ? 1 : 0], q[rem > 1 ? 2 : 0], q[rem > 2 ? 3 : 0]);
   };
   auto gload = [&](float4 (&ra)[A_PT], float4 (&rb)[B_PT], int kt) {
     const int kb = kt * BK;
@@ -323,7 +330,7 @@ __device__ __forceinline__ void gemm_body(const GemmP &p, const int L, const int
         ra[i] = load_kcontig(a_ptr[i] - a_k[i], kb + a_k[i], tail);
       } else {
         const int row = tail ? min(kb + a_k[i], klen - 1) : kb + a_k[i];
-        ra[i] = load4(a_ptr[i] + (int64_t)(row - a_k[i]) * lda);
+        ra[i] = load4(a_ptr[i] + (int64_t)(row - a_k[i]) * lda, a_rem[i]);
       }
     }
     if (BMODE == 0) {
@@ -340,7 +347,7 @@ __device__ __forceinline__ void gemm_body(const GemmP &p, const int L, const int
         for (int i = 0; i < B_PT; ++i) src[i] = p.bidx[src[i]];
       }
 #pragma unroll
-      for (int i = 0; i < B_PT; ++i) rb[i] = load4(b_ptr[i] + (int64_t)src[i] * ldb);
+      for (int i = 0; i < B_PT; ++i) rb[i] = load4(b_ptr[i] + (int64_t)src[i] * ldb, b_rem[i]);
     }
   };
   auto sstore = [&](int buf, const float4 (&ra)[A_PT], const float4 (&rb)[B_PT], int kt) {
