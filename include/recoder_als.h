@@ -487,6 +487,56 @@ int rk_als_ccl_scatter(const int32_t *keys, const int64_t *order, int32_t n, int
                        const float *Y, int32_t ldy, int32_t h, float scale, int32_t n_rows, float *G, int32_t ldg,
                        int32_t *count, void *stream);
 
+/* the limits of rk_als_sx_forward: at most this many entries of a user's history are pooled (max_history and E); the
+ * slots of rk_als_sx_backward's dW are summed in consecutive chunks of RK_ALS_SX_CHUNK */
+#define RK_ALS_SX_MAX_HISTORY 1024
+#define RK_ALS_SX_CHUNK 256
+
+/* bytes of the step's buffers B, dB (f32 [T, h]), hkey (int32 [T, E]), hcoef (f32 [T, E]), part (f32 [ceil(T /
+ * RK_ALS_SX_CHUNK), h, h]) and dW (f32 [h, h]), each rounded up to 256 bytes and laid out in that order; -2 unless
+ * 1 <= T <= RK_ALS_CCL_MAX_BATCH, 1 <= E <= RK_ALS_SX_MAX_HISTORY, T E <= RK_ALS_CCL_MAX_ENTRIES and 1 <= h <= 512 */
+int64_t rk_als_sx_workspace_bytes(int32_t T, int32_t E, int32_t h);
+
+/*
+ * SimpleX's user rows (Mao et al. 2021, average pooling) for the T slots users[t], over the user CSR indptr (int64
+ * [n_users + 1]) / indices (int32, ascending within a row; the stored values play no part), the item table Q
+ * [n_items, ldq], the users' own table P [n_users, ldp] (NULL: the term gamma P[u] is 0) and the map W [h, ldw].  With
+ * r the stored entries of row u and L = max_history, the history H_u is the whole row when r <= L and else the entries
+ * at the positions floor(j r / L), j = 0 .. L - 1 (64-bit integers), and
+ *   b      = (1 / |H_u|) sum_{k in H_u} Q[k]               (the zero vector for an empty row)
+ *   B[t]   = b                                             (f32 [T, h]; NULL: not stored)
+ *   X[row] = gamma P[u] + (1 - gamma) W b                  row = users[t], or t when compact != 0 (X [., ldx])
+ *   hkey[t, e], hcoef[t, e]   e < E: the items of H_u in ascending position with the coefficient 1 / |H_u|, then the
+ *                             sentinel n_items with +0 (both NULL: not stored).  E must be at least min(L, r) for every
+ *                             slot; entries past E are pooled but not listed
+ * A slot whose user lies outside [0, n_users) stores b = 0 and sentinels, and no row of X (a zero row when compact).
+ * Two slots of one user store the same bits to the same row.  The list is rk_als_ccl_scatter's entry layout: run on
+ * (hkey, hcoef, self = 0, the table dB of rk_als_sx_backward, users = the slot index) it sums the history's gradient
+ * per item.
+ * Numerics, all f32.  b: one add chain per column over H_u in ascending position from +0 (the rows are gathered
+ * several at a time; the order of the adds is fixed), then one multiply by 1.f / (float)|H_u|.  W b: one chain
+ * s_a = fmaf(W[a, c], b_c, s_a) over c ascending from +0 per element.  X = fmaf(gamma, p, (1.f - gamma) s_a).  One wave
+ * per slot, no atomics: the same inputs give the same bits, whatever T and the leading dimensions.
+ */
+int rk_als_sx_forward(const int32_t *users, int32_t T, const int64_t *indptr, const int32_t *indices,
+                      int32_t n_users, int32_t n_items, const float *Q, int32_t ldq, const float *P, int32_t ldp,
+                      const float *W, int32_t ldw, int32_t h, float gamma, int32_t max_history, int32_t E, float *B,
+                      float *X, int32_t ldx, int32_t compact, int32_t *hkey, float *hcoef, void *stream);
+
+/*
+ * The backward pass of the pooling branch, from DU (f32 [T, h]: the gradient at X[users[t]], as rk_als_ccl_grad leaves
+ * it), valid (f32 [T]), the pooled rows B (f32 [T, h]) and W [h, ldw]:
+ *   dB[t, c] = scale sum_a W[a, c] DU[t, a]                (+0 for an invalid slot)
+ *   dW[a, c] = scale sum_{t valid} DU[t, a] B[t, c]        (f32 [h, h])
+ * The caller's scale carries (1 - gamma) and the mean's 1 / T.  Numerics, all f32: dB is one chain fmaf(W[a, c],
+ * DU[t, a], .) over a ascending from +0, times scale.  dW is summed in consecutive chunks of RK_ALS_SX_CHUNK slots --
+ * part[ch, a, c] (f32 [ceil(T / RK_ALS_SX_CHUNK), h, h]) is one chain fmaf(DU[t, a], B[t, c], .) over the chunk's
+ * slots ascending from +0, an invalid slot entering with DU = +0 -- and a second launch adds the chunks in ascending
+ * order and multiplies by scale: the result does not depend on the grid.  Three launches, no atomics.
+ */
+int rk_als_sx_backward(const float *DU, const float *valid, const float *B, int32_t T, const float *W, int32_t ldw,
+                       int32_t h, float scale, float *dB, float *part, float *dW, void *stream);
+
 /* the metric kinds of rk_als_rank_metrics and how many records one call takes */
 #define RK_ALS_METRIC_RECALL 0
 #define RK_ALS_METRIC_NDCG 1

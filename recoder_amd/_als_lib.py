@@ -3,7 +3,8 @@ for recoder_amd.als, the BPR step (rk_als_bpr_*) for recoder_amd.bpr, the WARP /
 gradient (rk_als_rank_sample, rk_als_warp_grad) for recoder_amd.warp, the LightGCN kernels
 (rk_als_lgcn_*) for recoder_amd.lightgcn, SimGCL's (rk_als_gcl_*) for recoder_amd.simgcl, DirectAU's
 (rk_als_dau_*) for recoder_amd.directau, the sampled softmax's (rk_als_ssm_*) for recoder_amd.ssm, UltraGCN's (rk_als_ugcn_*) for
-recoder_amd.ultragcn and the cosine contrastive loss' (rk_als_ccl_*) for recoder_amd.ccl, and the ranking metrics of device-resident top-k lists (rk_als_rank_metrics) for recoder_amd.metrics
+recoder_amd.ultragcn, the cosine contrastive loss' (rk_als_ccl_*) for recoder_amd.ccl and SimpleX's pooled user rows
+(rk_als_sx_*) for recoder_amd.simplex, and the ranking metrics of device-resident top-k lists (rk_als_rank_metrics) for recoder_amd.metrics
 and recoder_amd.validation.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
 import os
 
@@ -27,6 +28,7 @@ SSM_MAX_BATCH, SSM_MAX_NEGATIVES = 4096, 4096  # RK_ALS_SSM_MAX_BATCH, RK_ALS_SS
 UGCN_MAX_BATCH, UGCN_MAX_NEGATIVES, UGCN_MAX_NEIGHBOURS = 4096, 1024, 64  # RK_ALS_UGCN_MAX_BATCH, _NEGATIVES, _NEIGHBOURS
 UGCN_MAX_ENTRIES, UGCN_LONG_KEY = 1 << 22, 1024  # RK_ALS_UGCN_MAX_ENTRIES, RK_ALS_UGCN_LONG_KEY
 CCL_MAX_BATCH, CCL_MAX_NEGATIVES, CCL_MAX_ENTRIES = 4096, 1024, 1 << 22  # RK_ALS_CCL_MAX_BATCH, _NEGATIVES, _ENTRIES
+SX_MAX_HISTORY, SX_CHUNK = 1024, 256  # RK_ALS_SX_MAX_HISTORY, RK_ALS_SX_CHUNK
 RANK_MAX_DRAWS = 256  # RK_ALS_RANK_MAX_DRAWS
 RANK_WARP, RANK_DNS = 0, 1  # RK_ALS_RANK_WARP, RK_ALS_RANK_DNS
 METRIC_RECALL, METRIC_NDCG, METRIC_AP = 0, 1, 2  # RK_ALS_METRIC_RECALL, _NDCG, _AP
@@ -83,6 +85,10 @@ SIGNATURES = {
                                 c_int32, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
   "rk_als_ccl_scatter": (c_int32, [_P, _P, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, c_int32, c_int32,
                                    c_float, c_int32, _P, c_int32, _P, _P]),
+  "rk_als_sx_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+  "rk_als_sx_forward": (c_int32, [_P, c_int32, _P, _P, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32,
+                                  c_float, c_int32, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P]),
+  "rk_als_sx_backward": (c_int32, [_P, _P, _P, c_int32, _P, c_int32, c_int32, c_float, _P, _P, _P, _P]),
   "rk_als_rank_metrics": (c_int32, [_P, c_int32, c_int32, c_int64, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P,
                                     _P, _P, _P]),
 }

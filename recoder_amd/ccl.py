@@ -17,8 +17,9 @@ zero vector and gets no gradient.  The hinge kills most negatives: rk_als_ccl_gr
 every slot with two coefficients and a key, the item where the entry carries a gradient and a sentinel past the table
 where it does not, so that the sort puts the dead entries last and rk_als_ccl_scatter walks the live ones only;
 rk_als_lgcn_scatter sums the users' rows; one ``lightgcn.forward`` propagates both back and Adam steps the base
-tables.  Of SimpleX itself only the loss is built: the pooling of a user's history into the user's vector, the
-embedding dropout and the attention pooling are not (``num_layers = 1`` is the closest thing the driver offers).
+tables.  This module is SimpleX's loss alone: the pooling of a user's history into the user's vector is
+recoder_amd/simplex.py (``Recoder.train_simplex``), which runs this loss at pooled user rows; the embedding dropout
+and the attention poolings are not built.
 
 ``Recoder.train_ccl`` is the public entry point; the functions below are the layer under it (and what the tests and
 tools/ccl_bench.py drive directly).

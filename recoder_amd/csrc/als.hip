@@ -64,6 +64,14 @@
 //   rk_als_ccl_scatter     the entry scatter (the same kernels, SELF) over the keys of the live entries only (the dead
 //                          carry a sentinel that sorts last), with the row's own -sum self Y[key] term
 //
+// SimpleX's history-pooled user rows under that loss (rk_als_sx_*): the step of recoder_amd/simplex.py adds
+//   rk_als_sx_forward      one wave per slot: the user's history (the whole row, or max_history entries spread over it)
+//                          gathered several rows at a time and averaged, the h x h map W through an LDS tile the
+//                          workgroup's four slots share, the mix with the user's own row; the history's entry list in
+//                          the entry scatter's layout
+//   rk_als_sx_backward     dB = scale W^T DU per slot and dW = scale DU^T B in fixed chunks of 256 slots, the chunks added
+//                          in ascending order by a second launch
+//
 // Ranking metrics on device-resident top-k lists (rk_als_rank_metrics): what recoder_amd/validation.py reads per epoch
 //   rk_als_rank_metrics    one wave per user: a binary search of each rank's id in the user's target row, a ballot per
 //                          64 ranks, Recall / NDCG / AP summed in float64 in ascending rank order; a second launch of
@@ -79,6 +87,7 @@
 #include "als/ssm.h"        // rk_als_ssm_*
 #include "als/ugcn.h"       // rk_als_ugcn_*, the candidate round, the entry scatter
 #include "als/ccl.h"        // rk_als_ccl_* (on ugcn.h)
+#include "als/simplex.h"    // rk_als_sx_* (beside ccl.h's loss)
 #include "als/metrics.h"    // rk_als_rank_metrics
 
 extern "C" int rk_als_version(void) { return 100; }

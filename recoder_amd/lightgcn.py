@@ -282,9 +282,18 @@ def bpr_sums_add(sums, ws):
 #                   a step adds to them, and the history entry from their values on the host
 #   workspace(n_users, n_items, T, h, device, **opts), extra_bytes(n_users, n_items, h, T, **opts)   its ``Workspace``
 #                   and that workspace's device bytes on top of ``required_bytes``, under ``opts(*hyper)``
+# A method whose final tables are not the layer mean of two base tables (recoder_amd/simplex.py: a third parameter, user
+# rows pooled from the batch's histories) also says, every field None for the methods above:
+#   step_forward(X, Y, graph, state, ws, hyper)   in place of the step's ``forward``, run AFTER the draw: the final rows
+#                   the step's gradient reads
+#   full_forward(X, Y, graph, state, ws, hyper)   in place of the ``forward`` at a validated epoch and at the fit's end
+#   backward(graph, state, ws, hyper)   in place of the gradient's ``forward``: returns the Adam jobs, one (parameter,
+#                   gradient, count, first moment, second moment) per parameter
+#   new_state(X, Y, num_layers, hyper), check_resume(state, num_layers, shapes, hyper)   its state and the resume check
 Method = collections.namedtuple(
-    "Method", "name method max_batch min_layers skip_layer0 gradient sums sums_add entry workspace extra_bytes opts",
-    defaults=(Workspace, lambda n_users, n_items, h, T: 0, lambda *hyper: {}))
+    "Method", "name method max_batch min_layers skip_layer0 gradient sums sums_add entry workspace extra_bytes opts "
+    "step_forward full_forward backward new_state check_resume",
+    defaults=(Workspace, lambda n_users, n_items, h, T: 0, lambda *hyper: {}, None, None, None, None, None))
 
 BPR_SUMS = (((), torch.float64), ((), torch.int64))     # the summed loss and the valid triples
 METHOD = Method("LightGCN", "train_lightgcn", bpr.MAX_BATCH, 1, skip_layer0=False,
@@ -296,14 +305,21 @@ def method_step(method, X, Y, graph, state, ws, seed, step_index, lr, reg, hyper
   """One step of ``method``: the state's base tables and moments move, X / Y receive the final tables of the base
   tables as they were at the START of the step; the draws of the step stay in ``ws.bpr``."""
   K, b = state["num_layers"], ws.bpr
-  forward(graph, state["E0"], K, ws.layers, (X, Y), method.skip_layer0)
-  bpr.sample(graph.ucsr, seed, step_index, b.users, b.pos, b.neg)
+  if method.step_forward is None:
+    forward(graph, state["E0"], K, ws.layers, (X, Y), method.skip_layer0)
+    bpr.sample(graph.ucsr, seed, step_index, b.users, b.pos, b.neg)
+  else:
+    bpr.sample(graph.ucsr, seed, step_index, b.users, b.pos, b.neg)
+    method.step_forward(X, Y, graph, state, ws, hyper)
   method.gradient(X, Y, graph, state, ws, seed, step_index, hyper)
-  forward(graph, ws.G, K, ws.layers, ws.H, method.skip_layer0)
+  if method.backward is None:
+    forward(graph, ws.G, K, ws.layers, ws.H, method.skip_layer0)
+    jobs = [(state["E0"][side], ws.H[side], ws.count[side], state["M"][side], state["V"][side]) for side in (0, 1)]
+  else:
+    jobs = method.backward(graph, state, ws, hyper)
   state["step"] += 1
-  for side in (0, 1):
-    adam(state["E0"][side], ws.H[side], ws.count[side], reg / b.T, state["M"][side], state["V"][side], lr,
-         state["step"])
+  for E0, H, count, M, V in jobs:
+    adam(E0, H, count, reg / b.T, M, V, lr, state["step"])
 
 
 def step(X, Y, graph, state, ws, seed, step_index, lr, reg):
@@ -333,14 +349,23 @@ def method_fit(method, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_siz
   history keeps every epoch that ran."""
   steps = bpr.check_data(ucsr.nnz, ucsr.shape[1], num_epochs, batch_size, method=method.method)
   if state is not None:
-    check_resume(state, num_layers, (X.shape, Y.shape), method=method.method)
+    if method.check_resume is None:
+      check_resume(state, num_layers, (X.shape, Y.shape), method=method.method)
+    else:
+      method.check_resume(state, num_layers, (X.shape, Y.shape), hyper)
   opts = method.opts(*hyper)
   method_check_memory(method, X.shape[0], Y.shape[0], X.shape[1], ucsr.nnz, batch_size, allocate_model=False,
                       allocate_state=state is None, allocate_csrs=False,
                       snapshot=monitor is not None and monitor.restore_best, **opts)
   if state is None:
-    state = new_state(X, Y, num_layers)
+    state = new_state(X, Y, num_layers) if method.new_state is None else method.new_state(X, Y, num_layers, hyper)
   graph = Graph(ucsr, icsr)
+
+  def final_tables():
+    if method.full_forward is None:
+      forward(graph, state["E0"], state["num_layers"], ws.layers, (X, Y), method.skip_layer0)
+    else:
+      method.full_forward(X, Y, graph, state, ws, hyper)
   ws = method.workspace(X.shape[0], Y.shape[0], int(batch_size), X.shape[1], X.device, **opts)
   bias.zero_()
   hist = []
@@ -354,13 +379,13 @@ def method_fit(method, X, Y, bias, ucsr, icsr, num_layers, num_epochs, batch_siz
     values = torch.cat([t.double().reshape(-1) for t in sums]).cpu().tolist()      # (the synchronisation)
     hist.append(method.entry(values, steps))
     if monitor is not None and monitor.due(e):
-      forward(graph, state["E0"], state["num_layers"], ws.layers, (X, Y), method.skip_layer0)
+      final_tables()
       if monitor.epoch_end(e, state_tensors(state), state["step"],
                            prepare=None if monitor_prepare is None else ((X, Y), monitor_prepare)):
         break
   if monitor is not None and monitor.finish(state_tensors(state), len(hist)):
     state["step"] = monitor.best_step
-  forward(graph, state["E0"], state["num_layers"], ws.layers, (X, Y), method.skip_layer0)
+  final_tables()
   return state, hist
 
 

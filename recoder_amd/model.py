@@ -112,11 +112,15 @@ class Recoder(object):
     self.ccl_history = []       # train_ccl: (positive term, negative term) means per valid slot of each epoch
     self.ccl_stats = []         # train_ccl: the mean share of live negatives of each epoch
     self.ccl_state = None       # train_ccl: base tables, Adam moments, step count, num_layers (device; not saved)
+    self.simplex_history = []   # train_simplex: (positive term, negative term) means per valid slot of each epoch
+    self.simplex_stats = []     # train_simplex: the mean share of live negatives of each epoch
+    self.simplex_state = None   # train_simplex: P, Q, W, Adam moments, step count, gamma, max_history (device; not saved)
     # the iterative trainers' validation curve of the last fit (None: it had no val_dataset): {"metric", "k",
     # "values", "epochs", "best_epoch", "stopped_epoch"}; not saved
     self.fit_validation = None  # validation settings for the iterative fits called without a val_dataset (_validated)
     self.bpr_validation = self.warp_validation = self.lightgcn_validation = self.simgcl_validation = None
     self.directau_validation = self.ssm_validation = self.ultragcn_validation = self.ccl_validation = None
+    self.simplex_validation = None
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -649,11 +653,12 @@ class Recoder(object):
         size_check=lambda c, host: warp.check_data(host().nnz, self.num_items, c[0], c[1]))
 
   def _graph_fit(self, mod, prefix, train_dataset, resume, log_format, *config,
-                 validation=(None, None, 1, 500, None, None, True)):
+                 validation=(None, None, 1, 500, None, None, True), hint_check=None):
     """``_closed_form_fit`` for the three methods that train base tables over the user-item graph (the driver of
     recoder_amd/lightgcn.py): ``mod.check_config(model, *config)``, then with ``resume`` the kept
     ``self.<prefix>_state`` checked and handed to ``mod.fit``; the history goes to ``self.<prefix>_history``.
-    ``validation``: the arguments of ``_validated``, the fit's one hook at the epoch's end."""
+    ``validation``: the arguments of ``_validated``, the fit's one hook at the epoch's end.  ``hint_check``:
+    ``_closed_form_fit``'s, what the method checks of the host matrix before any GPU work."""
     vcheck, monitor, vkeep = self._validated("train_" + prefix, prefix, train_dataset, validation)
 
     def check(m):
@@ -671,7 +676,7 @@ class Recoder(object):
       vkeep()
       return hist
     return self._closed_form_fit(
-        mod, train_dataset, prefix + "_history", copy=list, check=check, fit=fit,
+        mod, train_dataset, prefix + "_history", copy=list, check=check, fit=fit, hint_check=hint_check,
         log_line=lambda c: (log_format,) + c,
         size_check=lambda c, host: mod.check_data(host().nnz, self.num_items, c[1], c[2]))
 
@@ -822,8 +827,8 @@ class Recoder(object):
     negatives of max(0, cos(u, j) - ``margin``), the cosines taken between rows of the final tables.  A negative
     below the margin is dead: it gets no gradient, and the item-side sum never reads it.  The final tables are
     LightGCN's mean over ``num_layers`` + 1 layers; ``num_layers = 0`` trains the tables themselves and propagates
-    nothing.  Of SimpleX only the loss is built: the pooling of the user's history, the dropout and the attention
-    pooling are not.  Adam at learning rate ``lr``, the L2 term ``reg`` on the base rows a pair touches as its user
+    nothing.  This is SimpleX's loss alone: the pooling of the user's history is ``train_simplex``; the dropout and the
+    attention poolings are not built.  Adam at learning rate ``lr``, the L2 term ``reg`` on the base rows a pair touches as its user
     or its positive; ``batch_size`` is at most ``ccl.MAX_BATCH``, ``num_negatives`` at most ``ccl.MAX_NEGATIVES``
     and ``batch_size`` * (1 + ``num_negatives``) at most ``ccl.MAX_ENTRIES``; ``margin`` lies in [-1, 1).  The base
     tables of a first call are the tables as they stand; they, both Adam moments, the step count and ``num_layers``
@@ -844,6 +849,62 @@ class Recoder(object):
                            normalize, seed)
     self.ccl_stats = list(self.ccl_state["live_share"])
     return hist
+
+  def train_simplex(self, train_dataset, gamma=0.5, max_history=256, num_epochs=10, batch_size=1024, lr=0.01, reg=1e-3,
+                    num_negatives=64, negative_weight=16.0, margin=0.0, normalize=False, seed=0, resume=False,
+                    val_dataset=None, eval_metric=None, eval_freq=1, eval_batch_size=500, eval_num_users=None,
+                    patience=None, restore_best=True):
+    """SimpleX (Mao et al. 2021) for a MatrixFactorization with activation 'none' (recoder_amd/simplex.py):
+    ``train_ccl``'s loss, slots, negatives, L2 term and Adam at user rows pooled from the users' histories.  The
+    parameters are the tables P and Q and an h x h map W (the identity at the start of a fresh fit); a user's history
+    is the whole stored row, or for a row longer than ``max_history`` (1..``simplex.MAX_HISTORY``) the ``max_history``
+    entries at the positions floor(j r / max_history) of its stored order; the slot's own positive is not removed and
+    the stored values play no part.  The final tables are X[u] = ``gamma`` P[u] + (1 - ``gamma``) W mean(Q[history of
+    u]) and Y = Q, ``gamma`` in [0, 1].  A step pools the rows of its own ``batch_size`` slots only; history items and
+    W take no L2 term.  With ``gamma = 1`` the pooling branch is not run and the fit is ``train_ccl(num_layers=0)``
+    bit for bit.  ``batch_size`` * min(``max_history``, the longest stored row) is at most ``simplex.MAX_ENTRIES``.
+    P, Q, W, their Adam moments, the step count, ``gamma`` and ``max_history`` stay in ``simplex_state`` (device
+    tensors, not part of a checkpoint), and ``resume=True`` continues from them, at the same ``gamma`` and
+    ``max_history``, with the draws, moments and step count one longer call would have had.  The model's tables end
+    as X for every training user and Y -- un-normalised, or with ``normalize=True`` row-normalised, as in
+    ``train_ccl`` -- and the bias as 0: ``save_state``, ``recommend``, ``evaluate``, ``train``, ``train_als`` and
+    ``train_bpr`` take them as they are; ``simplex_encode`` gives the pooled row of any history.  Not built: SimpleX's
+    embedding dropout, its attention poolings, LightGCN layers under the pooling and multi-GPU training.  Returns (and
+    keeps in ``simplex_history``) one (positive term, negative term) pair of means per valid pair per epoch;
+    ``simplex_stats`` keeps the mean share of live negatives of each epoch.
+    ``val_dataset`` and the keywords after it: validation during the fit and early stopping (``_validated``).  With
+    ``normalize=True`` an evaluation scores the row-normalised tables, as the finished fit would."""
+    from . import simplex
+
+    def hint_check(c, users, items, host):
+      if c[0][0] < 1.0:
+        simplex.check_entries(c[2], simplex.entry_width(np.diff(host().indptr), c[0][1]))
+    hist = self._graph_fit(simplex, "simplex", train_dataset, resume,
+                           "SimpleX: (gamma, max_history) %s, %d epochs of batches of %d, lr %g, reg %g, %d negatives a "
+                           "slot at weight %g, margin %g, normalize %s, seed %d",
+                           gamma, max_history, num_epochs, batch_size, lr, reg, num_negatives, negative_weight, margin,
+                           normalize, seed, hint_check=hint_check,
+                           validation=(val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience,
+                                       restore_best))
+    self.simplex_stats = list(self.simplex_state["live_share"])
+    return hist
+
+  def simplex_encode(self, interactions_matrix):
+    """[B, h] on the device: the user rows (1 - gamma) W mean(Q[history]) that the last ``train_simplex`` gives the B
+    histories (the rows of ``interactions_matrix``, a scipy matrix over the model's items), users the fit never saw
+    included; an empty row gives the zero vector.  W, Q, ``gamma`` and the ``max_history`` rule are
+    ``simplex_state``'s; the users' own table P plays no part, so after a fit with ``gamma = 0`` the training rows
+    encode to the model's user table."""
+    import scipy.sparse as sp
+    from . import als, simplex
+    if self.simplex_state is None:
+      raise ValueError("simplex_encode needs the state of an earlier train_simplex on this Recoder (there is none)")
+    m = als.canonical_csr(interactions_matrix)
+    n_items = self.simplex_state["E0"][1].shape[0]
+    if m.shape[1] > n_items:
+      raise ValueError("interactions_matrix has %d columns, the fit has %d items" % (m.shape[1], n_items))
+    m = sp.csr_matrix((m.data, m.indices, m.indptr), shape=(m.shape[0], n_items))
+    return simplex.encode(als.AlsCSR(m, self.device), self.simplex_state)
 
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
