@@ -568,6 +568,38 @@ int rk_als_rank_metrics(const int64_t *recs, int32_t B, int32_t K, int64_t ld, c
                         const int32_t *ks, const int32_t *normalize, const double *inv_w, const double *ideal,
                         double *values, double *sums, int64_t *count, void *stream);
 
+/* largest embedding size rk_als_foldin takes (128) */
+int rk_als_foldin_max_h(void);
+
+/*
+ * Fold-in: the user row of a history the fit has not seen, for any MatrixFactorization state with activation "none".
+ * For every row u of the batch CSR (indptr [rows + 1] / indices / data; data NULL: all ones; columns are rows of Y) it
+ * solves the user-side normal equations at the head of this file EXACTLY, by a Cholesky factorisation:
+ *   (G + sum_{e in u} a_e y_e y_e^T) x_u = sum_e coef_e y_e - v,   a_e = alpha [r_e > 0],
+ *   coef_e = (1 + a_e) r_e - a_e b_e   (bias NULL: b = 0),
+ * with G [h, h] and v [h] from rk_als_gram(Y, w = bias, reg), and writes X[u, :h] (ldx >= h) and status[u].  Only
+ * the lower triangle of G is read.  One launch on `stream`; no workspace, no atomics.  -2 unless 1 <= h <=
+ * rk_als_foldin_max_h(), ldy, ldx >= h, rows >= 0, alpha finite and >= 0 and (with rows > 0) no pointer but data and
+ * bias is NULL: a larger h is refused, there is no other path.
+ * Arithmetic (all f32, bitwise repeatable; tests/foldin_util.py restates it, tests/test_foldin.py compares bit for
+ * bit).  Every fused operation is an fmaf and nothing else is contracted.
+ *   - the entries are taken in CSR order, never cut into pieces; coef_e is two rounded products and their rounded
+ *     difference, (1 + a_e) rounded first
+ *   - r_k starts as -v_k; r_k = fmaf(coef_e, Y[j_e][k], r_k) over e ascending
+ *   - the lower triangle k >= l: A[k][l] starts as G[k][l]; over the entries with a_e != 0, ascending,
+ *     t = a_e Y[j_e][k] (one rounding), A[k][l] = fmaf(t, Y[j_e][l], A[k][l])
+ *   - Cholesky A = L L^T: s = A[i][j], s = fmaf(-L[i][k], L[j][k], s) for k = 0 .. j - 1; L[j][j] = sqrt(s);
+ *     L[i][j] = s / L[j][j]; the root and the division correctly rounded
+ *   - z_i = (r_i - sum_{k < i} L[i][k] z_k) / L[i][i], the sum as fmaf(-L[i][k], z_k, .) over k ascending
+ *   - x_i = (z_i - sum_{k > i} L[k][i] x_k) / L[i][i], as fmaf(-L[k][i], x_k, .) over k DESCENDING from h - 1
+ *   - a pivot s that is not > 0 (nan included): X[u] = +0 and status[u] = 1; every other row has status[u] = 0
+ * A row's result depends on its own entries, Y, G, v, bias and alpha alone: not on the other rows, on `rows` or on
+ * the launch.
+ */
+int rk_als_foldin(const int64_t *indptr, const int32_t *indices, const float *data, int32_t rows, const float *Y,
+                  int32_t ldy, int32_t h, const float *G, const float *v, const float *bias, float alpha, float *X,
+                  int32_t ldx, int32_t *status, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

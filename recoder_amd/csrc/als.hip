@@ -77,6 +77,12 @@
 //                          64 ranks, Recall / NDCG / AP summed in float64 in ascending rank order; a second launch of
 //                          one workgroup adds the users in a fixed order.  No atomics
 //
+// Fold-in of a user the fit has not seen (rk_als_foldin): what recoder_amd/foldin.py calls per batch of histories
+//   rk_als_foldin          the user-side normal equations of a history solved exactly: A = G + the entries' outer
+//                          products in register tiles of the lower triangle, a right-looking Cholesky on the packed
+//                          triangle in LDS, both triangular solves by columns; one workgroup a row at h > 64, four rows
+//                          a workgroup below; h <= 128.  No atomics, no workspace
+//
 // One translation unit (one last-error buffer, one anonymous namespace), laid out by family under als/: every file
 // holds its kernels, then its extern "C" entry points.
 #include "als/common.h"     // the lane layout, the counter hash, the segment walk, the NT and lane-group dispatch
@@ -89,6 +95,7 @@
 #include "als/ccl.h"        // rk_als_ccl_* (on ugcn.h)
 #include "als/simplex.h"    // rk_als_sx_* (beside ccl.h's loss)
 #include "als/metrics.h"    // rk_als_rank_metrics
+#include "als/foldin.h"     // rk_als_foldin (beside solve.h's row solves)
 
 extern "C" int rk_als_version(void) { return 100; }
 extern "C" const char *rk_als_last_error(void) { return g_rk_side_err; }

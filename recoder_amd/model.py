@@ -906,6 +906,29 @@ class Recoder(object):
     m = sp.csr_matrix((m.data, m.indices, m.indptr), shape=(m.shape[0], n_items))
     return simplex.encode(als.AlsCSR(m, self.device), self.simplex_state)
 
+  def fold_in(self, interactions_matrix, alpha=30.0, reg=100.0):
+    """[B, h] f32 on the device: the user rows of the B histories (the rows of ``interactions_matrix``, a scipy
+    matrix over the model's items), users no fit has seen included, for a MatrixFactorization with activation
+    'none' left by any trainer (recoder_amd/foldin.py).  A row is the exact minimiser of the ALS user objective
+    sum_i (1 + ``alpha`` [r_i > 0]) (r_i - x . y_i - b_i)^2 + ``reg`` |x|^2 over all items with the item table
+    and the bias held as they stand, solved by Cholesky on the device (rk_als_foldin, embedding sizes up to
+    ``foldin.MAX_H``).  ``alpha = 0, reg = 0`` after ``train_svd`` gives the model's own rows; after ``train_als``
+    the loss's confidence and the fit's ``reg`` give the exact user half-step.  Nothing of the model is changed.
+    ValueError: another model class or activation, a larger embedding size, ``alpha`` or ``reg`` below 0, a model
+    not yet initialised, more than one rank, a matrix with more columns than the model has items.  A row whose
+    system is not positive definite (``reg = 0`` only) is returned as zeros, with one warning per call."""
+    from . import foldin
+    return foldin.fold_in(self, interactions_matrix, alpha, reg)
+
+  def recommend_folded(self, users_interactions, num_recommendations, alpha=30.0, reg=100.0):
+    """``recommend_array`` with the batch's user rows folded in from their histories (``fold_in`` of
+    ``users_interactions.interactions_matrix``) instead of looked up in the user table: [users, k] int64 item ids,
+    the seen items masked, ties to the lower id.  ``users_interactions.users`` is ignored, so the users need not
+    be the fit's."""
+    rows = self.fold_in(users_interactions.interactions_matrix, alpha, reg)
+    ids, _ = self._recommend_device(users_interactions, num_recommendations, user_rows=rows)
+    return ids.cpu().numpy().copy()
+
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
     (recoder_amd/svd.py): the item table becomes V, the top ``embedding_size`` right singular vectors of
@@ -1804,7 +1827,7 @@ class Recoder(object):
       return out, dense
     return out, out
 
-  def _input_block(self, users_interactions, ws=None):
+  def _input_block(self, users_interactions, ws=None, lookup_users=True):
     """The users' interactions as an unsampled device block (bitmap over the whole catalogue),
     in buffers that are kept and reused across predict / recommend calls (``ws``: in that
     workspace instead, ``recoder_amd.validation`` keeps one per batch)."""
@@ -1827,9 +1850,10 @@ class Recoder(object):
                               negative_sampling=False, need_bits_cr=False)
     rows = torch.arange(B, dtype=torch.int64, device=self.device)
     blk.collate(dcsr, rows, negative_sampling=False)
-    # MF looks user rows up by their global ids
-    blk.users = torch.as_tensor(np.asarray(users_interactions.users), dtype=torch.int64) \
-        .to(self.device)
+    # MF looks user rows up by their global ids (not with ``recommend_folded``'s rows, whose users have none)
+    if lookup_users:
+      blk.users = torch.as_tensor(np.asarray(users_interactions.users), dtype=torch.int64) \
+          .to(self.device)
     return blk, B, n_items
 
   @staticmethod
@@ -1880,13 +1904,16 @@ class Recoder(object):
       return ids
     return ids.cpu().numpy().copy()
 
-  def _recommend_device(self, users_interactions, num_recommendations, host_ok=False, ws=None, inputs=None):
+  def _recommend_device(self, users_interactions, num_recommendations, host_ok=False, ws=None, inputs=None,
+                        user_rows=None):
     """``recommend_array`` before its copy to the host: (ids, ld), an int64 device tensor [users, k] (possibly a
     strided view of the candidate buffer, valid until the next call on the same workspace) and its row stride.
     The fused form of ``engine.recommend_fused`` reads its ids back with its status word, so it is taken only
     with ``host_ok`` and then returns (the numpy array, k); without it the catalogue is decoded strip by strip.
     ``ws`` is the workspace of the scores and candidates (None: the Recoder's own ``_eval_ws``), ``inputs`` an
-    earlier ``(blk, B, n_items, dcsr)`` of ``_input_block`` for these users (None: collated now)."""
+    earlier ``(blk, B, n_items, dcsr)`` of ``_input_block`` for these users (None: collated now).  ``user_rows``
+    (``recommend_folded``): a [users, h] f32 device tensor scored in place of the encoder's output, strip by strip;
+    ``users_interactions.users`` is then not read."""
     self.model.eval()
     self._check_ranges()
     k = int(num_recommendations)
@@ -1896,16 +1923,26 @@ class Recoder(object):
     engine = self._engine()
     csr_model = self._scores_from_csr_rows()
     if (getattr(engine, "generic", False) and not csr_model) or k > lib.rk_topk_max_k():
+      if user_rows is not None:
+        raise ValueError("recommend_folded scores on the fused HIP engine (optimizer_type='adam', an embedding size "
+                         "that is a multiple of 4) and takes at most %d recommendations (got %d)"
+                         % (lib.rk_topk_max_k(), k))
       return self._recommend_dense_device(users_interactions, k), k
     if inputs is None:
-      blk, B, n_items = self._input_block(users_interactions, ws)
+      blk, B, n_items = self._input_block(users_interactions, ws, lookup_users=user_rows is None)
       if ws is None:
         ws = self._eval_ws
       dcsr = ws["dcsr"]
     else:
       blk, B, n_items, dcsr = inputs
       assert ws is not None and ws["n_items"] == n_items
-    z = None if csr_model else engine.encode_eval(blk, 0, B)
+    if user_rows is not None:
+      assert not csr_model and tuple(user_rows.shape) == (B, engine.h[0]) and user_rows.dtype == torch.float32
+      engine.ensure_capacity(B, blk.n_cap)
+      z = user_rows.contiguous()
+      host_ok = False                                             # (the fused form encodes the block's users itself)
+    else:
+      z = None if csr_model else engine.encode_eval(blk, 0, B)
     strip = max(k, min(n_items, int(self.eval_strip_items)))
     bounds = [(lo, min(n_items, lo + strip)) for lo in range(0, n_items, strip)]
     if len(bounds) > 1 and bounds[-1][1] - bounds[-1][0] < k:      # a last strip shorter than k:

@@ -173,3 +173,27 @@ class InferenceRecommender(Recommender):
     """The same lists left on the device: (int64 tensor [users, k], its row stride), what
     ``RecommenderEvaluator.evaluate(on_device=True)`` hands to rk_als_rank_metrics."""
     return self.model._recommend_device(users_hist, self.num_recommendations)
+
+
+class FoldInRecommender(Recommender):
+  """Recommends to users a ``Recoder``'s MatrixFactorization has not seen: every batch's user rows are folded in
+  from the users' histories (``Recoder.fold_in`` at ``alpha``, ``reg``; recoder_amd/foldin.py) and scored like
+  ``InferenceRecommender``'s.  ``users_hist.users`` is ignored.  With ``RecommenderEvaluator`` this evaluates strong
+  generalisation (held-out users), on its host path and with ``on_device=True``."""
+
+  def __init__(self, model, num_recommendations, alpha=30.0, reg=100.0):
+    self.model = model
+    self.num_recommendations = num_recommendations
+    self.alpha = alpha
+    self.reg = reg
+
+  def recommend(self, users_hist):
+    return self.recommend_array(users_hist).tolist()
+
+  def recommend_array(self, users_hist):
+    return self.model.recommend_folded(users_hist, self.num_recommendations, alpha=self.alpha, reg=self.reg)
+
+  def recommend_device(self, users_hist):
+    """(int64 device tensor [users, k], its row stride), as ``InferenceRecommender.recommend_device``."""
+    rows = self.model.fold_in(users_hist.interactions_matrix, self.alpha, self.reg)
+    return self.model._recommend_device(users_hist, self.num_recommendations, user_rows=rows)
