@@ -600,6 +600,91 @@ int rk_als_foldin(const int64_t *indptr, const int32_t *indices, const float *da
                   int32_t ldy, int32_t h, const float *G, const float *v, const float *bias, float alpha, float *X,
                   int32_t ldx, int32_t *status, void *stream);
 
+/* the limits of the iALS++ kernels: the embedding size (rk_als_ials_max_h(), 2048), the block width
+ * (rk_als_ials_max_block(), 128), and the entries from which rk_als_ials_block cuts a row over a whole workgroup */
+#define RK_ALS_IALS_LONG_ROW 1024
+int rk_als_ials_max_h(void);
+int rk_als_ials_max_block(void);
+
+/*
+ * iALS++ (Rendle, Krichene, Zhang & Koren 2021, "iALS++: Speeding up Matrix Factorization with Subspace
+ * Optimization") for the same model with the bias 0, on the objective of Rendle et al. 2022: with S the stored entries
+ * (their values play no part), X [n_users, ldx] and Y [n_items, ldy],
+ *   L = sum_{(u,i) in S} (x_u . y_i - 1)^2 + alpha0 sum_u sum_i (x_u . y_i)^2 + sum_u lam_u |x_u|^2 + sum_i mu_i |y_i|^2
+ * with per-row regularisers lam, mu the caller builds (recoder_amd/ials.py: reg (count + alpha0 n)^nu in float64,
+ * rounded once).  The solver keeps c[e] = x_u . y_i for every stored entry, in the order of the user-major CSR.
+ *
+ * rk_als_ials_predict: c[e] = X[u_e] . Y[indices[e]] for the nnz entries of the CSR indptr (int64 [rows + 1]) / indices;
+ * a wave takes 8 consecutive entries one after the other; per entry lane l runs the chain fmaf(x_k, y_k, .) over
+ * k = l + 64 q ascending from +0, then an xor butterfly over lane distances 32 .. 1.  nnz == 0: nothing is launched.
+ */
+int rk_als_ials_predict(const int64_t *indptr, const int32_t *indices, int32_t rows, int64_t nnz, const float *X,
+                        int32_t ldx, const float *Y, int32_t ldy, int32_t h, float *c, void *stream);
+
+/*
+ * One block step on the coordinates pi = [p0, p0 + k) of the rows [row_lo, row_hi) of one side.  indptr / indices is
+ * that side's CSR (the user-major one, or its transpose for the items), F [., ldf] the fixed table its columns index,
+ * X [., ldx] the table updated in place, P [k, ldp] the panel rk_als_ials_gram_panel(F, p0, k) = F[:, pi]^T F, reg one
+ * regulariser per row, and perm (int64 [nnz]; NULL on the user side) maps entry e of this CSR to its position in the
+ * cache: the cache entry of e is c[perm ? perm[e] : e].  Per row u, with S_u its entries:
+ *   g = sum_{e in S_u} (c_e - 1) f_e[pi] + alpha0 P x_u + reg_u x_u[pi]
+ *   A = sum_{e in S_u} f_e[pi] f_e[pi]^T + alpha0 P[:, pi] + reg_u I
+ *   delta = A^-1 g (Cholesky);  x_u[pi] -= delta;  c_e -= delta . f_e[pi] for e in S_u
+ * A row whose Cholesky meets a pivot that is not > 0 (nan included; possible only with reg_u = 0) is left as it is,
+ * cache included, and status[0] (int32, the caller zeroes it) is raised by one: an integer atomic, the only atomic.
+ * Nothing outside the rows' columns pi and the rows' own cache entries is written.
+ * Arithmetic (all f32, every fused operation an fmaf, nothing else contracted; the same inputs give the same bits):
+ *   - a row of fewer than RK_ALS_IALS_LONG_ROW entries is one part; a longer one is cut into NP = 8 (k <= 64) or 2
+ *     contiguous parts with the bounds p n / NP.  A part takes its entries in ascending order:
+ *     gp_j = fmaf(c_e - 1, f_e[j], gp_j) and, for the lower triangle, a_jl = fmaf(f_e[j], f_e[l], a_jl), from +0
+ *   - A_jl = fmaf(alpha0, P[j][p0 + l], [j == l] reg_u), then the parts' a_jl added in ascending part order
+ *   - g_j = fmaf(reg_u, x[p0 + j], alpha0 * d_j) with d_j = fmaf(P[j][c], x[c], .) over c = 0 .. h - 1 from +0, then
+ *     the parts' gp_j added in ascending part order
+ *   - Cholesky and both triangular solves as rk_als_foldin states them; x[p0 + j] = x[p0 + j] - delta_j
+ *   - c_e = c_e - s_e, s_e the sum over 16 lanes (xor butterfly over distances 8 .. 1) of lane l's chain
+ *     fmaf(delta_j, f_e[j], .) over j = l + 16 q ascending from +0
+ * A row's result depends on its own entries, its cache entries, F, P, reg_u, alpha0 and its own value alone.
+ * long_rows (int32 [n_long], or NULL): the caller's list of this CSR's rows with RK_ALS_IALS_LONG_ROW entries or more,
+ * every one of them, in any order; the long rows' launch then takes one workgroup per listed row (those outside the
+ * range leave at once) and none when the list is empty.  With NULL the launch takes one workgroup per row of the range
+ * and the short ones leave at once: the same bits, more empty workgroups.  Two
+ * launches on `stream` (the short rows, four or one a workgroup; the long rows, one workgroup of 512 threads each);
+ * no workspace.  -2 unless 1 <= h <= rk_als_ials_max_h(), 1 <= k <= rk_als_ials_max_block(), 0 <= p0 <= h - k, ldf,
+ * ldx, ldp >= h, 0 <= row_lo <= row_hi, alpha0 finite and >= 0 and (with rows) no pointer but perm is NULL.
+ */
+int rk_als_ials_block(const int64_t *indptr, const int32_t *indices, const int64_t *perm, int32_t row_lo,
+                      int32_t row_hi, const int32_t *long_rows, int32_t n_long, const float *F, int32_t ldf, float *X,
+                      int32_t ldx, int32_t h, const float *P, int32_t ldp, const float *reg, float alpha0, int32_t p0,
+                      int32_t k, float *cache, int32_t *status, void *stream);
+
+/* bytes of rk_als_ials_gram_panel's workspace; -2 unless rows >= 0, 1 <= k <= min(h, 128) and h <= 2048 */
+int64_t rk_als_ials_panel_workspace_bytes(int32_t rows, int32_t h, int32_t k);
+
+/*
+ * P[j, c] = sum_r F[r, p0 + j] F[r, c] for j < k, c < h (P [k, ldp], f32): the k rows p0 .. p0 + k - 1 of F^T F, without
+ * a ridge term.  The rows are cut into at most 64 chunks fixed by `rows` alone; a chunk is one chain fmaf(F[r, p0 + j],
+ * F[r, c], .) over r ascending from +0, and the chunks are added in ascending order.  P[j, p0 + l] and P[l, p0 + j]
+ * are the same bits.  rows == 0 gives zeros.  Two launches, no atomics.
+ */
+int rk_als_ials_gram_panel(const float *F, int32_t rows, int32_t ldf, int32_t h, int32_t p0, int32_t k, float *P,
+                           int32_t ldp, void *ws, int64_t ws_bytes, void *stream);
+
+/* bytes of rk_als_ials_objective's workspace (4 x 256 float64 partial sums) */
+int64_t rk_als_ials_objective_workspace_bytes(void);
+
+/*
+ * out[0] = L (float64, device memory) from the cache (f32 [nnz]: sum (c - 1)^2), the two full Grams Gx = X^T X and
+ * Gy = Y^T Y ([h, h], leading dimension h, no ridge: alpha0 <Gx, Gy>) and the weighted row norms sum_u lam_u |x_u|^2 +
+ * sum_i mu_i |y_i|^2.  Every product and sum is float64: element b 256 + t + 65536 j of a sum goes to thread t of block
+ * b in ascending j (for the norms: row b 4 + w + 1024 j to wave w, lanes over the columns, an xor butterfly), a block's
+ * threads are added by a halving tree, the 256 blocks in ascending order, and L = ((cache + alpha0 gram) + users) +
+ * items.  Two launches, no atomics.
+ */
+int rk_als_ials_objective(const float *cache, int64_t nnz, const float *Gx, const float *Gy, int32_t h,
+                          const float *X, int32_t ldx, int32_t n_users, const float *lam, const float *Y, int32_t ldy,
+                          int32_t n_items, const float *mu, float alpha0, void *ws, int64_t ws_bytes, double *out,
+                          void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

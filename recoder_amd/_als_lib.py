@@ -5,7 +5,8 @@ gradient (rk_als_rank_sample, rk_als_warp_grad) for recoder_amd.warp, the LightG
 (rk_als_dau_*) for recoder_amd.directau, the sampled softmax's (rk_als_ssm_*) for recoder_amd.ssm, UltraGCN's (rk_als_ugcn_*) for
 recoder_amd.ultragcn, the cosine contrastive loss' (rk_als_ccl_*) for recoder_amd.ccl and SimpleX's pooled user rows
 (rk_als_sx_*) for recoder_amd.simplex, and the ranking metrics of device-resident top-k lists (rk_als_rank_metrics) for recoder_amd.metrics
-and recoder_amd.validation, and the exact fold-in of unseen users (rk_als_foldin) for recoder_amd.foldin.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
+and recoder_amd.validation, the exact fold-in of unseen users (rk_als_foldin) for recoder_amd.foldin, and the iALS++ kernels
+(rk_als_ials_*) for recoder_amd.ials.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
 import os
 
 # PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
@@ -34,6 +35,7 @@ RANK_WARP, RANK_DNS = 0, 1  # RK_ALS_RANK_WARP, RK_ALS_RANK_DNS
 METRIC_RECALL, METRIC_NDCG, METRIC_AP = 0, 1, 2  # RK_ALS_METRIC_RECALL, _NDCG, _AP
 RANK_METRICS_MAX = 8  # RK_ALS_RANK_METRICS_MAX
 FOLDIN_MAX_H = 128  # rk_als_foldin_max_h()
+IALS_MAX_H, IALS_MAX_BLOCK, IALS_LONG_ROW = 2048, 128, 1024  # rk_als_ials_max_h(), _max_block(), RK_ALS_IALS_LONG_ROW
 
 # name -> (restype, argtypes); every symbol include/recoder_als.h declares
 SIGNATURES = {
@@ -94,6 +96,16 @@ SIGNATURES = {
                                     _P, _P, _P]),
   "rk_als_foldin_max_h": (c_int32, []),
   "rk_als_foldin": (c_int32, [_P, _P, _P, c_int32, _P, c_int32, c_int32, _P, _P, _P, c_float, _P, c_int32, _P, _P]),
+  "rk_als_ials_max_h": (c_int32, []),
+  "rk_als_ials_max_block": (c_int32, []),
+  "rk_als_ials_predict": (c_int32, [_P, _P, c_int32, c_int64, _P, c_int32, _P, c_int32, c_int32, _P, _P]),
+  "rk_als_ials_block": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32, _P,
+                                  c_int32, _P, c_float, c_int32, c_int32, _P, _P, _P]),
+  "rk_als_ials_panel_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+  "rk_als_ials_gram_panel": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int64, _P]),
+  "rk_als_ials_objective_workspace_bytes": (c_int64, []),
+  "rk_als_ials_objective": (c_int32, [_P, c_int64, _P, _P, c_int32, _P, c_int32, c_int32, _P, _P, c_int32, c_int32, _P,
+                                      c_float, _P, c_int64, _P, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

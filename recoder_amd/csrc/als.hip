@@ -83,6 +83,13 @@
 //                          triangle in LDS, both triangular solves by columns; one workgroup a row at h > 64, four rows
 //                          a workgroup below; h <= 128.  No atomics, no workspace
 //
+// iALS++ for the same model (rk_als_ials_*): the sweep of recoder_amd/ials.py adds
+//   rk_als_ials_predict     the prediction cache c[e] = x_u . y_i of every stored entry, a wave's dot chain per entry
+//   rk_als_ials_block       one block of k <= 128 coordinates of every row solved exactly against the cache: the fold-in's
+//                          register tiles, Cholesky and solves on a k x k system, a long row cut over one workgroup in
+//                          fixed parts, then the row's cache entries
+//   rk_als_ials_gram_panel  the k rows F[:, pi]^T F of a Gram in fixed row chunks; rk_als_ials_objective: L in float64
+//
 // One translation unit (one last-error buffer, one anonymous namespace), laid out by family under als/: every file
 // holds its kernels, then its extern "C" entry points.
 #include "als/common.h"     // the lane layout, the counter hash, the segment walk, the NT and lane-group dispatch
@@ -96,6 +103,7 @@
 #include "als/simplex.h"    // rk_als_sx_* (beside ccl.h's loss)
 #include "als/metrics.h"    // rk_als_rank_metrics
 #include "als/foldin.h"     // rk_als_foldin (beside solve.h's row solves)
+#include "als/ials.h"       // rk_als_ials_* (the fold-in's solve on a block of coordinates)
 
 extern "C" int rk_als_version(void) { return 100; }
 extern "C" const char *rk_als_last_error(void) { return g_rk_side_err; }

@@ -96,6 +96,7 @@ class Recoder(object):
     self.last_epoch_losses = None
     self.loss_history = []      # per-epoch arrays of the per-step training losses
     self.als_history = []       # train_als: the ALS objective after each iteration
+    self.ials_history = []      # train_ials: the iALS++ objective after each sweep
     self.bpr_history = []       # train_bpr: the mean loss per valid triple of each epoch
     self.warp_history = []      # train_warp: the mean loss per valid slot of each epoch
     self.warp_stats = []        # train_warp: (share of slots with a violator, their mean trials) of each epoch
@@ -120,7 +121,7 @@ class Recoder(object):
     self.fit_validation = None  # validation settings for the iterative fits called without a val_dataset (_validated)
     self.bpr_validation = self.warp_validation = self.lightgcn_validation = self.simgcl_validation = None
     self.directau_validation = self.ssm_validation = self.ultragcn_validation = self.ccl_validation = None
-    self.simplex_validation = None
+    self.simplex_validation = self.ials_validation = None
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -548,6 +549,49 @@ class Recoder(object):
                                 cg_steps),
         fit=lambda m, pair, alpha: als.fit(*_mf_tables(m), m.bias.data, *pair, alpha, float(reg), int(cg_steps),
                                            int(num_iterations)))
+
+  def train_ials(self, train_dataset, num_sweeps=16, block_size=64, alpha0=0.03, reg=0.03, nu=1.0, init_std=None,
+                 seed=0, val_dataset=None, eval_metric=None, eval_freq=1, eval_batch_size=500, eval_num_users=None,
+                 patience=None, restore_best=False):
+    """iALS++ (Rendle et al. 2021) on the iALS objective of Rendle et al. 2022 for a MatrixFactorization with
+    activation 'none' (recoder_amd/ials.py): minimises sum over the stored entries of (x_u . y_i - 1)^2 + ``alpha0``
+    times the sum over ALL pairs of (x_u . y_i)^2 + sum_u lam_u |x_u|^2 + sum_i mu_i |y_i|^2 with the frequency-scaled
+    regularisers lam_u = ``reg`` (r_u + ``alpha0`` n_items)^``nu`` and mu_i = ``reg`` (d_i + ``alpha0`` n_users)^``nu``
+    (r_u, d_i the row and column counts; ``nu = 0`` is one ``reg`` for every row).  A sweep visits the blocks of
+    ``block_size`` (1..``ials.MAX_BLOCK``, cut to h) coordinates in ascending order, all users for a block and then all
+    items, and solves every row's block exactly by Cholesky against a cache of the stored entries' predictions;
+    ``block_size = h`` is exact ALS.  Embedding sizes up to ``ials.MAX_H``.  ``init_std`` None trains the tables as
+    they stand (a warm start from any earlier fit, and how a later call continues: two calls of n sweeps are one of
+    2 n, bit for bit); a float draws both from N(0, init_std^2 / h) with a generator seeded by ``seed`` (torch's
+    global one is not touched).  The stored values and the configured ``loss`` play no part; the bias ends as 0.
+    Builds a fresh optimizer of ``optimizer_type``, so that ``save_state``, ``train``, ``train_als``, ``fold_in`` and
+    the embeddings index work on the tables it leaves.  A row whose block system is not positive definite (``reg = 0``
+    only) is left unchanged, with one warning per call.  Returns (and keeps in ``ials_history``) L after each sweep.
+    ``val_dataset`` and the keywords after it: validation during the fit and early stopping (``_validated``), once
+    per sweep."""
+    from . import ials
+    vcheck, monitor, vkeep = self._validated("train_ials", "ials", train_dataset, (val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience, restore_best))
+
+    def check(m):
+      c = ials.check_config(m, num_sweeps, block_size, alpha0, reg, nu, init_std, seed)
+      vcheck()
+      return c
+
+    def fit(m, pair, c):
+      X, Y = _mf_tables(m)
+      if c[5] is not None:
+        ials.init_tables(X, Y, c[5], c[6])
+      m.bias.data.zero_()
+      hist = ials.fit(X, Y, pair, c[2], c[3], c[4], c[1], c[0], monitor=monitor())
+      vkeep()
+      return hist
+    return self._closed_form_fit(
+        ials, train_dataset, "ials_history", copy=list, csrs=ials.csr_pair, check=check, fit=fit,
+        log_line=lambda c: ("iALS++: %d sweeps of blocks of %d, alpha0 %g, reg %g, nu %g, init_std %s, seed %d",) + c,
+        hint_check=lambda c, u, n, host: u and n and ials.check_memory(u, n, self.model.embedding_size, 0, c[1],
+                                                                       free_bytes=float("inf")),
+        size_check=lambda c, host: ials.check_memory(self.num_users, self.num_items, self.model.embedding_size,
+                                                     host().nnz, c[1], allocate_model=False))
 
   def _validated(self, method, prefix, train_dataset, args):
     """The validation keywords the iterative trainers share (recoder_amd/validation.py), ``args`` =
