@@ -685,6 +685,76 @@ int rk_als_ials_objective(const float *cache, int64_t nnz, const float *Gx, cons
                           int32_t n_items, const float *mu, float alpha0, void *ws, int64_t ws_bytes, double *out,
                           void *stream);
 
+/*
+ * NeuMF (He, Liao, Zhang, Nie, Hu & Chua 2017) for recoder_amd/ncf.py:
+ *   s(u, i) = w[:dg] . (Pg[u] o Qg[i]) + w[dg:] . phi_L + b0,  phi_0 = [Pm[u] ; Qm[i]],  phi_l = relu(W_l phi_{l-1} + c_l)
+ * with 1 <= L <= RK_ALS_NCF_MAX_LAYERS layers of widths d_1 .. d_L (d_l past L is ignored); dg, dm and every d_l are
+ * multiples of 4 in [4, RK_ALS_NCF_MAX_WIDTH].  The dense parameters are one f32 vector
+ *   theta = [W_1, c_1, ..., W_L, c_L, w, b0],  W_l row-major [d_l, d_{l-1}] (d_0 = 2 dm), w [dg + d_L],
+ * of rk_als_ncf_dense_count floats.  A workgroup takes a tile of RK_ALS_NCF_TILE entries (the step) or items (the
+ * scores); its matrix products are 16 x 16 tiles of the f32 MFMA over weights kept in LDS at a row pitch of d + 1.
+ * rk_als_ncf_lds_bytes gives a kernel's LDS (scores == 0: the step; else the scores), in floats
+ *   step    sum_l (d_l (d_{l-1} + 1) + d_l + 32 (d_l + 1)) + dg + d_L + 1 + 128
+ *   scores  sum_{l >= 2} (d_l (d_{l-1} + 1) + d_l) + dg + d_L + 1 + 32 (d_1 + 1) + 32 (dg + 1) + 64 (max_l d_l + 1) + d_1 + dg
+ * and a configuration fits when both are at most 160 KiB (163840 bytes); the entry points below return -2 otherwise.
+ * The three queries are host arithmetic (-2 on bad sizes).
+ */
+#define RK_ALS_NCF_TILE 32
+#define RK_ALS_NCF_MAX_WIDTH 128
+#define RK_ALS_NCF_MAX_LAYERS 3
+int64_t rk_als_ncf_dense_count(int32_t dg, int32_t dm, int32_t L, int32_t d1, int32_t d2, int32_t d3);
+int64_t rk_als_ncf_lds_bytes(int32_t dg, int32_t dm, int32_t L, int32_t d1, int32_t d2, int32_t d3, int32_t scores);
+
+/* bytes of the step's buffers ukey, ikey (int32 [E]), GU, GI (f32 [E, dg + dm]), slabs (f32 [ceil(E / 32), n + 1], n
+ * the dense count) and loss (f32 [1]), E = T (1 + R), each rounded up to 256 bytes and laid out in that order; -2 unless
+ * 1 <= T <= RK_ALS_CCL_MAX_BATCH, 1 <= R <= RK_ALS_CCL_MAX_NEGATIVES and E <= RK_ALS_CCL_MAX_ENTRIES */
+int64_t rk_als_ncf_workspace_bytes(int32_t T, int32_t R, int32_t dg, int32_t dm, int32_t L, int32_t d1, int32_t d2,
+                                   int32_t d3);
+
+/*
+ * Forward, loss and backward of one step in one launch.  Entry e = t (1 + R) + c of slot t (users[t], pos[t]: the
+ * stored entry rk_als_bpr_sample drew): c = 0 is the pair itself with label 1, c >= 1 the user with negative c - 1,
+ * label 0 -- the draw of rk_als_ugcn_grad and rk_als_ccl_grad for (seed, step, t R + c - 1), uniform over [0, n_items),
+ * nothing rejected: an item the user holds can be drawn as a negative, as in those two.  An entry with an id outside
+ * its table is invalid: no loss, zero gradients, the keys n_users and n_items.  With z = s(u, i):
+ *   loss term  softplus(z) - y z,  g = sigma(z) - y      (through e = exp(-|z|), as rk_als_bpr_grad)
+ *   ukey[e], ikey[e]  the entry's rows (to be sorted by the caller)
+ *   GU[e] = [g w[:dg] o Qg[i] ; d/dPm],  GI[e] = [g w[:dg] o Pg[u] ; d/dQm]      (f32 [E, dg + dm])
+ *   slabs[tile] = the tile's sums over its entries of dW_l, dc_l, dw, db0 in theta's layout, then its loss sum
+ * Nothing is divided by E here.  rk_als_lgcn_scatter (roles 1, g = ones, scale -1 / E) sums GU and GI per row and
+ * rk_als_lgcn_adam updates the tables [Pg | Pm] and [Qg | Qm] when each pair is one matrix of leading dimension dg + dm.
+ * Every sum has a fixed order; no atomics: the same inputs give the same bits.
+ */
+int rk_als_ncf_step(const int32_t *users, const int32_t *pos, int32_t T, int32_t R, int64_t seed, int32_t step,
+                    int32_t n_users, int32_t n_items, const float *Pg, int32_t ldpg, const float *Qg, int32_t ldqg,
+                    const float *Pm, int32_t ldpm, const float *Qm, int32_t ldqm, const float *theta, int32_t dg,
+                    int32_t dm, int32_t L, int32_t d1, int32_t d2, int32_t d3, int32_t *ukey, int32_t *ikey, float *GU,
+                    float *GI, float *slabs, void *stream);
+
+/*
+ * One Adam step t >= 1 on theta in place (moments M, V like theta): element x's gradient is the slabs' sum over the
+ * tiles in ascending order from +0, times 1.f / entries, plus reg theta[x] on W_l and w (one fmaf; not on c_l and b0);
+ * the update is rk_als_lgcn_adam's.  loss[0] receives the slabs' loss sum, in the same order.  One launch.
+ */
+int rk_als_ncf_dense_adam(float *theta, float *M, float *V, const float *slabs, int32_t tiles, int32_t entries,
+                          int32_t dg, int32_t dm, int32_t L, int32_t d1, int32_t d2, int32_t d3, float lr, float reg,
+                          float beta1, float beta2, float eps, int32_t t, float *loss, void *stream);
+
+/* A [n_items, d1] = Qm W_1[:, dm:]^T, the items' half of layer 1: one fmaf chain over k ascending per element */
+int rk_als_ncf_item_part(const float *Qm, int32_t ldqm, int32_t n_items, const float *theta, int32_t dm, int32_t d1,
+                         float *A, void *stream);
+
+/*
+ * out[b, c] = s(users[b], lo + c) for b < B and c < hi - lo (row stride ld; nothing else of out is written), from A of
+ * rk_als_ncf_item_part at the same theta.  UH (f32 [B, d1], scratch) receives the users' half W_1[:, :dm] Pm[u] + c_1,
+ * once per user; layer 1 is relu(UH[b] + A[i]), layers 2 .. L are MFMA tiles of 32 items, the GMF term is
+ * (Pg[u] o w[:dg]) . Qg[i].  A user id outside [0, n_users) gives a row of +0.  Two launches.
+ */
+int rk_als_ncf_scores(const int32_t *users, int32_t B, int32_t n_users, int32_t lo, int32_t hi, int32_t n_items,
+                      const float *Pg, int32_t ldpg, const float *Qg, int32_t ldqg, const float *Pm, int32_t ldpm,
+                      const float *A, const float *theta, int32_t dg, int32_t dm, int32_t L, int32_t d1, int32_t d2,
+                      int32_t d3, float *UH, float *out, int64_t ld, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@ Drop-in for the reference's training path: ``Recoder`` / ``FactorizationModel``
 __version__ = "0.4.0"
 
 __all__ = ["ShallowAutoencoder", "RandomWalkItemModel", "SparseLinearModel", "UserNeighbourhoodModel",
-           "ItemNeighbourhoodModel", "GraphFilterModel", "AdmmSlimModel", "LowRankShallowAutoencoder"]
+           "ItemNeighbourhoodModel", "GraphFilterModel", "AdmmSlimModel", "LowRankShallowAutoencoder",
+           "NeuralMatrixFactorization"]
 
 
 def __getattr__(name):
@@ -38,4 +39,7 @@ def __getattr__(name):
   if name == "LowRankShallowAutoencoder":
     from .nn import LowRankShallowAutoencoder
     return LowRankShallowAutoencoder
+  if name == "NeuralMatrixFactorization":
+    from .nn import NeuralMatrixFactorization
+    return NeuralMatrixFactorization
   raise AttributeError("module %r has no attribute %r" % (__name__, name))

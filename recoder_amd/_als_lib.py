@@ -6,7 +6,7 @@ gradient (rk_als_rank_sample, rk_als_warp_grad) for recoder_amd.warp, the LightG
 recoder_amd.ultragcn, the cosine contrastive loss' (rk_als_ccl_*) for recoder_amd.ccl and SimpleX's pooled user rows
 (rk_als_sx_*) for recoder_amd.simplex, and the ranking metrics of device-resident top-k lists (rk_als_rank_metrics) for recoder_amd.metrics
 and recoder_amd.validation, the exact fold-in of unseen users (rk_als_foldin) for recoder_amd.foldin, and the iALS++ kernels
-(rk_als_ials_*) for recoder_amd.ials.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
+(rk_als_ials_*) for recoder_amd.ials, and NeuMF's step and scores (rk_als_ncf_*) for recoder_amd.ncf.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
 import os
 
 # PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
@@ -36,6 +36,7 @@ METRIC_RECALL, METRIC_NDCG, METRIC_AP = 0, 1, 2  # RK_ALS_METRIC_RECALL, _NDCG, 
 RANK_METRICS_MAX = 8  # RK_ALS_RANK_METRICS_MAX
 FOLDIN_MAX_H = 128  # rk_als_foldin_max_h()
 IALS_MAX_H, IALS_MAX_BLOCK, IALS_LONG_ROW = 2048, 128, 1024  # rk_als_ials_max_h(), _max_block(), RK_ALS_IALS_LONG_ROW
+NCF_TILE, NCF_MAX_WIDTH, NCF_MAX_LAYERS = 32, 128, 3  # RK_ALS_NCF_TILE, _MAX_WIDTH, _MAX_LAYERS
 
 # name -> (restype, argtypes); every symbol include/recoder_als.h declares
 SIGNATURES = {
@@ -106,6 +107,18 @@ SIGNATURES = {
   "rk_als_ials_objective_workspace_bytes": (c_int64, []),
   "rk_als_ials_objective": (c_int32, [_P, c_int64, _P, _P, c_int32, _P, c_int32, c_int32, _P, _P, c_int32, c_int32, _P,
                                       c_float, _P, c_int64, _P, _P]),
+  "rk_als_ncf_dense_count": (c_int64, [c_int32] * 6),
+  "rk_als_ncf_lds_bytes": (c_int64, [c_int32] * 7),
+  "rk_als_ncf_workspace_bytes": (c_int64, [c_int32] * 8),
+  "rk_als_ncf_step": (c_int32, [_P, _P, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32,
+                                _P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P,
+                                _P, _P, _P, _P, _P]),
+  "rk_als_ncf_dense_adam": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                      c_int32, c_float, c_float, c_float, c_float, c_float, c_int32, _P, _P]),
+  "rk_als_ncf_item_part": (c_int32, [_P, c_int32, c_int32, _P, c_int32, c_int32, _P, _P]),
+  "rk_als_ncf_scores": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32, _P,
+                                  c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P,
+                                  c_int64, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

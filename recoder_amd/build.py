@@ -22,7 +22,9 @@ librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recode
                    item-side sum that gathers its user rows) and the cosine contrastive loss' (rk_als_ccl_workspace_bytes,
                    rk_als_ccl_grad, rk_als_ccl_scatter: the hinge on the cosine over a slot's private negatives, and
                    the item-side sum over the live entries only) and the ranking metrics of device-resident top-k lists
-                   (rk_als_rank_metrics: Recall / NDCG / AveragePrecision for validation during a fit)
+                   (rk_als_rank_metrics: Recall / NDCG / AveragePrecision for validation during a fit) and NeuMF's step,
+                   dense Adam, item half and scores for NeuralMatrixFactorization (rk_als_ncf_*: a per-pair MLP on
+                   16 x 16 f32-MFMA tiles against weights in LDS, csrc/als/ncf.h)
 librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own
 librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencoder

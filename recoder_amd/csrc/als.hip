@@ -90,6 +90,14 @@
 //                          fixed parts, then the row's cache entries
 //   rk_als_ials_gram_panel  the k rows F[:, pi]^T F of a Gram in fixed row chunks; rk_als_ials_objective: L in float64
 //
+// NeuMF (rk_als_ncf_*): the step of recoder_amd/ncf.py and the scores of nn.NeuralMatrixFactorization add
+//   rk_als_ncf_step         forward, loss and backward of a tile of 32 entries in one workgroup: the MLP on 16 x 16 tiles
+//                           of the f32 MFMA against weights in LDS, gradient rows per entry, a slab of dense partials
+//   rk_als_ncf_dense_adam   the slabs added in tile order and Adam on every dense parameter, one launch
+//   rk_als_ncf_item_part    the items' half of layer 1, once per model state
+//   rk_als_ncf_scores       a strip of scores for a batch of user ids: layer 1 as a sum of halves, the rest on MFMA tiles
+//                           of 32 items, no [B, strip, .] intermediate
+//
 // One translation unit (one last-error buffer, one anonymous namespace), laid out by family under als/: every file
 // holds its kernels, then its extern "C" entry points.
 #include "als/common.h"     // the lane layout, the counter hash, the segment walk, the NT and lane-group dispatch
@@ -104,6 +112,7 @@
 #include "als/metrics.h"    // rk_als_rank_metrics
 #include "als/foldin.h"     // rk_als_foldin (beside solve.h's row solves)
 #include "als/ials.h"       // rk_als_ials_* (the fold-in's solve on a block of coordinates)
+#include "als/ncf.h"        // rk_als_ncf_* (on ugcn.h's draw)
 
 extern "C" int rk_als_version(void) { return 100; }
 extern "C" const char *rk_als_last_error(void) { return g_rk_side_err; }

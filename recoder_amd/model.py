@@ -35,6 +35,7 @@ from .engine import FusedEngine
 from .losses import MSELoss, MultinomialNLLLoss
 from .metrics import RecommenderEvaluator
 from .nn import (CsrScoresModel, DynamicAutoencoder, FactorizationModel, MatrixFactorization,
+                 NeuralMatrixFactorization,
                  VariationalAutoencoder)
 from .recommender import InferenceRecommender
 
@@ -121,7 +122,9 @@ class Recoder(object):
     self.fit_validation = None  # validation settings for the iterative fits called without a val_dataset (_validated)
     self.bpr_validation = self.warp_validation = self.lightgcn_validation = self.simgcl_validation = None
     self.directau_validation = self.ssm_validation = self.ultragcn_validation = self.ccl_validation = None
-    self.simplex_validation = self.ials_validation = None
+    self.simplex_validation = self.ials_validation = self.ncf_validation = None
+    self.ncf_history = []       # train_ncf: the mean loss per entry of each epoch
+    self.ncf_state = None       # train_ncf: [Pg | Pm], [Qg | Qm], theta, Adam moments, step count (device; not saved)
     self.svd_info = None        # train_svd: what the last PureSVD fit reported
     self.rp3_info = None        # train_rp3beta: what the last RP3beta fit reported
     self.slim_info = None       # train_slim: what the last SLIM fit reported
@@ -461,6 +464,19 @@ class Recoder(object):
     """True for the models without an encoder (nn.CsrScoresModel: the item-item models, scores = the users' CSR
     rows times W, and the user-neighbourhood model): scores come from ``model.csr_scores``."""
     return isinstance(self.model, CsrScoresModel)
+
+  def _scores_from_user_ids(self):
+    """True for the model scored from user ids by a kernel of its own (nn.NeuralMatrixFactorization): scores come
+    from ``model.user_scores``."""
+    return isinstance(self.model, NeuralMatrixFactorization)
+
+  def _user_ids(self, users_interactions):
+    """The batch's user ids on the device (int32), each checked against [0, num_users) on the host."""
+    ids = np.asarray(users_interactions.users).astype(np.int64).reshape(-1)
+    n = self.model.Pg.shape[0]
+    if len(ids) and (ids.min() < 0 or ids.max() >= n):
+      raise ValueError("user ids must lie in [0, %d) (got %d .. %d)" % (n, ids.min(), ids.max()))
+    return torch.as_tensor(ids, dtype=torch.int32).to(self.device)
 
   def _size_hints(self, train_dataset):
     """(num_users, num_items) before the model is initialised: from the dataset's ids where unknown."""
@@ -932,6 +948,47 @@ class Recoder(object):
                                        restore_best))
     self.simplex_stats = list(self.simplex_state["live_share"])
     return hist
+
+  def train_ncf(self, train_dataset, num_epochs=10, batch_size=1024, lr=1e-3, reg=0.0, num_negatives=8, seed=0,
+                resume=False, val_dataset=None, eval_metric=None, eval_freq=1, eval_batch_size=500,
+                eval_num_users=None, patience=None, restore_best=True):
+    """NeuMF (He et al. 2017) for a NeuralMatrixFactorization (recoder_amd/ncf.py): a step takes ``batch_size``
+    (1..4096) of ``train_bpr``'s stored entries (u, i) with the label 1 and for each ``num_negatives`` (1..1024)
+    uniformly drawn items with the label 0 -- the candidate round of ``train_ultragcn`` and ``train_ccl``, which rejects
+    nothing: an item the user holds can come up -- and descends the mean binary cross-entropy of the logits over these
+    ``batch_size * (1 + num_negatives)`` entries (at most ``ncf.MAX_ENTRIES``) by one Adam step with learning rate
+    ``lr`` on the four tables (lazily: the L2 term ``reg`` reaches the rows the step touches) and on the dense
+    parameters (decay ``reg`` on the weights, none on the biases).  Forward, loss and backward are one HIP launch; the
+    draws are pure integer functions of (seed, step, slot), so a fixed seed gives the same bits.  A model that is not
+    initialised yet draws its parameters from ``seed``.  The tables, the dense parameters, their Adam moments and the
+    step count stay in ``ncf_state`` (device memory; not part of checkpoints) and ``resume=True`` continues from them:
+    2 + 1 epochs are 3 epochs bit for bit.  Returns (and keeps in ``ncf_history``) the mean loss per entry of each
+    epoch.  ``val_dataset`` and the keywords after it: validation during the fit and early stopping (``_validated``).
+    The defaults (10 epochs, lr 1e-3, 8 negatives, the model's (32, 32, (64, 32, 16))) are the best Recall@20 of the
+    float64 grid on the ML-20M slice (profiles/ncf_quality.jsonl): 0.1236; the fit overfits from there (0.1092 after 15).
+    Not built: GMF-only and MLP-only models and pre-training from them, other activations, dropout, multi-GPU."""
+    from . import bpr, ncf
+    vcheck, monitor, vkeep = self._validated("train_ncf", "ncf", train_dataset, (val_dataset, eval_metric, eval_freq, eval_batch_size, eval_num_users, patience, restore_best))
+
+    def check(m):
+      c = ncf.check_config(m, num_epochs, batch_size, lr, reg, num_negatives, seed)
+      if resume:
+        ncf.check_resume(self.ncf_state, c[0])
+      vcheck()
+      return c
+
+    def store(c):
+      return {} if self.model.Pg is not None else {"init_seed": c[6]}
+
+    def fit(m, ucsr, c):
+      state, hist = ncf.fit(m, ucsr, *c[1:], state=self.ncf_state if resume else None, monitor=monitor())
+      self.ncf_state = state
+      vkeep()
+      return hist
+    return self._closed_form_fit(
+        ncf, train_dataset, "ncf_history", copy=list, csrs=bpr.user_csr, check=check, fit=fit, store=store,
+        log_line=lambda c: ("NeuMF: sizes %r, %d epochs of batches of %d, lr %g, reg %g, %d negatives, seed %d",) + c,
+        size_check=lambda c, host: ncf.check_data(host().nnz, self.num_items, c[1], c[2]))
 
   def simplex_encode(self, interactions_matrix):
     """[B, h] on the device: the user rows (1 - gamma) W mean(Q[history]) that the last ``train_simplex`` gives the B
@@ -1912,6 +1969,9 @@ class Recoder(object):
     if self._scores_from_csr_rows():
       self.model.csr_scores(self._eval_ws["dcsr"], 0, n_items, out, ld, B)
       return out[:, :n_items], blk, B
+    if self._scores_from_user_ids():
+      self.model.user_scores(self._user_ids(users_interactions), 0, n_items, out, ld)
+      return out[:, :n_items], blk, B
     engine.predict_scores(blk, 0, B, out, ld, blk)
     return out[:, :n_items], blk, B
 
@@ -1965,7 +2025,8 @@ class Recoder(object):
     from .device import current_stream
     lib = _lib.load()
     engine = self._engine()
-    csr_model = self._scores_from_csr_rows()
+    ids_model = self._scores_from_user_ids()
+    csr_model = self._scores_from_csr_rows() or ids_model        # (either way: no encoder, a scores kernel of its own)
     if (getattr(engine, "generic", False) and not csr_model) or k > lib.rk_topk_max_k():
       if user_rows is not None:
         raise ValueError("recommend_folded scores on the fused HIP engine (optimizer_type='adam', an embedding size "
@@ -2016,10 +2077,15 @@ class Recoder(object):
                     torch.empty(B, ns * k, dtype=torch.float32, device=self.device))
     cand_idx, cand_val = ws["cand"][0][:B], ws["cand"][1][:B]
     scores = ws["scores"]
+    user_ids = self._user_ids(users_interactions) if ids_model else None
     for s, (lo, hi) in enumerate(bounds):
       if csr_model:
-        # an item-item model's strip of scores: the users' CSR rows times W[:, lo:hi]
-        self.model.csr_scores(dcsr, lo, hi, scores, ld, B)
+        if ids_model:
+          # scored from user ids: the strip of the model's own kernel (rk_als_ncf_scores)
+          self.model.user_scores(user_ids, lo, hi, scores, ld)
+        else:
+          # an item-item model's strip of scores: the users' CSR rows times W[:, lo:hi]
+          self.model.csr_scores(dcsr, lo, hi, scores, ld, B)
         _lib.check(lib.rk_topk_masked(scores.data_ptr(), B, hi - lo, ld, blk.ref, 0, k, lo, 1,
                                       cand_idx[:, s * k:].data_ptr(), cand_val[:, s * k:].data_ptr(),
                                       ns * k, current_stream()), "rk_topk_masked")

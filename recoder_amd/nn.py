@@ -1034,3 +1034,132 @@ class UserNeighbourhoodModel(CsrScoresModel):
     kept = torch.zeros_like(sim).scatter_(1, order, sim.gather(1, order))
     out = kept @ X
     return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
+
+
+class NeuralMatrixFactorization(FactorizationModel):
+  """NeuMF, the fusion of GMF and an MLP of Neural Collaborative Filtering (He, Liao, Zhang, Nie, Hu & Chua, WWW 2017):
+
+      s(u, i) = w[:dg] . (Pg[u] o Qg[i]) + w[dg:] . phi_L + b0,  phi_0 = [Pm[u] ; Qm[i]],  phi_l = relu(W_l phi_{l-1} + c_l)
+
+  the one model here whose score is neither a dot product nor a function of the user's row.  Parameters: the GMF tables
+  ``Pg`` [users, dg] and ``Qg`` [items, dg] (dg = ``embedding_size``), the MLP tables ``Pm`` [users, dm] and ``Qm``
+  [items, dm] (dm = ``mlp_embedding_size``), the layers ``mlp_weights[l]`` [d_l, d_{l-1}] (d_0 = 2 dm) and
+  ``mlp_biases[l]`` [d_l] for the 1..3 widths of ``mlp_layers``, and the output layer ``w`` [dg + d_L], ``b0`` [1].
+  Every size is a multiple of 4 in 4..128 and the layers' weights fit a workgroup's LDS together (``ncf.check_sizes``).
+  ``init_model`` draws as the paper: N(0, 0.01) tables, Xavier-uniform W_l, zero biases, ``w`` as a [1, dg + d_L]
+  linear layer -- on the host, from a ``torch.Generator`` seeded by ``init_seed`` (``Recoder.train_ncf`` sets it to the
+  fit's ``seed`` before the model is initialised).  Trained by ``Recoder.train_ncf`` (recoder_amd/ncf.py), which
+  ``Recoder.train`` points at.  Scores come from user ids: ``user_scores`` runs rk_als_ncf_scores over a strip, with the
+  items' half of layer 1 (``A`` = Qm W_1[:, dm:]^T, rk_als_ncf_item_part) and the packed dense parameters kept until
+  the parameters are written again (``_weights_written``).  ``forward`` on the host is the differentiable
+  ``torch_forward``; on the device it is the scores kernel, without autograd."""
+  fit_method = "train_ncf"
+  fit_sentence = ("a NeuralMatrixFactorization is trained on sampled (user, item) pairs under the binary "
+                  "cross-entropy, by its own HIP step: call %s(train_dataset)")
+
+  def __init__(self, embedding_size=32, mlp_embedding_size=32, mlp_layers=(64, 32, 16)):
+    super().__init__()
+    self.embedding_size = embedding_size
+    self.mlp_embedding_size = mlp_embedding_size
+    self.mlp_layers = mlp_layers
+    self.init_seed = 0
+    self.num_users = self.num_items = None
+    self.Pg = self.Qg = self.Pm = self.Qm = self.w = self.b0 = None
+    self.mlp_weights = self.mlp_biases = None
+    self._derived = None             # (A, theta) of the parameters as last written
+    self._validate()
+
+  def _validate(self):
+    from .ncf import check_sizes
+    self.embedding_size, self.mlp_embedding_size, self.mlp_layers = check_sizes(
+        self.embedding_size, self.mlp_embedding_size, self.mlp_layers)
+
+  def sizes(self):
+    return (self.embedding_size, self.mlp_embedding_size, tuple(self.mlp_layers))
+
+  def init_model(self, num_items=None, num_users=None):
+    self._validate()
+    self.num_users, self.num_items = num_users, num_items
+    dg, dm, layers = self.sizes()
+    gen = torch.Generator().manual_seed(int(self.init_seed) % (2 ** 63))
+
+    def table(rows, d):
+      return nn.Parameter(torch.empty(rows, d).normal_(0.0, 0.01, generator=gen), requires_grad=False)
+    self.Pg, self.Qg = table(num_users, dg), table(num_items, dg)
+    self.Pm, self.Qm = table(num_users, dm), table(num_items, dm)
+
+    def xavier(rows, cols):                                    # (Xavier-uniform of a [rows, cols] linear layer)
+      bound = (6.0 / (rows + cols)) ** 0.5
+      return nn.Parameter((torch.rand(rows, cols, generator=gen) * 2 - 1) * bound, requires_grad=False)
+    ws, cs, prev = [], [], 2 * dm
+    for d in layers:
+      ws.append(xavier(d, prev))
+      cs.append(nn.Parameter(torch.zeros(d), requires_grad=False))
+      prev = d
+    self.mlp_weights, self.mlp_biases = nn.ParameterList(ws), nn.ParameterList(cs)
+    self.w = nn.Parameter(xavier(1, dg + prev).data.reshape(-1), requires_grad=False)
+    self.b0 = nn.Parameter(torch.zeros(1), requires_grad=False)
+    self._weights_written()
+
+  def model_params(self):
+    return {"embedding_size": int(self.embedding_size), "mlp_embedding_size": int(self.mlp_embedding_size),
+            "mlp_layers": [int(d) for d in self.mlp_layers]}
+
+  def load_model_params(self, model_params):
+    self.embedding_size = model_params["embedding_size"]
+    self.mlp_embedding_size = model_params["mlp_embedding_size"]
+    self.mlp_layers = tuple(model_params["mlp_layers"])
+    self._validate()
+
+  def _weights_written(self):
+    """A parameter was written: the items' half of layer 1 and the packed dense parameters are taken again."""
+    self._derived = None
+
+  def _load_from_state_dict(self, *args, **kwargs):
+    self._weights_written()
+    return super()._load_from_state_dict(*args, **kwargs)
+
+  def derived(self):
+    """(A [items, d1], theta) on the parameters' device, kept until ``_weights_written``."""
+    from . import ncf
+    key = (self.Qm.data_ptr(), self.Qm.device)
+    if self._derived is None or self._derived[0] != key:
+      theta = ncf.pack(self)[2]
+      self._derived = (key, ncf.item_part(self.Qm.data, theta, self.sizes()), theta)
+    return self._derived[1:]
+
+  def user_scores(self, users, lo, hi, out=None, ld=None):
+    """out[b, c] = s(users[b], lo + c) for c < hi - lo, ``out`` f32 with row stride ``ld`` (None: a new [B, hi - lo]
+    tensor); ``users`` are ids on the device, each in [0, num_users) -- the caller checks that."""
+    from . import ncf
+    A, theta = self.derived()
+    users = users.to(torch.int32).contiguous()
+    if out is None:
+      ld = hi - lo if ld is None else ld
+      out = torch.empty(users.shape[0], ld, dtype=torch.float32, device=A.device)
+    ld = out.stride(0) if ld is None else ld
+    if users.shape[0] == 0:
+      return out
+    return ncf.scores(users, lo, hi, self.Pg.data, self.Qg.data, self.Pm.data, A, theta, self.sizes(), out, ld)
+
+  def forward(self, input, input_users=None, input_items=None, target_users=None,
+              target_items=None):
+    if not self.Pg.is_cuda:
+      return self.torch_forward(input, input_users, input_items, target_users, target_items)
+    out = self.user_scores(input_users, 0, self.num_items)
+    return out if target_items is None else out.index_select(1, target_items.to(torch.int64))
+
+  def torch_forward(self, input, input_users=None, input_items=None, target_users=None,
+                    target_items=None):
+    """The same scores in torch ops, differentiable: [B, items] (or [B, len(target_items)])."""
+    u = input_users.to(torch.int64)
+    items = torch.arange(self.Qg.shape[0], device=u.device) if target_items is None else target_items.to(torch.int64)
+    dg = self.Pg.shape[1]
+    gmf = (self.Pg[u] * self.w[:dg]) @ self.Qg[items].t()
+    dm = self.Pm.shape[1]
+    W1 = self.mlp_weights[0]
+    x = (self.Pm[u] @ W1[:, :dm].t() + self.mlp_biases[0])[:, None, :] + (self.Qm[items] @ W1[:, dm:].t())[None, :, :]
+    x = torch.relu(x)
+    for W, c in zip(list(self.mlp_weights)[1:], list(self.mlp_biases)[1:]):
+      x = torch.relu(x @ W.t() + c)
+    return gmf + x @ self.w[dg:] + self.b0
