@@ -755,6 +755,65 @@ int rk_als_ncf_scores(const int32_t *users, int32_t B, int32_t n_users, int32_t 
                       const float *A, const float *theta, int32_t dg, int32_t dm, int32_t L, int32_t d1, int32_t d2,
                       int32_t d3, float *UH, float *out, int64_t ld, void *stream);
 
+/*
+ * Constrained serving (recoder_amd/serve.py): item filters, candidate reranking, scores.
+ *
+ * The deny bitmap of a batch: bits (uint32 [B, ldw], 32 ldw >= n_items) has bit (c & 31) of word bits[r, c >> 5] set
+ * when item c is NOT eligible for row r, which is rk_block_t::bits_rc of an unsampled block with `implicit` set: what
+ * rk_topk_masked masks.  Item c is eligible for row r when all of these hold:
+ *   - seen_indptr is NULL, or (r, c) is not an entry of the seen CSR (int64 seen_indptr [B + 1], int32 seen_ids,
+ *     f32 seen_vals or NULL for all ones) with a value > 0: a stored value <= 0 does not mask
+ *   - cat_allow is NULL or has bit c set;  cat_deny is NULL or has bit c clear (uint32 [ceil(n_items / 32)] each)
+ *   - ua_indptr is NULL, or c is in row r of the allow CSR (ua_indptr [B + 1], ua_ids);  c is not in row r of the
+ *     deny CSR (ud_indptr, ud_ids; NULL: nobody is denied)
+ * The bits of the last word past n_items are 1 and the words from ceil(n_items / 32) to ldw are all-ones.
+ * eligible[r] (int32) is the number of eligible items of row r: the popcount of the complement over [0, n_items), taken
+ * after every OR of the row is complete.  An id outside [0, n_items) is skipped, an indptr clamped to [0, nnz]; ids may
+ * repeat and need no order.  One launch on `stream`, one workgroup a row; 32-bit integer atomicAnd / atomicOr on the
+ * row's own words, whose result does not depend on their order: the same inputs give the same bits.  -2 unless B >= 0,
+ * n_items >= 1, 32 ldw >= n_items, every nnz >= 0 and (with B > 0) bits and eligible are not NULL.
+ */
+int rk_als_serve_mask(int32_t B, int32_t n_items, int32_t ldw, const int64_t *seen_indptr, const int32_t *seen_ids,
+                      const float *seen_vals, int64_t seen_nnz, const uint32_t *cat_allow, const uint32_t *cat_deny,
+                      const int64_t *ua_indptr, const int32_t *ua_ids, int64_t ua_nnz, const int64_t *ud_indptr,
+                      const int32_t *ud_ids, int64_t ud_nnz, uint32_t *bits, int32_t *eligible, void *stream);
+
+/*
+ * scores[e] = z[r] . Y[ids[e]] + bias[ids[e]] for every entry e of row r < B of a ragged candidate list (int64 indptr
+ * [B + 1], int32 ids [nnz]); z [B, h] with row stride ldz, Y [n, h] with row stride ldy, bias [n] or NULL.  An entry
+ * whose id is outside [0, n), or whose bit is set in the optional deny bitmap (rk_als_serve_mask's, row stride ldw), is
+ * not gathered and scores -inf.  max_row, an upper bound of a row's length, only sizes the launch: any value gives the
+ * same scores.  h is a multiple of 4 in [4, rk_als_ials_max_h()]; ldz and ldy are multiples of 4 and z, Y 16-byte
+ * aligned (rows are read as float4); anything else is -2.
+ * The summation order depends on h alone.  A group of W lanes takes an entry, with
+ *   h <= 16: W = 4, Q = 1    h <= 32: W = 8, Q = 1    h <= 64: W = 16, Q = 1     h <= 128: W = 32, Q = 1
+ *   h <= 256: W = 64, Q = 1  h <= 512: W = 64, Q = 2  h <= 1024: W = 64, Q = 4   else: W = 64, Q = 8
+ * lane j < W owns the dimensions d = 4 (j + W q) + c (q < Q, c < 4, d < h): its partial is one chain from +0,
+ * s = fmaf(z[d], y[d], s), over q ascending and c ascending inside q.  The W partials are added by an xor butterfly at
+ * the distances W / 2, ..., 2, 1 (p_j = p_j + p_{j ^ distance}), and the bias last: score = p + bias[id], one rounded
+ * add.  tests/serve_util.py restates it; tests/test_serve.py compares bit for bit.  One launch, no atomics.
+ */
+int rk_als_pair_scores(const int64_t *indptr, const int32_t *ids, int64_t nnz, int32_t B, int32_t max_row,
+                       const float *z, int32_t ldz, const float *Y, int32_t ldy, int32_t n, int32_t h,
+                       const float *bias, const uint32_t *deny, int32_t ldw, float *scores, void *stream);
+
+/* the longest row rk_als_pairs_topk ranks (8192) */
+int32_t rk_als_pairs_topk_max_row(void);
+
+/*
+ * Ragged top-k: for every row r < B of the list (indptr, ids, scores as above) the eligible entries -- id in [0, n),
+ * its bit clear in the optional deny bitmap -- by (score descending, id ascending) in rk_topk_pairs' order: float32 by
+ * value, -0 and +0 one value, a NaN without the sign bit above +inf.  out_idx[r, i] (int64, row stride out_ld >= k) and
+ * out_val[r, i] (f32, the same stride; may be NULL) receive the first min(k, count) of them, then id -1 and score -inf
+ * up to k: the padding follows count[r] (int32, may be NULL), the row's number of eligible entries, never the score
+ * values.  A row with fewer than k entries, or none, is an ordinary case.  The ids of a row must be distinct.
+ * max_row bounds the rows' lengths (<= rk_als_pairs_topk_max_row(); a longer row is cut at the next power of two).
+ * One workgroup a row, a bitonic sort in LDS; one launch.  -2 unless 1 <= k <= 8192 and 0 <= max_row <= 8192.
+ */
+int rk_als_pairs_topk(const int64_t *indptr, const int32_t *ids, const float *scores, int64_t nnz, int32_t B,
+                      int32_t max_row, int32_t n, const uint32_t *deny, int32_t ldw, int32_t k, int64_t *out_idx,
+                      float *out_val, int32_t out_ld, int32_t *count, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@ gradient (rk_als_rank_sample, rk_als_warp_grad) for recoder_amd.warp, the LightG
 recoder_amd.ultragcn, the cosine contrastive loss' (rk_als_ccl_*) for recoder_amd.ccl and SimpleX's pooled user rows
 (rk_als_sx_*) for recoder_amd.simplex, and the ranking metrics of device-resident top-k lists (rk_als_rank_metrics) for recoder_amd.metrics
 and recoder_amd.validation, the exact fold-in of unseen users (rk_als_foldin) for recoder_amd.foldin, and the iALS++ kernels
-(rk_als_ials_*) for recoder_amd.ials, and NeuMF's step and scores (rk_als_ncf_*) for recoder_amd.ncf.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
+(rk_als_ials_*) for recoder_amd.ials, and NeuMF's step and scores (rk_als_ncf_*) for recoder_amd.ncf, and the
+constrained-serving kernels (rk_als_serve_mask, rk_als_pair_scores, rk_als_pairs_topk) for recoder_amd.serve.  Like _lib.py: plain pointers and sizes, no torch types across the boundary, no CPU fallback."""
 import os
 
 # PyTorch-ROCm loads its HIP runtime first (see _lib.py): one runtime instance per process
@@ -37,6 +38,7 @@ RANK_METRICS_MAX = 8  # RK_ALS_RANK_METRICS_MAX
 FOLDIN_MAX_H = 128  # rk_als_foldin_max_h()
 IALS_MAX_H, IALS_MAX_BLOCK, IALS_LONG_ROW = 2048, 128, 1024  # rk_als_ials_max_h(), _max_block(), RK_ALS_IALS_LONG_ROW
 NCF_TILE, NCF_MAX_WIDTH, NCF_MAX_LAYERS = 32, 128, 3  # RK_ALS_NCF_TILE, _MAX_WIDTH, _MAX_LAYERS
+PAIRS_TOPK_MAX_ROW = 8192  # rk_als_pairs_topk_max_row()
 
 # name -> (restype, argtypes); every symbol include/recoder_als.h declares
 SIGNATURES = {
@@ -119,6 +121,13 @@ SIGNATURES = {
   "rk_als_ncf_scores": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32, _P,
                                   c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P,
                                   c_int64, _P]),
+  "rk_als_serve_mask": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int64, _P, _P,
+                                  c_int64, _P, _P, _P]),
+  "rk_als_pair_scores": (c_int32, [_P, _P, c_int64, c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, _P,
+                                   _P, c_int32, _P, _P]),
+  "rk_als_pairs_topk_max_row": (c_int32, []),
+  "rk_als_pairs_topk": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P, _P,
+                                  c_int32, _P, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

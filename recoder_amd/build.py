@@ -24,7 +24,9 @@ librecoder_als.so  implicit-feedback ALS for MatrixFactorization (include/recode
                    the item-side sum over the live entries only) and the ranking metrics of device-resident top-k lists
                    (rk_als_rank_metrics: Recall / NDCG / AveragePrecision for validation during a fit) and NeuMF's step,
                    dense Adam, item half and scores for NeuralMatrixFactorization (rk_als_ncf_*: a per-pair MLP on
-                   16 x 16 f32-MFMA tiles against weights in LDS, csrc/als/ncf.h)
+                   16 x 16 f32-MFMA tiles against weights in LDS, csrc/als/ncf.h) and the constrained-serving kernels
+                   of Recoder.recommend_filtered (rk_als_serve_mask, rk_als_pair_scores, rk_als_pairs_topk: the per-row
+                   deny bitmap, the scores of ragged candidate lists and their ragged top-k, csrc/als/serve.h)
 librecoder_vae.so  the stochastic bottleneck of VariationalAutoencoder (include/recoder_vae.h),
                    likewise a library of its own
 librecoder_ease.so  the closed-form EASE fit and its scores for ShallowAutoencoder

@@ -98,6 +98,12 @@
 //   rk_als_ncf_scores       a strip of scores for a batch of user ids: layer 1 as a sum of halves, the rest on MFMA tiles
 //                           of 32 items, no [B, strip, .] intermediate
 //
+// Constrained serving (rk_als_serve_mask, rk_als_pair_scores, rk_als_pairs_topk): what recoder_amd/serve.py adds
+//   rk_als_serve_mask       the per-row deny bitmap rk_topk_masked reads, from the seen entries, a catalogue bitmap and
+//                           per-row allow / deny lists: integer atomicAnd / atomicOr on the row's words, then the count
+//   rk_als_pair_scores      z_r . Y[c] + b[c] of ragged candidate lists, lane groups by h, several rows in flight
+//   rk_als_pairs_topk       the ragged top-k of those lists with -1 / -inf padding from the count of eligible entries
+//
 // One translation unit (one last-error buffer, one anonymous namespace), laid out by family under als/: every file
 // holds its kernels, then its extern "C" entry points.
 #include "als/common.h"     // the lane layout, the counter hash, the segment walk, the NT and lane-group dispatch
@@ -113,6 +119,7 @@
 #include "als/foldin.h"     // rk_als_foldin (beside solve.h's row solves)
 #include "als/ials.h"       // rk_als_ials_* (the fold-in's solve on a block of coordinates)
 #include "als/ncf.h"        // rk_als_ncf_* (on ugcn.h's draw)
+#include "als/serve.h"      // rk_als_serve_mask, rk_als_pair_scores, rk_als_pairs_topk
 
 extern "C" int rk_als_version(void) { return 100; }
 extern "C" const char *rk_als_last_error(void) { return g_rk_side_err; }

@@ -109,7 +109,8 @@ def batch_metrics(recommendations, target_csr, metrics):
   tkeys = (np.arange(B, dtype=np.int64)[:, None] * n_items + recs).ravel()
   if len(ykeys):
     pos = np.minimum(np.searchsorted(ykeys, tkeys), len(ykeys) - 1)
-    hit = (ykeys[pos] == tkeys).reshape(B, K).astype(int)
+    # (an id outside the catalogue is a miss: recommend_filtered's padding id -1 would alias the row before's last item)
+    hit = ((ykeys[pos] == tkeys).reshape(B, K) & (recs >= 0) & (recs < n_items)).astype(int)
   else:
     hit = np.zeros((B, K), dtype=int)
   out = {}
@@ -130,6 +131,39 @@ def batch_metrics(recommendations, target_csr, metrics):
         ideal = np.concatenate([[0.0], np.cumsum(1.0 / w)])[np.minimum(m.k, ny)]
         out[m] = (got / ideal).tolist()
   return out
+
+
+def sampled_candidates(target_matrix, seen_matrix, num_negatives, seed):
+  """The candidate sets of the sampled-negatives protocol (one held-out positive among N sampled negatives, He et
+  al. 2017) as a CSR [num_users, n_items] of ones: each user's target items (the stored non-zeros of
+  ``target_matrix``) plus ``num_negatives`` items drawn uniformly without replacement from the items that are
+  neither stored non-zeros of ``seen_matrix`` nor targets; a user with fewer such items takes all of them.  It is
+  the ``user_allow`` of ``Recoder.recommend_filtered`` / ``recommender.FilteredRecommender``.  Host numpy, one
+  generator per user seeded with (seed, user): the same arguments give the same matrix, whatever the other rows
+  hold."""
+  import scipy.sparse as sp
+  if isinstance(num_negatives, bool) or not isinstance(num_negatives, (int, np.integer)) or num_negatives < 0:
+    raise ValueError("num_negatives must be an integer >= 0 (got %r)" % (num_negatives,))
+  tm, sm = sp.csr_matrix(target_matrix), sp.csr_matrix(seen_matrix)
+  if tm.shape != sm.shape:
+    raise ValueError("target_matrix %r and seen_matrix %r must have one shape" % (tm.shape, sm.shape))
+  n_users, n_items = tm.shape
+  indptr, indices = np.zeros(n_users + 1, dtype=np.int64), []
+  for u in range(n_users):
+    t = tm.indices[tm.indptr[u]:tm.indptr[u + 1]][tm.data[tm.indptr[u]:tm.indptr[u + 1]] != 0]
+    s = sm.indices[sm.indptr[u]:sm.indptr[u + 1]][sm.data[sm.indptr[u]:sm.indptr[u + 1]] != 0]
+    free = np.ones(n_items, dtype=bool)
+    free[t] = False
+    free[s] = False
+    pool = np.nonzero(free)[0]
+    rng = np.random.RandomState([int(seed) & 0x7fffffff, u])
+    neg = pool if len(pool) <= num_negatives else rng.choice(pool, size=int(num_negatives), replace=False)
+    row = np.union1d(t, neg)
+    indices.append(row)
+    indptr[u + 1] = indptr[u] + len(row)
+  indices = np.concatenate(indices) if indices else np.zeros(0, dtype=np.int64)
+  return sp.csr_matrix((np.ones(len(indices), dtype=np.float32), indices.astype(np.int32), indptr),
+                       shape=(n_users, n_items))
 
 
 # ---------------------------------------------------------------- on the device

@@ -1030,6 +1030,34 @@ class Recoder(object):
     ids, _ = self._recommend_device(users_interactions, num_recommendations, user_rows=rows)
     return ids.cpu().numpy().copy()
 
+  def recommend_filtered(self, users_interactions, num_recommendations, filter_seen=True, allow_items=None,
+                         deny_items=None, user_allow=None, user_deny=None, return_scores=False, route="auto",
+                         user_rows=None):
+    """``recommend_array`` under item filters, with scores on request (recoder_amd/serve.py): [users, k] int64 ids
+    and, with ``return_scores``, the f32 [users, k] values the ranking ranked.  Item c is eligible for row r when
+    it is not a stored POSITIVE entry of the row (``filter_seen``), is in ``allow_items`` (None: all) and not in
+    ``deny_items`` (1-D integer ids, duplicates allowed, or a boolean array over the items), is in row r of
+    ``user_allow`` (None: all) and not in row r of ``user_deny`` (scipy sparse [users, n_items], only the pattern
+    counts).  The eligible items come by (score descending, id ascending); a row with e < k of them returns its e
+    items, then id -1 with score -inf.  With every filter at its default the ids are ``recommend_array``'s.
+    ``route``: "mask" runs the filters as a bitmap through the strips of ``recommend`` (every model); "pairs"
+    scores only the candidates of ``user_allow`` (a MatrixFactorization with activation 'none' on the fused engine,
+    at most ``serve.PAIRS_MAX_ROW`` candidates a user); "auto" takes "pairs" whenever it is legal.  The two rank the
+    same set by the same rule, but the strips multiply split fp16 planes and the pair kernel plain f32: their score
+    bits, and on near-ties their ids, may differ.  ``user_rows``: ``fold_in``'s [users, h] device tensor, scored
+    in place of the users' own rows.  ValueError: an id out of range, a wrong shape, k above ``rk_topk_max_k()`` or
+    the number of items, the generic torch-autograd engine (there is no dense fallback), an illegal ``route``."""
+    from . import serve
+    return serve.recommend_filtered(self, users_interactions, num_recommendations, return_scores=return_scores,
+                                    filter_seen=filter_seen, allow_items=allow_items, deny_items=deny_items,
+                                    user_allow=user_allow, user_deny=user_deny, route=route, user_rows=user_rows)
+
+  def rerank(self, users_interactions, candidates, num_recommendations, return_scores=False, route="auto"):
+    """The best ``num_recommendations`` of every user's ``candidates`` (scipy sparse [users, n_items], the pattern):
+    ``recommend_filtered(filter_seen=False, user_allow=candidates)``, seen items included when they are candidates."""
+    return self.recommend_filtered(users_interactions, num_recommendations, filter_seen=False, user_allow=candidates,
+                                   return_scores=return_scores, route=route)
+
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
     (recoder_amd/svd.py): the item table becomes V, the top ``embedding_size`` right singular vectors of
@@ -2009,7 +2037,7 @@ class Recoder(object):
     return ids.cpu().numpy().copy()
 
   def _recommend_device(self, users_interactions, num_recommendations, host_ok=False, ws=None, inputs=None,
-                        user_rows=None):
+                        user_rows=None, seen=None, with_scores=False):
     """``recommend_array`` before its copy to the host: (ids, ld), an int64 device tensor [users, k] (possibly a
     strided view of the candidate buffer, valid until the next call on the same workspace) and its row stride.
     The fused form of ``engine.recommend_fused`` reads its ids back with its status word, so it is taken only
@@ -2017,7 +2045,9 @@ class Recoder(object):
     ``ws`` is the workspace of the scores and candidates (None: the Recoder's own ``_eval_ws``), ``inputs`` an
     earlier ``(blk, B, n_items, dcsr)`` of ``_input_block`` for these users (None: collated now).  ``user_rows``
     (``recommend_folded``): a [users, h] f32 device tensor scored in place of the encoder's output, strip by strip;
-    ``users_interactions.users`` is then not read."""
+    ``users_interactions.users`` is then not read.  ``seen`` (``recommend_filtered``): a block whose ``bits_rc`` is
+    a deny bitmap with ``implicit`` set, masked in place of the users' own input block, strip by strip; with
+    ``with_scores`` the result is (ids, ld, scores), the f32 values the ranking ranked laid out like the ids."""
     self.model.eval()
     self._check_ranges()
     k = int(num_recommendations)
@@ -2028,6 +2058,7 @@ class Recoder(object):
     ids_model = self._scores_from_user_ids()
     csr_model = self._scores_from_csr_rows() or ids_model        # (either way: no encoder, a scores kernel of its own)
     if (getattr(engine, "generic", False) and not csr_model) or k > lib.rk_topk_max_k():
+      assert seen is None and not with_scores                     # (serve.check_serving refused it)
       if user_rows is not None:
         raise ValueError("recommend_folded scores on the fused HIP engine (optimizer_type='adam', an embedding size "
                          "that is a multiple of 4) and takes at most %d recommendations (got %d)"
@@ -2048,6 +2079,9 @@ class Recoder(object):
       host_ok = False                                             # (the fused form encodes the block's users itself)
     else:
       z = None if csr_model else engine.encode_eval(blk, 0, B)
+    if seen is not None or with_scores:
+      host_ok = False                                             # (the strips: their mask is an argument, they keep scores)
+    seen_ref = blk.ref if seen is None else seen.ref
     strip = max(k, min(n_items, int(self.eval_strip_items)))
     bounds = [(lo, min(n_items, lo + strip)) for lo in range(0, n_items, strip)]
     if len(bounds) > 1 and bounds[-1][1] - bounds[-1][0] < k:      # a last strip shorter than k:
@@ -2086,7 +2120,7 @@ class Recoder(object):
         else:
           # an item-item model's strip of scores: the users' CSR rows times W[:, lo:hi]
           self.model.csr_scores(dcsr, lo, hi, scores, ld, B)
-        _lib.check(lib.rk_topk_masked(scores.data_ptr(), B, hi - lo, ld, blk.ref, 0, k, lo, 1,
+        _lib.check(lib.rk_topk_masked(scores.data_ptr(), B, hi - lo, ld, seen_ref, 0, k, lo, 1,
                                       cand_idx[:, s * k:].data_ptr(), cand_val[:, s * k:].data_ptr(),
                                       ns * k, current_stream()), "rk_topk_masked")
         continue
@@ -2100,17 +2134,19 @@ class Recoder(object):
           ws["strips"].clear()
         ws["strips"][key] = sblk
       engine.decode_scores(z, B, sblk, scores, ld)
-      _lib.check(lib.rk_topk_masked(scores.data_ptr(), B, hi - lo, ld, blk.ref, 0, k, lo, 1,
+      _lib.check(lib.rk_topk_masked(scores.data_ptr(), B, hi - lo, ld, seen_ref, 0, k, lo, 1,
                                           cand_idx[:, s * k:].data_ptr(), cand_val[:, s * k:].data_ptr(),
                                           ns * k, current_stream()), "rk_topk_masked")
     if ns == 1:
-      return cand_idx[:, :k], ns * k
+      return (cand_idx[:, :k], ns * k, cand_val[:, :k]) if with_scores else (cand_idx[:, :k], ns * k)
     # merge: top k of the ns * k candidates (positions), then their item ids.  Candidates are laid
     # out strip by strip, each sorted by (score desc, id asc): equal scores keep ascending ids
     pos = torch.empty(B, k, dtype=torch.int64, device=self.device)
+    val = torch.empty(B, k, dtype=torch.float32, device=self.device) if with_scores else None
     _lib.check(lib.rk_topk_masked(cand_val.data_ptr(), B, ns * k, ns * k, None, 0, k, 0, 1, pos.data_ptr(),
-                                  None, k, current_stream()), "rk_topk_masked")
-    return torch.gather(cand_idx, 1, pos), k
+                                  None if val is None else val.data_ptr(), k, current_stream()), "rk_topk_masked")
+    ids = torch.gather(cand_idx, 1, pos)
+    return (ids, k, val) if with_scores else (ids, k)
 
   def _recommend_dense(self, users_interactions, k):
     """Full score matrix + torch.topk: the generic (torch-autograd) engine and k above the

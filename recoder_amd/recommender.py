@@ -197,3 +197,38 @@ class FoldInRecommender(Recommender):
     """(int64 device tensor [users, k], its row stride), as ``InferenceRecommender.recommend_device``."""
     rows = self.model.fold_in(users_hist.interactions_matrix, self.alpha, self.reg)
     return self.model._recommend_device(users_hist, self.num_recommendations, user_rows=rows)
+
+
+class FilteredRecommender(Recommender):
+  """``InferenceRecommender`` under the filters of ``Recoder.recommend_filtered`` (recoder_amd/serve.py).
+  ``user_allow`` / ``user_deny`` are scipy sparse [num_users, n_items] and are row-indexed with every batch's
+  ``users_hist.users``; the other arguments are passed as they are.  A user with fewer than ``num_recommendations``
+  eligible items gets id -1 in the last positions, which no metric counts as a hit.  With ``RecommenderEvaluator``
+  and ``metrics.sampled_candidates`` as ``user_allow`` this is the sampled-negatives protocol, on the host path and
+  with ``on_device=True``."""
+
+  def __init__(self, model, num_recommendations, filter_seen=True, allow_items=None, deny_items=None, user_allow=None,
+               user_deny=None, route="auto"):
+    self.model = model
+    self.num_recommendations = num_recommendations
+    self.user_allow = None if user_allow is None else user_allow.tocsr()
+    self.user_deny = None if user_deny is None else user_deny.tocsr()
+    self.kw = dict(filter_seen=filter_seen, allow_items=allow_items, deny_items=deny_items, route=route)
+
+  def _filters(self, users_hist):
+    users = np.asarray(users_hist.users).astype(np.int64).reshape(-1)
+    rows = lambda m: None if m is None else m[users]
+    return dict(self.kw, user_allow=rows(self.user_allow), user_deny=rows(self.user_deny))
+
+  def recommend(self, users_hist):
+    return self.recommend_array(users_hist).tolist()
+
+  def recommend_array(self, users_hist):
+    return self.model.recommend_filtered(users_hist, self.num_recommendations, **self._filters(users_hist))
+
+  def recommend_device(self, users_hist):
+    """(int64 device tensor [users, k], its row stride), as ``InferenceRecommender.recommend_device``."""
+    from . import serve
+    ids, _ = serve.recommend_filtered_device(self.model, users_hist, self.num_recommendations,
+                                             **self._filters(users_hist))
+    return ids, int(ids.stride(0))
