@@ -814,6 +814,44 @@ int rk_als_pairs_topk(const int64_t *indptr, const int32_t *ids, const float *sc
                       int32_t max_row, int32_t n, const uint32_t *deny, int32_t ldw, int32_t k, int64_t *out_idx,
                       float *out_val, int32_t out_ld, int32_t *count, void *stream);
 
+/* bytes of workspace rk_als_explain needs for a CSR whose indices array holds nnz entries (host arithmetic; > 0;
+ * < 0 for nnz < 0) */
+int64_t rk_als_explain_workspace_bytes(int64_t nnz);
+
+/*
+ * Explanations of the folded-in user's scores: which entries of the history carry y_j . x_u + b_j.  With A_u, coef_e
+ * and v of rk_als_foldin and z = A_u^-1 y_j,
+ *   s_uj = sum_e coef_e (z . y_e) + (b_j - z . v):
+ * the contribution of entry e is c_e = coef_e (z . y_e), the rest is the baseline.  Arguments up to alpha are
+ * rk_als_foldin's (nnz: the entries of the indices array, which sizes the workspace; n_items: the rows of Y); items
+ * int64 [rows, J], a j outside [0, n_items) is padding (-1 by convention).  Outputs as rk_ease_explain's
+ * (include/recoder_ease.h: contributors int64 [rows, J, m], contributions f32 [rows, J, m], baseline and total f32
+ * [rows, J], the same order of the candidates from the same device code), and status int32 [rows] as rk_als_foldin's.
+ * Arithmetic (all f32, bitwise repeatable; tests/explain_util.py restates it, tests/test_explain.py compares bit for
+ * bit).  Every fused operation is an fmaf and nothing else is contracted.
+ *   - A_u and its Cholesky factor exactly as rk_als_foldin states them: one device function forms and factorises
+ *     the system for both entry points
+ *   - per target: z by rk_als_foldin's two triangular solves (one device function again) from the right-hand side y_j
+ *   - baseline: d = fmaf(z_k, v_k, d) over k ascending from +0; baseline = b_j - d, one rounded difference (bias NULL:
+ *     b_j = +0)
+ *   - c_e: d = fmaf(z_k, Y[i_e][k], d) over k ascending from +0; c_e = coef_e * d, one rounded product, coef_e as
+ *     rk_als_foldin rounds it
+ *   - total: t = baseline; t = t + c_e over ALL entries in CSR order, one rounded sum each
+ *   - a row whose system has a pivot that is not > 0: status 1, every c_e = +0 (so the contributors are the first
+ *     entries of the row), baseline = total = +0; a padding target: contributors -1, everything else +0
+ * The workgroups are rk_als_foldin's (a row a workgroup at h > 64, four rows below); a row's targets are taken one
+ * after the other, the c_e of a target go through the workspace at their entry's index, and the row's first wave
+ * selects.  One launch on `stream`, no atomics.  A (row, target) pair's result depends on the row's entries, the
+ * target, Y, G, v, bias and alpha alone: not on the other rows or targets, on rows, J or the launch.  -2 unless
+ * 1 <= h <= rk_als_foldin_max_h(), ldy >= h, rows >= 0, n_items >= 1, J >= 1, 1 <= m <= 64, alpha finite and >= 0,
+ * ws_bytes >= rk_als_explain_workspace_bytes(nnz) and (with rows > 0) no pointer but data and bias is NULL.
+ */
+int rk_als_explain(const int64_t *indptr, const int32_t *indices, const float *data, int32_t rows, int64_t nnz,
+                   const float *Y, int32_t ldy, int32_t n_items, int32_t h, const float *G, const float *v,
+                   const float *bias, float alpha, const int64_t *items, int32_t J, int32_t m, int64_t *contributors,
+                   float *contributions, float *baseline, float *total, int32_t *status, void *ws, int64_t ws_bytes,
+                   void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

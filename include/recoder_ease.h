@@ -238,6 +238,31 @@ int rk_ease_elsa_adam(float *W, int64_t ldw, const float *dA, int64_t ldd, float
 int rk_ease_csr_sub(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows, int32_t lo,
                     int32_t hi, float *out, int64_t ldo, void *stream);
 
+/* the largest m of rk_ease_explain, rk_slim_explain and rk_als_explain (64) */
+int rk_ease_explain_max_contributors(void);
+
+/*
+ * Explanations: which entries of a user's history carry the score of a target item.  For every row u of the batch
+ * CSR (indptr [n_rows + 1] / indices / data; data NULL: all ones) and every target j = items[u][q] (int64 [n_rows, J];
+ * a j outside [0, n_items) is padding, -1 by convention), with c_e = x_ue * W[i_e][j] (ONE rounded f32 product) for
+ * the entries e of the row in CSR order:
+ *   contributors  int64 [n_rows, J, m]  the item ids of the m best entries, best first; -1 where the row has fewer
+ *                                       than m entries, or the target is padding
+ *   contributions f32   [n_rows, J, m]  their c_e; +0 at padding
+ *   baseline      f32   [n_rows, J]     +0 (an item-item score has no part outside the history)
+ *   total         f32   [n_rows, J]     t = fmaf(x_ue, W[i_e][j], t) over ALL entries in CSR order from +0: one chain,
+ *                                       not the sum of the rounded c_e; +0 for padding
+ * Order, best first: the larger c_e (-0 and +0 are one value); equal values to the earlier entry of the row; a NaN
+ * behind every number.  A negative c_e is an ordinary value.  A target that is in the history is explained like any
+ * other.  1 <= m <= 64, J >= 1, n_rows * J < 2^31.  One wave per (user, target), one launch on `stream`; no workspace,
+ * no atomics; bitwise repeatable, and a pair's result depends on its own row, target and W alone -- not on n_rows, J,
+ * the other targets or the launch.  tests/explain_util.py restates it; tests/test_explain.py compares bit for bit.
+ * Here W is dense [n_items, ldw], ldw >= n_items: a lane gathers W[i_e * ldw + j], four entries in flight a lane.
+ */
+int rk_ease_explain(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows, const float *W,
+                    int64_t ldw, int32_t n_items, const int64_t *items, int32_t J, int32_t m, int64_t *contributors,
+                    float *contributions, float *baseline, float *total, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -148,6 +148,23 @@ int rk_slim_scores(const int64_t *indptr, const int32_t *indices, const float *d
                    int32_t n_items, const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count,
                    int32_t K, int32_t lo, int32_t hi, float *out, int64_t ldo, void *stream);
 
+/*
+ * rk_ease_explain (include/recoder_ease.h: the same outputs, order, product and chain, from the same device code) for
+ * a model stored as neighbour lists nbr_ids / nbr_w [n_items, K], nbr_count [n_items] (taken as 0 below 0 and as K
+ * above K), the ids of a list ascending without repeats as every fit stores them:
+ *   lists_are_columns = 1   row j of the three tensors is column j of W (rk_slim_fit, rk_rp3_item_fit): the list of the
+ *                           target is searched for each history item
+ *   lists_are_columns = 0   row i is row i of W (rk_rp3_fit): the list of each history item is searched for the target
+ * by binary search.  A pair that the lists do not hold has W[i][j] = +0: it contributes x_ue * +0 and is a candidate
+ * like any other, so a history shorter than m is not padded further.  On the dense matrix that holds the lists'
+ * entries and +0 elsewhere rk_ease_explain gives the same bits.  1 <= K <= rk_slim_max_neighbours(), 1 <= m <= 64,
+ * J >= 1, n_rows * J < 2^31.  No workspace, no atomics.
+ */
+int rk_slim_explain(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows, int32_t n_items,
+                    const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count, int32_t K,
+                    int32_t lists_are_columns, const int64_t *items, int32_t J, int32_t m, int64_t *contributors,
+                    float *contributions, float *baseline, float *total, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -125,6 +125,9 @@ SIGNATURES = {
                                   c_int64, _P, _P, _P]),
   "rk_als_pair_scores": (c_int32, [_P, _P, c_int64, c_int32, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, _P,
                                    _P, c_int32, _P, _P]),
+  "rk_als_explain_workspace_bytes": (c_int64, [c_int64]),
+  "rk_als_explain": (c_int32, [_P, _P, _P, c_int32, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_float, _P,
+                               c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int64, _P]),
   "rk_als_pairs_topk_max_row": (c_int32, []),
   "rk_als_pairs_topk": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P, _P,
                                   c_int32, _P, _P]),

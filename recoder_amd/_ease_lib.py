@@ -37,6 +37,8 @@ SIGNATURES = {
   "rk_ease_elsa_adam": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, c_int32, c_int32, c_float, c_float,
                                   c_float, c_float, c_float, _P]),
   "rk_ease_csr_sub": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P]),
+  "rk_ease_explain_max_contributors": (c_int32, []),
+  "rk_ease_explain": (c_int32, [_P, _P, _P, c_int32, _P, c_int64, c_int32, _P, c_int32, c_int32, _P, _P, _P, _P, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

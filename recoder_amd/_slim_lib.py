@@ -29,6 +29,8 @@ SIGNATURES = {
   "rk_slim_fit_sparse": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, c_int32, _P, c_float, c_int32,
                                    c_int32, c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
   "rk_slim_scores": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P]),
+  "rk_slim_explain": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int32, c_int32, _P, _P,
+                                _P, _P, _P]),
 }
 
 load = loader(LIB_PATH, SIGNATURES)

@@ -48,7 +48,9 @@ librecoder_slim.so  the SLIM coordinate-descent fit and its scores for SparseLin
                    (include/recoder_slim.h), likewise a library of its own
 
 The seven side libraries share csrc/side_error.h (the last-error buffer and the argument / launch
-checks); each stays one translation unit, so each has its own buffer.  A library's source may be laid out
+checks); each stays one translation unit, so each has its own buffer.  csrc/side_explain.h is shared likewise:
+the device code of the explanation kernels (rk_ease_explain, rk_slim_explain, rk_als_explain: the order of the
+candidates, a wave's selection, the one-wave kernel of the item-item models), which recoder_amd/explain.py calls.  A library's source may be laid out
 over private headers in csrc/<stem>/ (als.hip is: csrc/als/*.h, one file a family; ease.hip has csrc/ease/elsa.h); they are that library's
 dependencies and nobody else's.
 
@@ -64,7 +66,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE = os.path.join(os.path.dirname(CSRC), "..", "include")
 # one row per library, in build order: (stem, sources, public headers, whether it depends on the training
 # path's headers (every csrc/*.h and include/recoder_hip*.h), the prefix of its exported names).  A side
-# library depends on its own header, csrc/side_error.h and the headers in csrc/<stem>/; vae.hip and svd.hip also include csrc/common.h
+# library depends on its own header, csrc/side_error.h, csrc/side_explain.h and the headers in csrc/<stem>/; vae.hip and svd.hip also include csrc/common.h
 # (the counter RNG, the step cursor), so they follow the training headers too.
 LIBRARIES = (
     ("hip", ["capi.hip", "collate.hip", "encoder.hip", "gemm.hip", "decode16.hip", "linear.hip", "dw3.hip",
@@ -142,7 +144,7 @@ def headers_of(stem):
       [os.path.join(INCLUDE, h) for h in LIBRARIES[0][2]]
   own = [os.path.join(INCLUDE, h) for h in public]
   headers = training + [h for h in own if h not in training] if needs_training else \
-      own + [os.path.join(CSRC, "side_error.h")]
+      own + [os.path.join(CSRC, "side_error.h"), os.path.join(CSRC, "side_explain.h")]
   private = os.path.join(CSRC, stem)                 # csrc/<stem>/*.h: the library's own private headers
   if os.path.isdir(private):
     headers = headers + sorted(os.path.join(private, f) for f in os.listdir(private) if f.endswith(".h"))

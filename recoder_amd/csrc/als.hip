@@ -104,6 +104,10 @@
 //   rk_als_pair_scores      z_r . Y[c] + b[c] of ragged candidate lists, lane groups by h, several rows in flight
 //   rk_als_pairs_topk       the ragged top-k of those lists with -1 / -inf padding from the count of eligible entries
 //
+// Explanations (rk_als_explain): what recoder_amd/explain.py adds for the folded-in user
+//   rk_als_explain          the fold-in's system and factor, then per target z = A^-1 y_j, a dot chain per history entry
+//                           and the m largest contributions, selected by the row's first wave
+//
 // One translation unit (one last-error buffer, one anonymous namespace), laid out by family under als/: every file
 // holds its kernels, then its extern "C" entry points.
 #include "als/common.h"     // the lane layout, the counter hash, the segment walk, the NT and lane-group dispatch
@@ -120,6 +124,7 @@
 #include "als/ials.h"       // rk_als_ials_* (the fold-in's solve on a block of coordinates)
 #include "als/ncf.h"        // rk_als_ncf_* (on ugcn.h's draw)
 #include "als/serve.h"      // rk_als_serve_mask, rk_als_pair_scores, rk_als_pairs_topk
+#include "als/explain.h"    // rk_als_explain (on foldin.h's system and solves)
 
 extern "C" int rk_als_version(void) { return 100; }
 extern "C" const char *rk_als_last_error(void) { return g_rk_side_err; }

@@ -28,33 +28,54 @@ int fi_group_floats(int h, int tb) {
   return (FI_CHUNK * hp + 2 * hp + 3 * FI_CHUNK + fi_tri(h) + 3) & ~3;
 }
 
+// the LDS of one group, in the order above
+struct FiLds {
+  float *stage, *zs, *dg, *sa, *scoef;
+  int *scol;
+  float *Ls;
+};
+
+__device__ __forceinline__ FiLds fi_lds_of(float *base, int hp) {
+  FiLds L;
+  L.stage = base;
+  L.zs = L.stage + FI_CHUNK * hp;
+  L.dg = L.zs + hp;
+  L.sa = L.dg + hp;
+  L.scoef = L.sa + FI_CHUNK;
+  L.scol = (int *)(L.scoef + FI_CHUNK);
+  L.Ls = (float *)(L.scol + FI_CHUNK);
+  return L;
+}
+
+// coef_e of an entry with value val and item bias b; a = its confidence weight a_e
+__device__ __forceinline__ float fi_coef(float val, float alpha, float b, float &a) {
+#pragma clang fp contract(off)
+  a = val > 0.f ? alpha : 0.f;
+  return (1.f + a) * val - a * b;                   // (two products and a difference, each rounded)
+}
+
+// A_u of the group's row formed and factorised into Ls / dg, r = the right-hand side  sum_e coef_e y_e - v  in
+// thread t < h; returns true where the row is not live or a pivot was not positive.  rk_als_foldin and rk_als_explain
+// (explain.h) both stand on this one statement of the system.
 template <int TPR, int TB>
-__global__ __launch_bounds__(256) void als_foldin_kernel(const int64_t *__restrict__ indptr,
-                                                         const int32_t *__restrict__ indices,
-                                                         const float *__restrict__ data, int rows,
-                                                         const float *__restrict__ Y, int ldy, int h,
-                                                         const float *__restrict__ G, const float *__restrict__ v,
-                                                         const float *__restrict__ bias, float alpha,
-                                                         float *__restrict__ X, int ldx,
-                                                         int32_t *__restrict__ status, int gfloats) {
+__device__ __forceinline__ bool fi_form_factor(const FiLds &L, const int64_t *__restrict__ indptr,
+                                               const int32_t *__restrict__ indices, const float *__restrict__ data,
+                                               int rows, const float *__restrict__ Y, int ldy, int h,
+                                               const float *__restrict__ G, const float *__restrict__ v,
+                                               const float *__restrict__ bias, float alpha, int g, int t, float &r,
+                                               bool &live, int64_t &e0, int &n) {
 #pragma clang fp contract(off)                    // every fused operation below is written as fmaf
-  extern __shared__ __attribute__((aligned(16))) float fi_lds[];
   constexpr int R = 256 / TPR;
   constexpr int TX = TPR == 256 ? 16 : 8, TY = TPR / TX;
-  const int g = threadIdx.x / TPR, t = threadIdx.x % TPR;
   const int nb = (h + TB - 1) / TB, hp = nb * TB;
-  float *stage = fi_lds + (int64_t)g * gfloats;
-  float *zs = stage + FI_CHUNK * hp;
-  float *dg = zs + hp;
-  float *sa = dg + hp;
-  float *scoef = sa + FI_CHUNK;
-  int *scol = (int *)(scoef + FI_CHUNK);
-  float *Ls = (float *)(scol + FI_CHUNK);
+  float *stage = L.stage, *dg = L.dg, *sa = L.sa, *scoef = L.scoef, *Ls = L.Ls;
+  int *scol = L.scol;
 
   const int64_t row0 = (int64_t)blockIdx.x * R, row = row0 + g;
-  const bool live = row < rows;
-  int64_t e0 = 0;
-  int n = 0, nmax = 0;
+  live = row < rows;
+  e0 = 0;
+  n = 0;
+  int nmax = 0;
   if (live) {
     e0 = indptr[row];
     n = (int)(indptr[row + 1] - e0);
@@ -77,7 +98,7 @@ __global__ __launch_bounds__(256) void als_foldin_kernel(const int64_t *__restri
       const int k = min(bi * TB + a, h - 1), l = min(bj * TB + b, k);
       acc[a][b] = tile ? G[k * h + l] : 0.f;
     }
-  float r = (live && t < h) ? -v[t] : 0.f;
+  r = (live && t < h) ? -v[t] : 0.f;
 
   for (int c0 = 0; c0 < nmax; c0 += FI_CHUNK) {
     const int cnt = min(FI_CHUNK, n - c0);          // (<= 0: this row has no entry left)
@@ -87,10 +108,7 @@ __global__ __launch_bounds__(256) void als_foldin_kernel(const int64_t *__restri
       if (t < cnt) {
         const int64_t e = e0 + c0 + t;
         col = indices[e];
-        const float val = entry_value(data, e);
-        a = val > 0.f ? alpha : 0.f;
-        const float b = bias ? bias[col] : 0.f;
-        cf = (1.f + a) * val - a * b;               // (two products and a difference, each rounded)
+        cf = fi_coef(entry_value(data, e), alpha, bias ? bias[col] : 0.f, a);
       }
       sa[t] = a;
       scoef[t] = cf;
@@ -161,7 +179,15 @@ __global__ __launch_bounds__(256) void als_foldin_kernel(const int64_t *__restri
     }
     __syncthreads();
   }
-  // L z = r by columns, k ascending; then L^T x = z by columns, k descending
+  return bad;
+}
+
+// L z = r by columns, k ascending; then L^T x = z by columns, k descending: thread t < h comes in with r_t and leaves
+// with x_t, and zs holds all of x behind the last barrier.  Every thread of the workgroup reaches every barrier.
+__device__ __forceinline__ void fi_solve(const FiLds &L, int h, int t, bool bad, float &r) {
+#pragma clang fp contract(off)
+  float *zs = L.zs;
+  const float *dg = L.dg, *Ls = L.Ls;
   for (int k = 0; k < h; ++k) {
     if (!bad && t == k) {
       r = r / dg[k];
@@ -178,6 +204,29 @@ __global__ __launch_bounds__(256) void als_foldin_kernel(const int64_t *__restri
     __syncthreads();
     if (!bad && t < k) r = fmaf(-Ls[fi_tri(k) + t], zs[k], r);
   }
+}
+
+template <int TPR, int TB>
+__global__ __launch_bounds__(256) void als_foldin_kernel(const int64_t *__restrict__ indptr,
+                                                         const int32_t *__restrict__ indices,
+                                                         const float *__restrict__ data, int rows,
+                                                         const float *__restrict__ Y, int ldy, int h,
+                                                         const float *__restrict__ G, const float *__restrict__ v,
+                                                         const float *__restrict__ bias, float alpha,
+                                                         float *__restrict__ X, int ldx,
+                                                         int32_t *__restrict__ status, int gfloats) {
+  extern __shared__ __attribute__((aligned(16))) float fi_lds[];
+  const int g = threadIdx.x / TPR, t = threadIdx.x % TPR;
+  const int hp = (h + TB - 1) / TB * TB;
+  const FiLds L = fi_lds_of(fi_lds + (int64_t)g * gfloats, hp);
+  const int64_t row = (int64_t)blockIdx.x * (256 / TPR) + g;
+  float r;
+  bool live;
+  int64_t e0;
+  int n;
+  const bool bad = fi_form_factor<TPR, TB>(L, indptr, indices, data, rows, Y, ldy, h, G, v, bias, alpha, g, t, r, live,
+                                           e0, n);
+  fi_solve(L, h, t, bad, r);
   if (live) {
     if (t < h) X[row * ldx + t] = bad ? 0.f : r;
     if (t == 0) status[row] = bad ? 1 : 0;

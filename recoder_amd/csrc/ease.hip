@@ -26,6 +26,7 @@
 
 #include "../../include/recoder_ease.h"
 #include "side_error.h"
+#include "side_explain.h"      // rk_ease_explain: the order, the selection and the one-wave kernel
 
 namespace {
 
@@ -684,5 +685,34 @@ int rk_ease_admm_update(const float *T, int64_t ldt, const float *P, int64_t ldp
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------- explanations
+namespace {
+struct XpDenseFetch {                             // W[i][j] of a dense matrix
+  const float *W;
+  int64_t ldw;
+  __device__ __forceinline__ float operator()(int i, int j) const { return W[(int64_t)i * ldw + j]; }
+};
+}  // namespace
+
+extern "C" int rk_ease_explain_max_contributors(void) { return XP_MAX_M; }
+
+extern "C" int rk_ease_explain(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows,
+                               const float *W, int64_t ldw, int32_t n_items, const int64_t *items, int32_t J, int32_t m,
+                               int64_t *contributors, float *contributions, float *baseline, float *total,
+                               void *stream) {
+  RK_SIDE_REQUIRE(n_rows >= 0 && n_items >= 1 && ldw >= n_items, "bad sizes");
+  RK_SIDE_REQUIRE(J >= 1 && m >= 1 && m <= XP_MAX_M && (int64_t)n_rows * J <= 0x7fffffff,
+                  "J >= 1, 1 <= m <= 64, n_rows * J < 2^31");
+  if (n_rows == 0) return 0;
+  RK_SIDE_REQUIRE(indptr && indices && W && items && contributors && contributions && baseline && total,
+                  "null pointer");
+  const XpDenseFetch fetch{W, ldw};
+  hipLaunchKernelGGL(xp_item_kernel<XpDenseFetch>, dim3((unsigned)((int64_t)n_rows * J)), dim3(64), 0,
+                     (hipStream_t)stream, indptr, indices, data, n_items, items, J, m, fetch, contributors,
+                     contributions, baseline, total);
+  RK_SIDE_CHECK_LAUNCH("ease_explain_kernel");
+  return 0;
+}
 
 #include "ease/elsa.h"    // rk_ease_elsa_normalize, _rows, _scatter, _project, _adam, rk_ease_csr_sub

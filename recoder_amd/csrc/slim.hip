@@ -33,6 +33,7 @@
 
 #include "../../include/recoder_slim.h"
 #include "side_error.h"
+#include "side_explain.h"      // rk_slim_explain: the order, the selection and the one-wave kernel
 
 namespace {
 
@@ -475,6 +476,28 @@ __global__ __launch_bounds__(SC_THREADS) void slim_scores_kernel(
   out[(int64_t)u * ldo + c] = acc;
 }
 
+// ----------------------------------------------------------------- explanations
+// W[i][j] of a neighbour-list model: the list of column j (columns) or of row i searched for the other id.  The
+// lists ascend, as every fit stores them; a pair the list does not hold is +0.
+struct XpListFetch {
+  const int32_t *ids;
+  const float *w;
+  const int32_t *count;
+  int K, columns;
+  __device__ __forceinline__ float operator()(int i, int j) const {
+    const int list = columns ? j : i, key = columns ? i : j;
+    int cnt = count[list];
+    cnt = cnt < 0 ? 0 : (cnt > K ? K : cnt);
+    const int32_t *l = ids + (int64_t)list * K;
+    int a = 0, b = cnt;
+    while (a < b) {
+      const int mid = (a + b) >> 1;
+      if (l[mid] < key) a = mid + 1; else b = mid;
+    }
+    return (a < cnt && l[a] == key) ? w[(int64_t)list * K + a] : 0.f;
+  }
+};
+
 }  // namespace
 
 // ------------------------------------------------------------------------ ABI
@@ -590,6 +613,25 @@ int rk_slim_scores(const int64_t *indptr, const int32_t *indices, const float *d
   hipLaunchKernelGGL(slim_scores_kernel, grid, dim3(SC_THREADS), 0, (hipStream_t)stream, indptr, indices, data,
                      nbr_ids, nbr_w, nbr_count, K, lo, width, out, ldo);
   RK_SIDE_CHECK_LAUNCH("slim_scores_kernel");
+  return 0;
+}
+
+int rk_slim_explain(const int64_t *indptr, const int32_t *indices, const float *data, int32_t n_rows, int32_t n_items,
+                    const int32_t *nbr_ids, const float *nbr_w, const int32_t *nbr_count, int32_t K,
+                    int32_t lists_are_columns, const int64_t *items, int32_t J, int32_t m, int64_t *contributors,
+                    float *contributions, float *baseline, float *total, void *stream) {
+  RK_SIDE_REQUIRE(n_rows >= 0 && n_items >= 1 && K >= 1 && K <= SL_MAX_K, "bad sizes");
+  RK_SIDE_REQUIRE(lists_are_columns == 0 || lists_are_columns == 1, "lists_are_columns must be 0 or 1");
+  RK_SIDE_REQUIRE(J >= 1 && m >= 1 && m <= XP_MAX_M && (int64_t)n_rows * J <= 0x7fffffff,
+                  "J >= 1, 1 <= m <= 64, n_rows * J < 2^31");
+  if (n_rows == 0) return 0;
+  RK_SIDE_REQUIRE(indptr && indices && nbr_ids && nbr_w && nbr_count && items && contributors && contributions &&
+                  baseline && total, "null pointer");
+  const XpListFetch fetch{nbr_ids, nbr_w, nbr_count, K, lists_are_columns};
+  hipLaunchKernelGGL(xp_item_kernel<XpListFetch>, dim3((unsigned)((int64_t)n_rows * J)), dim3(64), 0,
+                     (hipStream_t)stream, indptr, indices, data, n_items, items, J, m, fetch, contributors,
+                     contributions, baseline, total);
+  RK_SIDE_CHECK_LAUNCH("slim_explain_kernel");
   return 0;
 }
 

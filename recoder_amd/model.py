@@ -1058,6 +1058,29 @@ class Recoder(object):
     return self.recommend_filtered(users_interactions, num_recommendations, filter_seen=False, user_allow=candidates,
                                    return_scores=return_scores, route=route)
 
+  def explain(self, users_interactions, items, num_contributors=5, alpha=30.0, reg=100.0):
+    """Why were these items served: for the batch's B users and the targets ``items`` (integer [B, J], J >= 1,
+    typically what ``recommend_array``, ``recommend_filtered`` or ``rerank`` returned; -1 padding and duplicates are
+    allowed) the ``num_contributors`` = m (1..64) items of each user's history that carry most of each target's
+    score (recoder_amd/explain.py).  Returns an ``explain.Explanation`` of host numpy arrays:
+    ``contributors`` int64 [B, J, m], history item ids by contribution, largest first, equal values to the smaller
+    id, a NaN behind every number, -1 where the history has fewer than m entries or the target is -1;
+    ``contributions`` f32 [B, J, m], their values, 0.0 at padding (a negative contribution is an ordinary value, kept
+    when fewer than m larger ones exist); ``baseline`` f32 [B, J], the part of the score that belongs to no history
+    item; ``total`` f32 [B, J], ALL of the history's contributions plus the baseline: the score being explained.
+    Exact for both families that are linear in the history.  The item-item models (ShallowAutoencoder,
+    GraphFilterModel, AdmmSlimModel, RandomWalkItemModel, SparseLinearModel, ItemNeighbourhoodModel): the contribution
+    of history item i to target j is x_ui W[i, j], the baseline 0 and ``total`` ``predict``'s score.  A
+    MatrixFactorization with activation 'none' and an embedding size up to ``foldin.MAX_H``: the user is ALWAYS the
+    folded-in one (``fold_in`` with ``alpha`` and ``reg``, which are read for this model only), known and unseen users
+    alike, so ``total`` is the score ``recommend_folded`` ranks by, NOT the score of the trained user row; the
+    baseline is b_j - z . v.  A target that is itself in the history is explained like any other; a user with an
+    empty history gets padding and total = baseline.  ValueError, naming the model's class, before any GPU work:
+    any other model class, another activation, a larger embedding size, a model not yet fitted, more than one rank,
+    an id outside [-1, n_items), ``items`` with another row count than the batch, m outside 1..64."""
+    from . import explain
+    return explain.explain(self, users_interactions, items, num_contributors, alpha, reg)
+
   def train_svd(self, train_dataset, num_power_iterations=6, oversample=16, seed=0):
     """PureSVD (Cremonesi, Koren & Turrin 2010) for a MatrixFactorization with activation 'none'
     (recoder_amd/svd.py): the item table becomes V, the top ``embedding_size`` right singular vectors of
